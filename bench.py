@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Headline benchmark: predicted token-embeddings/s over a full target vocab.
 
-    python bench.py --gpus N --steps K --warmup W [--workload NAME] [--precision bf16|f32]
+    python bench.py --gpus N --steps K --warmup W [--workload NAME] [--precision bf16|f32] [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the embedding-prediction hot path over the whole target
 vocab.  At N = 1 that is one forward (retokenization -> plan -> hoisted input projection
@@ -22,8 +22,15 @@ Rank 0 prints ONE JSON line.  `value` = vocab rows / wall time (whole job).
 `roofline` prices the dominant kernel (the MFMA GEMM): algorithmic FLOPs of every
 GEMM launch in the timed region (2*M*N*K, exactly what the launch computes) divided
 by the launch durations measured with HIP events on the launch stream.
-`cpu_baseline` times oracle/hypernet_ref.py (the as-written numpy port of the
-reference forward) on this box's host cores on a bounded row sample.
+
+A plain run sets up, warms up, times the K steps and prints the line; nothing else.
+--full adds everything measured or checked beyond the headline, after the timed region:
+`cpu_baseline` (oracle/hypernet_ref.py, the as-written numpy port of the reference
+forward, on the host cores on a bounded row sample, and its parity with the GPU rows),
+the uninstrumented re-timing, the other 16-bit arithmetic and fp32 mode, the side
+configs / kept-API / training lines, the live PMC traffic passes, and at N > 1 the
+bit-identity check of the gathered rows (which also prices that line's roofline).
+--dump-outputs DIR writes what the last timed step returned (see dump_outputs).
 """
 from __future__ import annotations
 
@@ -140,7 +147,7 @@ def measure_traffic_live(args, timeout_s=240):
             out_dir = os.path.join(work, counter)
             cmd = [prof, "--kernel-trace", "--pmc", counter, "--output-format", "csv", "-d", out_dir, "-o", "t", "--",
                    sys.executable, os.path.abspath(__file__), "--steps", "1", "--warmup", "0", "--workload", args.workload, "--precision", args.precision,
-                   "--no-cpu-baseline", "--no-alt-precision", "--no-live-traffic", "--no-side-configs"]
+                   "--full", "--no-cpu-baseline", "--no-alt-precision", "--no-live-traffic", "--no-side-configs"]
             # (the A/B switches of the parent run apply to the child too: the traffic is that of the kernels that were timed)
             for kv in args.option:
                 cmd += ["--option", kv]
@@ -640,19 +647,45 @@ def emit(result):
     print(compact_line(result), flush=True)
 
 
+DUMP_LIMIT = 48 << 20          # bytes of all --dump-outputs files together
+
+
+def dump_outputs(outs, directory, limit=DUMP_LIMIT):
+    """--dump-outputs DIR: what the last timed step returned, i.e. what a caller of the forward receives — pred_in, pred_out
+    (absent without separate output embeddings) and bias, all in vocabulary row order — as DIR/<name>.npy in float32.  If the
+    three together exceed `limit` bytes, every array keeps the same fixed sample of rows (numpy default_rng(0), ascending), so
+    that two builds run with the same arguments can be compared output for output."""
+    named = [(name, t) for name, t in zip(("pred_in", "pred_out", "bias"), outs) if t is not None]
+    rows = int(named[0][1].shape[0])
+    per_row = sum(t[0].numel() * 4 for _, t in named)
+    keep = min(rows, max(1, limit // per_row))
+    idx = None
+    if keep < rows:
+        idx = torch.from_numpy(np.sort(np.random.default_rng(0).choice(rows, keep, replace=False))).to(named[0][1].device)
+    os.makedirs(directory, exist_ok=True)
+    for name, t in named:
+        a = t if idx is None else t.index_select(0, idx)
+        np.save(os.path.join(directory, name + ".npy"), a.float().cpu().numpy())
+
+
 def self_launch(gpus):
-    """`python bench.py --gpus N` with N > 1 and no launcher around it: become `python -m torch.distributed.run --nnodes=1
-    --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py <same arguments>` (one rank per GPU; rank 0 prints the line)."""
+    """`python bench.py --gpus N` with N > 1 and no launcher around it: run `python -m torch.distributed.run --nnodes=1
+    --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py <same arguments>` as a child (one rank per GPU; rank 0
+    prints the line) and exit with its status.  A child, not exec: this process must not replace itself once anything in it may
+    have opened the GPU."""
     import socket
+    import subprocess
     with socket.socket() as sk:
         sk.bind(("127.0.0.1", 0))
         port = sk.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={gpus}", "--master-addr", "127.0.0.1", "--master-port", str(port),
            os.path.abspath(__file__)] + sys.argv[1:]
-    os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    print("bench.py: --gpus %d without a launcher: re-executing under torch.distributed.run (port %d)" % (gpus, port), file=sys.stderr, flush=True)
+    env = dict(os.environ)
+    env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
+    print("bench.py: --gpus %d without a launcher: running under torch.distributed.run (port %d)" % (gpus, port), file=sys.stderr, flush=True)
     sys.stdout.flush()
-    os.execv(sys.executable, cmd)
+    rc = subprocess.call(cmd, env=env)
+    sys.exit(rc if rc >= 0 else 128 - rc)
 
 
 def main():
@@ -695,19 +728,26 @@ def main():
                          "every rank retokenizes the whole vocabulary, computes 1/N of the table of its distinct ids and all-gathers the slices) instead of "
                          "per rank for the ids of its own rows; same rows, same bits")
     ap.add_argument("--no-early-gather", action="store_true", help="N > 1, A/B: start the exchange of pred_in / bias behind the whole forward instead of behind their own completion point")
+    ap.add_argument("--full", action="store_true", help="after the timed region, also run every side measurement and check (CPU baseline and parity, "
+                    "uninstrumented re-timing, other precisions, side configs, kept API, training step, live PMC traffic; N > 1: the gathered rows "
+                    "against a local forward, bit for bit, and the roofline of that pass); the --no-* switches above then leave parts out")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the outputs of the last timed step as DIR/<name>.npy (float32; "
+                    f"a fixed seeded row sample when they exceed {DUMP_LIMIT >> 20} MiB)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     import zett_amd
     zett_amd.configure_hw_queues()          # (N > 1: before the HIP runtime initialises)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
-    if not torch.cuda.is_available():
-        raise SystemExit("bench.py needs an MI355X: torch.cuda.is_available() is False")
     if world != args.gpus:
         if world == 1 and args.gpus > 1 and "RANK" not in os.environ:
-            self_launch(args.gpus)          # (does not return)
+            self_launch(args.gpus)          # (does not return; before this process touches the GPU)
         raise SystemExit(f"--gpus {args.gpus} does not match WORLD_SIZE {world}")
+    if not torch.cuda.is_available():
+        raise SystemExit("bench.py needs an MI355X: torch.cuda.is_available() is False")
     # ZETT_BENCH_ONE_DEVICE=1 (test hook): every rank uses cuda:0 and the collectives go through gloo, so
     # that the N > 1 control flow can be exercised on a 1-GPU box; never set for a measurement.
     one_device = os.environ.get("ZETT_BENCH_ONE_DEVICE") == "1"
@@ -762,7 +802,7 @@ def main():
         key, _, val = kv.partition("=")
         engine.set_option(key, int(val))
     # the same weights in the OTHER 16-bit arithmetic, for the side measurement after the timed region (N = 1 only)
-    alt_precision = {"f16": "bf16", "bf16": "f16"}.get(args.precision) if (world == 1 and not exchange and not args.no_alt_precision) else None
+    alt_precision = {"f16": "bf16", "bf16": "f16"}.get(args.precision) if (args.full and world == 1 and not exchange and not args.no_alt_precision) else None
     alt_engine = None
     if alt_precision:
         alt_engine = HipEngine(dims, 1e-5, device, alt_precision)
@@ -775,7 +815,7 @@ def main():
         for kv in args.option:
             key, _, val = kv.partition("=")
             alt_engine.set_option(key, int(val))
-    if rank != 0 or args.no_cpu_baseline or world > 1:
+    if rank != 0 or not args.full or args.no_cpu_baseline or world > 1:
         weights_keep = None
     else:
         weights_keep = weights
@@ -902,6 +942,8 @@ def main():
         t = torch.tensor([dt], device=device, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    post = None
+    if exchange and args.full:
         # untimed: the gathered matrix must hold this rank's rows bit for bit (rows are shard-independent)
         ids_dev = torch.from_numpy(ids_all).to(device) if affinity else None
         # the same untimed pass measures this rank's GEMM launches with per-launch HIP events (kept out of the timed steps: the sync that
@@ -923,16 +965,20 @@ def main():
                     raise SystemExit(f"rank {rank}: all-gathered rows [{b.lo}, {b.hi}) differ from the local forward")
         engine.set_option("time_gemm", 0)
     st = engine.stats()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(out, args.dump_outputs)
 
     ms_per_step = dt / args.steps * 1e3
     value = rows * args.steps / dt
     roofline_steps = args.steps
     roofline_source = "per-launch HIP events of the timed steps"
-    if exchange and gemm_ms <= 0 and post["gemm_ms"] > 0:
+    if exchange and gemm_ms <= 0 and post is not None and post["gemm_ms"] > 0:
         gemm_ms, gemm_fl, launches = post["gemm_ms"], post["gemm_flops_timed"], post["gemm_launches"]
         timed_classes = {k: list(v) for k, v in post_classes.items()}
         roofline_steps = 1
         roofline_source = "per-launch HIP events of ONE untimed pass over this rank's row blocks after the timed region (rank 0; the timed steps run without events)"
+    elif exchange and gemm_ms <= 0:
+        roofline_source = "not measured: the timed steps of an exchange run without per-launch events, the untimed pass that has them runs with --full"
     achieved = gemm_fl / (gemm_ms * 1e-3) / 1e12 if gemm_ms > 0 else 0.0
     peak = PEAK_TFLOPS[args.precision]
 
@@ -1002,7 +1048,7 @@ def main():
         "as_written_tflops": rows * f_ref * args.steps / dt / 1e12,
         "as_written_gflop_per_row": f_ref / 1e9,
     }
-    if world == 1 and not exchange:
+    if args.full and world == 1 and not exchange:
         # What a caller gets: the same steps with the per-launch HIP events (and the stream sync that reads them at the end of
         # every forward) switched off.  Measured after the timed region; `value` / `ms_per_step` stay the instrumented,
         # conservative figures the roofline is priced on.
@@ -1043,7 +1089,7 @@ def main():
                                            "bf16: rel-L2 ~0.97e-2 of the fp32 reference at this shape (tolerance 1e-2), f16: ~0.12e-2"}
         engine = main_engine
         alt_engine.close()
-    if world == 1 and not exchange and args.precision != "f32" and not args.no_alt_precision and not args.rows:
+    if args.full and world == 1 and not exchange and args.precision != "f32" and not args.no_alt_precision and not args.rows:
         # Side measurement, outside the timed region and never `value`: the same workload in exact fp32 MFMA arithmetic — the
         # mode whose tolerance north_star names (max |err| <= 1e-4 relative to the row maximum against the fp32 reference).
         engine.close()
@@ -1068,7 +1114,7 @@ def main():
                               "gemm_tflops": f32_tf, "roofline_frac": f32_tf / PEAK_TFLOPS["f32"], "peak": PEAK_TFLOPS["f32"],
                               "note": "exact fp32 MFMA (v_mfma_f32_32x32x2_f32, gemm8r tile); measured after the timed region"}
         f32_engine.close()
-    if rank == 0 and world == 1 and not exchange and not args.no_side_configs and not args.rows and args.workload == "mistral_gpt2_32k":
+    if args.full and rank == 0 and world == 1 and not exchange and not args.no_side_configs and not args.rows and args.workload == "mistral_gpt2_32k":
         # Side measurements, outside the timed region and never `value`: the other 1-GPU configs of BASELINE.json (C2, C3) and the
         # single-GPU proxy of the 8-GPU step (rank 0's share of the headline vocabulary), so that they are in the driver's record;
         # then the same workloads through the kept Python API.
@@ -1097,7 +1143,7 @@ def main():
             result["train_step"] = train_step_line(args.workload, 16384, "bf16", device)
         except Exception as e:
             result["train_step"] = {"error": f"{type(e).__name__}: {e}"}
-    if rank == 0 and world == 1 and not exchange and not args.no_live_traffic and not args.rows:
+    if args.full and rank == 0 and world == 1 and not exchange and not args.no_live_traffic and not args.rows:
         # roofline.traffic measured HERE: same build, same box, same workload, right after the timed region
         live, info = measure_traffic_live(args)
         if live is not None:
@@ -1108,7 +1154,7 @@ def main():
         else:
             src_info = result["roofline"].get("traffic_source") or {}
             result["roofline"]["traffic_source"] = dict(src_info, live=False, live_failure=str(info))
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cb, ref_out, n_ref = cpu_baseline(cfg, weights_keep, ids_all, src, lang, args.cpu_budget_s)
         result["cpu_baseline"] = cb
         got = out[0][:n_ref].float().cpu().numpy()

@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -24,7 +25,7 @@ def test_two_ranks_on_one_device(extra):
         launcher = [sys.executable]
         env.pop("RANK", None); env.pop("WORLD_SIZE", None)
     cmd = launcher + [os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                      "--workload", "tiny", "--rows", "20001", "--no-cpu-baseline"] + extra
+                      "--workload", "tiny", "--rows", "20001", "--no-cpu-baseline", "--full"] + extra
     out = subprocess.run(cmd, cwd=REPO, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -50,7 +51,7 @@ def test_two_ranks_share_the_hoisted_table(extra):
     env = dict(os.environ, ZETT_BENCH_ONE_DEVICE="1", MASTER_ADDR="127.0.0.1")
     env.pop("RANK", None); env.pop("WORLD_SIZE", None)
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--workload", "xlmr_gpt2", "--rows", "20001",
-           "--no-cpu-baseline", "--table-exchange"] + extra
+           "--no-cpu-baseline", "--table-exchange", "--full"] + extra
     out = subprocess.run(cmd, cwd=REPO, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -61,11 +62,11 @@ def test_two_ranks_share_the_hoisted_table(extra):
 
 
 def test_default_line_is_short_and_complete(tmp_path):
-    """The DEFAULT command (what the driver runs, with fewer steps): ONE `{` line on stdout, under 6 000 bytes (the driver keeps an
+    """The --full command (the plain one plus every side measurement, with fewer steps): ONE `{` line on stdout, under 6 000 bytes (the driver keeps an
     ~8 KB tail of stdout: round 5's 22 KB line was cut and its record did not parse), carrying the contract fields, `roofline`
     and `cpu_baseline`, the compact side measurements — and the full objects in bench_side.json."""
     env = dict(os.environ, ZETT_BENCH_SIDE_DIR=str(tmp_path))
-    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "2", "--warmup", "1", "--cpu-budget-s", "8"], cwd=REPO, env=env,
+    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "2", "--warmup", "1", "--cpu-budget-s", "8", "--full"], cwd=REPO, env=env,
                          capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
@@ -87,3 +88,34 @@ def test_default_line_is_short_and_complete(tmp_path):
     assert len(d["api_path"]) == 2 and all("error" not in a for a in d["api_path"]) and "error" not in d["train_step"]
     full = json.loads((tmp_path / "bench_side.json").read_text())
     assert abs(full["value"] / d["value"] - 1) < 1e-3 and "by_class" in full["configs"][0]["roofline"]
+
+
+def test_plain_line_times_the_steps_and_dumps_the_outputs(tmp_path):
+    """The plain command (no --full): ONE line with the contract fields, `steps` timed steps and nothing measured beyond them;
+    --dump-outputs writes the last step's outputs as float32 .npy within 64 MB, and a second run with the same arguments
+    writes the same bits."""
+    dumps = []
+    for run in ("a", "b"):
+        env = dict(os.environ, ZETT_BENCH_SIDE_DIR=str(tmp_path))
+        cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--workload", "xlmr_gpt2", "--rows", "20001",
+               "--dump-outputs", str(tmp_path / run)]
+        out = subprocess.run(cmd, cwd=REPO, env=env, capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [l for l in out.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1 and lines[0].startswith("{"), out.stdout[-3000:]
+        d = json.loads(lines[0])
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert k in d, k
+        assert d["steps"] == 3 and d["n_gpus"] == 1 and d["dtype"] == "f16" and d["higher_is_better"] is True
+        assert d["value"] == pytest.approx(20001 / (d["ms_per_step"] * 1e-3), rel=1e-3)
+        assert d["cpu_baseline"] is None and "configs" not in d and "alt_precision" not in d and "ms_per_step_uninstrumented" not in d
+        assert 0 < d["roofline"]["frac"] < 1
+        files = sorted(p.name for p in (tmp_path / run).iterdir())
+        assert files == ["bias.npy", "pred_in.npy"], files          # (XLM-R -> GPT-2: no separate output embeddings)
+        arrs = {f: np.load(tmp_path / run / f) for f in files}
+        assert sum(a.nbytes for a in arrs.values()) <= 64 * 2**20
+        # 20 001 rows of 768 + 1 floats exceed the limit: a row sample, the same rows in every file
+        assert all(a.dtype == np.float32 and 0 < a.shape[0] == arrs["bias.npy"].shape[0] < 20001 and np.isfinite(a).all() for a in arrs.values())
+        dumps.append(arrs)
+    for f in dumps[0]:
+        assert np.array_equal(dumps[0][f], dumps[1][f]), f

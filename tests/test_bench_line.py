@@ -4,7 +4,9 @@ import json
 import os
 import sys
 
+import numpy as np
 import pytest
+import torch
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
@@ -66,11 +68,16 @@ def test_compact_line_multi_gpu_fields():
 
 
 def test_self_launch_command(monkeypatch):
+    import subprocess
     seen = {}
-    monkeypatch.setattr(os, "execv", lambda exe, argv: seen.update(exe=exe, argv=argv))
+    monkeypatch.setattr(subprocess, "call", lambda argv, env=None: seen.update(exe=argv[0], argv=argv, env=env) or 3)
+    monkeypatch.setattr(os, "execv", lambda exe, argv: pytest.fail("bench.py must start the launcher as a child, not exec it"))
     monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "8", "--steps", "20", "--warmup", "3"])
-    bench.self_launch(8)
+    with pytest.raises(SystemExit) as ex:
+        bench.self_launch(8)
+    assert ex.value.code == 3                                   # the launcher's exit status is this process's
     a = seen["argv"]
+    assert seen["env"]["HSA_ENABLE_IPC_MODE_LEGACY"] in ("0", os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY"))
     assert seen["exe"] == sys.executable and a[:3] == [sys.executable, "-m", "torch.distributed.run"]
     assert "--nnodes=1" in a and "--nproc-per-node=8" in a and a[a.index("--master-addr") + 1] == "127.0.0.1"
     assert 1024 < int(a[a.index("--master-port") + 1]) < 65536
@@ -101,3 +108,27 @@ def test_cached_cpu_baselines_cover_the_side_configs():
     d = json.loads(bench.compact_line(full))
     assert d["configs"][0]["cpu_baseline"]["value"] == pytest.approx(cached["configs"]["xlmr_gpt2"]["value"], rel=1e-3)
     assert d["configs"][1]["cpu_baseline"]["kind"] == "port" and "cpu_baseline" not in d["configs"][2]
+
+
+def test_dump_outputs_sample_is_fixed_and_bounded(tmp_path):
+    """--dump-outputs: float32 .npy files of what the last step returned; over the byte limit every array keeps the same
+    seeded row sample, identical from run to run."""
+    rows, e = 5000, 64
+    g = torch.Generator().manual_seed(0)
+    outs = (torch.randn(rows, e, generator=g), None, torch.randn(rows, generator=g))
+    limit = 150 * (e + 1) * 4                                   # room for 150 rows of pred_in + bias
+    bench.dump_outputs(outs, str(tmp_path / "a"), limit=limit)
+    bench.dump_outputs(outs, str(tmp_path / "b"), limit=limit)
+    names = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert names == ["bias.npy", "pred_in.npy"]                 # (no pred_out without separate output embeddings)
+    a_in, a_b = np.load(tmp_path / "a" / "pred_in.npy"), np.load(tmp_path / "a" / "bias.npy")
+    assert a_in.dtype == np.float32 and a_b.dtype == np.float32 and a_in.nbytes + a_b.nbytes <= limit
+    assert a_in.shape[0] == a_b.shape[0] == 150 and a_in.shape[1] == e
+    # the same rows of every output, and the same rows in both runs
+    pos = [int(np.nonzero((outs[0].numpy() == r).all(1))[0][0]) for r in a_in]
+    assert pos == sorted(pos) and np.array_equal(outs[2].numpy()[pos], a_b)
+    for n in names:
+        assert np.array_equal(np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n))
+    # under the limit: the whole outputs
+    bench.dump_outputs(outs, str(tmp_path / "c"))
+    assert np.array_equal(np.load(tmp_path / "c" / "pred_in.npy"), outs[0].numpy())

@@ -132,30 +132,45 @@ def test_state_dict_names_and_automodel_roundtrip(tmp_path):
     assert c.model_type == "zett_hypernetwork" and c.hn_surface_maxlen == 7 and c.original_vocab_size == 300
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/hf_hypernet"), reason="reference only exists in the build container")
+def _reference_checkpoint(dst, seed, config_name="config.json"):
+    """The checkpoint the reference's own torch class writes for the "tiny" hypernet with synth.make_weights(cfg, seed)
+    (tests/golden/make_golden_ref_checkpoint.py): its config.json verbatim, and model.safetensors rebuilt from the recorded
+    header and the seeded weights, checked against the sha256 of the file the reference wrote."""
+    import hashlib
+    import json
+    import shutil
+    golden = os.path.join(REPO, "tests", "golden", "ref_checkpoint")
+    meta = json.load(open(os.path.join(golden, "model_safetensors.json")))
+    header = meta["header"].encode()
+    layout = json.loads(header)
+    cfg, *_ = synth.workload("tiny")
+    w = synth.make_weights(cfg, seed)
+    assert set(layout) - {"__metadata__"} == set(w)
+    body = bytearray(max(v["data_offsets"][1] for k, v in layout.items() if k != "__metadata__"))
+    for k, v in layout.items():
+        if k == "__metadata__":
+            continue
+        lo, hi = v["data_offsets"]
+        a = np.ascontiguousarray(w[k], dtype="<f4")
+        assert v["dtype"] == "F32" and list(a.shape) == v["shape"] and a.nbytes == hi - lo, k
+        body[lo:hi] = a.tobytes()
+    blob = len(header).to_bytes(8, "little") + header + bytes(body)
+    want = meta["by_seed"][str(seed)]
+    assert len(blob) == want["size"] and hashlib.sha256(blob).hexdigest() == want["sha256"], "not the file the reference wrote"
+    os.makedirs(dst)
+    open(os.path.join(dst, "model.safetensors"), "wb").write(blob)
+    shutil.copyfile(os.path.join(golden, config_name), os.path.join(dst, "config.json"))
+    return dst
+
+
 def test_loads_checkpoint_written_by_reference(tmp_path):
     """A checkpoint saved by the reference's own torch class loads into ours unchanged."""
-    code = f"""
-import sys, json, torch, numpy as np
-sys.path.insert(0, "/root/reference"); sys.path.insert(0, {REPO!r})
-from hf_hypernet.configuration_hypernet import ZettHypernetConfig
-from hf_hypernet.modeling_hypernet import ZettHypernet
-from zett_amd import synth
-import os
-rb = os.path.join({str(tmp_path)!r}, "rb"); os.makedirs(rb)
-json.dump({{"model_type": "roberta", "max_position_embeddings": 514, "type_vocab_size": 1, "layer_norm_eps": 1e-5,
-           "hidden_act": "gelu", "vocab_size": 50265, "pad_token_id": 1}}, open(os.path.join(rb, "config.json"), "w"))
-cfg, *_ = synth.workload("tiny")
-m = ZettHypernet(ZettHypernetConfig(**dict(cfg, hn_model_name_or_path=rb)))
-m.load_state_dict({{k: torch.from_numpy(v) for k, v in synth.make_weights(cfg, 5).items()}})
-m.save_pretrained(os.path.join({str(tmp_path)!r}, "ckpt"))
-"""
-    subprocess.run([sys.executable, "-c", code], check=True, cwd="/tmp")
+    ckpt = _reference_checkpoint(os.path.join(tmp_path, "ckpt"), 5)
     # reference checkpoints carry no usable model_type (the class sets it on the instance only) and are
     # loaded by remote code upstream; here the class is addressed directly.
     from zett_amd.hypernet import ZettHypernet
     cfg, *_ = synth.workload("tiny")
-    model = ZettHypernet.from_pretrained(os.path.join(tmp_path, "ckpt"))
+    model = ZettHypernet.from_pretrained(ckpt)
     assert model.config.hn_surface_maxlen == 7 and model.dims.original_vocab_size == 300
     for k, v in synth.make_weights(cfg, 5).items():
         assert torch.equal(model.state_dict()[k], torch.from_numpy(v)), k
@@ -428,27 +443,13 @@ def test_cli_prediction_shards_batches_over_ranks_gloo(tmp_path):
     assert res["rows_all_ranks"] == 8 * 128          # 1003 rows in 8 batches of 128 (the last one padded), each computed once
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/hf_hypernet"), reason="reference only exists in the build container")
 def test_install_remote_code_routes_reference_checkpoint(tmp_path):
     """AutoModel(..., trust_remote_code=True) on a reference-written checkpoint returns the zett_amd class."""
-    code = f"""
-import sys, json, torch, os
-sys.path.insert(0, "/root/reference"); sys.path.insert(0, {REPO!r})
-from hf_hypernet.configuration_hypernet import ZettHypernetConfig
-from hf_hypernet.modeling_hypernet import ZettHypernet
-from zett_amd import synth
-rb = os.path.join({str(tmp_path)!r}, "rb"); os.makedirs(rb)
-json.dump({{"model_type": "roberta", "max_position_embeddings": 514, "type_vocab_size": 1, "layer_norm_eps": 1e-5,
-           "hidden_act": "gelu", "vocab_size": 50265, "pad_token_id": 1}}, open(os.path.join(rb, "config.json"), "w"))
-cfg, *_ = synth.workload("tiny")
-ZettHypernetConfig.register_for_auto_class()
-ZettHypernet.register_for_auto_class("AutoModel")
-m = ZettHypernet(ZettHypernetConfig(**dict(cfg, hn_model_name_or_path=rb)))
-m.load_state_dict({{k: torch.from_numpy(v) for k, v in synth.make_weights(cfg, 8).items()}})
-m.save_pretrained(os.path.join({str(tmp_path)!r}, "ckpt"))
-"""
-    subprocess.run([sys.executable, "-c", code], check=True, cwd="/tmp")
-    ckpt = os.path.join(tmp_path, "ckpt")
+    # (saved with the auto classes registered: config.json carries the reference's auto_map; the modules it names are
+    # written by install_remote_code)
+    ckpt = _reference_checkpoint(os.path.join(tmp_path, "ckpt"), 8, "config_auto_map.json")
+    import json
+    assert "auto_map" in json.load(open(os.path.join(ckpt, "config.json")))
     import zett_amd
     zett_amd.install_remote_code(ckpt)
     check = f"""
@@ -466,7 +467,7 @@ for k, v in synth.make_weights(cfg, 8).items():
 assert hasattr(m, "engine")
 print("ok")
 """
-    out = subprocess.run([sys.executable, "-c", check], check=True, cwd="/tmp", capture_output=True, text=True)
+    out = subprocess.run([sys.executable, "-c", check], check=True, cwd=str(tmp_path), capture_output=True, text=True)
     assert "ok" in out.stdout
 
 

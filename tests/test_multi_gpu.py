@@ -37,7 +37,7 @@ def _torchrun(script_args, port, timeout=900):
                          ids=["two-blocks-self-launched", "serial", "three-blocks", "fanout", "serial-fanout", "serial-late", "affinity-fanout", "shared-table"])
 def test_bench_two_gpus_nccl(extra):
     bench_args = [os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--workload", "tinyllama_neox",
-                  "--rows", "30001", "--no-cpu-baseline"] + extra
+                  "--rows", "30001", "--no-cpu-baseline", "--full"] + extra
     if not extra:
         # the driver's form: `python bench.py --gpus N` with no launcher — bench.py re-executes itself under torch.distributed.run
         env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "ZETT_BENCH_ONE_DEVICE")}

@@ -105,7 +105,7 @@ def test_bench_through_a_one_rank_rccl_group():
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(29900 + os.getpid() % 90), HSA_ENABLE_IPC_MODE_LEGACY="0")
     for extra in ([], ["--gather-mode", "fanout"], ["--serial-allgather", "--no-early-gather"]):
         cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--force-gather", "--steps", "3", "--warmup", "1",
-               "--workload", "tiny", "--rows", "20001", "--no-cpu-baseline"] + extra
+               "--workload", "tiny", "--rows", "20001", "--no-cpu-baseline", "--full"] + extra
         out = subprocess.run(cmd, cwd=REPO, env=env, capture_output=True, text=True, timeout=600)
         assert out.returncode == 0, out.stderr[-2000:]
         lines = [l for l in out.stdout.splitlines() if l.startswith("{")]

@@ -273,7 +273,8 @@ del os.environ["ZETT_SHARED_TABLE"]
 got = predict_vocabulary(model, sfm, src, lang, Args(output="", do_batching=False))
 assert predict_vocabulary.last_job_table is False and same(got, one), "one-batch job, own tables"
 dist.barrier(); dist.destroy_process_group()
-print("rank", os.environ["RANK"], "ok")
+sys.stdout.write("rank %s ok\\n" % os.environ["RANK"])          # one write: the two ranks share the pipe, print's pieces interleave
+sys.stdout.flush()
 """)
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     if torch.cuda.device_count() < 2:

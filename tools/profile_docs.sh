@@ -13,10 +13,10 @@ for r in 16384 8192 4096; do cp $src/bench_rows_$r.json profiles/${tag}_bench_ro
 grep "zett gemm" $src/gemm_launch_log.txt | tail -39 > profiles/${tag}_gemm_launch_log.txt
 {
   echo "# $tag — $title (commit $H)"; echo
-  echo "Command (MI355X box, \`tools/profile_round.sh $tag\`): \`rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/$tag/prof -o $tag -- python bench.py --steps 3 --warmup 1 --no-cpu-baseline\`"
+  echo "Command (MI355X box, \`tools/profile_round.sh $tag\`): \`rocprofv3 --kernel-trace --stats --output-format csv -d <out>/prof -o $tag -- python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline\`"
   echo "(8 forward passes in the trace: 1 warm-up + 3 timed with per-launch HIP events, then bench.py's 1 + 3 passes without them — the \`ms_per_step_uninstrumented\` figure; workload mistral_gpt2_32k, f16 = the default precision.  The trace covers the WHOLE process: the \`__amd_rocclr_copyBuffer\`, \`at::native\` and \`convert_f32_to_lo\` rows are the untimed set-up — random weights generated with torch on the GPU, ~100 weight uploads and conversions — not part of a step, which launches no torch kernel.)  Source: \`${tag}_kernel_stats.csv\` as written by rocprofv3."; echo
   echo "bench line of the same (profiled) run:"; echo; echo '```'; cat $src/prof_bench.json; echo '```'; echo
-  echo "un-profiled default run on the same box (\`python bench.py\`, with the CPU baseline): \`profiles/${tag}_bench.json\`."; echo
+  echo "un-profiled default run on the same box (\`python bench.py --full\`, with the CPU baseline): \`profiles/${tag}_bench.json\`."; echo
   python tools/kernel_stats_md.py profiles/${tag}_kernel_stats.csv; echo
   python - "$tag" <<'PY'
 import csv, sys
@@ -31,7 +31,7 @@ PY
 {
   echo "# $tag — PMC passes on bench.py (commit $H)"; echo
   echo "Three separate passes (\`--pmc\` only with \`--kernel-trace\`, as the MI355X guide prescribes), each:"
-  echo "\`rocprofv3 --kernel-trace --pmc <COUNTERS> --output-format csv -d gpurun_out/$tag/pmc_X -o t -- python bench.py --steps 1 --warmup 1 --no-cpu-baseline\`"
+  echo "\`rocprofv3 --kernel-trace --pmc <COUNTERS> --output-format csv -d <out>/pmc_X -o t -- python bench.py --full --steps 1 --warmup 1 --no-cpu-baseline\`"
   echo "with COUNTERS = \`FETCH_SIZE\` | \`WRITE_SIZE\` | \`SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE\` (workload mistral_gpt2_32k, f16; four forwards per pass: two with bench.py's per-launch HIP events, two without)."
   echo "Summarised by \`tools/pmc_summary.py\` (FETCH_SIZE doubled per the gfx950 correction; GRBM_GUI_ACTIVE is summed over the 8 XCDs)."; echo
   python tools/pmc_summary.py $src/pmc_FETCH_SIZE $src/pmc_WRITE_SIZE $src/pmc_SQ_VALU_MFMA_BUSY_CYCLES

@@ -4,11 +4,12 @@
 #   gpurun --timeout 1500 -- 'bash tools/profile_round.sh r1d'
 set -u
 tag=${1:-rX}
+repo=$(cd "$(dirname "$0")/.." && pwd)
 out=$GRAFT_REPO_ROOT/gpurun_out/$tag
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
-bench="python $GRAFT_REPO_ROOT/bench.py --no-live-traffic --no-side-configs"      # (the PMC passes below are the profile set; the default line measures its own traffic and carries the side lines)
-python $GRAFT_REPO_ROOT/bench.py 2>/dev/null | tail -1 > $out/bench_default.json
+bench="python $repo/bench.py --full --no-live-traffic --no-side-configs"      # (the PMC passes below are the profile set; the --full line measures its own traffic and carries the side lines)
+python "$repo/bench.py" --full 2>/dev/null | tail -1 > $out/bench_default.json
 cp $GRAFT_REPO_ROOT/bench_side.json $out/bench_default_side.json      # (r6: stdout is the compact line; the full objects — per-class tables of every side config — are in bench_side.json)
 for w in xlmr_gpt2 tinyllama_neox mistral_neox llama3_256k; do $bench --workload $w --no-cpu-baseline 2>/dev/null | tail -1 > $out/bench_$w.json; cp $GRAFT_REPO_ROOT/bench_side.json $out/bench_${w}_side.json; done
 $bench --precision f32 --no-cpu-baseline 2>/dev/null | tail -1 > $out/bench_default_f32.json

@@ -5,10 +5,11 @@
 set -u
 tag=${1:-rX}; w=${2:-xlmr_gpt2}; shift 2
 extra="$*"
+repo=$(cd "$(dirname "$0")/.." && pwd)
 out=$GRAFT_REPO_ROOT/gpurun_out/${tag}_$w
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
-bench="python $GRAFT_REPO_ROOT/bench.py --workload $w --no-live-traffic --no-cpu-baseline --no-alt-precision --no-side-configs $extra"
+bench="python $repo/bench.py --full --workload $w --no-live-traffic --no-cpu-baseline --no-alt-precision --no-side-configs $extra"
 $bench 2>/dev/null | tail -1 > $out/bench.json
 cp $GRAFT_REPO_ROOT/bench_side.json $out/bench_side.json
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof -o $tag -- $bench --steps 3 --warmup 1 > $out/prof_bench.json 2> $out/prof.err

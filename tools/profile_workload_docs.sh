@@ -9,7 +9,7 @@ cp $src/bench.json ${pre}_bench.json
 grep "zett gemm" $src/gemm_launch_log.txt > ${pre}_gemm_launch_log.txt
 {
   echo "# ${tag} / $w — $title (commit $H)"; echo
-  echo "Command (MI355X box, \`tools/profile_workload.sh $tag $w\`): \`rocprofv3 --kernel-trace --stats --output-format csv -- python bench.py --workload $w --no-live-traffic --no-cpu-baseline --no-alt-precision --steps 3 --warmup 1\`"
+  echo "Command (MI355X box, \`tools/profile_workload.sh $tag $w\`): \`rocprofv3 --kernel-trace --stats --output-format csv -- python bench.py --full --workload $w --no-live-traffic --no-cpu-baseline --no-alt-precision --steps 3 --warmup 1\`"
   echo "(8 forward passes in the trace: 1 warm-up + 3 timed with per-launch HIP events, then 1 + 3 without them; f16.  The \`__amd_rocclr_copyBuffer\`, \`at::native\` and \`convert_f32_to_lo\` rows are the untimed set-up.)  Source: \`${tag}_${w}_kernel_stats.csv\` as written by rocprofv3."; echo
   echo "bench line of the same (profiled) run:"; echo; echo '```'; cat $src/prof_bench.json; echo '```'; echo
   echo "un-profiled run on the same box: \`${pre}_bench.json\`."; echo
@@ -30,7 +30,7 @@ PY
 {
   echo "# ${tag} / $w — PMC passes on bench.py --workload $w (commit $H)"; echo
   echo "Three separate passes (\`--pmc\` only with \`--kernel-trace\`, as the MI355X guide prescribes), each:"
-  echo "\`rocprofv3 --kernel-trace --pmc <COUNTERS> --output-format csv -- python bench.py --workload $w --steps 1 --warmup 1 ...\`"
+  echo "\`rocprofv3 --kernel-trace --pmc <COUNTERS> --output-format csv -- python bench.py --full --workload $w --steps 1 --warmup 1 ...\`"
   echo "with COUNTERS = \`FETCH_SIZE\` | \`WRITE_SIZE\` | \`SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE\` (f16; four forwards per pass)."
   echo "Summarised by \`tools/pmc_summary.py\` (FETCH_SIZE doubled per the gfx950 correction; GRBM_GUI_ACTIVE is summed over the 8 XCDs)."; echo
   python tools/pmc_summary.py $src/pmc_FETCH_SIZE $src/pmc_WRITE_SIZE $src/pmc_SQ_VALU_MFMA_BUSY_CYCLES
