@@ -31,7 +31,8 @@ extern "C" {
                                    5: zett_forward_prepare, zett_retokenize_async / zett_retok_result;
                                    6: zett_retokenize_async takes NUL-separated text (offsets == NULL); options gemm_tail_split;
                                    7: zett_retok_set_option;
-                                   8: zett_table_plan, zett_table_rows, zett_forward_table (the hoisted table shared between ranks) */
+                                   8: zett_table_plan, zett_table_rows, zett_forward_table (the hoisted table shared between ranks);
+                                      additive, ABI 8: zett_forward_into, zett_forward_table_into, struct zett_dest, ZETT_RANGE_DEST */
 
 enum zett_status {
     ZETT_OK = 0,
@@ -50,7 +51,9 @@ enum zett_range_bits {
     ZETT_RANGE_SOURCE = 1,      /* in_scaler(source_embeddings[id]) of a referenced id does not fit the operand type */
     ZETT_RANGE_ACTIVATION = 2,  /* a 16-bit GEMM output (Q/K/V, FFN intermediate, the operand copy of the residual sum) */
     ZETT_RANGE_OUTPUT = 4,      /* a predicted embedding is inf / NaN                                                */
-    ZETT_RANGE_WEIGHT = 8       /* a GEMM weight (or a LayerNorm-folded weight) does not fit: reported by zett_finalize */
+    ZETT_RANGE_WEIGHT = 8,      /* a GEMM weight (or a LayerNorm-folded weight) does not fit: reported by zett_finalize */
+    ZETT_RANGE_DEST = 16        /* zett_forward_into: a finite value did not fit an f16 destination; stored as inf.  Repeating the
+                                   call in bf16 arithmetic would not help: the destination's type is the caller's choice     */
 };
 
 enum zett_dtype { ZETT_F32 = 0, ZETT_F16 = 1, ZETT_BF16 = 2 };
@@ -143,6 +146,42 @@ int zett_forward(zett_hypernet* h, const int32_t* surface_forms, int64_t n_rows,
                  const void* source_embeddings, int src_dtype, int64_t v_src, int32_t lang_index,
                  float* out_in, float* out_out, float* out_bias, void* stream);
 
+/* ---- predicted rows straight into a destination matrix (additive, ABI 8) ------------------------------------------------
+ * Replaces: what every caller of the reference's hypernet(...) does next — resize the model's embedding matrix, then copy the
+ * predicted rows in with index_put_ and cast them to the model's dtype (README `hypernet(sfm, source_embeddings=...)`), or
+ * accumulate them into [V, E] matrices with index_add_ (scripts/transfer.py:96-111).
+ * zett_forward_into / zett_forward_table_into are zett_forward / zett_forward_table whose three outputs go to the caller's
+ * matrices: input row i goes to row rows[i] (< 0: not written; rows == NULL: row i) of `in` / `out` / `bias`, with the
+ * destination's own leading dimension (elements) and type.  The stored value is the fp32 value zett_forward stores: bit for bit
+ * in an fp32 destination, rounded to nearest even in a bf16 / f16 one (what torch's .to(dtype) gives, inf included).
+ *   in / out      [n_dest_rows, >= ld] of `dtype`; out is NULL iff the config has no second output
+ *   bias          [n_dest_rows] of `bias_dtype`, or NULL: the bias is not written
+ *   rows          device int64 [n_rows], or NULL (then n_dest_rows >= n_rows).  Checked against n_dest_rows on the device with the
+ *                 plan's error word: ZETT_E_INDEX at the point where zett_forward reports a bad id, before any output is written.
+ *                 (The check runs on `stream`, behind whatever wrote the map: with a prepared plan the host waits for `stream`
+ *                 too.)  Two input rows with the same destination row: undefined which one lands.
+ * ld_in / ld_out < n_embd, an unknown dtype, a NULL `in` or a NULL / non-NULL `out` that does not match the config: ZETT_E_INVALID.
+ * Everything else as zett_forward: zett_forward_prepare, chunking, "concurrent_lanes", the pair plan, zett_stream_wait_output
+ * (ZETT_OUT_IN: the destination's `in` rows are written; ZETT_OUT_BIAS: its bias).  ZETT_RANGE_OUTPUT is tested on the fp32
+ * value, ZETT_RANGE_DEST on the destination's.
+ * Where the conversion happens: in the 16-bit arithmetic modes the output heads' GEMM epilogues store into the destination
+ * themselves (gemm4d's F32_SCALE / F32_SCALE_FOLD epilogues, 256x256 and 128x256 tiles; gemm log bit 10), and the position-0
+ * readout stores the bias.  These launches instead write fp32 rows to the handle's workspace and a converting scatter
+ * (the counterpart of zett_scatter_rows) moves them (gemm log bit 11): every head of the F32 arithmetic mode; hn_single_head with
+ * separate outputs (one launch, two destinations); head launches that take another tile than gemm4d (M or N <= 128, K below
+ * "gemm4d_min_k", a forced "gemm_variant"); heads without the Rescaler and without the LayerNorm fold (plain F32 epilogue); a
+ * destination whose base or leading dimension is not a multiple of four values.  Same bits either way. */
+typedef struct zett_dest {
+    void* in; void* out; void* bias;      /* out: NULL iff the config has no second output; bias: NULL = not written */
+    int32_t dtype; int32_t bias_dtype;    /* zett_dtype: ZETT_F32 / ZETT_F16 / ZETT_BF16 */
+    int64_t ld_in; int64_t ld_out;        /* elements between destination rows, >= n_embd */
+    const int64_t* rows;                  /* [n_rows] destination row of each input row, < 0 = skip; NULL = identity */
+    int64_t n_dest_rows;                  /* rows in the destination (bounds of `rows`) */
+} zett_dest;
+int zett_forward_into(zett_hypernet* h, const int32_t* surface_forms, int64_t n_rows, int32_t seq,
+                      const void* source_embeddings, int src_dtype, int64_t v_src, int32_t lang_index,
+                      const zett_dest* dest, void* stream);
+
 /* How asynchronous zett_forward is.  The launches of a forward are sized by its PLAN (packed positions, distinct source ids,
  * distinct (id, position) pairs: integers computed on the device from the surface forms), so zett_forward enqueues the plan
  * (six small kernels), waits on the HOST for it and for its error word (ZETT_E_INDEX is returned synchronously, as the
@@ -167,7 +206,8 @@ typedef struct zett_gemm_record {
     int32_t epilogue;             /* bit 0 16-bit output, 1 fp32 output, 2 residual, 3 Rescaler, 4 LayerNorm-fold producer
                                      (16-bit copy + partial statistics), 5 LayerNorm-fold consumer, 6 residual read from the
                                      16-bit stream; bits 8-9 activation
-                                     (0 none, 1 tanh-GELU, 2 erf-GELU)                                            */
+                                     (0 none, 1 tanh-GELU, 2 erf-GELU); 10 zett_forward_into: the epilogue stores into
+                                     the destination, 11 zett_forward_into: fp32 rows staged for the converting scatter */
     float ms;                     /* launch duration (0 when "time_gemm" is off)                                  */
     double flops;                 /* 2*m*n*k                                                                      */
     double bytes;                 /* algorithmic HBM bytes of the launch: A and W read once, every output written
@@ -293,6 +333,9 @@ int zett_table_rows(zett_hypernet* h, const int32_t* id_list, int64_t first, int
                     int64_t v_src, void* table_out, float* stats_out, void* stream);
 int zett_forward_table(zett_hypernet* h, const int32_t* surface_forms, int64_t n_rows, int32_t seq, const void* table, const float* table_stats,
                        const int32_t* id_slot, int32_t lang_index, float* out_in, float* out_out, float* out_bias, void* stream);
+/* zett_forward_table storing into a destination (additive, ABI 8): see zett_forward_into */
+int zett_forward_table_into(zett_hypernet* h, const int32_t* surface_forms, int64_t n_rows, int32_t seq, const void* table,
+                            const float* table_stats, const int32_t* id_slot, int32_t lang_index, const zett_dest* dest, void* stream);
 
 /* ---- retokenizer ------------------------------------------------------------
  * Replaces: zett.utils.get_surface_form_matrix (zett/utils.py:651-689) and the

@@ -13,7 +13,7 @@ from .build import LIB_PATH
 
 ZETT_OK = 0
 E_INVALID, E_HIP, E_STATE, E_INDEX, E_NOT_IMPLEMENTED, E_KEY, E_RANGE = -1, -2, -3, -4, -5, -6, -7
-RANGE_SOURCE, RANGE_ACTIVATION, RANGE_OUTPUT, RANGE_WEIGHT = 1, 2, 4, 8      # zett_range_bits
+RANGE_SOURCE, RANGE_ACTIVATION, RANGE_OUTPUT, RANGE_WEIGHT, RANGE_DEST = 1, 2, 4, 8, 16      # zett_range_bits
 DTYPE_F32, DTYPE_F16, DTYPE_BF16 = 0, 1, 2
 PREC_BF16, PREC_F32, PREC_F16 = 0, 1, 2
 RETOK_BPE, RETOK_UNIGRAM, RETOK_WORDPIECE = 0, 1, 2
@@ -26,6 +26,7 @@ ABI_SYMBOLS = (
     "zett_stream_wait_output", "zett_forward_prepare", "zett_retokenize_async", "zett_retok_result", "zett_retok_set_option",
     "zett_partition_rows", "zett_partition_workspace_bytes", "zett_scatter_rows",
     "zett_table_plan", "zett_table_rows", "zett_forward_table",
+    "zett_forward_into", "zett_forward_table_into",
     # training primitives (zett_amd/autograd.py)
     "zett_op_gemm_f32", "zett_op_transpose_f32", "zett_op_colsum_f32", "zett_op_elementwise_f32", "zett_op_rowdot_f32",
     "zett_op_layernorm_fwd_f32", "zett_op_layernorm_bwd_f32", "zett_op_gelu_fwd_f32", "zett_op_gelu_bwd_f32",
@@ -54,6 +55,12 @@ class ZettStats(C.Structure):
 class ZettGemmRecord(C.Structure):
     _fields_ = [("m", C.c_int32), ("n", C.c_int32), ("k", C.c_int32), ("variant", C.c_int32), ("epilogue", C.c_int32),
                 ("ms", C.c_float), ("flops", C.c_double), ("bytes", C.c_double)]
+
+
+class ZettDest(C.Structure):
+    """struct zett_dest (zett_forward_into / zett_forward_table_into): where the predicted rows go."""
+    _fields_ = [("in_", C.c_void_p), ("out", C.c_void_p), ("bias", C.c_void_p), ("dtype", C.c_int32), ("bias_dtype", C.c_int32),
+                ("ld_in", C.c_int64), ("ld_out", C.c_int64), ("rows", C.c_void_p), ("n_dest_rows", C.c_int64)]
 
 
 class ZettRetokModel(C.Structure):
@@ -119,6 +126,10 @@ def load():
         lib.zett_table_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.zett_forward_table.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.zett_forward_into.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int, C.c_int64, C.c_int32,
+                                          C.POINTER(ZettDest), C.c_void_p]
+        lib.zett_forward_table_into.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                                C.POINTER(ZettDest), C.c_void_p]
         lib.zett_partition_workspace_bytes.argtypes = [C.c_int64, C.c_int32, C.POINTER(C.c_int64)]
         lib.zett_scatter_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p]
         lib.zett_partition_rows.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32),

@@ -20,6 +20,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 // M tiles per group of the tile order of the large-tile kernels (gemm8r / gemm8x / gemm4d): consecutive workgroups of
 // an XCD walk GROUP_M row tiles down before moving one column tile right, so the 32 tiles an XCD runs at a time form
 // a GROUP_M x (32 / GROUP_M) block and share GROUP_M + 32 / GROUP_M operand panels in its L2.  4 x 8 and 8 x 4 are the
@@ -282,6 +284,13 @@ struct GemmEpilogue {
     // state (type T) instead of `residual`; res_stats / res_gamma / res_beta / res_index apply to it as they do to `residual`
     const T* residual_lo;
     int ld_res_lo;
+    // Destination-aware store of the predicted rows (zett_forward_into; gemm4d's F32_SCALE / F32_SCALE_FOLD dst instantiations
+    // only): row m of the launch goes to dst + dst_rows[m] * ld_dst (dst_rows null: row m; < 0: not written) in the type
+    // dst_dtype names (zett_dtype), instead of out_f32.  Null on every other launch.
+    void* dst;
+    const int64_t* dst_rows;
+    int64_t ld_dst;
+    int dst_dtype;
 };
 
 // Largest finite value of the operand type: what a value written as a 16-bit operand is checked against.  bf16 and fp32
@@ -291,7 +300,13 @@ template <> struct LoRange<f16_t> { static constexpr bool checked = true; static
 // true where v would not survive: beyond the limit, or NaN (the comparison is false for NaN)
 __device__ __forceinline__ bool out_of_range(float v, float limit) { return !(__builtin_fabsf(v) <= limit); }
 constexpr float ZETT_F32_MAX = 3.402823466e38f;
-constexpr int ZETT_RANGE_BIT_SOURCE = 1, ZETT_RANGE_BIT_ACTIVATION = 2, ZETT_RANGE_BIT_OUTPUT = 4, ZETT_RANGE_BIT_WEIGHT = 8;
+constexpr int ZETT_RANGE_BIT_SOURCE = 1, ZETT_RANGE_BIT_ACTIVATION = 2, ZETT_RANGE_BIT_OUTPUT = 4, ZETT_RANGE_BIT_WEIGHT = 8, ZETT_RANGE_BIT_DEST = 16;
+// Destination store (zett_forward_into): true where a FINITE fp32 value became inf in the destination type.  Only half can: a value
+// rounds to inf from 65520 up (65504 + half an ulp); bf16 and fp32 share fp32's exponent range.
+template <typename OT> __device__ __forceinline__ bool dest_overflow(float v) {
+    if constexpr (std::is_same<OT, f16_t>::value) { const float a = __builtin_fabsf(v); return a >= 65520.0f && a <= 3.402823466e38f; }
+    else return false;
+}
 __device__ __forceinline__ void range_report(int32_t* flag, bool bad, int bit) {
     if (bad && flag) atomicOr(flag, bit);      // (never taken on a healthy checkpoint)
 }

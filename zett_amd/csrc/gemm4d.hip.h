@@ -152,12 +152,19 @@ template <bool HALF> struct G4dGeom {
 // K step is 64 MFMAs against 12 LDS-DMA requests and 12 + 12 fragment reads (the full tile: 128 against 16 and 16 + 16), so its
 // K loop is slower per FLOP (NOTEBOOK R3.1 measured 28 % for two half tiles per CU) — it only ever replaces idle CUs.  Same K
 // order per accumulator, same epilogue arithmetic: identical bits (tests/test_invariants_gpu.py).
-template <typename T, int ACT = ACT_NONE, bool RES = false, int EPI = G4D_EPI_GENERIC, bool HALF = false>
+//
+// OT (zett_forward_into): void = the fp32 store into out_f32 every forward takes; float / f16_t / bf16_t = the DESTINATION store of
+// the output heads (F32_SCALE and F32_SCALE_FOLD only, launch_gemm4d_dst_inst): the same fp32 value, converted to OT
+// (round to nearest even) and stored at row dst_rows[m] (< 0: skipped; null: m) of the caller's matrix with its own leading
+// dimension — four values per lane and store, as the fp32 rows (8-byte stores of 16-bit values).
+template <typename T, int ACT = ACT_NONE, bool RES = false, int EPI = G4D_EPI_GENERIC, bool HALF = false, typename OT = void>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void gemm4d_tn_kernel(GemmArgs<T> g) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int BK = GEMM_ROW_BYTES / (int)sizeof(T);
     typedef G4dGeom<HALF> GEO;          // (static members, not constexpr locals: see G4dGeom)
     static_assert(!HALF || EPI != G4D_EPI_GENERIC, "the half tile carries the streamlined epilogues only");
+    constexpr bool DST = !std::is_void<OT>::value;
+    static_assert(!DST || EPI == G4D_EPI_F32_SCALE || EPI == G4D_EPI_F32_SCALE_FOLD, "destination stores: the output heads' epilogues only");
 
     const int tiles_m = (g.M - g.row0 + GEO::BM - 1) / GEO::BM;
     const int tiles_n = (g.N + G256_BN - 1) / G256_BN;
@@ -565,6 +572,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                 fst[p] = *(const float2*)(e.fold_stats + 2 * (size_t)srow);
             }
         }
+        // destination rows (DST): lane l holds the destination row of row l of each pass (identity without a row map), fetched
+        // per instruction with v_readlane like the statistics
+        int64_t drow[2] = {0, 0};
+        if constexpr (DST) {
+#pragma unroll
+            for (int p = 0; p < GEO::NPASS; ++p) {
+                int srow = m0 + wm * GEO::WROWS + p * 64 + lane_e; srow = srow < g.M ? srow : g.M - 1;
+                drow[p] = e.dst_rows ? e.dst_rows[srow] : (int64_t)srow;
+            }
+        }
+        bool bad_dst = false;
         // residual rows of both passes: requested before any store leaves (pass 1's right after pass 0 is staged, by
         // which time the accumulators of pass 0 have left their registers)
         // (LNP: ONE buffer — pass 1's rows are requested after pass 0 has drained; the row statistics and the second
@@ -745,7 +763,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                         store_out8<T>(e.out_lo + (size_t)grow * e.ld_lo + gcol, a, b);
                     } else {
                         const f32x4 x = {v[u * 4], v[u * 4 + 1], v[u * 4 + 2], v[u * 4 + 3]};
-                        if constexpr (WF32) {
+                        if constexpr (DST) {
+                            const int r0 = (t0 + u) * RPI;          // rows r0 (rsub = 0) and r0 + 1 (rsub = 1) of the pass
+                            static_assert(!DST || RPI == 2, "two rows per instruction");
+                            const uint64_t d64 = (uint64_t)drow[p];
+                            const uint32_t lo0 = __builtin_amdgcn_readlane((uint32_t)d64, r0), hi0 = __builtin_amdgcn_readlane((uint32_t)(d64 >> 32), r0);
+                            const uint32_t lo1 = __builtin_amdgcn_readlane((uint32_t)d64, r0 + 1), hi1 = __builtin_amdgcn_readlane((uint32_t)(d64 >> 32), r0 + 1);
+                            const int64_t d = (int64_t)(((uint64_t)(rsub ? hi1 : hi0) << 32) | (rsub ? lo1 : lo0));
+                            if (d >= 0) {
+                                store_out4<OT>((OT*)e.dst + d * e.ld_dst + gcol, make_float4(x[0], x[1], x[2], x[3]));
+#pragma unroll
+                                for (int c = 0; c < 4; ++c) bad_dst |= dest_overflow<OT>(x[c]);
+                            }
+                        } else if constexpr (WF32) {
                             float* d = e.out_f32 + (size_t)grow * e.ld_f32 + gcol;
                             if (RES) asm volatile("global_store_dwordx4 %0, %1, off nt\n\ts_nop 1" :: "v"(d), "v"(x) : "memory");
                             else *(f32x4*)d = x;
@@ -786,6 +816,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             drain_pass(1);
         }
         range_report(e.range_flag, bad, W16 ? ZETT_RANGE_BIT_ACTIVATION : ZETT_RANGE_BIT_OUTPUT);
+        if constexpr (DST) range_report(e.range_flag, bad_dst, ZETT_RANGE_BIT_DEST);
     }
 }
 
@@ -902,13 +933,65 @@ inline int gemm4d_row_split(int M, int N, int cus = 256, double half_cost = 0.62
     return cost < (double)rounds - 0.05 ? (int)row0 : M;
 }
 
+// (zett_forward_into) the destination instantiations: mode F32_SCALE or F32_SCALE_FOLD (gemm4d_dst_mode), one per destination type
+template <typename T, int EPI, typename OT, bool HALF>
+inline hipError_t launch_gemm4d_dst_inst(const GemmArgs<T>& g, hipStream_t stream) {
+    constexpr int lds = G4dGeom<HALF>::LDS_BYTES > G4D_LDS_BYTES ? G4dGeom<HALF>::LDS_BYTES : G4D_LDS_BYTES;
+    static DeviceFlags attr;
+    bool* done = attr.current();
+    if (!done || !*done) {
+        hipError_t e = hipFuncSetAttribute((const void*)gemm4d_tn_kernel<T, ACT_NONE, false, EPI, HALF, OT>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        if (e != hipSuccess) return e;
+        if (done) *done = true;
+    }
+    constexpr int BM = HALF ? 128 : G256_BM;
+    const int tiles_m = (g.M - g.row0 + BM - 1) / BM;
+    const int tiles_n = (g.N + G256_BN - 1) / G256_BN;
+    if (tiles_m <= 0 || tiles_n <= 0) return hipSuccess;
+    hipLaunchKernelGGL((gemm4d_tn_kernel<T, ACT_NONE, false, EPI, HALF, OT>), dim3(tiles_m * tiles_n), dim3(256), lds, stream, g);
+    return hipGetLastError();
+}
+
+template <typename T, bool HALF>
+inline hipError_t launch_gemm4d_dst_mode(const GemmArgs<T>& g, hipStream_t stream, int mode) {
+    const int dt = g.epi.dst_dtype;
+    if (mode == G4D_EPI_F32_SCALE_FOLD) {
+        if (dt == 1) return launch_gemm4d_dst_inst<T, G4D_EPI_F32_SCALE_FOLD, f16_t, HALF>(g, stream);
+        if (dt == 2) return launch_gemm4d_dst_inst<T, G4D_EPI_F32_SCALE_FOLD, bf16_t, HALF>(g, stream);
+        return launch_gemm4d_dst_inst<T, G4D_EPI_F32_SCALE_FOLD, float, HALF>(g, stream);
+    }
+    if (dt == 1) return launch_gemm4d_dst_inst<T, G4D_EPI_F32_SCALE, f16_t, HALF>(g, stream);
+    if (dt == 2) return launch_gemm4d_dst_inst<T, G4D_EPI_F32_SCALE, bf16_t, HALF>(g, stream);
+    return launch_gemm4d_dst_inst<T, G4D_EPI_F32_SCALE, float, HALF>(g, stream);
+}
+
+// The epilogue a destination launch gets: F32_SCALE / F32_SCALE_FOLD as gemm4d_epi_mode picks them for the same launch with an
+// fp32 output, with the destination's own alignment (four values per store); -1 = no destination instantiation (the caller stages
+// the fp32 rows and converts them: zett_hip.hip Runner::gemm)
+template <typename T>
+inline int gemm4d_dst_mode(const GemmArgs<T>& g) {
+    const GemmEpilogue<T>& e = g.epi;
+    if (!e.dst || e.dst_dtype < 0 || e.dst_dtype > 2 || e.ld_dst % 4 != 0) return -1;
+    const size_t align = e.dst_dtype == 0 ? 16 : 8;
+    if ((uintptr_t)e.dst % align) return -1;
+    GemmArgs<T> f = g;
+    f.epi.out_f32 = (float*)e.dst;          // (what the selection looks at: an fp32 output with 16-byte rows)
+    f.epi.ld_f32 = 4;
+    const int mode = gemm4d_epi_mode(f);
+    return (mode == G4D_EPI_F32_SCALE || mode == G4D_EPI_F32_SCALE_FOLD) ? mode : -1;
+}
+
 hipError_t launch_gemm_4d_half(const GemmArgs<f16_t>& g, hipStream_t stream, int mode);
 hipError_t launch_gemm_4d_half(const GemmArgs<bf16_t>& g, hipStream_t stream, int mode);
 
+hipError_t launch_gemm_4d_half_dst(const GemmArgs<f16_t>& g, hipStream_t stream, int mode);
+hipError_t launch_gemm_4d_half_dst(const GemmArgs<bf16_t>& g, hipStream_t stream, int mode);
+
 template <typename T>
 inline hipError_t launch_gemm4d(const GemmArgs<T>& g, hipStream_t stream, bool force_generic = false) {
-    const int mode = (force_generic && !g.epi.stats_part && !g.epi.fold_stats) ? G4D_EPI_GENERIC : gemm4d_epi_mode(g);
-    if (mode < 0) return hipErrorInvalidValue;       // a LayerNorm-fold launch whose outputs no instantiation carries
+    const bool dst = g.epi.dst != nullptr;
+    const int mode = dst ? gemm4d_dst_mode(g) : (force_generic && !g.epi.stats_part && !g.epi.fold_stats) ? G4D_EPI_GENERIC : gemm4d_epi_mode(g);
+    if (mode < 0) return hipErrorInvalidValue;       // a LayerNorm-fold launch whose outputs no instantiation carries (or a destination none takes)
     // g.row0 on entry: -1 = let the launcher cut the launch (gemm4d_row_split), 0 = full tiles only, > 0 = the caller's cut (a multiple
     // of 256), -2 = half tiles only (tests and A/Bs)
     int split = g.row0 == -1 ? gemm4d_row_split(g.M, g.N) : (g.row0 == -2 ? 0 : (g.row0 > 0 ? std::min(g.row0, g.M) : g.M));
@@ -918,12 +1001,13 @@ inline hipError_t launch_gemm4d(const GemmArgs<T>& g, hipStream_t stream, bool f
     if (split < g.M) {
         full.M = split;
         if (split > 0)
-            if (hipError_t e = launch_gemm4d_mode<T, false>(full, stream, mode); e != hipSuccess) return e;
+            if (hipError_t e = dst ? launch_gemm4d_dst_mode<T, false>(full, stream, mode) : launch_gemm4d_mode<T, false>(full, stream, mode); e != hipSuccess) return e;
         GemmArgs<T> rest = g;
         rest.row0 = split;
-        return launch_gemm_4d_half(rest, stream, mode);          // (the HALF instantiations live in their own translation units: gemm4dh_<type>.hip)
+        // (the HALF instantiations live in their own translation units: gemm4dh_<type>.hip)
+        return dst ? launch_gemm_4d_half_dst(rest, stream, mode) : launch_gemm_4d_half(rest, stream, mode);
     }
-    return launch_gemm4d_mode<T, false>(full, stream, mode);
+    return dst ? launch_gemm4d_dst_mode<T, false>(full, stream, mode) : launch_gemm4d_mode<T, false>(full, stream, mode);
 }
 
 }  // namespace zett

@@ -12,4 +12,6 @@ hipError_t launch_gemm_4d(const GemmArgs<ZETT_GEMM_T>& g, hipStream_t stream, bo
     return launch_gemm4d<ZETT_GEMM_T>(g, stream, generic_epilogue);
 }
 
+int gemm_4d_dst_mode(const GemmArgs<ZETT_GEMM_T>& g) { return gemm4d_dst_mode<ZETT_GEMM_T>(g); }
+
 }  // namespace zett

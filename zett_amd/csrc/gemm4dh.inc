@@ -12,4 +12,8 @@ hipError_t launch_gemm_4d_half(const GemmArgs<ZETT_GEMM_T>& g, hipStream_t strea
     return launch_gemm4d_mode<ZETT_GEMM_T, true>(g, stream, mode);
 }
 
+hipError_t launch_gemm_4d_half_dst(const GemmArgs<ZETT_GEMM_T>& g, hipStream_t stream, int mode) {
+    return launch_gemm4d_dst_mode<ZETT_GEMM_T, true>(g, stream, mode);
+}
+
 }  // namespace zett

@@ -24,5 +24,10 @@ hipError_t launch_gemm_x(int variant, const GemmArgs<bf16_t>& g, hipStream_t str
 hipError_t launch_gemm_x(int variant, const GemmArgs<float>& g, hipStream_t stream);
 hipError_t launch_gemm_4d(const GemmArgs<f16_t>& g, hipStream_t stream, bool generic_epilogue);
 hipError_t launch_gemm_4d(const GemmArgs<bf16_t>& g, hipStream_t stream, bool generic_epilogue);
+// (zett_forward_into) >= 0 when a gemm4d launch (variant 7) of these arguments stores into g.epi.dst itself: the output heads'
+// F32_SCALE / F32_SCALE_FOLD epilogues with an aligned destination; -1 = the caller stages fp32 rows and converts them
+int gemm_4d_dst_mode(const GemmArgs<f16_t>& g);
+int gemm_4d_dst_mode(const GemmArgs<bf16_t>& g);
+inline int gemm_4d_dst_mode(const GemmArgs<float>&) { return -1; }
 
 }  // namespace zett

@@ -354,7 +354,24 @@ struct LnReadout {
     const float* bias_b;       // [1]
     float* out_bias;           // [rows] (already offset to the chunk's first row), or null: no readout
     const void* in_lo;         // 16-bit residual stream: the rows come from here ([rows, ld_in] of the launch's operand type) instead of `in`
+    // (zett_forward_into: the instantiations with a destination type BT) the bias of row r goes to element bias_rows[r] (< 0: not written; null:
+    // r) of out_bias, which then points at the caller's destination of the kernel's destination type
+    const int64_t* bias_rows;
+    int32_t* range_flag;       // ZETT_RANGE_DEST: a finite bias that became inf in an f16 destination
 };
+
+// The bias of row r: today's fp32 store (BT = void), or the destination store of zett_forward_into (BT = float / f16_t / bf16_t:
+// the same fp32 value rounded to nearest even)
+template <typename BT> __device__ __forceinline__ void ln_readout_store(const LnReadout& ro, int r, float v) {
+    if constexpr (std::is_void<BT>::value) {
+        ro.out_bias[r] = v;
+    } else {
+        const int64_t d = ro.bias_rows ? ro.bias_rows[r] : (int64_t)r;
+        if (d < 0) return;
+        ((BT*)ro.out_bias)[d] = to_lo<BT>(v);
+        range_report(ro.range_flag, dest_overflow<BT>(v), ZETT_RANGE_BIT_DEST);
+    }
+}
 
 constexpr int LN_MAX_VEC = 8;   // 8 float4 x 256 threads = 8192 columns in registers
 
@@ -367,7 +384,7 @@ constexpr int LN_MAX_VEC = 8;   // 8 float4 x 256 threads = 8192 columns in regi
 // sum_out (embed variant) = the pre-LayerNorm sum itself, which those consumers then read.
 // The embed variant takes packed position tok0 + r and writes buffer row chunk_row(...) (position 0 first).
 // READOUT: the instantiation that also carries the bias head (LnReadout); the others ignore the argument.
-template <typename T, bool EMBED, int TPR = 256, bool READOUT = false>
+template <typename T, bool EMBED, int TPR = 256, bool READOUT = false, typename BT = void>
 __global__ __launch_bounds__(256) void layernorm_rows_kernel(const float* __restrict__ in, int ld_in, int rows, int H,
                                                              const float* __restrict__ gamma,
                                                              const float* __restrict__ beta, float eps,
@@ -485,7 +502,7 @@ __global__ __launch_bounds__(256) void layernorm_rows_kernel(const float* __rest
     if constexpr (READOUT) {
         if (readout.out_bias) {            // (uniform over the launch: every thread of the row takes the reduction)
             const float tot = row_sum(dot);
-            if (tid == 0) readout.out_bias[r] = readout.bias_w ? tot + readout.bias_b[0] : 0.f;
+            if (tid == 0) ln_readout_store<BT>(readout, r, readout.bias_w ? tot + readout.bias_b[0] : 0.f);
         }
     }
 }
@@ -547,7 +564,7 @@ inline int ln_rows8_tpr(int H) {
     return 0;
 }
 
-template <typename T, bool EMBED, int TPR, bool READOUT>
+template <typename T, bool EMBED, int TPR, bool READOUT, typename BT = void>
 __global__ __launch_bounds__(256) void layernorm_rows8_kernel(const float* __restrict__ in, int ld_in, int rows, int H,
                                                               const float* __restrict__ gamma,
                                                               const float* __restrict__ beta, float eps,
@@ -660,7 +677,7 @@ __global__ __launch_bounds__(256) void layernorm_rows8_kernel(const float* __res
     if constexpr (READOUT) {
         if (readout.out_bias) {
             const float tot = group_sum<TPR>(dot);
-            if (tid == 0) readout.out_bias[r] = readout.bias_w ? tot + readout.bias_b[0] : 0.f;
+            if (tid == 0) ln_readout_store<BT>(readout, r, readout.bias_w ? tot + readout.bias_b[0] : 0.f);
         }
     }
 }
@@ -968,6 +985,48 @@ __global__ void convert_to_f32_kernel(const void* __restrict__ in, float* __rest
         if constexpr (SRC_DTYPE == 1) out[i] = (float)((const _Float16*)in)[i];
         else out[i] = __uint_as_float(((uint32_t)((const uint16_t*)in)[i]) << 16);
     }
+}
+
+// ---- zett_forward_into: the destination stores that are not fused into a GEMM epilogue ------------------------------------
+// Four fp32 values converted to OT (round to nearest even) in one store: 16 bytes for fp32, 8 for a 16-bit type.
+template <typename OT> __device__ __forceinline__ void store4_dst(OT* d, float4 v) {
+    if constexpr (std::is_same<OT, float>::value) *(float4*)d = v;
+    else *(uint2*)d = make_uint2(pack2_lo<OT>(v.x, v.y), pack2_lo<OT>(v.z, v.w));
+}
+
+// The fallback of the destination store (include/zett_hip.h zett_forward_into): fp32 rows staged in the workspace (src, ld_src)
+// go to row rows[i] (< 0: skipped; null: i) of the destination, converted to OT.  One workgroup per row; VEC: four values per lane
+// and store (cols and both leading dimensions multiples of 4, 16-byte aligned bases), else one.
+template <typename OT, bool VEC>
+__global__ __launch_bounds__(256) void dest_store_rows_kernel(const float* __restrict__ src, int64_t ld_src, OT* __restrict__ dst, int64_t ld_dst,
+                                                              const int64_t* __restrict__ rows, int64_t n_rows, int cols, int32_t* range_flag) {
+    bool bad = false;
+    for (int64_t i = blockIdx.x; i < n_rows; i += gridDim.x) {
+        const int64_t d = rows ? rows[i] : i;
+        if (d < 0) continue;
+        const float* s = src + i * ld_src;
+        OT* o = dst + d * ld_dst;
+        if constexpr (VEC) {
+            for (int c = (int)threadIdx.x * 4; c < cols; c += 256 * 4) {
+                const float4 v = *(const float4*)(s + c);
+                store4_dst<OT>(o + c, v);
+                bad |= dest_overflow<OT>(v.x) | dest_overflow<OT>(v.y) | dest_overflow<OT>(v.z) | dest_overflow<OT>(v.w);
+            }
+        } else {
+            for (int c = (int)threadIdx.x; c < cols; c += 256) {
+                const float v = s[c];
+                o[c] = to_lo<OT>(v);
+                bad |= dest_overflow<OT>(v);
+            }
+        }
+    }
+    range_report(range_flag, bad, ZETT_RANGE_BIT_DEST);
+}
+
+// The row map of a destination against its size: err = 1 + (an index i with rows[i] >= n_dest), 0 when every row fits
+__global__ void dest_rows_check_kernel(const int64_t* __restrict__ rows, int64_t n, int64_t n_dest, int32_t* err) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n && rows[i] >= n_dest) atomicMax(err, (int)(i < 0x7ffffffe ? i + 1 : 0x7fffffff));
 }
 
 }  // namespace zett

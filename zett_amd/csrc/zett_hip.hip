@@ -123,6 +123,12 @@ struct zett_hypernet {
                                       // that runs several asynchronous forwards and asks once at the end: zett_amd/sharding.py)
     int32_t* range_word = nullptr;    // device: zett_range_bits of the forward in flight (cleared when a forward starts)
     int32_t* range_host = nullptr;    // pinned: where zett_check_range / zett_finalize read it
+    // (zett_forward_into) the row map's check against the destination (read with the plan's error word), and the fp32 rows of the head
+    // launches that take the staged fallback of the destination store (Runner::head_gemm)
+    // (dest_stage[1]: lane 1 of a "concurrent_lanes" pair — the two lanes' staged heads run at the same time)
+    DevBuf dest_word, dest_stage[2], dest_sink;
+    int32_t* dest_host = nullptr;
+    hipEvent_t dest_checked = nullptr;
     std::vector<hipEvent_t> ev;
     size_t ev_used = 0;
     std::vector<double> ev_flops;
@@ -350,7 +356,7 @@ static int enqueue_plan(zett_hypernet* h, zett_hypernet::PlanSlot& s, const int3
 }
 
 template <typename T>
-int do_forward(zett_hypernet* h, const int32_t* sfm, int64_t N, int seq, const void* src, int src_dtype,
+int do_forward(zett_hypernet* h, const int32_t* sfm, int64_t N, int seq, const void* src, int src_dtype, const zett_dest* dest,
                int64_t v_src, int lang_index, float* out_in, float* out_out, float* out_bias, hipStream_t st);
 template <typename T>
 int do_table_rows(zett_hypernet* h, const int32_t* id_list, int first, int count, const void* src, int src_dtype, void* table_out, float* stats_out, hipStream_t st);
@@ -394,7 +400,7 @@ int zett_destroy(zett_hypernet* h) {
         if (kv.second.lo && kv.second.lo != (void*)kv.second.f32) (void)hipFree(kv.second.lo);
     }
     for (void* p : h->owned) (void)hipFree(p);
-    for (DevBuf* b : {&h->table, &h->x0, &h->yf, &h->yt, &h->big, &h->pre, &h->ctx, &h->cf, &h->ct, &h->lnstats, &h->lnparts})
+    for (DevBuf* b : {&h->table, &h->x0, &h->yf, &h->yt, &h->big, &h->pre, &h->ctx, &h->cf, &h->ct, &h->lnstats, &h->lnparts, &h->dest_word, &h->dest_stage[0], &h->dest_stage[1], &h->dest_sink})
         b->release();
     for (zett_hypernet::PlanSlot* psp : {&h->plan[0], &h->plan[1], &h->table_plan}) {
         zett_hypernet::PlanSlot& ps = *psp;
@@ -407,6 +413,8 @@ int zett_destroy(zett_hypernet* h) {
     if (h->plan_fork) (void)hipEventDestroy(h->plan_fork);
     if (h->range_word) (void)hipFree(h->range_word);
     if (h->range_host) (void)hipHostFree(h->range_host);
+    if (h->dest_host) (void)hipHostFree(h->dest_host);
+    if (h->dest_checked) (void)hipEventDestroy(h->dest_checked);
     for (hipEvent_t e : h->out_ready) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : h->lane_ev) if (e) (void)hipEventDestroy(e);
     if (h->lane_stream) (void)hipStreamDestroy(h->lane_stream);
@@ -676,10 +684,11 @@ int zett_check_range(zett_hypernet* h, void* stream, int32_t* flags) {
     if (h->range_accumulate && w) HIP_TRY(hipMemsetAsync(h->range_word, 0, 4, st));
     if (flags) *flags = w;
     if (!w) return 0;
-    return fail(ZETT_E_RANGE, "the last forward left the range of its arithmetic:%s%s%s (precision %s)",
+    return fail(ZETT_E_RANGE, "the last forward left the range of its arithmetic:%s%s%s%s (precision %s)",
                 (w & ZETT_RANGE_SOURCE) ? " in_scaler(source_embeddings) beyond the half range;" : "",
                 (w & ZETT_RANGE_ACTIVATION) ? " a 16-bit activation (Q/K/V, FFN intermediate or the operand copy of the residual sum) beyond the half range;" : "",
                 (w & ZETT_RANGE_OUTPUT) ? " non-finite predicted embeddings;" : "",
+                (w & ZETT_RANGE_DEST) ? " a finite value beyond the range of an f16 destination (stored as inf);" : "",
                 h->precision == ZETT_PREC_F16 ? "f16: re-run with ZETT_PREC_BF16" : h->precision == ZETT_PREC_BF16 ? "bf16" : "f32");
 }
 
@@ -769,9 +778,29 @@ int zett_forward_prepare(zett_hypernet* h, const int32_t* surface_forms, int64_t
     return 0;
 }
 
-int zett_forward(zett_hypernet* h, const int32_t* surface_forms, int64_t n_rows, int32_t seq,
-                 const void* source_embeddings, int src_dtype, int64_t v_src, int32_t lang_index,
-                 float* out_in, float* out_out, float* out_bias, void* stream) {
+}  // extern "C"
+
+namespace {
+
+// (zett_forward_into) the destination's own arguments; the row map is checked against n_dest_rows on the device (do_forward)
+int check_dest(const zett_hypernet* h, const zett_dest* d, int64_t n_rows) {
+    const zett_config& c = h->cfg;
+    if (!d) return fail(ZETT_E_INVALID, "null destination");
+    if (!d->in) return fail(ZETT_E_INVALID, "the destination's `in` matrix is null");
+    if (c.separate_out != (d->out != nullptr))
+        return fail(ZETT_E_INVALID, c.separate_out ? "the destination's `out` matrix is required when separate_out_embeddings is set"
+                                                   : "the destination's `out` must be null: this config has no second output");
+    if (d->dtype < ZETT_F32 || d->dtype > ZETT_BF16) return fail(ZETT_E_INVALID, "unknown destination dtype %d", d->dtype);
+    if (d->bias && (d->bias_dtype < ZETT_F32 || d->bias_dtype > ZETT_BF16)) return fail(ZETT_E_INVALID, "unknown bias destination dtype %d", d->bias_dtype);
+    if (d->ld_in < c.n_embd || (d->out && d->ld_out < c.n_embd))
+        return fail(ZETT_E_INVALID, "destination leading dimension (%lld, %lld) below n_embd %d", (long long)d->ld_in, (long long)d->ld_out, c.n_embd);
+    if (d->n_dest_rows < 0 || (!d->rows && d->n_dest_rows < n_rows))
+        return fail(ZETT_E_INVALID, "the destination has %lld rows, the identity map needs %lld", (long long)d->n_dest_rows, (long long)n_rows);
+    return 0;
+}
+
+int forward_entry(zett_hypernet* h, const int32_t* surface_forms, int64_t n_rows, int32_t seq, const void* source_embeddings, int src_dtype,
+                  int64_t v_src, int32_t lang_index, const zett_dest* dest, float* out_in, float* out_out, float* out_bias, void* stream) {
     if (!h) return fail(ZETT_E_INVALID, "null handle");
     if (!h->finalized) return fail(ZETT_E_STATE, "zett_finalize has not been called");
     const zett_config& c = h->cfg;
@@ -788,9 +817,9 @@ int zett_forward(zett_hypernet* h, const int32_t* surface_forms, int64_t n_rows,
         h->out_recorded = true;
         return 0;
     }
-    if (!surface_forms || !source_embeddings || !out_in || !out_bias) return fail(ZETT_E_INVALID, "null tensor argument");
+    if (!surface_forms || !source_embeddings || (!dest && (!out_in || !out_bias))) return fail(ZETT_E_INVALID, "null tensor argument");
     const bool has_out = c.separate_out;
-    if (has_out && !out_out) return fail(ZETT_E_INVALID, "out_out is required when separate_out_embeddings is set");
+    if (!dest && has_out && !out_out) return fail(ZETT_E_INVALID, "out_out is required when separate_out_embeddings is set");
     if (src_dtype < ZETT_F32 || src_dtype > ZETT_BF16) return fail(ZETT_E_INVALID, "unknown source dtype %d", src_dtype);
     if (v_src < c.original_vocab_size) return fail(ZETT_E_INDEX, "source_embeddings has %lld rows, config.original_vocab_size is %d", (long long)v_src, c.original_vocab_size);
     if (c.embed_lang && (lang_index < 0 || lang_index >= c.n_langs)) return fail(ZETT_E_INDEX, "lang_index %d outside [0,%d)", lang_index, c.n_langs);
@@ -798,10 +827,27 @@ int zett_forward(zett_hypernet* h, const int32_t* surface_forms, int64_t n_rows,
     ZETT_ON_DEVICE(h->device);
     hipStream_t st = (hipStream_t)stream;
     if (h->precision == ZETT_PREC_F16)
-        return do_forward<f16_t>(h, surface_forms, n_rows, seq, source_embeddings, src_dtype, v_src, lang_index, out_in, out_out, out_bias, st);
+        return do_forward<f16_t>(h, surface_forms, n_rows, seq, source_embeddings, src_dtype, dest, v_src, lang_index, out_in, out_out, out_bias, st);
     if (h->precision == ZETT_PREC_BF16)
-        return do_forward<bf16_t>(h, surface_forms, n_rows, seq, source_embeddings, src_dtype, v_src, lang_index, out_in, out_out, out_bias, st);
-    return do_forward<float>(h, surface_forms, n_rows, seq, source_embeddings, src_dtype, v_src, lang_index, out_in, out_out, out_bias, st);
+        return do_forward<bf16_t>(h, surface_forms, n_rows, seq, source_embeddings, src_dtype, dest, v_src, lang_index, out_in, out_out, out_bias, st);
+    return do_forward<float>(h, surface_forms, n_rows, seq, source_embeddings, src_dtype, dest, v_src, lang_index, out_in, out_out, out_bias, st);
+}
+
+}  // namespace
+
+extern "C" {
+
+int zett_forward(zett_hypernet* h, const int32_t* surface_forms, int64_t n_rows, int32_t seq,
+                 const void* source_embeddings, int src_dtype, int64_t v_src, int32_t lang_index,
+                 float* out_in, float* out_out, float* out_bias, void* stream) {
+    return forward_entry(h, surface_forms, n_rows, seq, source_embeddings, src_dtype, v_src, lang_index, nullptr, out_in, out_out, out_bias, stream);
+}
+
+int zett_forward_into(zett_hypernet* h, const int32_t* surface_forms, int64_t n_rows, int32_t seq, const void* source_embeddings, int src_dtype,
+                      int64_t v_src, int32_t lang_index, const zett_dest* dest, void* stream) {
+    if (!h) return fail(ZETT_E_INVALID, "null handle");
+    if (int rc = check_dest(h, dest, n_rows)) return rc;
+    return forward_entry(h, surface_forms, n_rows, seq, source_embeddings, src_dtype, v_src, lang_index, dest, nullptr, nullptr, nullptr, stream);
 }
 
 // ---- (ABI 8) the hoisted table shared between ranks: SURVEY 8e's optional second exchange ---------------------------------
@@ -851,15 +897,18 @@ int zett_table_rows(zett_hypernet* h, const int32_t* id_list, int64_t first, int
     return fail(ZETT_E_INVALID, "zett_table_rows: the folded 16-bit table exists in the 16-bit modes only");
 }
 
-int zett_forward_table(zett_hypernet* h, const int32_t* surface_forms, int64_t n_rows, int32_t seq, const void* table, const float* table_stats,
-                       const int32_t* id_slot, int32_t lang_index, float* out_in, float* out_out, float* out_bias, void* stream) {
+}  // extern "C"
+
+namespace {
+int forward_table_entry(zett_hypernet* h, const int32_t* surface_forms, int64_t n_rows, int32_t seq, const void* table, const float* table_stats,
+                        const int32_t* id_slot, int32_t lang_index, const zett_dest* dest, float* out_in, float* out_out, float* out_bias, void* stream) {
     if (!h) return fail(ZETT_E_INVALID, "null handle");
     if (!h->finalized) return fail(ZETT_E_STATE, "zett_finalize has not been called");
     const zett_config& c = h->cfg;
     if (n_rows < 1 || seq < 1) return fail(ZETT_E_INVALID, "bad surface-form shape [%lld, %d]", (long long)n_rows, seq);
     if (seq + (c.embed_lang ? 1 : 0) > c.max_positions) return fail(ZETT_E_INDEX, "sequence %d exceeds position_embeddings (%d rows)", seq, c.max_positions);
-    if (!surface_forms || !table || !table_stats || !id_slot || !out_in || !out_bias) return fail(ZETT_E_INVALID, "null tensor argument");
-    if (c.separate_out && !out_out) return fail(ZETT_E_INVALID, "out_out is required when separate_out_embeddings is set");
+    if (!surface_forms || !table || !table_stats || !id_slot || (!dest && (!out_in || !out_bias))) return fail(ZETT_E_INVALID, "null tensor argument");
+    if (!dest && c.separate_out && !out_out) return fail(ZETT_E_INVALID, "out_out is required when separate_out_embeddings is set");
     if (c.embed_lang && (lang_index < 0 || lang_index >= c.n_langs)) return fail(ZETT_E_INDEX, "lang_index %d outside [0,%d)", lang_index, c.n_langs);
     if (n_rows * (int64_t)(seq + 1) >= (int64_t)0x7fffffff) return fail(ZETT_E_INVALID, "too many positions for one call");
     if (h->precision == ZETT_PREC_F32) return fail(ZETT_E_INVALID, "zett_forward_table: the folded 16-bit table exists in the 16-bit modes only");
@@ -868,11 +917,27 @@ int zett_forward_table(zett_hypernet* h, const int32_t* surface_forms, int64_t n
     h->ext.table = table; h->ext.stats = table_stats; h->ext.id_slot = id_slot;
     int rc;
     if (h->precision == ZETT_PREC_F16)
-        rc = do_forward<f16_t>(h, surface_forms, n_rows, seq, nullptr, ZETT_F32, 0, lang_index, out_in, out_out, out_bias, st);
+        rc = do_forward<f16_t>(h, surface_forms, n_rows, seq, nullptr, ZETT_F32, dest, 0, lang_index, out_in, out_out, out_bias, st);
     else
-        rc = do_forward<bf16_t>(h, surface_forms, n_rows, seq, nullptr, ZETT_F32, 0, lang_index, out_in, out_out, out_bias, st);
+        rc = do_forward<bf16_t>(h, surface_forms, n_rows, seq, nullptr, ZETT_F32, dest, 0, lang_index, out_in, out_out, out_bias, st);
     h->ext = zett_hypernet::ExtTable{};
     return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int zett_forward_table(zett_hypernet* h, const int32_t* surface_forms, int64_t n_rows, int32_t seq, const void* table, const float* table_stats,
+                       const int32_t* id_slot, int32_t lang_index, float* out_in, float* out_out, float* out_bias, void* stream) {
+    return forward_table_entry(h, surface_forms, n_rows, seq, table, table_stats, id_slot, lang_index, nullptr, out_in, out_out, out_bias, stream);
+}
+
+int zett_forward_table_into(zett_hypernet* h, const int32_t* surface_forms, int64_t n_rows, int32_t seq, const void* table, const float* table_stats,
+                            const int32_t* id_slot, int32_t lang_index, const zett_dest* dest, void* stream) {
+    if (!h) return fail(ZETT_E_INVALID, "null handle");
+    if (int rc = check_dest(h, dest, n_rows)) return rc;
+    return forward_table_entry(h, surface_forms, n_rows, seq, table, table_stats, id_slot, lang_index, dest, nullptr, nullptr, nullptr, stream);
 }
 
 }  // extern "C"
@@ -898,6 +963,45 @@ struct Runner {
     }
 
     long a_rows_readable = 0;   // rows every A operand buffer can be read for (workspace slack)
+    bool staged_dst = false;    // (zett_forward_into) the launch in flight writes the staged fp32 rows of a destination (gemm log bit 11)
+    int stage_lane = 0;         // (zett_forward_into) which staging buffer head_gemm uses: the lane's own (h->dest_stage[lane])
+
+    // the tile variant a launch takes
+    int variant_for(int M, int N, int K, const GemmEpilogue<T>& e) const {
+    // Tile choice.  Small problems: 128x128.  Otherwise the 256x256 register-staged eight-wave
+    // kernel (gemm8r), unless the 384x256 LDS-DMA tile needs fewer rounds over the 256 CUs (it
+    // runs ~1.7x as long per tile): wave quantisation decides, e.g. M = 5 111 at N = 4096.
+    // The 384-row kernel has no registers to spare for a residual or scale/shift epilogue
+    // (168 per wave: it would spill to scratch, and no kernel with scratch is ever launched)
+    // and does not clamp rows, so A must have
+    // `a_rows_readable` >= tiles*384 rows (every A operand here is a workspace buffer with
+    // that slack) and N must be a multiple of 256.  (The kernels that led to gemm8r and gemm4d
+    // -- four-wave register-staged, eight-wave LDS-DMA, gemm8r on 16x16x32 MFMAs -- live in
+    // tools/experiments/ with tools/gemm_bench on the `experiments` branch.)
+    constexpr bool is_f32 = std::is_same<T, float>::value;
+    int variant = h->gemm_variant;
+    if (variant == 0) {
+        variant = (M > 128 && N > 128) ? 2 : 1;
+        if (variant != 1 && N % 256 == 0 && !e.scale && !e.residual) {
+            const long t256 = (long)((M + 255) / 256) * (N / 256), t384 = (long)((M + 383) / 384) * (N / 256);
+            const double c256 = (double)((t256 + 255) / 256), c384 = 1.7 * (double)((t384 + 255) / 256);
+            if (c384 < c256) variant = 3;
+        }
+    }
+    if (variant == 3 && (N % 256 != 0 || (long)((M + 383) / 384) * 384 > a_rows_readable || e.scale || e.shift || e.residual || e.range_final)) variant = 2;
+    // 16-bit operands, K >= 2048: the four-wave direct-to-LDS tile on 16x16x32 MFMAs (4-8 % ahead of the
+    // register-staged eight-wave kernels on the launches of the benchmark step; identical bits).
+    if (h->gemm_variant == 0 && variant == 2 && !is_f32 && K >= h->gemm4d_min_k) variant = 7;
+    if ((variant == 7 || variant == 8) && is_f32) variant = 2;
+    // the large tiles drain eight columns per lane with 16-byte accesses
+    const bool wide_ok = N % 8 == 0 && (!e.out_lo || e.ld_lo % 8 == 0) && e.ld_f32 % 4 == 0 && (!e.residual || e.ld_res % 4 == 0) &&
+                         (e.split_col >= N || e.split_col % 8 == 0);
+    if (variant != 1 && !wide_ok) variant = 1;
+    if (e.residual && (e.scale || e.shift)) variant = 1;      // the large tiles compile their residual epilogues without the Rescaler
+    if (e.stats_part || e.fold_stats) variant = 7;       // LayerNorm-fold launches exist in gemm4d only (any M)
+        return variant;
+    }
+
 
     void gemm(const T* A, int lda, const T* Wp, int ldw, int M, int N, int K, const GemmEpilogue<T>& e) {
         if (rc || M <= 0) return;
@@ -919,46 +1023,19 @@ struct Runner {
             h->ev_shape.push_back({M, N, K, 0});
             (void)hipEventRecord(e0, st);
         }
-        // Tile choice.  Small problems: 128x128.  Otherwise the 256x256 register-staged eight-wave
-        // kernel (gemm8r), unless the 384x256 LDS-DMA tile needs fewer rounds over the 256 CUs (it
-        // runs ~1.7x as long per tile): wave quantisation decides, e.g. M = 5 111 at N = 4096.
-        // The 384-row kernel has no registers to spare for a residual or scale/shift epilogue
-        // (168 per wave: it would spill to scratch, and no kernel with scratch is ever launched)
-        // and does not clamp rows, so A must have
-        // `a_rows_readable` >= tiles*384 rows (every A operand here is a workspace buffer with
-        // that slack) and N must be a multiple of 256.  (The kernels that led to gemm8r and gemm4d
-        // -- four-wave register-staged, eight-wave LDS-DMA, gemm8r on 16x16x32 MFMAs -- live in
-        // tools/experiments/ with tools/gemm_bench on the `experiments` branch.)
-        constexpr bool is_f32 = std::is_same<T, float>::value;
-        int variant = h->gemm_variant;
-        if (variant == 0) {
-            variant = (M > 128 && N > 128) ? 2 : 1;
-            if (variant != 1 && N % 256 == 0 && !e.scale && !e.residual) {
-                const long t256 = (long)((M + 255) / 256) * (N / 256), t384 = (long)((M + 383) / 384) * (N / 256);
-                const double c256 = (double)((t256 + 255) / 256), c384 = 1.7 * (double)((t384 + 255) / 256);
-                if (c384 < c256) variant = 3;
-            }
-        }
-        if (variant == 3 && (N % 256 != 0 || (long)((M + 383) / 384) * 384 > a_rows_readable || e.scale || e.shift || e.residual || e.range_final)) variant = 2;
-        // 16-bit operands, K >= 2048: the four-wave direct-to-LDS tile on 16x16x32 MFMAs (4-8 % ahead of the
-        // register-staged eight-wave kernels on the launches of the benchmark step; identical bits).
-        if (h->gemm_variant == 0 && variant == 2 && !is_f32 && K >= h->gemm4d_min_k) variant = 7;
-        if ((variant == 7 || variant == 8) && is_f32) variant = 2;
-        // the large tiles drain eight columns per lane with 16-byte accesses
-        const bool wide_ok = N % 8 == 0 && (!e.out_lo || e.ld_lo % 8 == 0) && e.ld_f32 % 4 == 0 && (!e.residual || e.ld_res % 4 == 0) &&
-                             (e.split_col >= N || e.split_col % 8 == 0);
-        if (variant != 1 && !wide_ok) variant = 1;
-        if (e.residual && (e.scale || e.shift)) variant = 1;      // the large tiles compile their residual epilogues without the Rescaler
-        if (e.stats_part || e.fold_stats) variant = 7;       // LayerNorm-fold launches exist in gemm4d only (any M)
+        const int variant = variant_for(M, N, K, e);
         if (h->time_gemm && !h->ev_shape.empty()) h->ev_shape.back()[3] = variant;
         {
             zett_gemm_record r{};
             r.m = M; r.n = N; r.k = K; r.variant = variant;
             r.epilogue = (e.out_lo ? 1 : 0) | ((e.out_f32 || e.out_f32_b) ? 2 : 0) | (e.residual ? 4 : 0) | ((e.scale || e.shift) ? 8 : 0) |
-                         (e.stats_part ? 16 : 0) | (e.fold_stats ? 32 : 0) | (e.residual_lo ? 64 : 0) | (e.act << 8);
+                         (e.stats_part ? 16 : 0) | (e.fold_stats ? 32 : 0) | (e.residual_lo ? 64 : 0) | (e.act << 8) |
+                         (e.dst ? 1024 : 0) | (staged_dst ? 2048 : 0);
             r.flops = fl;
             const double mn = (double)M * (double)N;
+            const double dst_es = e.dst_dtype == ZETT_F32 ? 4.0 : 2.0;
             r.bytes = ((double)M + (double)N) * (double)K * sizeof(T) + (e.out_lo ? mn * sizeof(T) : 0.0) + ((e.out_f32 || e.out_f32_b) ? mn * 4.0 : 0.0) +
+                      (e.dst ? mn * dst_es : 0.0) +
                       (e.residual ? mn * 4.0 : 0.0) + (e.residual_lo ? mn * sizeof(T) : 0.0) + (e.stats_part ? (double)M * (N / 128) * 8.0 : 0.0) + ((e.fold_stats || e.res_stats) ? (double)M * 8.0 : 0.0);
             h->gemm_log.push_back(r);
         }
@@ -969,6 +1046,68 @@ struct Runner {
         h->stats.gemm_launches += 1;
     }
 
+    // (zett_forward_into) one output of a head launch in the caller's matrix: base (already at the chunk's first row for the identity
+    // map), row map (already offset to the chunk; null = identity), leading dimension, zett_dtype
+    struct DestOut { void* p; const int64_t* rows; int64_t ld; int dtype; };
+
+    // An output head's final GEMM (A [M, K] . W [N, K]^T, epilogue e with an fp32 output) storing into `d` (null: e's own fp32 rows, as
+    // zett_forward).  Fused where gemm4d has a destination instantiation for the launch (variant 7, F32_SCALE / F32_SCALE_FOLD); the
+    // other launches write fp32 rows to the workspace and dest_store converts them.  d_b: the columns from `split` on (hn_single_head
+    // with separate outputs: always staged).
+    void head_gemm(const T* A, const T* Wp, int M, int N, int K, const GemmEpilogue<T>& e, const DestOut* d, const DestOut* d_b, int split) {
+        if (rc || M <= 0) return;
+        if (!d) { gemm(A, K, Wp, K, M, N, K, e); return; }
+        GemmEpilogue<T> ed = e;
+        ed.out_f32 = nullptr; ed.out_f32_b = nullptr; ed.ld_f32 = N;
+        ed.dst = d->p; ed.dst_rows = d->rows; ed.ld_dst = d->ld; ed.dst_dtype = d->dtype;
+        const GemmArgs<T> probe{A, K, Wp, K, M, N, K, ed};
+        if (!d_b && variant_for(M, N, K, ed) == 7 && gemm_4d_dst_mode(probe) >= 0) { gemm(A, K, Wp, K, M, N, K, ed); return; }
+        DevBuf& stage_buf = h->dest_stage[stage_lane];
+        if (int r = stage_buf.reserve((size_t)M * (size_t)N * sizeof(float))) { rc = r; return; }
+        float* S = stage_buf.as<float>();
+        GemmEpilogue<T> es = e;
+        es.out_f32 = S; es.ld_f32 = N;
+        if (d_b) es.out_f32_b = S + split;
+        staged_dst = true;
+        gemm(A, K, Wp, K, M, N, K, es);
+        staged_dst = false;
+        dest_store(S, N, *d, M, d_b ? split : N);
+        if (d_b) dest_store(S + split, N, *d_b, M, N - split);
+    }
+
+    // the staged fallback: fp32 rows (S, ld_s) converted into the destination (dest_store_rows_kernel)
+    void dest_store(const float* S, int64_t ld_s, const DestOut& d, int rows, int cols) {
+        if (rc || rows <= 0) return;
+        const bool vec = cols % 4 == 0 && ld_s % 4 == 0 && d.ld % 4 == 0 && (uintptr_t)S % 16 == 0 && (uintptr_t)d.p % (d.dtype == ZETT_F32 ? 16 : 8) == 0;
+        const dim3 grid((unsigned)std::min<int64_t>(rows, 65535 * 16));
+#define ZETT_DEST_STORE(OT) do { if (vec) hipLaunchKernelGGL((dest_store_rows_kernel<OT, true>), grid, dim3(256), 0, st, S, ld_s, (OT*)d.p, d.ld, d.rows, (int64_t)rows, cols, h->range_word); \
+                                 else hipLaunchKernelGGL((dest_store_rows_kernel<OT, false>), grid, dim3(256), 0, st, S, ld_s, (OT*)d.p, d.ld, d.rows, (int64_t)rows, cols, h->range_word); } while (0)
+        if (d.dtype == ZETT_F16) ZETT_DEST_STORE(f16_t);
+        else if (d.dtype == ZETT_BF16) ZETT_DEST_STORE(bf16_t);
+        else ZETT_DEST_STORE(float);
+#undef ZETT_DEST_STORE
+        check("dest_store");
+    }
+
+    // the position-0 readout with the bias stored into the caller's destination of type BT (layernorm_rows{,8}_kernel with a destination type)
+    template <typename BT>
+    void readout_dst(const float* in, int rows, const float* gamma, const float* beta, float eps, float* of, T* ol, const LnReadout& readout) {
+        const int H = h->cfg.hidden;
+        if constexpr (sizeof(T) == 2) {
+            const int tpr8 = h->ln_rows8 ? ln_rows8_tpr(H) : 0;
+            if (tpr8) {
+                const dim3 grid8((rows + 256 / tpr8 - 1) / (256 / tpr8));
+                if (tpr8 == 32) hipLaunchKernelGGL((layernorm_rows8_kernel<T, false, 32, true, BT>), grid8, dim3(256), 0, st, in, H, rows, H, gamma, beta, eps, of, ol, (float*)nullptr, (float*)nullptr, LnEmbed{}, 0, readout);
+                else hipLaunchKernelGGL((layernorm_rows8_kernel<T, false, 64, true, BT>), grid8, dim3(256), 0, st, in, H, rows, H, gamma, beta, eps, of, ol, (float*)nullptr, (float*)nullptr, LnEmbed{}, 0, readout);
+                check("readout");
+                return;
+            }
+        }
+        if (H <= 2048) hipLaunchKernelGGL((layernorm_rows_kernel<T, false, 64, true, BT>), dim3((rows + 3) / 4), dim3(256), 0, st, in, H, rows, H, gamma, beta, eps, of, ol, (float*)nullptr, (float*)nullptr, LnEmbed{}, 0, readout);
+        else hipLaunchKernelGGL((layernorm_rows_kernel<T, false, 256, true, BT>), dim3(rows), dim3(256), 0, st, in, H, rows, H, gamma, beta, eps, of, ol, (float*)nullptr, (float*)nullptr, LnEmbed{}, 0, readout);
+        check("readout");
+    }
+
     void check(const char* what) {
         if (rc) return;
         hipError_t e = hipGetLastError();
@@ -976,9 +1115,15 @@ struct Runner {
     }
 
     void layernorm(const float* in, int rows, const float* gamma, const float* beta, float eps, float* of, T* ol, float* stats = nullptr,
-                   LnReadout readout = LnReadout{}, const T* in_lo = nullptr) {
+                   LnReadout readout = LnReadout{}, const T* in_lo = nullptr, int bias_dtype = -1) {
         if (rc || rows <= 0) return;
         readout.in_lo = in_lo;          // (16-bit residual stream: the rows are read from the 16-bit copy of the sum; READOUT instantiations only)
+        if (bias_dtype >= 0 && readout.out_bias) {          // (zett_forward_into: the bias goes to the caller's destination; no statistics are asked for)
+            if (bias_dtype == ZETT_F16) readout_dst<f16_t>(in, rows, gamma, beta, eps, of, ol, readout);
+            else if (bias_dtype == ZETT_BF16) readout_dst<bf16_t>(in, rows, gamma, beta, eps, of, ol, readout);
+            else readout_dst<float>(in, rows, gamma, beta, eps, of, ol, readout);
+            return;
+        }
         const int H = h->cfg.hidden;
         // (r6) 16-bit modes, narrow rows: eight columns per lane, 32 lanes per row up to H = 1024 (two rows per wave), 64 up to 2048
         if constexpr (sizeof(T) == 2) {
@@ -1101,7 +1246,7 @@ int do_table_rows(zett_hypernet* h, const int32_t* id_list, int first, int count
 }
 
 template <typename T>
-int do_forward(zett_hypernet* h, const int32_t* sfm, int64_t N, int seq, const void* src, int src_dtype,
+int do_forward(zett_hypernet* h, const int32_t* sfm, int64_t N, int seq, const void* src, int src_dtype, const zett_dest* dest,
                int64_t v_src, int lang_index, float* out_in, float* out_out, float* out_bias, hipStream_t st) {
     (void)v_src;
     const zett_config& c = h->cfg;
@@ -1151,11 +1296,29 @@ int do_forward(zett_hypernet* h, const int32_t* sfm, int64_t N, int seq, const v
     if (!h->range_accumulate) HIP_TRY(hipMemsetAsync(h->range_word, 0, 4, st));          // range guard: the word of THIS forward (zett_check_range)
     for (hipEvent_t& e : h->out_ready)
         if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    // (zett_forward_into) the row map against the destination, answered with the plan's error word: on `stream`, behind whatever wrote
+    // the map (with a prepared plan the host therefore waits for `stream` too)
+    const bool dest_check = dest && dest->rows;
+    if (dest_check) {
+        if (int rc = h->dest_word.reserve(4)) return rc;
+        if (!h->dest_host) HIP_TRY(hipHostMalloc((void**)&h->dest_host, 4, hipHostMallocDefault));
+        if (!h->dest_checked) HIP_TRY(hipEventCreateWithFlags(&h->dest_checked, hipEventDisableTiming));
+        HIP_TRY(hipMemsetAsync(h->dest_word.p, 0, 4, st));
+        hipLaunchKernelGGL(dest_rows_check_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, dest->rows, N, dest->n_dest_rows, h->dest_word.as<int32_t>());
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(h->dest_host, h->dest_word.p, 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipEventRecord(h->dest_checked, st));
+    }
     HIP_TRY(hipEventSynchronize(ps.done));
     int32_t* hoff = ps.host;
     if (hoff[N + 2] != 0)
         return fail(ZETT_E_INDEX, "surface-form row %d holds an id outside [0, %d) (original_vocab_size %d + %d fallback rows)",
                     hoff[N + 2] - 1, V, c.original_vocab_size, c.n_extra);
+    if (dest_check) {
+        HIP_TRY(hipEventSynchronize(h->dest_checked));
+        if (h->dest_host[0] != 0)
+            return fail(ZETT_E_INDEX, "destination row map: rows[%d] is outside the destination's %lld rows", h->dest_host[0] - 1, (long long)dest->n_dest_rows);
+    }
     const int64_t Ttot = hoff[N];
     const int D = hoff[N + 1];
     h->stats.packed_tokens = Ttot;
@@ -1245,6 +1408,11 @@ int do_forward(zett_hypernet* h, const int32_t* sfm, int64_t N, int seq, const v
     // does not depend on the chunk it is in.)  ev_mode: 0 = no completion events, 1 = record out_ready on this lane's stream,
     // 2 = lane 1 of a pair (records lane_ev[1..3]), 3 = lane 0 of a pair (out_ready follows lane 1's events).
     struct Lane { hipStream_t st; size_t off; };
+    // (zett_forward_into) a destination matrix as the heads of the chunk starting at vocabulary row r0 see it
+    auto dest_out = [&](void* base, int64_t ld, int64_t r0) {
+        const size_t es = dest->dtype == ZETT_F32 ? 4 : 2;
+        return typename Runner<T>::DestOut{dest->rows ? base : (void*)((char*)base + (size_t)r0 * (size_t)ld * es), dest->rows ? dest->rows + r0 : nullptr, ld, dest->dtype};
+    };
     const size_t ld_parts = MCS;
     auto run_chunk = [&](int64_t r0, int64_t r1, const Lane& lane, int ev_mode) -> int {
         const int rows = (int)(r1 - r0);
@@ -1253,6 +1421,7 @@ int do_forward(zett_hypernet* h, const int32_t* sfm, int64_t N, int seq, const v
         h->stats.chunks += 1;
         hipStream_t st = lane.st;
         R.st = lane.st;
+        R.stage_lane = ev_mode == 2 ? 1 : 0;      // (the staged fallback of the destination store: each lane of a pair has its own buffer)
         R.a_rows_readable = (long)(MCS - lane.off);
         float* const Zf = h->yf.as<float>() + lane.off * H;
         T* const Zt = h->yt.as<T>() + lane.off * H;
@@ -1425,10 +1594,27 @@ int do_forward(zett_hypernet* h, const int32_t* sfm, int64_t N, int seq, const v
         // position-0 readout + bias head (modeling_hypernet.py:231-234, 260-265) = the last LayerNorm, on the first `rows`
         // buffer rows: Cf = fp32 hidden[:,0] (residual of the heads' ProjectorBlocks), Ct its operand copy, bias head fused.
         // (no encoder layer: the embeddings' LayerNorm is simply taken again for those rows)
-        R.layernorm(hs_sum, rows, hs_gamma, hs_beta, c.ln_eps_encoder, Cf, Ct, nullptr,
-                    LnReadout{c.predict_bias ? R.Wf("bias_projection.weight") : (const float*)nullptr,
-                              c.predict_bias ? R.Wf("bias_projection.bias") : (const float*)nullptr, out_bias + r0},
-                    lo_stream ? (const T*)Zt : (const T*)nullptr);
+        // (zett_forward_into: the bias goes to the destination's bias vector — row map offset to the chunk, or the identity from r0 on.
+        //  A destination without one still takes the READOUT instantiation — only it reads the 16-bit residual stream — into a
+        //  workspace vector that nothing reads)
+        float* bias_out = out_bias ? out_bias + r0 : nullptr;
+        const int64_t* bias_rows = nullptr;
+        int bias_dtype = -1;
+        if (dest && dest->bias) {
+            const size_t bes = dest->bias_dtype == ZETT_F32 ? 4 : 2;
+            bias_rows = dest->rows ? dest->rows + r0 : nullptr;
+            bias_out = (float*)((char*)dest->bias + (dest->rows ? 0 : (size_t)r0 * bes));
+            bias_dtype = dest->bias_dtype;
+        } else if (dest) {
+            if (int rc = h->dest_sink.reserve((size_t)N * sizeof(float))) return rc;      // (the whole call: both lanes of a pair share it)
+            bias_out = h->dest_sink.as<float>() + r0;
+        }
+        LnReadout ro{c.predict_bias ? R.Wf("bias_projection.weight") : (const float*)nullptr,
+                     c.predict_bias ? R.Wf("bias_projection.bias") : (const float*)nullptr, bias_out};
+        ro.bias_rows = bias_rows;
+        ro.range_flag = h->range_word;
+        R.layernorm(hs_sum, rows, hs_gamma, hs_beta, c.ln_eps_encoder, Cf, Ct, nullptr, ro,
+                    lo_stream ? (const T*)Zt : (const T*)nullptr, bias_dtype);
         R.check("readout");
         if (!R.rc) {          // out_bias complete (zett_stream_wait_output)
             if (ev_mode == 2) HIP_TRY(hipEventRecord(h->lane_ev[1], st));
@@ -1447,10 +1633,22 @@ int do_forward(zett_hypernet* h, const int32_t* sfm, int64_t N, int seq, const v
             e.scale = c.rescale ? h->head_scale : (fold_heads ? h->head_one : nullptr);
             e.shift = c.rescale ? h->head_shift : (fold_heads ? h->head_zero : nullptr);
             if (fold_heads) { e.fold_stats = STa; e.fold_c = h->fold_head_in.c; }
-            e.out_f32 = out_in + (size_t)r0 * E; e.ld_f32 = E; e.range_final = 1;
+            e.ld_f32 = E; e.range_final = 1;
             const int width = c.single_head ? EIN : E;
-            if (c.single_head && c.separate_out) { e.split_col = E; e.out_f32_b = out_out + (size_t)r0 * E; }
-            R.gemm(CTX, H, fold_heads ? (const T*)h->fold_head_in.w : R.Wlo("output_projection.1.weight"), H, rows, width, H, e);
+            const bool split = c.single_head && c.separate_out;
+            if (!dest) {
+                e.out_f32 = out_in + (size_t)r0 * E;
+                if (split) { e.split_col = E; e.out_f32_b = out_out + (size_t)r0 * E; }
+            } else if (split) {
+                e.split_col = E;
+            }
+            const T* w1 = fold_heads ? (const T*)h->fold_head_in.w : R.Wlo("output_projection.1.weight");
+            if (dest) {
+                const typename Runner<T>::DestOut din = dest_out(dest->in, dest->ld_in, r0), dout = dest_out(dest->out, dest->ld_out, r0);
+                R.head_gemm(CTX, w1, rows, width, H, e, &din, split ? &dout : nullptr, E);
+            } else {
+                R.gemm(CTX, H, w1, H, rows, width, H, e);
+            }
             if (!R.rc) {      // out_in complete: the second head runs behind it
                 if (ev_mode == 2) HIP_TRY(hipEventRecord(h->lane_ev[2], st));
                 if (ev_mode == 3) HIP_TRY(hipStreamWaitEvent(st, h->lane_ev[2], 0));
@@ -1465,8 +1663,15 @@ int do_forward(zett_hypernet* h, const int32_t* sfm, int64_t N, int seq, const v
             e.scale = c.rescale ? R.Wf("out_scaler.w") : (fold_heads ? h->head_one : nullptr);
             e.shift = c.rescale ? R.Wf("out_scaler.b") : (fold_heads ? h->head_zero : nullptr);
             if (fold_heads) { e.fold_stats = STa; e.fold_c = h->fold_head_out.c; }
-            e.out_f32 = out_out + (size_t)r0 * E; e.ld_f32 = E; e.range_final = 1;
-            R.gemm(CTX, H, fold_heads ? (const T*)h->fold_head_out.w : R.Wlo("output_projection_out.1.weight"), H, rows, E, H, e);
+            e.ld_f32 = E; e.range_final = 1;
+            const T* w2 = fold_heads ? (const T*)h->fold_head_out.w : R.Wlo("output_projection_out.1.weight");
+            if (dest) {
+                const typename Runner<T>::DestOut dout = dest_out(dest->out, dest->ld_out, r0);
+                R.head_gemm(CTX, w2, rows, E, H, e, &dout, nullptr, E);
+            } else {
+                e.out_f32 = out_out + (size_t)r0 * E;
+                R.gemm(CTX, H, w2, H, rows, E, H, e);
+            }
         }
         return R.rc;
     };

@@ -186,6 +186,94 @@ class HipEngine:
         _lib.check(rc, "zett_forward")
         return out_in, out_out, out_bias
 
+    # ---- predicted rows straight into the caller's matrices (zett_forward_into / zett_forward_table_into) ----------------------
+    def _dest(self, n: int, out_in: torch.Tensor, out_out: Optional[torch.Tensor], out_bias: Optional[torch.Tensor], rows):
+        """The zett_dest of a call on n rows, after checking the destination tensors; returns (struct, tensors to keep alive)."""
+        d = self.dims
+
+        def matrix(t, what):
+            if not torch.is_tensor(t) or t.dim() != 2:
+                raise ValueError(f"{what} must be a 2-d tensor")
+            if t.device != self.device:
+                raise ValueError(f"{what} must live on {self.device}, got {t.device}")
+            if t.dtype not in _TORCH_TO_ZETT:
+                raise ValueError(f"{what}: dtype {t.dtype} is not one of float32 / float16 / bfloat16")
+            if t.shape[1] != d.n_embd or t.stride(1) != 1:
+                raise ValueError(f"{what} must be [rows, {d.n_embd}] with unit column stride, got shape {tuple(t.shape)} strides {t.stride()}")
+            return t
+
+        out_in = matrix(out_in, "out_in")
+        if d.separate_out:
+            if out_out is None:
+                raise ValueError("out_out is required: this hypernetwork predicts separate output embeddings")
+            out_out = matrix(out_out, "out_out")
+            if out_out.dtype != out_in.dtype or out_out.shape[0] != out_in.shape[0]:
+                raise ValueError("out_out must have out_in's dtype and number of rows")
+        elif out_out is not None:
+            raise ValueError("out_out must be None: this hypernetwork has no separate output embeddings")
+        if out_bias is not None:
+            if not torch.is_tensor(out_bias) or out_bias.dim() != 1 or out_bias.device != self.device or out_bias.dtype not in _TORCH_TO_ZETT:
+                raise ValueError(f"out_bias must be a 1-d float32 / float16 / bfloat16 tensor on {self.device}")
+            if out_bias.stride(0) != 1 or out_bias.shape[0] != out_in.shape[0]:
+                raise ValueError("out_bias must be contiguous with one entry per row of out_in")
+        keep = [out_in, out_out, out_bias]
+        if rows is not None:
+            if not torch.is_tensor(rows) or rows.dtype != torch.int64 or rows.device != self.device or rows.dim() != 1 or rows.shape[0] != n:
+                raise ValueError(f"rows must be an int64 tensor of {n} entries on {self.device}")
+            rows = rows.contiguous()
+            keep.append(rows)
+        st = _lib.ZettDest(in_=out_in.data_ptr(), out=out_out.data_ptr() if out_out is not None else None,
+                           bias=out_bias.data_ptr() if out_bias is not None else None, dtype=_TORCH_TO_ZETT[out_in.dtype],
+                           bias_dtype=_TORCH_TO_ZETT[out_bias.dtype] if out_bias is not None else 0, ld_in=out_in.stride(0),
+                           ld_out=out_out.stride(0) if out_out is not None else 0, rows=rows.data_ptr() if rows is not None else None,
+                           n_dest_rows=out_in.shape[0])
+        return st, keep
+
+    def forward_into(self, surface_forms: torch.Tensor, source_embeddings: torch.Tensor, lang_index: int, out_in: torch.Tensor,
+                     out_out: Optional[torch.Tensor] = None, out_bias: Optional[torch.Tensor] = None, rows: Optional[torch.Tensor] = None) -> None:
+        """zett_forward_into: forward(), with input row i written to row rows[i] (< 0: skipped; None: row i) of out_in / out_out /
+        out_bias in their own dtype (float32: forward()'s bits; float16 / bfloat16: those rounded to nearest even) and row stride.
+        out_bias None: the bias is not written.  Asynchronous as forward(); the range word gains RANGE_DEST when a finite value
+        overflowed a float16 destination."""
+        d = self.dims
+        if surface_forms.dim() != 2:
+            raise ValueError("target_surface_forms must be [n_tokens, surface_maxlen]")
+        if surface_forms.device != self.device or source_embeddings.device != self.device:
+            raise RuntimeError(f"all tensors must be on {self.device}")
+        ids = surface_forms.to(torch.int32).contiguous()
+        src = source_embeddings
+        if src.dtype not in _TORCH_TO_ZETT:
+            src = src.float()
+        src = src.contiguous()
+        if src.dim() != 2 or src.shape[1] != d.n_in_embd:
+            raise ValueError(f"source_embeddings must be [V, {d.n_in_embd}], got {tuple(src.shape)}")
+        n, seq = ids.shape
+        dest, keep = self._dest(n, out_in, out_out, out_bias, rows)
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            rc = self.lib.zett_forward_into(self.handle, C.c_void_p(ids.data_ptr()), n, seq, C.c_void_p(src.data_ptr()), _TORCH_TO_ZETT[src.dtype],
+                                            src.shape[0], int(lang_index), C.byref(dest), C.c_void_p(stream))
+        self._prepared = None
+        _lib.check(rc, "zett_forward_into")
+        del keep
+
+    def forward_table_into(self, surface_forms: torch.Tensor, table: torch.Tensor, stats: torch.Tensor, id_slot: torch.Tensor, lang_index: int,
+                           out_in: torch.Tensor, out_out: Optional[torch.Tensor] = None, out_bias: Optional[torch.Tensor] = None,
+                           rows: Optional[torch.Tensor] = None) -> None:
+        """zett_forward_table_into: forward_table() storing into a destination, as forward_into()."""
+        if surface_forms.dim() != 2 or surface_forms.device != self.device:
+            raise ValueError(f"target_surface_forms must be [n_tokens, surface_maxlen] on {self.device}")
+        ids = surface_forms.to(torch.int32).contiguous()
+        n, seq = ids.shape
+        dest, keep = self._dest(n, out_in, out_out, out_bias, rows)
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            rc = self.lib.zett_forward_table_into(self.handle, C.c_void_p(ids.data_ptr()), n, seq, C.c_void_p(table.data_ptr()), C.c_void_p(stats.data_ptr()),
+                                                  C.c_void_p(id_slot.data_ptr()), int(lang_index), C.byref(dest), C.c_void_p(stream))
+        self._prepared = None
+        _lib.check(rc, "zett_forward_table_into")
+        del keep
+
     # ---- the hoisted table shared between ranks (ABI 8; zett_amd/sharding.py SharedTable) -----------------------------------
     def table_plan(self, surface_forms_all: torch.Tensor):
         """zett_table_plan: the distinct source ids the WHOLE vocabulary's surface-form matrix references, ascending ->
@@ -465,6 +553,62 @@ class ZettHypernet(PreTrainedModel):
         eng = self.engine(device)
         self._last_engine = eng
         return eng.forward(surface_forms, source_embeddings, lang)
+
+    def predict_into(self, target_surface_forms, source_embeddings, lang_index=None, *, out_in, out_out=None, out_bias=None, rows=None) -> None:
+        """Predict the embeddings of `target_surface_forms` straight into the caller's matrices (HipEngine.forward_into): input row i
+        goes to row rows[i] (None: row i; < 0: skipped) of out_in / out_out / out_bias, in their dtype and row stride — e.g. the bf16
+        `weight` of a resized nn.Embedding, with rows = the new token ids (vocabulary extension).  `rows` may be a list,
+        a numpy array or a tensor.  The values are those of __call__, rounded to the destination's dtype.  Same precision policy as
+        __call__: in f16 with the range guard on, a SOURCE / ACTIVATION / OUTPUT hit repeats the call in bf16 into the same rows (the
+        model stays on bf16); a float16 destination that overflowed (RANGE_DEST) only warns — bf16 arithmetic would not help."""
+        import warnings
+        if not getattr(self.config, "hn_embed_using_source_embeddings", False):
+            raise NotImplementedError()
+        if source_embeddings is None:
+            raise ValueError("source_embeddings is required")
+        device = source_embeddings.device
+        if device.type != "cuda":
+            raise RuntimeError("zett_amd computes on MI355X only: source_embeddings must live on a cuda (ROCm) device")
+        if not torch.is_tensor(target_surface_forms):
+            target_surface_forms = torch.as_tensor(target_surface_forms)
+        target_surface_forms = target_surface_forms.to(device)
+        if self.dims.embed_lang:
+            if lang_index is None:
+                raise ValueError("this hypernetwork embeds a language id: lang_index is required")
+            lang = int(lang_index.item()) if torch.is_tensor(lang_index) else int(lang_index)
+        else:
+            lang = -1
+        if rows is not None:
+            rows = torch.as_tensor(rows if torch.is_tensor(rows) else list(rows) if not hasattr(rows, "dtype") else rows)
+            rows = rows.to(device=device, dtype=torch.int64).reshape(-1).contiguous()
+
+        def run(precision):
+            eng = self.engine(device, precision)
+            self._last_engine = eng
+            eng.forward_into(target_surface_forms, source_embeddings, lang, out_in, out_out, out_bias, rows)
+            return eng
+
+        def warn_dest(flags):
+            if flags & _lib.RANGE_DEST:
+                warnings.warn("zett_amd: predicted values beyond the float16 range of the destination were stored as inf "
+                              "(a float16 destination cannot hold them; use a bfloat16 or float32 destination)")
+
+        if self.precision in ("f16", "fp16", "float16") and self.range_guard:
+            try:
+                flags = run(self.precision).range_flags()
+            except _lib.RangeError as err:           # zett_finalize: a weight does not fit the half type
+                flags = _lib.RANGE_WEIGHT
+                warnings.warn(f"zett_amd: {err}; continuing with bf16 operands")
+            warn_dest(flags)
+            if not flags & (_lib.RANGE_SOURCE | _lib.RANGE_ACTIVATION | _lib.RANGE_OUTPUT | _lib.RANGE_WEIGHT):
+                return
+            if not flags & _lib.RANGE_WEIGHT:
+                warnings.warn("zett_amd: the f16 forward left the half range; repeating the call with bf16 operands into the same rows. "
+                              "The model stays on bf16.")
+            self.precision = "bf16"
+            warn_dest(run("bf16").range_flags())
+            return
+        run(self.precision)          # (bf16 / f32: asynchronous, as __call__; check_outputs() asks when the caller chooses)
 
     def check_outputs(self) -> int:
         """Range word of the most recent bf16 / f32 forward (waits for the stream): 0, or _lib.RANGE_* bits; warns when the

@@ -79,12 +79,17 @@ def get_sample_indices(n: int, p: np.ndarray, batch_size: int, min_k: int, n_sam
 
 def batched_inference(predict: Predict, target_surface_form_matrix: torch.Tensor, n_embd: int, batch_size: int = 16384,
                       sample_batches: bool = False, target_priors: Optional[np.ndarray] = None, min_k: int = 10,
-                      n_samples: int = 100, rng: Optional[np.random.Generator] = None):
+                      n_samples: int = 100, rng: Optional[np.random.Generator] = None, predict_into: Optional[Callable] = None,
+                      separate_out: bool = False):
     """scripts/transfer.py:54-124 with device-resident accumulation.
 
     Rows are visited in a random permutation, the last batch is padded with row 0, predictions
     are accumulated into fp32 [V, E] matrices (and averaged by visit count when batches are
     sampled).  Rows are independent, so the result does not depend on the batching.
+
+    `predict_into(rows, index, out_in, out_out, out_bias)` (the direct path; without --sample_batches): every batch writes its
+    rows straight into the [V, E] fp32 results, row i of the batch to row index[i] (-1: the padded tail, not written) — every
+    row is written exactly once, so there is no zero fill, no index_add_ and no counts.  `separate_out`: allocate out_out.
     """
     rng = rng or np.random.default_rng()
     sfm = target_surface_form_matrix
@@ -99,6 +104,18 @@ def batched_inference(predict: Predict, target_surface_form_matrix: torch.Tensor
         padded = np.pad(rng.permutation(n), (0, total - n))
         batches = np.array_split(padded, total // batch_size)
         empty_in_last = total - n
+    if predict_into is not None and not sample_batches:
+        res_in = torch.empty((n, n_embd), dtype=torch.float32, device=device)
+        res_out = torch.empty((n, n_embd), dtype=torch.float32, device=device) if separate_out else None
+        res_bias = torch.empty((n,), dtype=torch.float32, device=device)
+        for bi, idx in enumerate(batches):
+            idx = np.asarray(idx, dtype=np.int64)
+            dest = idx.copy()
+            if bi == len(batches) - 1 and empty_in_last > 0:
+                dest[len(idx) - empty_in_last:] = -1
+            index = torch.from_numpy(idx).to(device)
+            predict_into(sfm.index_select(0, index), torch.from_numpy(dest).to(device), res_in, res_out, res_bias)
+        return res_in, res_out, res_bias
     acc_in = torch.zeros((n, n_embd), dtype=torch.float32, device=device)
     acc_out = None
     acc_bias = torch.zeros((n,), dtype=torch.float32, device=device)
@@ -163,6 +180,12 @@ def predict_vocabulary(hypernet, target_surface_form_matrix: torch.Tensor, sourc
         return n_batches >= 2 or (_world_size() > 1 and os.environ.get("ZETT_SHARED_TABLE") == "1")
 
     sharded = hasattr(hypernet, "engine") and (_world_size() > 1 or want_table(getattr(hypernet, "precision", None)))
+    # The direct path (one process, no --sample_batches): every batch stores its rows straight into the [V, E] fp32 results
+    # (zett_forward_into with the batch's vocabulary indices as the row map) instead of zero-filled accumulators and index_add_.
+    # Same bits, up to the sign of zero (index_add_ into zeros turns -0.0 into +0.0).  ZETT_DIRECT_OUT=0: the accumulating path.
+    direct = (hasattr(hypernet, "engine") and hasattr(hypernet, "predict_into") and not args.sample_batches and _world_size() == 1
+              and os.environ.get("ZETT_DIRECT_OUT", "1") != "0")
+    predict_vocabulary.last_direct = bool(direct and args.do_batching)      # (what the last call did: tests, logs)
     if _world_size() > 1 and not sharded:              # (a stand-in model without an engine: plain sharding)
         from zett_amd.sharding import predict_sharded
 
@@ -208,13 +231,21 @@ def predict_vocabulary(hypernet, target_surface_form_matrix: torch.Tensor, sourc
                 r32 = rows.to(device=device, dtype=torch.int32).contiguous()        # what the C ABI takes: prepare() and forward() see one pointer
                 return predict_sharded(fwd, r32, ready=eng.stream_wait_output, prepare=None if shared is not None else eng.prepare)
 
+            def predict_rows_into(rows, index, out_in, out_out, out_bias):          # (the direct path: one process)
+                r32 = rows.to(device=device, dtype=torch.int32).contiguous()
+                if shared is not None:
+                    eng.forward_table_into(r32, shared.table, shared.stats, shared.id_slot, lang, out_in, out_out, out_bias, index)
+                else:
+                    eng.forward_into(r32, source_embeddings, lang, out_in, out_out, out_bias, index)
+
             if not args.do_batching:
                 out = predict_rows(target_surface_form_matrix)
             else:
                 gen = np.random.default_rng()
                 gen.bit_generator.state = state["rng_state"]        # the same batch order on a repeat
                 out = batched_inference(predict_rows, target_surface_form_matrix, hypernet.config.n_embd, args.batch_size,
-                                        args.sample_batches, target_priors, args.min_k, args.n_samples, gen)
+                                        args.sample_batches, target_priors, args.min_k, args.n_samples, gen,
+                                        predict_into=predict_rows_into if direct else None, separate_out=hypernet.dims.separate_out)
             flags = reduce_flag_word(eng.range_flags(), device) if _world_size() > 1 else eng.range_flags()
             eng.set_option("range_accumulate", 0)
             return out, flags
@@ -234,8 +265,12 @@ def predict_vocabulary(hypernet, target_surface_form_matrix: torch.Tensor, sourc
     if not args.do_batching:   # scripts/transfer.py:243-262 pads to a multiple of 128 for XLA; no need here
         out = predict(target_surface_form_matrix)
     else:
+        def predict_into(rows, index, out_in, out_out, out_bias):
+            hypernet.predict_into(rows, source_embeddings, lang_index, out_in=out_in, out_out=out_out, out_bias=out_bias, rows=index)
+
         out = batched_inference(predict, target_surface_form_matrix, hypernet.config.n_embd, args.batch_size, args.sample_batches,
-                                target_priors, args.min_k, args.n_samples, rng)
+                                target_priors, args.min_k, args.n_samples, rng, predict_into=predict_into if direct else None,
+                                separate_out=bool(direct and hypernet.dims.separate_out))
     # bf16 / f32 forwards are asynchronous and unguarded (ZettHypernet._guarded_forward): ask once, here, whether the last
     # forward's outputs were finite (warns; the f16 path has asked after every call)
     if hasattr(hypernet, "check_outputs"):
