@@ -32,7 +32,8 @@ extern "C" {
                                    6: zett_retokenize_async takes NUL-separated text (offsets == NULL); options gemm_tail_split;
                                    7: zett_retok_set_option;
                                    8: zett_table_plan, zett_table_rows, zett_forward_table (the hoisted table shared between ranks);
-                                      additive, ABI 8: zett_forward_into, zett_forward_table_into, struct zett_dest, ZETT_RANGE_DEST */
+                                      additive, ABI 8: zett_forward_into, zett_forward_table_into, struct zett_dest, ZETT_RANGE_DEST;
+                                      additive, ABI 8: zett_lexical_create / _destroy / _plan / _rows_into, enum zett_lexical_mode */
 
 enum zett_status {
     ZETT_OK = 0,
@@ -113,6 +114,7 @@ typedef struct zett_stats {
 
 typedef struct zett_hypernet zett_hypernet;
 typedef struct zett_retok zett_retok;
+typedef struct zett_lexical zett_lexical;
 
 const char* zett_last_error(void);
 int zett_abi_version(void);
@@ -416,6 +418,58 @@ int zett_retokenize(zett_retok* r, const uint8_t* token_chars, const int32_t* of
 int zett_retokenize_async(zett_retok* r, const uint8_t* token_chars, const int32_t* offsets, int64_t n_tokens, int64_t n_text,
                           int32_t maxlen, int32_t pad_id, int32_t* out, void* stream);
 int zett_retok_result(zett_retok* r, int64_t* n_truncated, int64_t* bad_call, int64_t* bad_token);
+
+/* ---- lexical (FVT / BFVT) embedding transfer (additive, ABI 8) ------------------------------------------------------------
+ * Replaces: the per-token loop of the reference's lexical baseline (scripts/transfer_lexical.py:50-91): for every target token
+ * the row of the same string in the source vocabulary, else the mean of the source rows of its decomposition under the source
+ * tokenizer's bare model, else a fallback row.  S = the source matrix of R rows (R is the MATRIX's row count, not the
+ * tokenizer's length: the two differ in both directions in practice).
+ *
+ * THE MEAN: add the rows in `ids` order in fp32, then one IEEE (correctly rounded) division by float(n); n = 1 is a plain copy.
+ * Every row of the reference's output with n <= 16 constituents has exactly these bits (torch's CPU mean(0) adds in order up to
+ * there; beyond, its sum cascades in blocks and the reference's bits are another rounding of the same sum). */
+enum zett_lexical_mode { ZETT_LEXICAL_NO = 0, ZETT_LEXICAL_FVT = 1, ZETT_LEXICAL_BFVT = 2 };      /* fvt_mode "no" / "fvt" / "bfvt" */
+
+/* The lexicon of a source tokenizer (transfer_lexical.py:27-34, 65, 77): `model` is its bare model as for zett_retok_create; its
+ * n_special / special_* fields are IGNORED — the decomposition never matches special tokens by string (a special token whose id
+ * is >= R is tokenized by the reference like any other text).  vocab_*: the WHOLE source_tokenizer.get_vocab() dictionary, added
+ * and special tokens included, as raw bytes / offsets [n_vocab + 1] / ids (host arrays, the layout of the pieces; entries with
+ * a character outside the byte table can never equal a byte-level token and must be omitted).  It becomes an exact-match table
+ * on the device (the retokenizer's whole-token table: open addressing, load <= 1/8). */
+int zett_lexical_create(const zett_retok_model* model, int32_t n_vocab, const uint8_t* vocab_bytes, const int32_t* vocab_offsets,
+                        const int32_t* vocab_ids, int device, zett_lexical** out);
+int zett_lexical_destroy(zett_lexical* h);
+
+/* transfer_lexical.py:65-86 without the arithmetic: for each of the n_tokens target tokens (token_chars: NUL-separated byte-level
+ * text of n_text bytes, as zett_retokenize_async with offsets == NULL; boundaries found on the device) what its row is a mean of.
+ *   ids    device int32 [n_tokens, width]; count device int32 [n_tokens]
+ *   exact match (get_vocab().get(t) exists and is < n_source_rows, :65-67): count = 1, ids[i, 0] = that id;
+ *   else, unless fvt_mode is NO, the ids of model.tokenize(t) (:77), filtered against n_source_rows — FVT (:78-81): any id >=
+ *   n_source_rows, or no id at all, gives count = 0; BFVT (:82-86): such ids are removed and the others close up in order;
+ *   count = 0 means "fallback row".  The empty token has count = 0.
+ * count[i] is the TRUE number of ids even when it exceeds `width` (then only the first `width` are stored; ids[i, count[i]:] is
+ * unspecified otherwise): *n_wide receives the number of such rows, which the caller plans again at the width they need, so no
+ * decomposition is ever cut.  *n_overlap = rows with count > 0 (the reference's "Overlapping tokens", :88-91), *n_ids = the
+ * sum of the counts; all three reduced on the device, all nullable.  Waits for `stream`.
+ * A character outside the byte table: ZETT_E_KEY with the token index in *bad_token, as zett_retokenize (the reference would
+ * hand such a string to the model as it is: a deliberate deviation).  A token that needs an unk id the model lacks:
+ * ZETT_E_STATE, where tokenizers raises. */
+int zett_lexical_plan(zett_lexical* h, const uint8_t* token_chars, int64_t n_tokens, int64_t n_text, int64_t n_source_rows, int32_t fvt_mode,
+                      int32_t width, int32_t* ids, int32_t* count, int64_t* n_overlap, int64_t* n_wide, int64_t* n_ids, int64_t* bad_token,
+                      void* stream);
+
+/* transfer_lexical.py:50-63, 67, 81, 86, 93-103 (the arithmetic): destination row dest->rows[i] (< 0: skipped; NULL: i) =
+ * the mean (above) of source rows ids[i, :count[i]]; count[i] == 0: source row fallback_id (fallback_mode "unk": the source
+ * tokenizer's unk_token_id), or with fallback_id == -1 the row is left untouched (fallback_mode "random": the caller has put its
+ * draws there).  The reference's cat([in, out], dim=1) is never materialised: src_in [R, >= ld_src_in] feeds dest->in, src_out
+ * (NULL iff dest->out is NULL: tied embeddings) feeds dest->out, n_embd columns each, src_dtype F32 / F16 / BF16 upcast to fp32 on
+ * load.  Stored as zett_forward_into stores: the fp32 value bit for bit in an fp32 destination, round-to-nearest-even in a 16-bit
+ * one.  dest->bias must be NULL.  Nothing is trusted: every id in use is checked against n_source_rows and every dest->rows[i]
+ * against dest->n_dest_rows on the device through an error word — ZETT_E_INDEX BEFORE anything is written (one host round trip on
+ * `stream`); a count outside [0, width] (a row that was not planned again) is ZETT_E_INVALID.  The stores are asynchronous on `stream`. */
+int zett_lexical_rows_into(zett_lexical* h, const int32_t* ids, const int32_t* count, int64_t n_tokens, int32_t width, const void* src_in,
+                           int64_t ld_src_in, const void* src_out, int64_t ld_src_out, int32_t src_dtype, int64_t n_source_rows, int32_t n_embd,
+                           int64_t fallback_id, const zett_dest* dest, void* stream);
 
 /* ---- training use of the forward ---------------------------------------------------------
  * Replaces: the hypernetwork forward inside the loss of the reference's train_step / eval_step (train.py:1007-1013,

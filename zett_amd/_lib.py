@@ -18,6 +18,7 @@ DTYPE_F32, DTYPE_F16, DTYPE_BF16 = 0, 1, 2
 PREC_BF16, PREC_F32, PREC_F16 = 0, 1, 2
 RETOK_BPE, RETOK_UNIGRAM, RETOK_WORDPIECE = 0, 1, 2
 OUT_IN, OUT_BIAS = 0, 1              # zett_output
+LEXICAL_NO, LEXICAL_FVT, LEXICAL_BFVT = 0, 1, 2      # zett_lexical_mode
 
 ABI_SYMBOLS = (
     "zett_last_error", "zett_abi_version", "zett_create", "zett_destroy", "zett_load_weight",
@@ -27,6 +28,7 @@ ABI_SYMBOLS = (
     "zett_partition_rows", "zett_partition_workspace_bytes", "zett_scatter_rows",
     "zett_table_plan", "zett_table_rows", "zett_forward_table",
     "zett_forward_into", "zett_forward_table_into",
+    "zett_lexical_create", "zett_lexical_destroy", "zett_lexical_plan", "zett_lexical_rows_into",
     # training primitives (zett_amd/autograd.py)
     "zett_op_gemm_f32", "zett_op_transpose_f32", "zett_op_colsum_f32", "zett_op_elementwise_f32", "zett_op_rowdot_f32",
     "zett_op_layernorm_fwd_f32", "zett_op_layernorm_bwd_f32", "zett_op_gelu_fwd_f32", "zett_op_gelu_bwd_f32",
@@ -130,6 +132,12 @@ def load():
                                           C.POINTER(ZettDest), C.c_void_p]
         lib.zett_forward_table_into.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                                 C.POINTER(ZettDest), C.c_void_p]
+        lib.zett_lexical_create.argtypes = [C.POINTER(ZettRetokModel), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
+        lib.zett_lexical_destroy.argtypes = [C.c_void_p]
+        lib.zett_lexical_plan.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                          C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_void_p]
+        lib.zett_lexical_rows_into.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                               C.c_int32, C.c_int64, C.c_int32, C.c_int64, C.POINTER(ZettDest), C.c_void_p]
         lib.zett_partition_workspace_bytes.argtypes = [C.c_int64, C.c_int32, C.POINTER(C.c_int64)]
         lib.zett_scatter_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p]
         lib.zett_partition_rows.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32),

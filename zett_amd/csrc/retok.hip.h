@@ -354,7 +354,25 @@ struct RowWriter {
     int32_t* row;
     int maxlen;
     int n;
-    __device__ void push(int32_t id) { if (n < maxlen) row[n] = id; ++n; }
+    int32_t drop_from = 0x7fffffff;      // the lexical plan (lexical.hip.h): ids from here on have no source row — counted, not written
+    int dropped = 0;
+    __device__ void push(int32_t id) {
+        if (id >= drop_from) { ++dropped; return; }
+        if (n < maxlen) row[n] = id;
+        ++n;
+    }
+};
+
+// What zett_lexical_plan asks of stage 2 on top of the id rows (counts == nullptr: the plain retokenizer).  The handle's "special"
+// table then holds the source tokenizer's whole dictionary: a whole-token hit with an id below n_rows is an exact match (count 1);
+// every other token is segmented by the bare model (mode 0: not at all) with the ids >= n_rows filtered — mode 1 (fvt): one such
+// id makes the count 0, mode 2 (bfvt): they are dropped and the others close up.  counts[token] is the TRUE number of ids kept,
+// also beyond maxlen.
+struct LexPlan {
+    int32_t* counts;
+    int32_t n_rows;
+    int32_t mode;
+    __device__ int count_of(const RowWriter& w) const { return (mode == 1 && w.dropped) ? 0 : w.n; }
 };
 
 // worst-case words of a token's region of the global scratch buffer (the fallback of the LDS arena)
@@ -639,6 +657,7 @@ __device__ inline bool wordpiece_token(const RetokTables& t, typename M::bytes r
             if (t.unk_id < 0) return false;
             for (int i = n0; i < w.n && i < w.maxlen; ++i) w.row[i] = pad_id;
             w.n = n0;
+            w.dropped = 0;
             w.push(t.unk_id);
             return true;
         }
@@ -670,7 +689,7 @@ __global__ __launch_bounds__(64) void retok_tokens_kernel(RetokTables t, const u
                                                           const int32_t* __restrict__ raw_off, int64_t n_tokens,
                                                           int maxlen, int32_t pad_id, int32_t* __restrict__ out, int32_t* __restrict__ scratch,
                                                           unsigned long long* __restrict__ n_truncated,
-                                                          unsigned long long* __restrict__ err_unk, uint32_t call) {
+                                                          unsigned long long* __restrict__ err_unk, uint32_t call, LexPlan lex) {
     __shared__ RetokLds L;
     __shared__ __attribute__((aligned(16))) uint8_t s_text[RT_TEXT_BYTES + 16];
     __shared__ __attribute__((aligned(8))) int32_t s_arena[RT_ARENA_WORDS];
@@ -693,12 +712,14 @@ __global__ __launch_bounds__(64) void retok_tokens_kernel(RetokTables t, const u
     const lds_u8* sl = (const lds_u8*)s_text + mis + (o0 - w_lo);
     const uint8_t* sg = raw + o0;
     RowWriter w{out + tok * maxlen, maxlen, 0};
-    bool todo = live && len > 0;
+    if (lex.counts && lex.mode) w.drop_from = lex.n_rows;
+    bool todo = live && len > 0, exact = false;
     if (todo && t.special_mask != 0xffffffffu) {              // zett/utils.py:671-673
         const int id = text_lds ? whole_token_id<LdsMem>(t.specials, t.special_mask, t.special_blob, sl, len)
                                 : whole_token_id<GlobalMem>(t.specials, t.special_mask, t.special_blob, sg, len);
-        if (id >= 0) { w.row[0] = id; todo = false; }
+        if (id >= 0 && (!lex.counts || id < lex.n_rows)) { w.row[0] = id; todo = false; exact = true; }
     }
+    if (lex.counts && lex.mode == 0) todo = false;
     if (todo && t.kind == ZETT_RETOK_BPE && t.ignore_merges) {
         const int id = text_lds ? whole_token_id<LdsMem>(t.pieces, t.piece_mask, t.piece_blob, sl, len)
                                 : whole_token_id<GlobalMem>(t.pieces, t.piece_mask, t.piece_blob, sg, len);
@@ -738,6 +759,7 @@ __global__ __launch_bounds__(64) void retok_tokens_kernel(RetokTables t, const u
         }
         if (w.n > maxlen) atomicAdd(n_truncated, 1ull);      // zett/utils.py:683-685
     }
+    if (lex.counts && live) lex.counts[tok] = exact ? 1 : lex.count_of(w);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -764,7 +786,7 @@ __global__ __launch_bounds__(UG_THREADS) void retok_unigram_kernel(RetokTables t
                                                                    const int32_t* __restrict__ raw_off, int64_t n_tokens,
                                                                    int maxlen, int32_t pad_id, int32_t* __restrict__ out, int32_t* __restrict__ scratch,
                                                                    unsigned long long* __restrict__ n_truncated,
-                                                                   unsigned long long* __restrict__ err_unk, uint32_t call) {
+                                                                   unsigned long long* __restrict__ err_unk, uint32_t call, LexPlan lex) {
     __shared__ RetokLds L;
     __shared__ __attribute__((aligned(16))) uint8_t s_text[RT_TEXT_BYTES + 16];
     __shared__ __attribute__((aligned(8))) int32_t s_arena[RT_ARENA_WORDS];
@@ -791,12 +813,15 @@ __global__ __launch_bounds__(UG_THREADS) void retok_unigram_kernel(RetokTables t
     const lds_u8* sl = (const lds_u8*)s_text + mis + (o0 - w_lo);
     const uint8_t* sg = raw + o0;
     RowWriter w{out + (live ? tok : 0) * maxlen, maxlen, 0};
-    bool todo = live && len > 0;
+    if (lex.counts && lex.mode) w.drop_from = lex.n_rows;
+    bool todo = live && len > 0, exact = false;
     if (todo && t.special_mask != 0xffffffffu) {              // zett/utils.py:671-673
         const int id = text_lds ? whole_token_id<LdsMem>(t.specials, t.special_mask, t.special_blob, sl, len)
                                 : whole_token_id<GlobalMem>(t.specials, t.special_mask, t.special_blob, sg, len);
-        if (id >= 0) { w.row[0] = id; todo = false; }
+        if (id >= 0 && (!lex.counts || id < lex.n_rows)) { w.row[0] = id; todo = false; exact = true; }
     }
+    if (lex.counts && lex.mode == 0) todo = false;
+    if (lex.counts && live && !todo) lex.counts[tok] = exact ? 1 : 0;      // (a segmented token's count: finish())
     int need = todo ? ((unigram_state_words(len) + 1) & ~1) : 0;
     const int W_mine = len < t.max_piece_len ? len : t.max_piece_len;
     int slots = (todo && text_lds) ? len * W_mine : 0;
@@ -821,6 +846,7 @@ __global__ __launch_bounds__(UG_THREADS) void retok_unigram_kernel(RetokTables t
         if (!todo) return;
         if (!ok) { atomicMin(err_unk, ((unsigned long long)call << 32) | (uint32_t)(tok < 0x7ffffffe ? tok : 0x7ffffffe)); return; }
         if (w.n > maxlen) atomicAdd(n_truncated, 1ull);       // zett/utils.py:683-685
+        if (lex.counts) lex.counts[tok] = lex.count_of(w);
     };
     if (!text_lds) {          // (uniform) more than 4 KiB of text in 64 tokens: the per-lane code on global memory
         if (todo) {
@@ -1101,8 +1127,9 @@ static int retok_reset_words(zett_retok* r, hipStream_t st) {
     return 0;
 }
 
-int zett_retokenize_async(zett_retok* r, const uint8_t* token_chars, const int32_t* offsets, int64_t n_tokens, int64_t n_text,
-                          int32_t maxlen, int32_t pad_id, int32_t* out, void* stream) {
+// zett_retokenize_async, and with lex.counts set the same call as stage 1 and 2 of zett_lexical_plan (lexical.hip.h)
+static int retok_enqueue_call(zett_retok* r, const uint8_t* token_chars, const int32_t* offsets, int64_t n_tokens, int64_t n_text,
+                              int32_t maxlen, int32_t pad_id, int32_t* out, void* stream, zett::LexPlan lex) {
     using namespace zett;
     if (!r) return fail(ZETT_E_INVALID, "null argument");
     if (n_tokens < 0 || maxlen < 1 || n_text < 0 || n_text >= (int64_t)0x7fffffff) return fail(ZETT_E_INVALID, "bad shape");
@@ -1157,10 +1184,10 @@ int zett_retokenize_async(zett_retok* r, const uint8_t* token_chars, const int32
         // (profiles/r6_retok_ab.jsonl); "unigram_workgroup" 2 / 0 force one of them
         if (r->t.kind == ZETT_RETOK_UNIGRAM && (r->unigram_wg == 2 || (r->unigram_wg == 1 && n_tokens <= 32768)))
             hipLaunchKernelGGL(retok_unigram_kernel, dim3((unsigned)((n_tokens + UG_TOKENS - 1) / UG_TOKENS)), dim3(UG_THREADS), 0, st, r->t, r->raw.as<uint8_t>(),
-                               r->raw_off.as<int32_t>(), n_tokens, maxlen, pad_id, out, r->scratch.as<int32_t>(), words + 2, words + 1, call);
+                               r->raw_off.as<int32_t>(), n_tokens, maxlen, pad_id, out, r->scratch.as<int32_t>(), words + 2, words + 1, call, lex);
         else
             hipLaunchKernelGGL(retok_tokens_kernel, dim3((unsigned)((n_tokens + 63) / 64)), dim3(64), 0, st, r->t, r->raw.as<uint8_t>(),
-                               r->raw_off.as<int32_t>(), n_tokens, maxlen, pad_id, out, r->scratch.as<int32_t>(), words + 2, words + 1, call);
+                               r->raw_off.as<int32_t>(), n_tokens, maxlen, pad_id, out, r->scratch.as<int32_t>(), words + 2, words + 1, call, lex);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(r->host_pinned + 4, words, 24, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipEventRecord(r->done, st));
@@ -1174,6 +1201,11 @@ int zett_retokenize_async(zett_retok* r, const uint8_t* token_chars, const int32
         return rc;
     }
     return 0;
+}
+
+int zett_retokenize_async(zett_retok* r, const uint8_t* token_chars, const int32_t* offsets, int64_t n_tokens, int64_t n_text,
+                          int32_t maxlen, int32_t pad_id, int32_t* out, void* stream) {
+    return retok_enqueue_call(r, token_chars, offsets, n_tokens, n_text, maxlen, pad_id, out, stream, zett::LexPlan{nullptr, 0, 0});
 }
 
 int zett_retok_result(zett_retok* r, int64_t* n_truncated, int64_t* bad_call, int64_t* bad_token) {

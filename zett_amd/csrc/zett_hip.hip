@@ -33,6 +33,7 @@
 #include "gemm_launch.hip.h"
 #include "rowops.hip.h"
 #include "retok.hip.h"
+#include "lexical.hip.h"
 #include "partition.hip.h"
 
 using namespace zett;
