@@ -549,6 +549,53 @@ int zett_op_gather_fwd_f32(const int32_t* ids, int64_t n_tokens, const void* src
 int zett_op_gather_bwd_f32(const int32_t* ids, int64_t n_tokens, const void* src, int32_t src_dtype, int32_t e_in, int32_t v0, const float* dx,
                            float* dfallback, float* prod, float* keep, void* stream);
 
+/* ---- the losses and the parameter update of a training step (zett_amd/training.py) ----------------------------------------------
+ * What the reference's trainer puts around the hypernetwork forward: the squared-error loss of the identity warm-up
+ * (identity_train_step, train.py:914-975), the lexical loss (train.py:1074-1141) and optax.chain(clip_by_global_norm,
+ * multi_transform({train: adamw, freeze: set_to_zero})) (train.py:591-656).  All pointers are device pointers unless said
+ * otherwise; everything is asynchronous on `stream` and none of these calls waits for the host.  Every reduction is per-workgroup partials
+ * summed in a fixed order (no float atomics): the same inputs give the same bits on every run. */
+enum zett_distance { ZETT_DIST_MSE = 0, ZETT_DIST_RMSE = 1, ZETT_DIST_HUBER = 2 };      /* lexical_loss_kind, train.py:1096-1115 */
+enum zett_loss_mode { ZETT_LOSS_MEAN = 0, ZETT_LOSS_LEXICAL = 1 };
+enum zett_adamw_flags { ZETT_ADAMW_DECAY = 1, ZETT_ADAMW_FROZEN = 2 };
+#define ZETT_MT_CHUNK 65536      /* elements per work item of the multi-tensor kernels: zett_op_grad_norm needs one float of `partials`
+                                    per started chunk of every tensor */
+/* mask[r] = 1.0 where ids[r, 1:] are all pad_token_id, else 0.0 (lexical_overlap_mask, train.py:1092-1094).  ids is int32
+ * (ids_bytes 4) or int64 (8), [n, width] with leading dimension ld. */
+int zett_op_single_token_mask(const void* ids, int32_t ids_bytes, int64_t n, int32_t width, int64_t ld, int64_t pad_token_id, float* mask, void* stream);
+/* Rows pass of an embedding distance.  The target of row r is src[clamp(ids[r * ids_stride], 0, src_rows - 1), col0 : col0 + e]
+ * (src: zett_dtype src_dtype, leading dimension ld_src; the clamp is JAX's gather rule for train.py:941 / 1086).
+ * row_dist[r] = distance(pred[r], target) * mask[r] (mask NULL: 1), row_tnorm[r] = ||target||_2.  kind: ZETT_DIST_MSE sum (x-y)^2
+ * (train.py:943-944, 1099), ZETT_DIST_RMSE ||x-y||_2 (:1104), ZETT_DIST_HUBER sum huber(x-y; 1e-3) / 1e-3 / 30 (:1107-1115). */
+int zett_op_embed_dist_rows(const float* pred, int64_t ld_pred, const void* src, int32_t src_dtype, int64_t ld_src, int64_t src_rows, int32_t col0, const void* ids,
+                            int32_t ids_bytes, int64_t ids_stride, const float* mask, int64_t n, int32_t e, int32_t kind, float* row_dist, float* row_tnorm,
+                            void* stream);
+/* record[0..3] = { loss, gradient scale, sum(mask) / n, 0 }.  ZETT_LOSS_MEAN: loss = sum(row_dist) / n (train.py:942-946);
+ * ZETT_LOSS_LEXICAL: loss = sum(row_dist) / (sum(mask) + 1e-8) / mean(row_tnorm), the mean over ALL rows (train.py:1121-1125;
+ * 1e-8 is EPSILON of zett/utils.py).  The gradient scale is d loss / d sum(row_dist). */
+int zett_op_embed_dist_finalize(const float* row_dist, const float* row_tnorm, const float* mask, int64_t n, int32_t mode, float* record, void* stream);
+/* dpred[r, :] = (accumulate ? dpred[r, :] : 0) + upstream[0] * record[1] * mask[r] * d distance / d pred[r, :] — what
+ * jax.value_and_grad (train.py:964) yields for these terms.  row_dist and record are the outputs of the two calls above;
+ * upstream is a device scalar.  ZETT_DIST_RMSE at distance 0: gradient 0 (the reference's is NaN there). */
+int zett_op_embed_dist_grad(const float* pred, int64_t ld_pred, const void* src, int32_t src_dtype, int64_t ld_src, int64_t src_rows, int32_t col0, const void* ids,
+                            int32_t ids_bytes, int64_t ids_stride, const float* mask, const float* row_dist, int64_t n, int32_t e, int32_t kind, const float* record,
+                            const float* upstream, float* dpred, int64_t ld_dpred, int32_t accumulate, void* stream);
+/* optax.clip_by_global_norm (train.py:653-654) over n_tensors fp32 tensors.  grads / numel are HOST arrays of device pointers and
+ * element counts: they travel to the kernels as launch arguments, so the caller's arrays are free again when the call returns.
+ * record (8 words, zeroed once by the caller and then owned by these two calls):
+ *   [0] norm  [1] coef = 1 if norm < max_norm else max_norm / norm  [2] int32 skip = the norm is not finite
+ *   [3] int32 step count, advanced unless skip  [4] 1 - b1^step  [5] 1 - b2^step. */
+int zett_op_grad_norm(const void* const* grads, const int64_t* numel, int32_t n_tensors, double max_norm, double b1, double b2, float* partials,
+                      int64_t partials_capacity, float* record, void* stream);
+/* optax.adamw with a decay mask inside multi_transform (train.py:638-650), one pass over all tensors:
+ *   g' = coef g;  m = b1 m + (1-b1) g';  v = b2 v + (1-b2) g'^2;  p -= lr ((m / c1) / (sqrt(v / c2) + eps) + decay ? weight_decay p : 0)
+ * coef, c1, c2 and skip come from `record` (zett_op_grad_norm); with skip set no parameter and no moment is written.  flags[i]:
+ * ZETT_ADAMW_DECAY, ZETT_ADAMW_FROZEN (set_to_zero: the tensor is left alone; params / moments may be NULL).  zero_grad: gradients are
+ * zeroed in the same pass — those of frozen tensors and, on a skipped step, all of them too, so that a non-finite gradient does not
+ * stay behind for the next backward to accumulate into.  The pointer and count arrays are HOST arrays, as above.  Any element count and any 4-byte-aligned pointer. */
+int zett_op_adamw(void* const* params, void* const* grads, void* const* exp_avg, void* const* exp_avg_sq, const int64_t* numel, const uint8_t* flags, int32_t n_tensors,
+                  double lr, double b1, double b2, double eps, double weight_decay, int32_t zero_grad, const float* record, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -19,6 +19,10 @@ PREC_BF16, PREC_F32, PREC_F16 = 0, 1, 2
 RETOK_BPE, RETOK_UNIGRAM, RETOK_WORDPIECE = 0, 1, 2
 OUT_IN, OUT_BIAS = 0, 1              # zett_output
 LEXICAL_NO, LEXICAL_FVT, LEXICAL_BFVT = 0, 1, 2      # zett_lexical_mode
+DIST_MSE, DIST_RMSE, DIST_HUBER = 0, 1, 2            # zett_distance
+LOSS_MEAN, LOSS_LEXICAL = 0, 1                       # zett_loss_mode
+ADAMW_DECAY, ADAMW_FROZEN = 1, 2                     # zett_adamw_flags
+MT_CHUNK = 65536                                     # ZETT_MT_CHUNK
 
 ABI_SYMBOLS = (
     "zett_last_error", "zett_abi_version", "zett_create", "zett_destroy", "zett_load_weight",
@@ -34,6 +38,8 @@ ABI_SYMBOLS = (
     "zett_op_layernorm_fwd_f32", "zett_op_layernorm_bwd_f32", "zett_op_gelu_fwd_f32", "zett_op_gelu_bwd_f32",
     "zett_op_attention_fwd_f32", "zett_op_attention_bwd_f32", "zett_op_gather_fwd_f32", "zett_op_gather_bwd_f32",
     "zett_op_gather_rows_f32", "zett_op_scatter_add_rows_f32", "zett_op_gemm_lo", "zett_op_convert_lo", "zett_op_transpose_lo", "zett_op_grad_operands_lo", "zett_op_transpose_lo16", "zett_op_gelu_fwd_lo",
+    # losses and the parameter update of a training step (zett_amd/training.py)
+    "zett_op_single_token_mask", "zett_op_embed_dist_rows", "zett_op_embed_dist_finalize", "zett_op_embed_dist_grad", "zett_op_grad_norm", "zett_op_adamw",
 )
 
 
@@ -164,6 +170,13 @@ def load():
         lib.zett_op_scatter_add_rows_f32.argtypes = [P, I32, P, P, I64, I32, P]
         lib.zett_op_gather_fwd_f32.argtypes = [P, I64, P, I32, I32, I32, P, P, P, P, P]
         lib.zett_op_gather_bwd_f32.argtypes = [P, I64, P, I32, I32, I32, P, P, P, P, P]
+        D = C.c_double
+        lib.zett_op_single_token_mask.argtypes = [P, I32, I64, I32, I64, I64, P, P]
+        lib.zett_op_embed_dist_rows.argtypes = [P, I64, P, I32, I64, I64, I32, P, I32, I64, P, I64, I32, I32, P, P, P]
+        lib.zett_op_embed_dist_finalize.argtypes = [P, P, P, I64, I32, P, P]
+        lib.zett_op_embed_dist_grad.argtypes = [P, I64, P, I32, I64, I64, I32, P, I32, I64, P, P, I64, I32, I32, P, P, P, I64, I32, P]
+        lib.zett_op_grad_norm.argtypes = [P, P, I32, D, D, D, P, I64, P, P]
+        lib.zett_op_adamw.argtypes = [P, P, P, P, P, P, I32, D, D, D, D, D, I32, P, P]
         for name in ABI_SYMBOLS:
             fn = getattr(lib, name)
             if name != "zett_last_error":
