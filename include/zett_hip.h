@@ -596,6 +596,41 @@ int zett_op_grad_norm(const void* const* grads, const int64_t* numel, int32_t n_
 int zett_op_adamw(void* const* params, void* const* grads, void* const* exp_avg, void* const* exp_avg_sq, const int64_t* numel, const uint8_t* flags, int32_t n_tensors,
                   double lr, double b1, double b2, double eps, double weight_decay, int32_t zero_grad, const float* record, void* stream);
 
+/* ---- the language-model loss over predicted output embeddings (zett_amd/training.py lm_head_loss) --------------------------------
+ * train_step / eval_step of the reference (train.py:1039-1056, 874-912, 1226-1255):
+ *     logits = hidden . pred_out^T + where(vocab_mask, 0, -100000) + bias + priors           [T, V]
+ *     loss   = sum_t w_t (logsumexp(logits[t]) - logits[t, label_t]) / sum_t w_t
+ * The contractions are zett_op_gemm_lo / zett_op_gemm_f32 (the column addend enters through the bias epilogue); the calls below
+ * are the kernels between them (csrc/train_loss.hip).  Asynchronous on `stream`, no float atomics, nothing waits for the host. */
+enum zett_ce_path { ZETT_CE_AUTO = 0, ZETT_CE_ONCE = 1, ZETT_CE_TWICE = 2 };
+#define ZETT_CE_ONCE_MAX_COLS 32768      /* the longest (padded) row the rows pass reads once and keeps in registers */
+/* out[c] = (vocab_mask ? (vocab_mask[c] ? 0 : -100000) : 0) + bias[c] + priors[c] for c < v, 0 for v <= c < v_padded (all three
+ * nullable; vocab_mask: one byte per column, nonzero = the column is in the vocabulary). */
+int zett_op_ce_addend(const float* bias, const float* priors, const uint8_t* vocab_mask, int32_t v, int32_t v_padded, float* out, void* stream);
+/* Softmax cross-entropy rows pass over fp32 logits [rows, v] (leading dimension ld_z >= v_padded, rows 16-byte aligned).  Per row t:
+ *   argmax[t] = the FIRST maximum (jnp.argmax);  lse[t] = max + log sum exp(z - max);  row_loss[t] = w_t (lse[t] - z[label_t]).
+ * A label outside [0, v) is an all-zero one-hot (jax.nn.one_hot; -100 included): row_loss = w_t lse, and the label is never an
+ * index.  weight NULL: 1.  A row with w_t == 0 has row_loss 0 whatever its label.
+ * g (nullable; zett_dtype g_dtype, leading dimension ld_g >= v_padded): the gradient operand
+ *   g[t, c] = w_t (exp(z[t, c] - lse[t]) - [c == label_t]),  0 for v <= c < v_padded,  all zero for w_t == 0,
+ * NOT scaled by 1 / sum(w) or an upstream gradient (zett_op_ce_scale applies both to the fp32 results of the contractions).  An
+ * fp32 g may be the logits themselves (ld_g == ld_z).  v_padded % 4 == 0.
+ * path: ZETT_CE_ONCE reads a row once and keeps it in registers (v_padded <= ZETT_CE_ONCE_MAX_COLS), ZETT_CE_TWICE reads it
+ * twice (any v), ZETT_CE_AUTO takes the first where it applies.  Both give the same bits. */
+int zett_op_ce_rows(float* logits, int64_t ld_z, const int32_t* labels, const float* weight, int64_t rows, int32_t v, int32_t v_padded, void* g, int32_t g_dtype,
+                    int64_t ld_g, float* row_loss, float* lse, int32_t* argmax, int32_t path, void* stream);
+/* record (8 words) = { loss = sum(row_loss) / sum(w), sum(w), 1 / sum(w), int32 n_correct, int32 n_counted, 0, 0, 0 } over all n
+ * rows: n_counted = rows with w > 0, n_correct = those whose argmax equals their label.  sum(w) == 0: loss 0 and 1 / sum(w) = 0,
+ * so every gradient is 0 (the reference's are NaN). */
+int zett_op_ce_finalize(const float* row_loss, const float* weight, const int32_t* labels, const int32_t* argmax, int64_t n, float* record, void* stream);
+/* out[c] = (accumulate ? out[c] : 0) + sum_t g[t, c], c < v: the (unscaled) bias gradient */
+int zett_op_ce_colsum(const void* g, int32_t g_dtype, int64_t ld_g, int64_t rows, int32_t v, float* out, int32_t accumulate, void* stream);
+/* out[i] = (out_dtype) (in[i] * upstream[0] * record[2]): an unscaled gradient times upstream / sum(w), both read on the device */
+int zett_op_ce_scale(const float* in, int64_t n, const float* record, const float* upstream, void* out, int32_t out_dtype, void* stream);
+/* out[r, c] = (out_dtype) in[r, c] for c < cols, 0 for cols <= c < cols_padded (zett_dtype both): an operand of the contractions */
+int zett_op_ce_cast(const void* in, int32_t in_dtype, int64_t ld_in, void* out, int32_t out_dtype, int64_t ld_out, int64_t rows, int32_t cols, int32_t cols_padded,
+                    void* stream);
+
 #ifdef __cplusplus
 }
 #endif

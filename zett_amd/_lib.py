@@ -23,6 +23,8 @@ DIST_MSE, DIST_RMSE, DIST_HUBER = 0, 1, 2            # zett_distance
 LOSS_MEAN, LOSS_LEXICAL = 0, 1                       # zett_loss_mode
 ADAMW_DECAY, ADAMW_FROZEN = 1, 2                     # zett_adamw_flags
 MT_CHUNK = 65536                                     # ZETT_MT_CHUNK
+CE_AUTO, CE_ONCE, CE_TWICE = 0, 1, 2                 # zett_ce_path
+CE_ONCE_MAX_COLS = 32768                             # ZETT_CE_ONCE_MAX_COLS
 
 ABI_SYMBOLS = (
     "zett_last_error", "zett_abi_version", "zett_create", "zett_destroy", "zett_load_weight",
@@ -40,6 +42,8 @@ ABI_SYMBOLS = (
     "zett_op_gather_rows_f32", "zett_op_scatter_add_rows_f32", "zett_op_gemm_lo", "zett_op_convert_lo", "zett_op_transpose_lo", "zett_op_grad_operands_lo", "zett_op_transpose_lo16", "zett_op_gelu_fwd_lo",
     # losses and the parameter update of a training step (zett_amd/training.py)
     "zett_op_single_token_mask", "zett_op_embed_dist_rows", "zett_op_embed_dist_finalize", "zett_op_embed_dist_grad", "zett_op_grad_norm", "zett_op_adamw",
+    # the language-model loss over predicted output embeddings (zett_amd/training.py lm_head_loss)
+    "zett_op_ce_addend", "zett_op_ce_rows", "zett_op_ce_finalize", "zett_op_ce_colsum", "zett_op_ce_scale", "zett_op_ce_cast",
 )
 
 
@@ -177,6 +181,12 @@ def load():
         lib.zett_op_embed_dist_grad.argtypes = [P, I64, P, I32, I64, I64, I32, P, I32, I64, P, P, I64, I32, I32, P, P, P, I64, I32, P]
         lib.zett_op_grad_norm.argtypes = [P, P, I32, D, D, D, P, I64, P, P]
         lib.zett_op_adamw.argtypes = [P, P, P, P, P, P, I32, D, D, D, D, D, I32, P, P]
+        lib.zett_op_ce_addend.argtypes = [P, P, P, I32, I32, P, P]
+        lib.zett_op_ce_rows.argtypes = [P, I64, P, P, I64, I32, I32, P, I32, I64, P, P, P, I32, P]
+        lib.zett_op_ce_finalize.argtypes = [P, P, P, P, I64, P, P]
+        lib.zett_op_ce_colsum.argtypes = [P, I32, I64, I64, I32, P, I32, P]
+        lib.zett_op_ce_scale.argtypes = [P, I64, P, P, P, I32, P]
+        lib.zett_op_ce_cast.argtypes = [P, I32, I64, P, I32, I64, I64, I32, I32, P]
         for name in ABI_SYMBOLS:
             fn = getattr(lib, name)
             if name != "zett_last_error":

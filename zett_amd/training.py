@@ -8,7 +8,9 @@ warm-up loss (train.py:914-975), the lexical loss (train.py:1074-1141) and the p
     loss.backward()
     opt.step(lr=schedule(step), zero_grad=True)
 
-Losses and update are HIP kernels (csrc/train_step.hip); torch holds the tensors and the tape.  Nothing in this module waits for
+    loss, stats = lm_head_loss(hidden, pred_out, labels, attention_mask, mode="clm", vocab_mask=mask)      # the language-model loss (train.py:1039-1056)
+
+Losses and update are HIP kernels (csrc/train_step.hip, csrc/train_loss.hip); torch holds the tensors and the tape.  Nothing in this module waits for
 the host except ``last_step_stats()`` and ``state_dict()`` (the model's forward in front of it still reads its id range back once per
 step).  Results are bit-reproducible from run to run.
 """
@@ -166,6 +168,289 @@ def lexical_loss(pred_in, pred_out, source_embeddings, target_surface_forms, pad
         raise ValueError("target_surface_forms must be [n, L] with one row per predicted row")
     mask = single_token_mask(tsf, pad_token_id)
     return _pair(pred_in, pred_out, source_embeddings, tsf, tsf.stride(0), mask, kind, _lib.LOSS_LEXICAL)
+
+
+# ---- the language-model loss over predicted output embeddings ----------------------------------------------------------------
+_LM_PRECISIONS = {"f32": (None, torch.float32, 32), "bf16": (_lib.PREC_BF16, torch.bfloat16, 64), "f16": (_lib.PREC_F16, torch.float16, 64)}      # (prec, operand dtype, K step)
+_LM_PATHS = {None: _lib.CE_AUTO, "auto": _lib.CE_AUTO, "once": _lib.CE_ONCE, "twice": _lib.CE_TWICE}
+LM_LOGITS_BYTES = 1 << 30          # the logits chunk of lm_head_loss stays at or below this
+
+
+def lm_label_arrays(labels, attention_mask=None, mode=None, weight=None):
+    """The reference's loss_fn (train.py:874-912) as one label and one weight per position, ``(labels' int32 [T], weight fp32 [T] | None)``:
+
+    - "clm": position s is scored against ``labels[..., s + 1]`` with weight ``attention_mask[..., s]``; the last position of a sequence has
+      weight 0 (``logits[..., :-1, :]``, ``labels[..., 1:]``, ``attention_mask[..., :-1]``, train.py:883-885) — no view of the logits or the
+      hidden state is shifted;
+    - "mlm": ``weight = (labels != -100) & (attention_mask == 1)`` (train.py:902);
+    - None: the given `weight`, or None for all ones.
+
+    Small integer arrays, prepared with torch on the device the labels are on."""
+    if mode not in ("clm", "mlm", None):
+        raise ValueError(f'mode must be "clm", "mlm" or None, got {mode!r}')
+    if labels.dtype not in (torch.int32, torch.int64) or labels.dim() < 1:
+        raise ValueError("labels must be an int32 / int64 tensor with at least one dimension")
+    if attention_mask is not None and attention_mask.shape != labels.shape:
+        raise ValueError(f"attention_mask {tuple(attention_mask.shape)} must have the shape of labels {tuple(labels.shape)}")
+    if weight is not None and weight.shape != labels.shape:
+        raise ValueError(f"weight {tuple(weight.shape)} must have the shape of labels {tuple(labels.shape)}")
+    if mode is not None and weight is not None:
+        raise ValueError(f'mode "{mode}" derives the weights from labels and attention_mask: pass weight with mode=None only')
+    if mode is None and attention_mask is not None:
+        raise ValueError("attention_mask needs mode=\"clm\" or \"mlm\"; with mode=None pass the weights as weight")
+    labels = labels.clamp(-(2 ** 31), 2 ** 31 - 1)
+    if mode == "clm":
+        lab = torch.full_like(labels, -100)
+        lab[..., :-1] = labels[..., 1:]
+        w = torch.zeros(labels.shape, dtype=torch.float32, device=labels.device)
+        w[..., :-1] = 1.0 if attention_mask is None else attention_mask[..., :-1].to(torch.float32)
+    elif mode == "mlm":
+        lab = labels
+        keep = labels != -100
+        if attention_mask is not None:
+            keep = keep & (attention_mask == 1)
+        w = keep.to(torch.float32)
+    else:
+        lab, w = labels, None if weight is None else weight.to(torch.float32)
+    return lab.to(torch.int32).reshape(-1).contiguous(), None if w is None else w.reshape(-1).contiguous()
+
+
+def lm_default_chunk_rows(vocab: int, precision: str = "bf16") -> int:
+    """Rows of one logits chunk: the largest multiple of 64 whose fp32 logits ``rows x V_padded x 4`` bytes fit LM_LOGITS_BYTES (1 GiB), at
+    least 64.  V = 32 768: 8 192 rows; V = 262 144: 1 024 rows."""
+    kstep = _LM_PRECISIONS[precision][2]
+    vp = -(-int(vocab) // kstep) * kstep
+    return max(64, (LM_LOGITS_BYTES // (4 * vp)) // 64 * 64)
+
+
+def _lm_check(hidden, pred_out, labels, bias, priors, vocab_mask, precision, chunk_rows, path):
+    """Everything that can be refused is refused here, before the first launch."""
+    if precision not in _LM_PRECISIONS:
+        raise ValueError(f"precision must be one of {sorted(_LM_PRECISIONS)}, got {precision!r}")
+    if path not in _LM_PATHS:
+        raise ValueError(f'rows_path must be None, "auto", "once" or "twice", got {path!r}')
+    if hidden.dim() < 2 or hidden.dtype not in _SRC_DTYPES:
+        raise ValueError("hidden must be a [..., E] fp32 / f16 / bf16 tensor")
+    if pred_out.dim() != 2 or pred_out.dtype != torch.float32 or pred_out.shape[1] != hidden.shape[-1]:
+        raise ValueError(f"pred_out must be a [V, E] fp32 tensor with E = {hidden.shape[-1]}, got {tuple(pred_out.shape)} {pred_out.dtype}")
+    v, e = pred_out.shape
+    t = hidden.numel() // max(e, 1)
+    if v == 0 or e == 0 or t == 0:
+        raise ValueError("the loss of an empty hidden state or vocabulary is undefined")
+    if tuple(labels.shape) != tuple(hidden.shape[:-1]):
+        raise ValueError(f"labels {tuple(labels.shape)} must have the leading shape of hidden {tuple(hidden.shape[:-1])}")
+    for name, x in (("bias", bias), ("priors", priors), ("vocab_mask", vocab_mask)):
+        if x is None:
+            continue
+        if tuple(x.shape) != (v,):
+            raise ValueError(f"{name} must be [V] = [{v}], got {tuple(x.shape)}")
+        if name == "vocab_mask" and x.dtype != torch.bool:
+            raise ValueError("vocab_mask must be a bool tensor (True: the column is in the vocabulary)")
+        if name != "vocab_mask" and not x.dtype.is_floating_point:
+            raise ValueError(f"{name} must be a floating-point tensor")
+    if chunk_rows is not None and (int(chunk_rows) != chunk_rows or chunk_rows < 1):
+        raise ValueError(f"chunk_rows must be a positive integer, got {chunk_rows!r}")
+    if path == "once" and -(-v // _LM_PRECISIONS[precision][2]) * _LM_PRECISIONS[precision][2] > _lib.CE_ONCE_MAX_COLS:
+        raise ValueError(f"the read-once rows pass holds at most {_lib.CE_ONCE_MAX_COLS} columns")
+
+
+def _lm_check_device(pred_out, **others):
+    if not pred_out.is_cuda:
+        raise ValueError("zett_amd computes on the GPU only: pred_out must be a cuda (ROCm) tensor; there is no CPU path")
+    for name, x in others.items():
+        if x is not None and x.device != pred_out.device:
+            raise ValueError(f"{name} must be on the device of pred_out ({pred_out.device}), got {x.device}")
+
+
+def _lm_run(hidden, w_out, bias, priors, vocab_mask, lab, wgt, precision, chunk_rows, path, want_h, want_w, want_b):
+    """The launches of lm_head_loss on flattened, detached inputs.  -> record [8], row_loss, lse, argmax, d hidden | None, d pred_out | None,
+    d bias | None (the gradients unscaled: zett_op_ce_scale multiplies them by upstream / sum(w) in the backward)."""
+    lib = _lib.load()
+    dev = w_out.device
+    prec, lo_dtype, kstep = _LM_PRECISIONS[precision]
+    lo_code = _SRC_DTYPES[lo_dtype]
+    t, e = hidden.shape
+    v = w_out.shape[0]
+    vp, ep = -(-v // kstep) * kstep, -(-e // kstep) * kstep
+    tc = min(t, int(chunk_rows) if chunk_rows is not None else lm_default_chunk_rows(v, precision))
+    tcp = -(-tc // kstep) * kstep
+    want = want_h or want_w or want_b
+    f32 = torch.float32
+
+    def new(*shape, dtype=f32):
+        return torch.empty(shape, dtype=dtype, device=dev)
+
+    with torch.cuda.device(dev):
+        st = _stream(dev)
+
+        def gemm(a, lda, w, ldw, m, n, k, out, ld_out, addend=None, residual=None, ld_res=0):
+            if prec is None:
+                _lib.check(lib.zett_op_gemm_f32(_ptr(a), lda, _ptr(w), ldw, m, n, k, _ptr(addend), 0, _ptr(residual), ld_res, _ptr(out), ld_out, st), "zett_op_gemm_f32")
+            else:
+                _lib.check(lib.zett_op_gemm_lo(prec, _ptr(a), lda, _ptr(w), ldw, m, n, k, _ptr(addend), 0, _ptr(residual), ld_res, _ptr(out), ld_out, st), "zett_op_gemm_lo")
+
+        def transpose(x, ld_in, out, ld_out, rows, cols, rows_padded):          # out[c, r] = x[r, c], rows zero-padded: operands of the training GEMMs
+            if prec is None:
+                _lib.check(lib.zett_op_transpose_f32(_ptr(x), ld_in, _ptr(out), ld_out, rows, cols, rows_padded, st), "zett_op_transpose_f32")
+            else:
+                _lib.check(lib.zett_op_transpose_lo16(prec, _ptr(x), ld_in, _ptr(out), ld_out, rows, cols, rows_padded, st), "zett_op_transpose_lo16")
+
+        # once per call: the addend vector and the operand forms of pred_out
+        addend = None
+        if bias is not None or priors is not None or vocab_mask is not None:
+            addend = new(vp)
+            _lib.check(lib.zett_op_ce_addend(_ptr(bias), _ptr(priors), _ptr(None if vocab_mask is None else vocab_mask.view(torch.uint8)), v, vp, _ptr(addend), st), "zett_op_ce_addend")
+        if prec is None:
+            if ep == e and w_out.stride(0) % 4 == 0 and w_out.data_ptr() % 16 == 0:
+                w_op = w_out
+            else:
+                w_op = new(v, ep)
+                _lib.check(lib.zett_op_ce_cast(_ptr(w_out), _lib.DTYPE_F32, w_out.stride(0), _ptr(w_op), _lib.DTYPE_F32, ep, v, e, ep, st), "zett_op_ce_cast")
+        else:
+            w_op = new(v, ep, dtype=lo_dtype)
+            _lib.check(lib.zett_op_convert_lo(prec, _ptr(w_out), w_out.stride(0), _ptr(w_op), ep, v, e, ep, st), "zett_op_convert_lo")
+        w_t = None
+        if want_h:                                   # lo(W)^T [E, V'] (V zero-padded to the K step): the operand of d hidden = G . W
+            w_t = new(e, vp, dtype=lo_dtype)
+            if prec is None:
+                _lib.check(lib.zett_op_transpose_f32(_ptr(w_out), w_out.stride(0), _ptr(w_t), vp, v, e, vp, st), "zett_op_transpose_f32")
+            else:
+                _lib.check(lib.zett_op_transpose_lo(prec, _ptr(w_out), w_out.stride(0), _ptr(w_t), vp, v, e, vp, st), "zett_op_transpose_lo")
+
+        direct = hidden.dtype == lo_dtype and ep == e and hidden.stride(0) % 8 == 0 and hidden.data_ptr() % 16 == 0          # the hidden state is an operand as it is
+        a_buf = None if direct else new(tc, ep, dtype=lo_dtype)
+        logits = new(tc, vp)
+        g = None if not want else (logits if prec is None else new(tc, vp, dtype=lo_dtype))
+        row_loss, lse, argmax, record = new(t), new(t), new(t, dtype=torch.int32), new(8)
+        d_hidden = new(t, e) if want_h else None
+        d_bias = new(v) if want_b else None
+        g_t = h_t = d_w = d_w_prev = None
+        if want_w:
+            g_t, h_t, d_w = new(v, tcp, dtype=lo_dtype), new(e, tcp, dtype=lo_dtype), new(v, e)
+            if t > tc:
+                d_w_prev = new(v, e)              # the accumulation goes through the GEMM's residual input, from one buffer into the other
+
+        for i, r0 in enumerate(range(0, t, tc)):
+            n = min(tc, t - r0)
+            np_ = -(-n // kstep) * kstep
+            if direct:
+                a, lda = hidden[r0:r0 + n], hidden.stride(0)
+            else:
+                a, lda = a_buf, ep
+                _lib.check(lib.zett_op_ce_cast(_ptr(hidden[r0:r0 + n]), _SRC_DTYPES[hidden.dtype], hidden.stride(0), _ptr(a), lo_code, ep, n, e, ep, st), "zett_op_ce_cast")
+            gemm(a, lda, w_op, w_op.stride(0), n, v, ep, logits, vp, addend=addend)
+            _lib.check(lib.zett_op_ce_rows(_ptr(logits), vp, _ptr(lab[r0:]), _ptr(None if wgt is None else wgt[r0:]), n, v, vp, _ptr(g), lo_code, vp,
+                                           _ptr(row_loss[r0:]), _ptr(lse[r0:]), _ptr(argmax[r0:]), _LM_PATHS[path], st), "zett_op_ce_rows")
+            if want_b:
+                _lib.check(lib.zett_op_ce_colsum(_ptr(g), lo_code, vp, n, v, _ptr(d_bias), int(i > 0), st), "zett_op_ce_colsum")
+            if want_w:                               # dW += G^T . hidden_chunk
+                transpose(g, vp, g_t, tcp, n, v, np_)
+                transpose(a, lda, h_t, tcp, n, e, np_)
+                if i > 0:
+                    d_w, d_w_prev = d_w_prev, d_w
+                gemm(g_t, tcp, h_t, tcp, v, e, np_, d_w, e, residual=d_w_prev if i > 0 else None, ld_res=e if i > 0 else 0)
+            if want_h:                               # d hidden_chunk = G . W
+                gemm(g, vp, w_t, vp, n, e, vp, d_hidden[r0:], e)
+        _lib.check(lib.zett_op_ce_finalize(_ptr(row_loss), _ptr(wgt), _ptr(lab), _ptr(argmax), t, _ptr(record), st), "zett_op_ce_finalize")
+    return record, row_loss, lse, argmax, d_hidden, d_w if want_w else None, d_bias
+
+
+def _lm_scale(x, record, upstream, dtype):
+    """x * upstream / sum(w) as `dtype`; both factors are read on the device."""
+    out = torch.empty(x.shape, dtype=dtype, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.load().zett_op_ce_scale(_ptr(x), x.numel(), _ptr(record), _ptr(upstream), _ptr(out), _SRC_DTYPES[dtype], _stream(x.device)), "zett_op_ce_scale")
+    return out
+
+
+class _LMHeadLoss(torch.autograd.Function):
+    """(hidden [T, E], pred_out, bias) -> (loss, row_loss, lse, argmax, record).  The gradients are computed in the forward — the logits
+    are not kept — and stored unscaled; the backward multiplies them by upstream / sum(w)."""
+
+    @staticmethod
+    def forward(ctx, hidden, pred_out, bias, priors, vocab_mask, lab, wgt, precision, chunk_rows, path):
+        want_h, want_w, want_b = hidden.requires_grad, pred_out.requires_grad, bias is not None and bias.requires_grad
+        record, row_loss, lse, argmax, d_h, d_w, d_b = _lm_run(hidden.detach(), pred_out.detach(), None if bias is None else bias.detach(), priors, vocab_mask, lab, wgt,
+                                                               precision, chunk_rows, path, want_h, want_w, want_b)
+        ctx.save_for_backward(record, *(x for x in (d_h, d_w, d_b) if x is not None))
+        ctx.have = (d_h is not None, d_w is not None, d_b is not None)
+        ctx.hidden_dtype = hidden.dtype
+        loss, stats_record = record[0].clone(), record.clone()          # (own storage: autograd outputs must not alias the saved record)
+        ctx.mark_non_differentiable(row_loss, lse, argmax, stats_record)
+        return loss, row_loss, lse, argmax, stats_record
+
+    @staticmethod
+    def backward(ctx, d_loss, *_):
+        record, *grads = ctx.saved_tensors
+        grads = iter(grads)
+        upstream = d_loss.detach().to(device=record.device, dtype=torch.float32).reshape(1)
+        out = []
+        for have, dtype in zip(ctx.have, (ctx.hidden_dtype, torch.float32, torch.float32)):
+            out.append(_lm_scale(next(grads), record, upstream, dtype) if have else None)
+        return (*out, None, None, None, None, None, None, None)
+
+
+def lm_head_loss(hidden, pred_out, labels, attention_mask=None, *, mode=None, weight=None, bias=None, priors=None, vocab_mask=None, precision="bf16",
+                 chunk_rows=None, rows_path=None):
+    """The language-model loss of the reference's train_step / eval_step over PREDICTED output embeddings (train.py:1039-1056, 874-912,
+    1226-1255) — the term every gradient of ``pred_out`` and of the predicted bias comes from:
+
+        logits = hidden @ pred_out.T                                  [T, V], V = the sampled vocabulary
+        logits += where(vocab_mask, 0, -100000)                       NEGATIVE_INF_FILL_VALUE, zett/utils.py:23
+        logits += bias                                                learnable_bias
+        logits += priors                                              add_target_priors_to_bias
+        loss = sum(softmax_cross_entropy(logits, onehot(labels)) * weight) / sum(weight)
+
+    hidden: ``[..., E]`` fp32 / bf16 / f16, the backbone's final hidden state (leading dimensions are flattened to T; may require grad).
+    pred_out: ``[V, E]`` fp32, what ``ZettHypernet.forward`` returns (``pred_in`` for tied models).  bias / priors (floating point) and
+    vocab_mask (bool, True = in the vocabulary) are ``[V]``: one addend vector, built once per call on the device and added in the logits
+    GEMM's epilogue.  labels: integers of hidden's leading shape; a label outside ``[0, V)`` — ``-100`` included — is an all-zero one-hot
+    (jax.nn.one_hot): the row's loss is ``weight * logsumexp``.
+
+    mode: "clm" takes UNSHIFTED ``[B, S]`` labels and attention mask (position s is scored against ``labels[b, s + 1]`` with weight
+    ``attention_mask[b, s]``, the last position has weight 0: train.py:883-885 as a label and a weight array — hidden is never sliced);
+    "mlm" uses ``weight = (labels != -100) & (attention_mask == 1)``; None uses `weight`, or all ones (lm_label_arrays).
+
+    precision: the arithmetic of the three contractions — "bf16" / "f16" MFMA operands with fp32 accumulation, or exact "f32"; softmax,
+    sums and gradients are fp32.  A 16-bit hidden of the operand type with ``E % 64 == 0`` is used as it is.
+
+    T is processed in chunks of `chunk_rows` rows (default lm_default_chunk_rows: the largest multiple of 64 whose fp32 logits chunk
+    ``chunk_rows x V_padded x 4`` bytes stays at or below 1 GiB — 8 192 rows at V = 32 768): the logits GEMM, the softmax rows pass
+    (csrc/train_loss.hip) and, when any of hidden / pred_out / bias requires grad, ``dW += G^T . hidden_chunk`` and
+    ``d hidden_chunk = G . W`` with ``G = weight * (softmax - onehot)`` in the operand type.  The full ``[T, V]`` logits never exist.  loss,
+    row_loss, lse, argmax and d hidden do not depend on the chunk size (same bits); d pred_out and d bias are summed over T chunk by
+    chunk, so their last bits do.  rows_path ("once" | "twice", tests): force the rows pass to keep a row in registers or to read it
+    twice — same bits.
+
+    Returns ``(loss, stats)``: loss 0-dim on the device, differentiable in hidden, pred_out and bias (the gradients are formed in the forward
+    and stored unscaled; backward multiplies them by ``upstream / sum(weight)`` read from device memory and returns d hidden in hidden's
+    dtype).  stats (device tensors, no gradient): ``row_loss [T]`` = weight * cross-entropy, ``lse [T]``, ``argmax [T]`` int32 (the first
+    maximum), ``n_correct`` / ``n_counted`` (int32: rows with weight > 0, and those of them whose argmax is the label), ``weight_sum``.
+    Under ``torch.no_grad()`` or when nothing requires grad — eval_step — only the logits GEMM and the rows pass run and nothing is saved; the
+    reference's ``acc`` is ``n_correct / n_counted`` and its bits per byte (clm, train.py:894-898) are
+    ``(stats["row_loss"].view(B, S).sum(-1) / byte_lengths.sum(-1)).mean()``.
+
+    Nothing here waits for the host; two runs give the same bits.  Deviation: ``sum(weight) == 0`` gives loss 0 and zero gradients (the
+    reference divides 0 by 0 and returns NaN), as the "rmse" gradient at distance 0 does in lexical_loss."""
+    _lm_check(hidden, pred_out, labels, bias, priors, vocab_mask, precision, chunk_rows, rows_path)
+    lab, wgt = lm_label_arrays(labels, attention_mask, mode, weight)
+    _lm_check_device(pred_out, hidden=hidden, labels=labels, bias=bias, priors=priors, vocab_mask=vocab_mask, weights=wgt)
+    e = hidden.shape[-1]
+    h2 = hidden.reshape(-1, e)
+    if h2.stride(1) != 1:
+        h2 = h2.contiguous()
+    bias32 = None if bias is None else bias.to(torch.float32)
+    priors32 = None if priors is None else priors.detach().to(torch.float32).contiguous()
+    mask = None if vocab_mask is None else vocab_mask.contiguous()
+    if torch.is_grad_enabled() and (h2.requires_grad or pred_out.requires_grad or (bias32 is not None and bias32.requires_grad)):
+        loss, row_loss, lse, argmax, record = _LMHeadLoss.apply(h2, pred_out, None if bias32 is None else bias32.contiguous(), priors32, mask, lab, wgt, precision,
+                                                               chunk_rows, rows_path)
+    else:
+        record, row_loss, lse, argmax, _, _, _ = _lm_run(h2.detach(), pred_out.detach(), None if bias32 is None else bias32.detach().contiguous(), priors32, mask, lab, wgt,
+                                                         precision, chunk_rows, rows_path, False, False, False)
+        loss = record[0]
+    counts = record.view(torch.int32)
+    return loss, {"row_loss": row_loss, "lse": lse, "argmax": argmax, "n_correct": counts[3], "n_counted": counts[4], "weight_sum": record[1]}
 
 
 # ---- which parameters train, and which decay -------------------------------------------------------------------------------
