@@ -631,6 +631,42 @@ int zett_op_ce_scale(const float* in, int64_t n, const float* record, const floa
 int zett_op_ce_cast(const void* in, int32_t in_dtype, int64_t ld_in, void* out, int32_t out_dtype, int64_t ld_out, int64_t rows, int32_t cols, int32_t cols_padded,
                     void* stream);
 
+/* ---- the input side of a training step (zett_amd/training.py splice_special_rows, token_embeddings) ------------------------------
+ * train_step of the reference (train.py:998-1037): the special rows of the predicted matrices are overwritten with source rows, and
+ * the backbone looks input_ids up in the spliced input matrix; the backward of that lookup is where pred_in gets its gradient.
+ * The calls below are csrc/train_embed.hip.  Asynchronous on `stream`, nothing waits for the host, no float atomics: the same
+ * inputs give the same bits on every run. */
+#define ZETT_SPLICE_MAX_ROWS 256       /* the longest splice list: the lists travel as kernel arguments (tokenizer.all_special_ids is far shorter) */
+#define ZETT_EMBED_BWD_CHUNK 64        /* positions of one partial sum of the lookup's backward: part of the definition of the result */
+/* out[rows[i], 0:e] = (float) src[ref_rows[i], col0 : col0 + e] for i < n (src: zett_dtype src_dtype, leading dimension ld_src,
+ * src_rows rows; src NULL: the listed rows become 0 and ref_rows is not read).  in != NULL: every other row of out [v, e] is a copy
+ * of in's, in ONE pass over the matrix; in NULL: no other row of out is touched.  rows / ref_rows are HOST arrays, validated before
+ * any launch: a row outside [0, v) or a source row outside [0, src_rows) is ZETT_E_INDEX, a row listed twice or more than
+ * ZETT_SPLICE_MAX_ROWS rows ZETT_E_INVALID.  They travel to the kernel as launch arguments, so the caller's arrays are free again
+ * when the call returns.  Any e and any 4-byte aligned pointers; 16-byte accesses where pointers and leading dimensions allow them. */
+int zett_op_splice_rows(const float* in, int64_t ld_in, float* out, int64_t ld_out, int64_t v, int32_t e, const void* src, int32_t src_dtype, int64_t ld_src,
+                        int64_t src_rows, int32_t col0, const int32_t* rows, const int32_t* ref_rows, int32_t n, void* stream);
+/* out[p, 0:e] = (out_dtype) table[ids[p], 0:e] for p < t (zett_dtype both; out contiguous [t, e]; ids int32 (ids_bytes 4) or int64
+ * (8)).  fp32 -> 16 bits rounds to nearest even, equal types copy the bits.  An id outside [0, v) gives a zero row, is never used as
+ * an address, and ORs 1 into *error_word (device, nullable, zeroed by the caller). */
+int zett_op_embed_lookup(const void* table, int32_t table_dtype, int64_t ld_table, int64_t v, int32_t e, const void* ids, int32_t ids_bytes, int64_t t, void* out,
+                         int32_t out_dtype, int32_t* error_word, void* stream);
+/* bytes of the plan of t positions over v rows (what the backward reads: keep it until then), of the scratch buffer that only the plan
+ * call itself uses (free once that call's work on the stream is done), and of the partial-sum rows the backward needs for e columns */
+int zett_op_embed_lookup_workspace_bytes(int64_t t, int64_t v, int32_t e, int64_t* plan_bytes, int64_t* scratch_bytes, int64_t* partial_bytes);
+/* The inverted index of ids: per id in [0, v) its positions in ASCENDING order, and the chunk table of the ids that hold more than
+ * ZETT_EMBED_BWD_CHUNK positions.  Ids outside [0, v) are in no list.  Integers only (a histogram, a scan, a placement that depends
+ * on tile indices and counts alone): the plan is a pure function of ids.  `plan`, `scratch`: device, 4-byte aligned, sizes as queried. */
+int zett_op_embed_lookup_plan(const void* ids, int32_t ids_bytes, int64_t t, int64_t v, void* plan, int64_t plan_bytes, void* scratch, int64_t scratch_bytes,
+                              void* stream);
+/* d_table[id, 0:e] for EVERY id in [0, v), each row written exactly once (no memset, no read-modify-write): with p_0 < p_1 < ... the
+ * positions of id and C = ZETT_EMBED_BWD_CHUNK,
+ *     partial_j = ((g[p_jC] + g[p_jC+1]) + ...) + g[p_jC+C-1]        fp32, ascending positions, the last chunk ragged
+ *     d_table[id] = ((partial_0 + partial_1) + ...) + partial_last   fp32, ascending chunks; no position: zeros
+ * g: [t, e] contiguous, zett_dtype g_dtype, converted exactly to fp32.  plan: what the plan call wrote for the same t and v. */
+int zett_op_embed_lookup_bwd(const void* g, int32_t g_dtype, int64_t t, int64_t v, int32_t e, const void* plan, int64_t plan_bytes, float* partials,
+                             int64_t partial_bytes, float* d_table, int64_t ld_d, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

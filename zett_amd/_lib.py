@@ -25,6 +25,8 @@ ADAMW_DECAY, ADAMW_FROZEN = 1, 2                     # zett_adamw_flags
 MT_CHUNK = 65536                                     # ZETT_MT_CHUNK
 CE_AUTO, CE_ONCE, CE_TWICE = 0, 1, 2                 # zett_ce_path
 CE_ONCE_MAX_COLS = 32768                             # ZETT_CE_ONCE_MAX_COLS
+SPLICE_MAX_ROWS = 256                                # ZETT_SPLICE_MAX_ROWS
+EMBED_BWD_CHUNK = 64                                 # ZETT_EMBED_BWD_CHUNK
 
 ABI_SYMBOLS = (
     "zett_last_error", "zett_abi_version", "zett_create", "zett_destroy", "zett_load_weight",
@@ -44,6 +46,8 @@ ABI_SYMBOLS = (
     "zett_op_single_token_mask", "zett_op_embed_dist_rows", "zett_op_embed_dist_finalize", "zett_op_embed_dist_grad", "zett_op_grad_norm", "zett_op_adamw",
     # the language-model loss over predicted output embeddings (zett_amd/training.py lm_head_loss)
     "zett_op_ce_addend", "zett_op_ce_rows", "zett_op_ce_finalize", "zett_op_ce_colsum", "zett_op_ce_scale", "zett_op_ce_cast",
+    # the input side of a training step (zett_amd/training.py splice_special_rows, token_embeddings)
+    "zett_op_splice_rows", "zett_op_embed_lookup", "zett_op_embed_lookup_workspace_bytes", "zett_op_embed_lookup_plan", "zett_op_embed_lookup_bwd",
 )
 
 
@@ -187,6 +191,11 @@ def load():
         lib.zett_op_ce_colsum.argtypes = [P, I32, I64, I64, I32, P, I32, P]
         lib.zett_op_ce_scale.argtypes = [P, I64, P, P, P, I32, P]
         lib.zett_op_ce_cast.argtypes = [P, I32, I64, P, I32, I64, I64, I32, I32, P]
+        lib.zett_op_splice_rows.argtypes = [P, I64, P, I64, I64, I32, P, I32, I64, I64, I32, P, P, I32, P]
+        lib.zett_op_embed_lookup.argtypes = [P, I32, I64, I64, I32, P, I32, I64, P, I32, P, P]
+        lib.zett_op_embed_lookup_workspace_bytes.argtypes = [I64, I64, I32, C.POINTER(I64), C.POINTER(I64), C.POINTER(I64)]
+        lib.zett_op_embed_lookup_plan.argtypes = [P, I32, I64, I64, P, I64, P, I64, P]
+        lib.zett_op_embed_lookup_bwd.argtypes = [P, I32, I64, I64, I32, P, I64, P, I64, P, I64, P]
         for name in ABI_SYMBOLS:
             fn = getattr(lib, name)
             if name != "zett_last_error":

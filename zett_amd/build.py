@@ -22,7 +22,7 @@ HIPCC_FLAGS = ("--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC")
 OBJ_DIR = os.path.join(CSRC, "build")
 
 
-TRAINING_ONLY = ("train_loss.hip", "train_ops.hip", "train_step.hip")      # primitives of zett_amd/autograd.py and zett_amd/training.py: not on the path bench.py measures
+TRAINING_ONLY = ("train_embed.hip", "train_loss.hip", "train_ops.hip", "train_step.hip")      # primitives of zett_amd/autograd.py and zett_amd/training.py: not on the path bench.py measures
 
 
 def source_hash() -> str:

@@ -10,8 +10,11 @@ warm-up loss (train.py:914-975), the lexical loss (train.py:1074-1141) and the p
 
     loss, stats = lm_head_loss(hidden, pred_out, labels, attention_mask, mode="clm", vocab_mask=mask)      # the language-model loss (train.py:1039-1056)
 
-Losses and update are HIP kernels (csrc/train_step.hip, csrc/train_loss.hip); torch holds the tensors and the tape.  Nothing in this module waits for
-the host except ``last_step_stats()`` and ``state_dict()`` (the model's forward in front of it still reads its id range back once per
+    pred_in, pred_out = splice_special_rows(pred_in, pred_out, src, special_indices, special_indices_in_reference, inplace=True)      # train.py:1014-1030
+    inputs_embeds = token_embeddings(pred_in, input_ids, dtype=torch.bfloat16)      # for a backbone that takes inputs_embeds; d pred_in comes back through it
+
+Losses, update, splice and lookup are HIP kernels (csrc/train_step.hip, csrc/train_loss.hip, csrc/train_embed.hip); torch holds the tensors and the tape.  Nothing in this module waits for
+the host except ``last_step_stats()``, ``state_dict()`` and ``token_embeddings(check_ids=True)`` (the model's forward in front of it still reads its id range back once per
 step).  Results are bit-reproducible from run to run.
 """
 from __future__ import annotations
@@ -21,6 +24,7 @@ import math
 from typing import Callable, Dict, Mapping, Optional, Union
 
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import _lib
 
@@ -451,6 +455,235 @@ def lm_head_loss(hidden, pred_out, labels, attention_mask=None, *, mode=None, we
         loss = record[0]
     counts = record.view(torch.int32)
     return loss, {"row_loss": row_loss, "lse": lse, "argmax": argmax, "n_correct": counts[3], "n_counted": counts[4], "weight_sum": record[1]}
+
+
+# ---- the input side: special rows, token lookup ------------------------------------------------------------------------------
+EMBED_BWD_CHUNK = _lib.EMBED_BWD_CHUNK          # positions of one partial sum of token_embeddings' backward: part of the definition of d pred_in
+
+
+def _index_list(x, name):
+    """A small index list (Python sequence, numpy array, CPU or device integer tensor) as a 1-D int64 numpy array on the host."""
+    import numpy as np
+    if isinstance(x, torch.Tensor):
+        if x.dtype.is_floating_point or x.dtype == torch.bool:
+            raise ValueError(f"{name} must hold integers, got {x.dtype}")
+        x = x.detach().cpu().numpy()          # (a device tensor: one small copy to the host)
+    a = np.asarray(x)
+    if a.size == 0:
+        return np.zeros(0, dtype=np.int64)
+    if a.dtype.kind not in "iu":
+        raise ValueError(f"{name} must hold integers, got dtype {a.dtype}")
+    if a.ndim != 1:
+        raise ValueError(f"{name} must be one-dimensional, got shape {a.shape}")
+    return a.astype(np.int64)
+
+
+def check_special_indices(special_indices, special_indices_in_reference, n_rows: int, n_reference_rows: int):
+    """The host-side validation of splice_special_rows, before the library is touched: -> (rows, reference rows) as int32 numpy arrays.
+    Lists of different length or a duplicate in special_indices: ValueError; an index outside [0, n_rows) or a reference row outside
+    [0, n_reference_rows): IndexError; more than 256 entries: ValueError."""
+    import numpy as np
+    rows, refs = _index_list(special_indices, "special_indices"), _index_list(special_indices_in_reference, "special_indices_in_reference")
+    if rows.shape != refs.shape:
+        raise ValueError(f"special_indices holds {rows.size} entries, special_indices_in_reference {refs.size}")
+    bad = rows[(rows < 0) | (rows >= n_rows)]
+    if bad.size:
+        raise IndexError(f"special index {int(bad[0])} is outside the {n_rows} predicted rows")
+    bad = refs[(refs < 0) | (refs >= n_reference_rows)]
+    if bad.size:
+        raise IndexError(f"reference row {int(bad[0])} is outside the {n_reference_rows} rows of source_embeddings")
+    if rows.size > _lib.SPLICE_MAX_ROWS:
+        raise ValueError(f"special_indices holds {rows.size} entries, at most {_lib.SPLICE_MAX_ROWS} travel with a launch")
+    if np.unique(rows).size != rows.size:
+        raise ValueError("special_indices holds a row twice: which source row wins would be unspecified (JAX leaves it open)")
+    return rows.astype(np.int32), refs.astype(np.int32)
+
+
+def _splice_launch(src_matrix, out, source, col0, rows, refs):
+    """out[rows] = source[refs, col0 : col0 + E] (source None: zeros); every other row of out from src_matrix (None: left as it is)."""
+    n = len(rows)
+    r = (C.c_int32 * max(n, 1))(*rows.tolist())
+    f = (C.c_int32 * max(n, 1))(*(refs.tolist() if refs is not None else []))
+    v, e = out.shape
+    with torch.cuda.device(out.device):
+        _lib.check(_lib.load().zett_op_splice_rows(_ptr(src_matrix), 0 if src_matrix is None else src_matrix.stride(0), _ptr(out), out.stride(0), v, e, _ptr(source),
+                                                   _lib.DTYPE_F32 if source is None else _SRC_DTYPES[source.dtype], 0 if source is None else source.stride(0),
+                                                   0 if source is None else source.shape[0], int(col0), r, f, n, _stream(out.device)), "splice_rows")
+    return out
+
+
+class _SpliceRows(torch.autograd.Function):
+    """pred -> pred with the listed rows replaced by source rows.  Gradient: the incoming one with those rows zero, written to a fresh matrix
+    in one pass; the source is a frozen target."""
+
+    @staticmethod
+    def forward(ctx, pred, source, col0, rows, refs, inplace):
+        ctx.rows = rows
+        if inplace:
+            ctx.mark_dirty(pred)
+            return _splice_launch(None, pred, source, col0, rows, refs)
+        return _splice_launch(pred.detach(), torch.empty(pred.shape, dtype=torch.float32, device=pred.device), source, col0, rows, refs)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad):
+        g = grad.detach()
+        if g.dtype != torch.float32 or g.stride(1) != 1:
+            g = g.float().contiguous()
+        return _splice_launch(g, torch.empty(g.shape, dtype=torch.float32, device=g.device), None, 0, ctx.rows, None), None, None, None, None, None
+
+
+def splice_special_rows(pred_in, pred_out, source_embeddings, special_indices, special_indices_in_reference, *, inplace=False):
+    """The special rows of the predicted matrices (train.py:1014-1017, 1027-1030; eval 1198-1205): for every i, row
+    ``special_indices[i]`` of pred_in becomes ``source_embeddings[special_indices_in_reference[i], 0:E]`` and the same row of pred_out
+    becomes ``source_embeddings[.., E:2E]`` — the column split of identity_loss / lexical_loss.  Returns ``(pred_in', pred_out')``;
+    pred_out may be None (tied embeddings), then pred_out' is None.  The lexical loss and the logits both take the spliced matrices.
+
+    pred_in / pred_out: ``[V, E]`` fp32 device tensors with unit column stride.  source_embeddings: fp32 / f16 / bf16, converted exactly; a
+    source with fewer than 2E columns and a pred_out is a ValueError.  The index lists are small (``tokenizer.all_special_ids``): Python
+    sequences, numpy arrays, CPU or device integer tensors — a device tensor costs one small copy to the host, the collator produces
+    numpy anyway.  They are validated on the host before any launch (duplicates in special_indices: ValueError — JAX leaves the winner
+    unspecified; an index outside ``[0, V)`` or a reference row outside the source: IndexError) and travel to the kernel as kernel
+    arguments, so nothing is staged in a buffer a later call could overwrite.
+
+    inplace=False writes fresh matrices in ONE pass (copy, listed rows from the source).  inplace=True overwrites the listed rows of the
+    given tensors and moves nothing else; autograd sees an in-place operation, which is safe on the outputs of the hypernetwork (its
+    Function does not save them) and refused by torch on a leaf that requires grad.  Either way the gradient of each output is the
+    incoming gradient with the listed rows zero — a fresh matrix, the incoming one is never modified — and source_embeddings gets none.
+    With no special indices the inputs are returned as they are."""
+    if pred_in.dim() != 2:
+        raise ValueError("predicted embeddings must be [V, E]")
+    v, e = pred_in.shape
+    src = source_embeddings
+    need = e if pred_out is None else 2 * e
+    if src.dim() != 2 or src.shape[1] < need:
+        raise ValueError(f"source_embeddings must be [R, >= {need}] (input half{'' if pred_out is None else ' + output half'}), got {tuple(src.shape)}")
+    if pred_out is not None and pred_out.shape != pred_in.shape:
+        raise ValueError("pred_in and pred_out must have the same shape")
+    rows, refs = check_special_indices(special_indices, special_indices_in_reference, v, src.shape[0])
+    if rows.size == 0:
+        return pred_in, pred_out
+    for name, p in (("pred_in", pred_in), ("pred_out", pred_out)):
+        if p is not None and (p.dtype != torch.float32 or not p.is_cuda or p.device != pred_in.device or (inplace and p.stride(1) != 1)):
+            raise ValueError(f"{name} must be a [V, E] fp32 device tensor{' with unit column stride' if inplace else ''}")
+        if p is not None and inplace and torch.is_grad_enabled() and p.requires_grad and p.is_leaf:          # (torch would say so only after the rows are written)
+            raise RuntimeError(f"{name} is a leaf that requires grad: it cannot be spliced in place (use inplace=False, or splice the hypernetwork's outputs)")
+    if src.dtype not in _SRC_DTYPES:
+        src = src.float()
+    if src.device != pred_in.device or src.stride(1) != 1:
+        raise ValueError("source_embeddings must be on the device of the predictions, with unit column stride")
+    src = src.detach()
+    out = []
+    for p, col0 in ((pred_in, 0), (pred_out, e)):
+        if p is not None and not inplace and p.stride(1) != 1:
+            p = p.contiguous()
+        out.append(None if p is None else _SpliceRows.apply(p, src, col0, rows, refs, bool(inplace)))
+    return out[0], out[1]
+
+
+def _lookup(table, ids, dtype, check_ids):
+    t, (v, e) = ids.numel(), table.shape
+    out = torch.empty(tuple(ids.shape) + (e,), dtype=dtype, device=table.device)
+    if t == 0:
+        return out
+    with torch.cuda.device(table.device):
+        word = torch.zeros(1, dtype=torch.int32, device=table.device) if check_ids else None
+        _lib.check(_lib.load().zett_op_embed_lookup(_ptr(table), _SRC_DTYPES[table.dtype], table.stride(0), v, e, _ptr(ids), ids.element_size(), t, _ptr(out),
+                                                    _SRC_DTYPES[dtype], _ptr(word), _stream(table.device)), "embed_lookup")
+    if check_ids and int(word.item()):          # (the one host read of this call)
+        raise IndexError(f"token_embeddings: an id in input_ids is outside [0, {v})")
+    return out
+
+
+def embed_lookup_workspace(t: int, v: int, e: int):
+    """(bytes of the plan, bytes of the scratch buffer that only the plan call uses, bytes of the partial-sum rows) of token_embeddings'
+    backward for t positions, v rows, e columns."""
+    plan, scratch, partial = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+    _lib.check(_lib.load().zett_op_embed_lookup_workspace_bytes(int(t), int(v), int(e), C.byref(plan), C.byref(scratch), C.byref(partial)), "embed_lookup_workspace_bytes")
+    return plan.value, scratch.value, partial.value
+
+
+def embed_lookup_plan(ids, v: int):
+    """The inverted index of `ids` over v rows (per id, its positions in ascending order) as an opaque int32 device tensor: a pure
+    function of ids, built on the current stream without a host round trip.  What only the building needs (about 4T + 2V words) is a
+    scratch tensor that is released on return — the caching allocator reuses it in stream order — so the plan that autograd holds until
+    the backward is T + 2V + T/32 words."""
+    plan_bytes, scratch_bytes, _ = embed_lookup_workspace(ids.numel(), v, 1)
+    plan = torch.empty(plan_bytes // 4, dtype=torch.int32, device=ids.device)
+    scratch = torch.empty(max(scratch_bytes // 4, 1), dtype=torch.int32, device=ids.device)
+    with torch.cuda.device(ids.device):
+        _lib.check(_lib.load().zett_op_embed_lookup_plan(_ptr(ids), ids.element_size(), ids.numel(), int(v), _ptr(plan), plan.numel() * 4, _ptr(scratch),
+                                                         scratch.numel() * 4, _stream(ids.device)), "embed_lookup_plan")
+    return plan
+
+
+def embed_lookup_backward(grad, plan, t: int, v: int, e: int):
+    """d table ``[v, e]`` fp32 from the incoming gradient ``[t, e]`` (fp32 / f16 / bf16, contiguous) and the plan of the ids: every row written once."""
+    d = torch.empty((v, e), dtype=torch.float32, device=grad.device)
+    partials = torch.empty(embed_lookup_workspace(t, v, e)[2] // 4, dtype=torch.float32, device=grad.device)
+    with torch.cuda.device(grad.device):
+        _lib.check(_lib.load().zett_op_embed_lookup_bwd(_ptr(grad), _SRC_DTYPES[grad.dtype], int(t), int(v), int(e), _ptr(plan), plan.numel() * 4, _ptr(partials),
+                                                        partials.numel() * 4, _ptr(d), e, _stream(grad.device)), "embed_lookup_bwd")
+    return d
+
+
+class _TokenEmbeddings(torch.autograd.Function):
+    """(pred_in fp32, ids) -> inputs_embeds.  The plan is built in the forward, behind the gather, and is all that is saved."""
+
+    @staticmethod
+    def forward(ctx, table, ids, dtype, check_ids):
+        out = _lookup(table.detach(), ids, dtype, check_ids)
+        ctx.save_for_backward(embed_lookup_plan(ids, table.shape[0]))
+        ctx.shape = (ids.numel(), table.shape[0], table.shape[1])
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad):
+        plan, = ctx.saved_tensors
+        t, v, e = ctx.shape
+        g = grad.detach().reshape(t, e)
+        if g.dtype not in _SRC_DTYPES:
+            g = g.float()
+        return embed_lookup_backward(g.contiguous(), plan, t, v, e), None, None, None
+
+
+def token_embeddings(pred_in, input_ids, *, dtype=None, check_ids=True):
+    """The backbone's embedding lookup in the (spliced) predicted input matrix: ``out[..., :] = pred_in[input_ids[...], :]`` converted to
+    `dtype` — shape ``input_ids.shape + (E,)``, dtype ``dtype or pred_in.dtype`` — for a backbone that takes ``inputs_embeds``.
+
+    pred_in: ``[V, E]`` fp32 / f16 / bf16 on the device, row stride >= E, unit column stride.  input_ids: int32 / int64 of any shape.  dtype:
+    one of the three; fp32 -> 16 bits rounds to nearest even (what ``tensor.to(dtype)`` gives), equal dtypes copy the bits.
+
+    check_ids=True: the kernel ORs into a device error word when it meets an id outside ``[0, V)``; the host reads that word once after
+    the launch and raises IndexError, as ``F.embedding`` does.  check_ids=False: no host read; an id outside ``[0, V)`` gives a zero row
+    and contributes to no gradient (deviation: torch faults) — it is never used as an address, forward or backward.
+
+    Gradient (an fp32 pred_in only; a 16-bit pred_in that requires grad is a ValueError): a dense fp32 ``[V, E]``.  With
+    ``p_0 < p_1 < ...`` the flattened positions that hold id v, g the incoming gradient converted exactly to fp32 and C = EMBED_BWD_CHUNK = 64,
+
+        partial_j    = ((g[p_jC] + g[p_jC+1]) + ...) + g[p_jC+C-1]          fp32, ascending positions, the last chunk ragged
+        d pred_in[v] = ((partial_0 + partial_1) + ...) + partial_last       fp32, ascending chunks;  no position: zeros
+
+    — a fixed order that depends on nothing but input_ids (for at most 64 positions the plain sequential sum, the bits of ``np.add.at``), so
+    two runs give the same bits; no float atomics.  Every row of d pred_in is written exactly once, zeros included.  The forward builds the
+    inverted index of input_ids on the stream (integers only) and saves nothing else.  Under ``torch.no_grad()`` or when pred_in does not
+    require grad — eval_step — only the gather runs: no plan, nothing saved."""
+    if pred_in.dim() != 2 or pred_in.dtype not in _SRC_DTYPES or pred_in.stride(1) != 1 or pred_in.shape[0] == 0 or pred_in.shape[1] == 0:
+        raise ValueError("pred_in must be a non-empty [V, E] fp32 / f16 / bf16 tensor with unit column stride")
+    if not pred_in.is_cuda:
+        raise ValueError("zett_amd computes on the GPU only: pred_in must be a cuda (ROCm) tensor; there is no CPU path")
+    if input_ids.dtype not in (torch.int32, torch.int64) or input_ids.device != pred_in.device:
+        raise ValueError("input_ids must be an int32 / int64 tensor on the device of pred_in")
+    dtype = pred_in.dtype if dtype is None else dtype
+    if dtype not in _SRC_DTYPES:
+        raise ValueError(f"dtype must be torch.float32, torch.float16 or torch.bfloat16, got {dtype!r}")
+    ids = input_ids.detach().contiguous()
+    if torch.is_grad_enabled() and pred_in.requires_grad:
+        if pred_in.dtype != torch.float32:
+            raise ValueError("the gradient of token_embeddings is defined for an fp32 pred_in; a 16-bit pred_in must not require grad")
+        return _TokenEmbeddings.apply(pred_in, ids, dtype, bool(check_ids))
+    return _lookup(pred_in.detach(), ids, dtype, bool(check_ids))
 
 
 # ---- which parameters train, and which decay -------------------------------------------------------------------------------
