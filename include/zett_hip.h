@@ -482,11 +482,17 @@ int zett_lexical_rows_into(zett_lexical* h, const int32_t* ids, const int32_t* c
  * GEMM family (fp32 MFMA): dgrad is the same contraction against the transposed weight, wgrad the same contraction of
  * the two transposed activations (zett_op_transpose_f32 zero-pads the row count to the 32-wide K step). */
 /* out[m, n] = act(a[m, :] . w[n, :] + bias[n]) + residual[m, n]   (bias, residual nullable; act: 0 none, 1 tanh-GELU, 2 erf-GELU;
- * k % 32 == 0, lda / ldw % 4 == 0) */
+ * k % 32 == 0, lda / ldw % 4 == 0)
+ * Pointers (this entry point and zett_op_gemm_lo): every tile fetches the operands as 16-byte pieces of a row, so `a` and `w` must be
+ * 16-byte aligned (with the leading dimensions above, every row then is); bias, residual and out are fp32 and must be 4-byte
+ * aligned.  Anything else is ZETT_E_INVALID before any launch.  ld_out and ld_res may be any value >= n.  The 256x256 tiles move
+ * bias, residual and out as float4: they are taken for m > 128 and n > 128 when n % 8 == 0, ld_out % 4 == 0, ld_res % 4 == 0 and
+ * out, residual and bias are 16-byte aligned; every other call runs on the 128x128 tile, which reads and writes them one float at
+ * a time.  The choice does not change a bit of the result. */
 int zett_op_gemm_f32(const float* a, int32_t lda, const float* w, int32_t ldw, int64_t m, int32_t n, int32_t k, const float* bias, int32_t act,
                      const float* residual, int32_t ld_res, float* out, int32_t ld_out, void* stream);
 /* The same contraction on 16-bit MFMA operands (prec = ZETT_PREC_BF16 | ZETT_PREC_F16), fp32 accumulate, fp32 epilogue and output
- * (k % 64 == 0, lda / ldw % 8 == 0): the tile kernels of the inference path.  Operands are made by zett_op_convert_lo
+ * (k % 64 == 0, lda / ldw % 8 == 0; pointer alignment as above): the tile kernels of the inference path.  Operands are made by zett_op_convert_lo
  * (out[r, c] = lo(in[r, c]), columns zero-padded to cols_padded) and zett_op_transpose_lo (out[c, r] = lo(in[r, c]), rows
  * zero-padded to rows_padded): the conversion is fused with the layout change dgrad / wgrad need anyway. */
 int zett_op_gemm_lo(int32_t prec, const void* a, int32_t lda, const void* w, int32_t ldw, int64_t m, int32_t n, int32_t k, const float* bias, int32_t act,

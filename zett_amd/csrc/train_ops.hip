@@ -631,8 +631,25 @@ int grid_for(int64_t n) { return (int)std::min<int64_t>((n + 255) / 256, 65535);
 
 }  // namespace
 
+// Pointer contract of zett_op_gemm_f32 / zett_op_gemm_lo (include/zett_hip.h).  Every tile fetches its operands as 16-byte
+// pieces of a row (global_load_dwordx4 in the 128x128 tile, buffer_load_dwordx4 in gemm8r, 16-byte LDS-DMA requests in gemm4d):
+// `a` and `w` are 16-byte aligned for all three or the call is refused.  bias, residual and out are fp32: 4-byte aligned or
+// refused.  The 128x128 tile reads and writes them one float at a time and takes any such pointer; both 256x256 tiles (gemm8r's
+// and gemm4d's drains, generic and streamlined) move them as float4, so they additionally need 16-byte aligned bases there.
+static inline bool aligned_to(const void* p, uintptr_t bytes) { return ((uintptr_t)p & (bytes - 1)) == 0; }
+static int gemm_pointers_ok(const void* a, const void* w, const float* bias, const float* residual, const float* out) {
+    if (!aligned_to(a, 16) || !aligned_to(w, 16)) return fail(ZETT_E_INVALID, "operand pointers a and w must be 16-byte aligned");
+    if (!aligned_to(bias, 4) || !aligned_to(residual, 4) || !aligned_to(out, 4)) return fail(ZETT_E_INVALID, "bias, residual and out must be 4-byte aligned");
+    return 0;
+}
+// what the float4 drains of the 256x256 tiles need beyond the 128x128 tile: eight columns per lane, 16-byte rows and bases
+static inline bool gemm_wide_ok(int n, const float* bias, const float* residual, int ld_res, const float* out, int ld_out) {
+    return n % 8 == 0 && ld_out % 4 == 0 && (!residual || ld_res % 4 == 0) && aligned_to(out, 16) && aligned_to(residual, 16) && aligned_to(bias, 16);
+}
+
 // 16-bit MFMA operands, fp32 accumulate and output: the tile choice of the inference path (gemm4d from K = 512, gemm8r below,
 // 128x128 for small or unaligned outputs); prec = ZETT_PREC_BF16 | ZETT_PREC_F16
+// (tests/test_gemm_direct_gpu.py expected_tile mirrors this rule and gemm4d_epi_mode's choice of drain)
 template <typename T>
 static int gemm_lo(const T* a, int lda, const T* w, int ldw, int64_t m, int n, int k, const float* bias, int act, const float* residual, int ld_res,
                    float* out, int ld_out, hipStream_t st) {
@@ -640,7 +657,7 @@ static int gemm_lo(const T* a, int lda, const T* w, int ldw, int64_t m, int n, i
     g.A = a; g.lda = lda; g.W = w; g.ldw = ldw; g.M = (int)m; g.N = n; g.K = k;
     g.epi.split_col = 0x7fffffff;
     g.epi.bias = bias; g.epi.act = act; g.epi.residual = residual; g.epi.ld_res = ld_res; g.epi.out_f32 = out; g.epi.ld_f32 = ld_out;
-    const bool wide_ok = n % 8 == 0 && ld_out % 4 == 0 && (!residual || ld_res % 4 == 0);
+    const bool wide_ok = gemm_wide_ok(n, bias, residual, ld_res, out, ld_out);
     const int variant = (m > 128 && n > 128 && wide_ok) ? (k >= 512 ? 7 : 2) : 1;
     const hipError_t e = launch_gemm_variant(variant, g, st);
     if (e != hipSuccess) return fail(ZETT_E_HIP, "gemm launch failed: %s", hipGetErrorString(e));
@@ -689,12 +706,13 @@ int zett_op_gemm_f32(const float* a, int32_t lda, const float* w, int32_t ldw, i
     if (k <= 0 || k % 32) return fail(ZETT_E_INVALID, "contraction width %d is not a positive multiple of 32", k);
     if (lda % 4 || ldw % 4) return fail(ZETT_E_INVALID, "operand leading dimensions must be multiples of 4 floats");
     if (m >= (int64_t)0x7fffffff) return fail(ZETT_E_INVALID, "too many rows");
+    if (const int rc = gemm_pointers_ok(a, w, bias, residual, out)) return rc;
     GemmArgs<float> g{};
     g.A = a; g.lda = lda; g.W = w; g.ldw = ldw; g.M = (int)m; g.N = n; g.K = k;
     g.epi.split_col = 0x7fffffff;
     g.epi.bias = bias; g.epi.act = act; g.epi.residual = residual; g.epi.ld_res = ld_res; g.epi.out_f32 = out; g.epi.ld_f32 = ld_out;
     // the 256x256 register-staged tile where it pays and its 16-byte drains apply, the 128x128 tile otherwise (identical bits)
-    const bool wide_ok = n % 8 == 0 && ld_out % 4 == 0 && (!residual || ld_res % 4 == 0);
+    const bool wide_ok = gemm_wide_ok(n, bias, residual, ld_res, out, ld_out);
     const int variant = (m > 128 && n > 128 && wide_ok) ? 2 : 1;
     const hipError_t e = launch_gemm_variant(variant, g, (hipStream_t)stream);
     if (e != hipSuccess) return fail(ZETT_E_HIP, "gemm launch failed: %s", hipGetErrorString(e));
@@ -709,6 +727,7 @@ int zett_op_gemm_lo(int32_t prec, const void* a, int32_t lda, const void* w, int
     if (k <= 0 || k % 64) return fail(ZETT_E_INVALID, "contraction width %d is not a positive multiple of 64", k);
     if (lda % 8 || ldw % 8) return fail(ZETT_E_INVALID, "operand leading dimensions must be multiples of 8 elements");
     if (m >= (int64_t)0x7fffffff) return fail(ZETT_E_INVALID, "too many rows");
+    if (const int rc = gemm_pointers_ok(a, w, bias, residual, out)) return rc;
     if (prec == ZETT_PREC_F16) return gemm_lo<f16_t>((const f16_t*)a, lda, (const f16_t*)w, ldw, m, n, k, bias, act, residual, ld_res, out, ld_out, (hipStream_t)stream);
     return gemm_lo<bf16_t>((const bf16_t*)a, lda, (const bf16_t*)w, ldw, m, n, k, bias, act, residual, ld_res, out, ld_out, (hipStream_t)stream);
 }
