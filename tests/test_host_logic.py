@@ -502,6 +502,28 @@ def test_no_product_kernel_uses_scratch(tmp_path):
     assert not bad, bad
 
 
+def test_no_forward_source_reaches_a_training_only_header():
+    """build.source_hash() leaves the TRAINING_ONLY names out, headers included: it still covers everything the forward is built from
+    only while no other source includes, directly or through another header, a header listed there."""
+    from zett_amd import build
+    headers = [f for f in build.TRAINING_ONLY if not f.endswith(".hip")]
+    units = [f for f in build.TRAINING_ONLY if f.endswith(".hip")]
+    assert headers == ["train_common.hip.h"], headers
+    assert all(f in build.HEADERS for f in headers), headers
+    assert all(f in build.SOURCES for f in units), units
+    forward = [f for f in build.SOURCES if f not in build.TRAINING_ONLY]
+    assert len(forward) >= 5
+
+    def reached(name):
+        return {os.path.basename(p) for p in build._includes(os.path.join(build.CSRC, name))}
+
+    for name in forward:
+        assert len(reached(name)) >= 2, (name, reached(name))            # (the walk does follow this unit's includes)
+        assert not reached(name) & set(build.TRAINING_ONLY), (name, reached(name) & set(build.TRAINING_ONLY))
+    for name in units:                                                   # and the walk sees the header where it IS included
+        assert "train_common.hip.h" in reached(name), name
+
+
 def test_training_primitives_refuse_bad_arguments_before_touching_the_device():
     """Error behaviour of the zett_op_* entry points at the boundary: arguments are validated before any launch, the return code is
     ZETT_E_INVALID and zett_last_error says why (no GPU needed: nothing is launched)."""

@@ -393,3 +393,47 @@ def test_training_a_tiny_hypernet_with_the_lm_loss():
     losses = [float(x) for x in torch.stack(losses).cpu()]
     assert all(np.isfinite(losses)) and losses[-1] < losses[0], losses
     assert opt.last_step_stats()["step"] == 5
+
+
+# ---- 5. the kernels shared with the primitives of zett_amd/autograd.py -------------------------------------------------------------
+def _call_op(fn, *args):
+    """a zett_op_* entry point on the NULL stream (the trailing stream argument), checked and waited for"""
+    from zett_amd import _lib
+    stream = None
+    _lib.check(getattr(_lib.load(), fn)(*args, stream), fn)
+    torch.cuda.synchronize()
+
+
+def test_colsum_f32_and_ce_colsum_share_one_kernel():
+    """zett_op_colsum_f32 and zett_op_ce_colsum(ZETT_F32) run the same kernel: the same bits, and — small integers, every fp32 sum
+    exact — numpy's column sums.  65 columns reach into a second 64-column workgroup; 5 rows leave the four waves uneven shares."""
+    from zett_amd import _lib
+    rows, v, ld = 5, 65, 72
+    x = np.random.default_rng(7).integers(-8, 9, size=(rows, ld)).astype(np.float32)
+    start = np.arange(v, dtype=np.float32) - 30.0
+    dx = torch.from_numpy(x).to(DEV)
+    for accumulate in (0, 1):
+        want = x[:, :v].sum(0) + (start if accumulate else 0.0)
+        plain, ce = torch.from_numpy(start).to(DEV), torch.from_numpy(start).to(DEV)
+        _call_op("zett_op_colsum_f32", dx.data_ptr(), ld, rows, v, plain.data_ptr(), accumulate)
+        _call_op("zett_op_ce_colsum", dx.data_ptr(), _lib.DTYPE_F32, ld, rows, v, ce.data_ptr(), accumulate)
+        assert np.array_equal(plain.cpu().numpy().view(np.uint32), ce.cpu().numpy().view(np.uint32)), accumulate
+        assert np.array_equal(plain.cpu().numpy(), want.astype(np.float32)), accumulate
+
+
+@pytest.mark.parametrize("cols", (5, 8))
+@pytest.mark.parametrize("precision", ("f16", "bf16"))
+def test_convert_lo_and_ce_cast_share_one_kernel(precision, cols):
+    """zett_op_convert_lo and zett_op_ce_cast from fp32 give the same bits: cols = 5 of 8 is the general path of both (one kernel, a
+    zero-filled pad), cols = 8 of 8 convert's float4 path against that kernel."""
+    from zett_amd import _lib
+    rows, cp = 3, 8
+    prec, code = {"f16": (_lib.PREC_F16, _lib.DTYPE_F16), "bf16": (_lib.PREC_BF16, _lib.DTYPE_BF16)}[precision]
+    x = (torch.randn(rows, cols, generator=torch.Generator().manual_seed(11)) * 3.0).to(DEV)
+    a = torch.full((rows, cp), 7.0, device=DEV).to(LO[precision])          # (stale contents: the pad must be written)
+    b = a.clone()
+    _call_op("zett_op_convert_lo", prec, x.data_ptr(), cols, a.data_ptr(), cp, rows, cols, cp)
+    _call_op("zett_op_ce_cast", x.data_ptr(), _lib.DTYPE_F32, cols, b.data_ptr(), code, cp, rows, cols, cp)
+    assert torch.equal(a.view(torch.int16), b.view(torch.int16))
+    assert torch.equal(a[:, :cols], x.to(LO[precision]))                    # round to nearest even, as torch's cast
+    assert torch.equal(a.view(torch.int16)[:, cols:], torch.zeros(rows, cp - cols, dtype=torch.int16, device=DEV))

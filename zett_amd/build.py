@@ -22,7 +22,8 @@ HIPCC_FLAGS = ("--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC")
 OBJ_DIR = os.path.join(CSRC, "build")
 
 
-TRAINING_ONLY = ("train_embed.hip", "train_loss.hip", "train_ops.hip", "train_step.hip")      # primitives of zett_amd/autograd.py and zett_amd/training.py: not on the path bench.py measures
+# primitives of zett_amd/autograd.py and zett_amd/training.py, and the header only they include: not on the path bench.py measures
+TRAINING_ONLY = ("train_common.hip.h", "train_embed.hip", "train_loss.hip", "train_ops.hip", "train_step.hip")
 
 
 def source_hash() -> str:
@@ -30,7 +31,7 @@ def source_hash() -> str:
     (profiles/pmc_traffic.json) to the kernels it was taken on."""
     import hashlib
     h = hashlib.sha256()
-    for rel in sorted(tuple(f for f in SOURCES if f not in TRAINING_ONLY) + tuple(f for f in HEADERS if not f.startswith(".."))):
+    for rel in sorted(f for f in SOURCES + HEADERS if f not in TRAINING_ONLY and not f.startswith("..")):
         with open(os.path.join(CSRC, rel), "rb") as f:
             h.update(rel.encode() + b"\0" + f.read())
     return h.hexdigest()[:16]

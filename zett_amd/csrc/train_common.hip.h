@@ -1,0 +1,111 @@
+// train_common.hip.h — the small device / host layer the four training units (train_ops.hip, train_step.hip, train_loss.hip,
+// train_embed.hip) share: the zett_dtype -> storage-type map, element accessors over gemm.hip.h's conversions (to_lo, lo_to_f32,
+// pack2_lo, unpack2_lo: widen on load — bf16 by the 16-bit left shift —, round to nearest even on store), the reductions, the id
+// read and the dtype dispatch of the launches.  The device helpers here hold only conversions and additions, so a caller's
+// `#pragma clang fp contract(off)` keeps its meaning.  Training only (zett_amd/build.py TRAINING_ONLY): no forward source includes it.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <type_traits>
+
+#include "../../include/zett_hip.h"
+#include "gemm.hip.h"
+
+namespace zett {
+
+// ---- element types: fp32 / f16 / bf16 storage ----------------------------------------------------------------------------------
+template <int DT> struct Elem;
+template <> struct Elem<ZETT_F32> { using type = float; };
+template <> struct Elem<ZETT_F16> { using type = f16_t; };
+template <> struct Elem<ZETT_BF16> { using type = bf16_t; };
+template <int DT> using elem_t = typename Elem<DT>::type;
+
+template <typename T> __device__ __forceinline__ float load1(const T* p) { return lo_to_f32<T>(*p); }
+template <typename T> __device__ __forceinline__ void store1(T* p, float v) { *p = to_lo<T>(v); }
+
+// four consecutive elements, p aligned to four elements: one 16-byte (fp32) or 8-byte (16-bit) access
+template <typename T> __device__ __forceinline__ float4 load4(const T* p) {
+    if constexpr (std::is_same<T, float>::value) {
+        return *(const float4*)p;
+    } else {
+        const uint2 u = *(const uint2*)p;
+        float4 v;
+        unpack2_lo<T>(u.x, v.x, v.y);
+        unpack2_lo<T>(u.y, v.z, v.w);
+        return v;
+    }
+}
+template <typename T> __device__ __forceinline__ void store4(T* p, float4 v) {
+    if constexpr (std::is_same<T, float>::value) *(float4*)p = v;
+    else *(uint2*)p = make_uint2(pack2_lo<T>(v.x, v.y), pack2_lo<T>(v.z, v.w));
+}
+
+// W elements moved by one access (train_embed.hip: 1, 4 or 8), and their conversion.  Equal types copy the bits and never go through
+// float: a bf16 -> bf16 or f16 -> f16 lookup keeps NaN payloads and signalling bits.
+template <typename T, int W> struct alignas(sizeof(T) * W) Pack { T v[W]; };
+template <typename TO, typename TI> struct Convert { static __device__ __forceinline__ TO go(TI x) { return to_lo<TO>(lo_to_f32<TI>(x)); } };
+template <typename T> struct Convert<T, T> { static __device__ __forceinline__ T go(T x) { return x; } };
+
+__device__ __forceinline__ int64_t load_id(const void* ids, int ids64, int64_t i) {
+    return ids64 ? ((const int64_t*)ids)[i] : (int64_t)((const int32_t*)ids)[i];
+}
+
+// ---- reductions -----------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+// The two sums of a 256-thread workgroup differ in how the four wave results are added, and the bits of their callers depend on it:
+// they are not interchangeable.
+// left to right, ((r0 + r1) + r2) + r3: train_ops.hip (LayerNorm forward statistics, rowdot)
+__device__ __forceinline__ float block_sum_ltr(float v, float* red /* [4] */) {
+    v = wave_sum(v);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return red[0] + red[1] + red[2] + red[3];
+}
+// pairwise, (r0 + r1) + (r2 + r3): train_step.hip (the sums of squares behind the gradient norm)
+__device__ __forceinline__ float block_sum_pairwise(float v, float* red /* [4] */) {
+    v = wave_sum(v);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return (red[0] + red[1]) + (red[2] + red[3]);
+}
+// 256 threads, a binary tree over LDS
+__device__ __forceinline__ double block_sum_f64(double v, double* red /* [256] */) {
+    red[threadIdx.x] = v;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+        __syncthreads();
+    }
+    const double s = red[0];
+    __syncthreads();
+    return s;
+}
+
+// ---- host side ------------------------------------------------------------------------------------------------------------------
+inline bool is_dtype(int32_t d) { return d == ZETT_F32 || d == ZETT_F16 || d == ZETT_BF16; }
+
+// f(std::integral_constant<int, dtype>{}): a checked (is_dtype) runtime dtype code as a compile-time constant, e.g.
+//     with_dtype(d, [&](auto dt) { hipLaunchKernelGGL((kernel<decltype(dt)::value>), ...); });
+template <typename F> inline void with_dtype(int32_t dtype, F&& f) {
+    if (dtype == ZETT_F32) f(std::integral_constant<int, ZETT_F32>{});
+    else if (dtype == ZETT_F16) f(std::integral_constant<int, ZETT_F16>{});
+    else f(std::integral_constant<int, ZETT_BF16>{});
+}
+
+// Declared here, DEFINED in train_loss.hip, which holds the one column-sum kernel and the one converting-copy kernel of the training
+// units: out[c] (+)= sum_r in[r, c], and out[r, c] = convert(in[r, c]) with columns [cols, cols_padded) zero.  train_ops.hip
+// (zett_op_colsum_f32, the general path of zett_op_convert_lo) links against them; they are internal to the library (hidden).
+// Arguments are the callers' to check.
+__attribute__((visibility("hidden"))) void launch_colsum(int32_t dtype, const void* in, int64_t ld, int64_t rows, int cols, float* out, int accumulate, hipStream_t st);
+__attribute__((visibility("hidden"))) void launch_cast(int32_t in_dtype, int32_t out_dtype, const void* in, int64_t ld_in, void* out, int64_t ld_out, int64_t rows, int cols,
+                                                       int cols_padded, hipStream_t st);
+
+}  // namespace zett

@@ -16,6 +16,7 @@
 
 #include "../../include/zett_hip.h"
 #include "common.hip.h"
+#include "train_common.hip.h"
 
 using namespace zett;
 
@@ -26,23 +27,6 @@ constexpr int kListMax = ZETT_SPLICE_MAX_ROWS;        // the longest list: the t
 constexpr int kMaxGrid = 1 << 18;
 static_assert(kChunk == 64, "a chunk is one wave of positions: the plan's tile and the sum's position register are 64 lanes wide");
 
-// ---- element types: fp32 / f16 / bf16 storage --------------------------------------------------------------------------------
-struct bf16 { uint16_t u; };
-template <typename T, int W> struct alignas(sizeof(T) * W) Pack { T v[W]; };          // W elements moved by one access
-
-__device__ __forceinline__ float to_f32(float x) { return x; }
-__device__ __forceinline__ float to_f32(_Float16 x) { return (float)x; }
-__device__ __forceinline__ float to_f32(bf16 x) { return __uint_as_float((uint32_t)x.u << 16); }
-template <typename T> __device__ __forceinline__ T from_f32(float x);
-template <> __device__ __forceinline__ float from_f32<float>(float x) { return x; }
-template <> __device__ __forceinline__ _Float16 from_f32<_Float16>(float x) { return (_Float16)x; }                                  // round to nearest even
-template <> __device__ __forceinline__ bf16 from_f32<bf16>(float x) { return bf16{__builtin_bit_cast(uint16_t, (__bf16)x)}; }      // round to nearest even
-template <typename TO, typename TI> struct Convert { static __device__ __forceinline__ TO go(TI x) { return from_f32<TO>(to_f32(x)); } };
-template <typename T> struct Convert<T, T> { static __device__ __forceinline__ T go(T x) { return x; } };          // equal types: the bits
-
-__device__ __forceinline__ int64_t load_id(const void* ids, int ids64, int64_t i) {
-    return ids64 ? ((const int64_t*)ids)[i] : (int64_t)((const int32_t*)ids)[i];
-}
 __device__ __forceinline__ int wave_index() { return __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); }
 
 // ---- splice: listed rows from the source (or zero), every other row copied or left alone ----------------------------------------
@@ -82,11 +66,8 @@ __global__ __launch_bounds__(256) void splice_rows_kernel(const float* __restric
             for (int c = tail + lane; c < e; c += 64) o[c] = x[c];
         } else if (src) {
             const TS* y = src + (int64_t)list.ref[j] * ld_src + col0;
-            for (int c = lane * 4; c < tail; c += 256) {
-                const Pack<TS, 4> s = *(const Pack<TS, 4>*)(y + c);
-                *(float4*)(o + c) = make_float4(to_f32(s.v[0]), to_f32(s.v[1]), to_f32(s.v[2]), to_f32(s.v[3]));
-            }
-            for (int c = tail + lane; c < e; c += 64) o[c] = to_f32(y[c]);
+            for (int c = lane * 4; c < tail; c += 256) *(float4*)(o + c) = load4(y + c);
+            for (int c = tail + lane; c < e; c += 64) o[c] = load1(y + c);
         } else {
             for (int c = lane * 4; c < tail; c += 256) *(float4*)(o + c) = make_float4(0.f, 0.f, 0.f, 0.f);
             for (int c = tail + lane; c < e; c += 64) o[c] = 0.f;
@@ -321,7 +302,7 @@ __global__ __launch_bounds__(256) void embed_bwd_sum_kernel(const TG* __restrict
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
 #pragma unroll
-                for (int i = 0; i < W; ++i) acc[i] = k + u < n ? acc[i] + to_f32(x[u].v[i]) : acc[i];
+                for (int i = 0; i < W; ++i) acc[i] = k + u < n ? acc[i] + lo_to_f32<TG>(x[u].v[i]) : acc[i];
             }
         }
         if (live) store_f32<W>(dst + col, acc);
@@ -362,42 +343,35 @@ __global__ __launch_bounds__(256) void embed_bwd_fin_kernel(const float* __restr
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------------------------
-bool known_dtype(int32_t d) { return d == ZETT_F32 || d == ZETT_F16 || d == ZETT_BF16; }
 int elem_bytes(int32_t d) { return d == ZETT_F32 ? 4 : 2; }
 bool aligned(const void* p, size_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
 int grid_for(int64_t workgroups) { return (int)std::max<int64_t>(1, std::min<int64_t>(workgroups, kMaxGrid)); }
 
+// W elements per access where W is one of the widths the element type takes (8: 16-bit on both sides), one otherwise
 template <typename TI, typename TO>
 void lookup_go(int w, hipStream_t st, const void* table, int64_t ld, int64_t v, int e, const void* ids, int ids64, int64_t t, void* out, int* error_word) {
     const int nvec = e / w;
     int shift = 0;
     while (shift < 8 && (1 << shift) < nvec) ++shift;
     const int grid = grid_for((t + (256 >> shift) - 1) / (256 >> shift));
-#define GO(W) hipLaunchKernelGGL((embed_lookup_kernel<TI, TO, W>), dim3(grid), dim3(256), 0, st, (const TI*)table, ld, v, e, ids, ids64, t, (TO*)out, shift, error_word)
+    auto kernel = embed_lookup_kernel<TI, TO, 1>;
+    if (w == 4) kernel = embed_lookup_kernel<TI, TO, 4>;
     if constexpr (sizeof(TI) == 2 && sizeof(TO) == 2) {
-        if (w == 8) { GO(8); return; }
+        if (w == 8) kernel = embed_lookup_kernel<TI, TO, 8>;
     }
-    if (w == 4) GO(4); else GO(1);
-#undef GO
-}
-template <typename TI>
-void lookup_from(int32_t out_dtype, int w, hipStream_t st, const void* table, int64_t ld, int64_t v, int e, const void* ids, int ids64, int64_t t, void* out, int* error_word) {
-    if (out_dtype == ZETT_F32) lookup_go<TI, float>(w, st, table, ld, v, e, ids, ids64, t, out, error_word);
-    else if (out_dtype == ZETT_F16) lookup_go<TI, _Float16>(w, st, table, ld, v, e, ids, ids64, t, out, error_word);
-    else lookup_go<TI, bf16>(w, st, table, ld, v, e, ids, ids64, t, out, error_word);
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, st, (const TI*)table, ld, v, e, ids, ids64, t, (TO*)out, shift, error_word);
 }
 
 template <typename TG>
 void bwd_sum_go(int w, hipStream_t st, const void* g, int e, int64_t v, const int* plan, const PlanLayout& L, float* partials, float* d, int64_t ld_d) {
     const int nslices = (e + 64 * w - 1) / (64 * w);
     const int grid = grid_for(((L.maxch + v) * nslices + 3) / 4);
-#define GO(W) hipLaunchKernelGGL((embed_bwd_sum_kernel<TG, W>), dim3(grid), dim3(256), 0, st, (const TG*)g, e, v, plan + L.offsets, plan + L.mstart, plan + L.mchunk, \
-                                 plan + L.pos, L.maxch, nslices, partials, d, ld_d)
+    auto kernel = embed_bwd_sum_kernel<TG, 1>;
+    if (w == 4) kernel = embed_bwd_sum_kernel<TG, 4>;
     if constexpr (sizeof(TG) == 2) {
-        if (w == 8) { GO(8); return; }
+        if (w == 8) kernel = embed_bwd_sum_kernel<TG, 8>;
     }
-    if (w == 4) GO(4); else GO(1);
-#undef GO
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, st, (const TG*)g, e, v, plan + L.offsets, plan + L.mstart, plan + L.mchunk, plan + L.pos, L.maxch, nslices, partials, d, ld_d);
 }
 
 int plan_args(int64_t t, int64_t v, const void* plan, int64_t plan_bytes, PlanLayout* L) {
@@ -421,7 +395,7 @@ int zett_op_splice_rows(const float* in, int64_t ld_in, float* out, int64_t ld_o
     if (ld_out < e || (in && ld_in < e)) return fail(ZETT_E_INVALID, "a leading dimension is below %d columns", (int)e);
     if (in == out) return fail(ZETT_E_INVALID, "in and out are the same matrix: pass in = NULL to overwrite the rows in place");
     if (src) {
-        if (!known_dtype(src_dtype)) return fail(ZETT_E_INVALID, "unknown source dtype %d", (int)src_dtype);
+        if (!is_dtype(src_dtype)) return fail(ZETT_E_INVALID, "unknown source dtype %d", (int)src_dtype);
         if (n && !ref_rows) return fail(ZETT_E_INVALID, "null argument");
         if (src_rows <= 0 || col0 < 0 || (int64_t)col0 + e > ld_src) return fail(ZETT_E_INVALID, "columns [%d, %d) do not fit the source's leading dimension", (int)col0, (int)(col0 + e));
     }
@@ -445,9 +419,10 @@ int zett_op_splice_rows(const float* in, int64_t ld_in, float* out, int64_t ld_o
     }
     const int copy_all = in != nullptr;
     const int grid = grid_for(((copy_all ? v : (int64_t)n) + 3) / 4);
-#define GO(TS) hipLaunchKernelGGL((splice_rows_kernel<TS>), dim3(grid), dim3(256), 0, st, in, ld_in, out, ld_out, v, (int)e, (const TS*)src, ld_src, (int)col0, copy_all, vec_ok, list)
-    if (!src || src_dtype == ZETT_F32) GO(float); else if (src_dtype == ZETT_F16) GO(_Float16); else GO(bf16);
-#undef GO
+    with_dtype(src ? src_dtype : ZETT_F32, [&](auto dt) {
+        using TS = elem_t<decltype(dt)::value>;
+        hipLaunchKernelGGL(splice_rows_kernel<TS>, dim3(grid), dim3(256), 0, st, in, ld_in, out, ld_out, v, (int)e, (const TS*)src, ld_src, (int)col0, copy_all, vec_ok, list);
+    });
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -455,7 +430,7 @@ int zett_op_splice_rows(const float* in, int64_t ld_in, float* out, int64_t ld_o
 int zett_op_embed_lookup(const void* table, int32_t table_dtype, int64_t ld_table, int64_t v, int32_t e, const void* ids, int32_t ids_bytes, int64_t t, void* out,
                          int32_t out_dtype, int32_t* error_word, void* stream) {
     if (!table || !ids || !out) return fail(ZETT_E_INVALID, "null argument");
-    if (!known_dtype(table_dtype) || !known_dtype(out_dtype)) return fail(ZETT_E_INVALID, "unknown dtype %d -> %d", (int)table_dtype, (int)out_dtype);
+    if (!is_dtype(table_dtype) || !is_dtype(out_dtype)) return fail(ZETT_E_INVALID, "unknown dtype %d -> %d", (int)table_dtype, (int)out_dtype);
     if (ids_bytes != 4 && ids_bytes != 8) return fail(ZETT_E_INVALID, "ids must be int32 or int64");
     if (v <= 0 || e <= 0 || t < 0 || ld_table < e) return fail(ZETT_E_INVALID, "the lookup needs v > 0 rows of e > 0 columns, ld_table >= e and t >= 0 (v = %lld, e = %d, ld = %lld, t = %lld)",
                                                                (long long)v, (int)e, (long long)ld_table, (long long)t);
@@ -464,9 +439,11 @@ int zett_op_embed_lookup(const void* table, int32_t table_dtype, int64_t ld_tabl
     int w = (table_dtype != ZETT_F32 && out_dtype != ZETT_F32) ? 8 : 4;
     while (w > 1 && !(e % w == 0 && ld_table % w == 0 && aligned(table, w * elem_bytes(table_dtype)) && aligned(out, w * elem_bytes(out_dtype)))) w = w == 8 ? 4 : 1;
     hipStream_t st = (hipStream_t)stream;
-    if (table_dtype == ZETT_F32) lookup_from<float>(out_dtype, w, st, table, ld_table, v, e, ids, ids_bytes == 8, t, out, error_word);
-    else if (table_dtype == ZETT_F16) lookup_from<_Float16>(out_dtype, w, st, table, ld_table, v, e, ids, ids_bytes == 8, t, out, error_word);
-    else lookup_from<bf16>(out_dtype, w, st, table, ld_table, v, e, ids, ids_bytes == 8, t, out, error_word);
+    with_dtype(table_dtype, [&](auto it) {
+        with_dtype(out_dtype, [&](auto ot) {
+            lookup_go<elem_t<decltype(it)::value>, elem_t<decltype(ot)::value>>(w, st, table, ld_table, v, e, ids, ids_bytes == 8, t, out, error_word);
+        });
+    });
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -511,7 +488,7 @@ int zett_op_embed_lookup_bwd(const void* g, int32_t g_dtype, int64_t t, int64_t 
     PlanLayout L;
     if (int rc = plan_args(t, v, plan, plan_bytes, &L)) return rc;
     if ((t && !g) || !partials || !d_table) return fail(ZETT_E_INVALID, "null argument");
-    if (!known_dtype(g_dtype)) return fail(ZETT_E_INVALID, "unknown gradient dtype %d", (int)g_dtype);
+    if (!is_dtype(g_dtype)) return fail(ZETT_E_INVALID, "unknown gradient dtype %d", (int)g_dtype);
     if (e <= 0 || ld_d < e) return fail(ZETT_E_INVALID, "ld_d %lld < %d columns", (long long)ld_d, (int)e);
     if (partial_bytes < L.maxch * (int64_t)e * 4) return fail(ZETT_E_INVALID, "partials holds %lld bytes, %lld are needed", (long long)partial_bytes, (long long)(L.maxch * (int64_t)e * 4));
     // columns per lane: 16 bytes of g; 4 columns (8 bytes of a 16-bit g) where 8 do not divide e; else one
@@ -521,9 +498,7 @@ int zett_op_embed_lookup_bwd(const void* g, int32_t g_dtype, int64_t t, int64_t 
     while (vec > 1 && !(e % vec == 0 && aligned(g, vec * gb))) vec = vec == 8 ? 4 : 1;
     hipStream_t st = (hipStream_t)stream;
     const int* w = (const int*)plan;
-    if (g_dtype == ZETT_F32) bwd_sum_go<float>(vec, st, g, e, v, w, L, partials, d_table, ld_d);
-    else if (g_dtype == ZETT_F16) bwd_sum_go<_Float16>(vec, st, g, e, v, w, L, partials, d_table, ld_d);
-    else bwd_sum_go<bf16>(vec, st, g, e, v, w, L, partials, d_table, ld_d);
+    with_dtype(g_dtype, [&](auto dt) { bwd_sum_go<elem_t<decltype(dt)::value>>(vec, st, g, e, v, w, L, partials, d_table, ld_d); });
     const int wf = vec_out ? 4 : 1;
     const int nslices = (e + 64 * wf - 1) / (64 * wf);
     const int grid = grid_for((L.maxch * nslices + 3) / 4);

@@ -21,6 +21,7 @@
 
 #include "../../include/zett_hip.h"
 #include "common.hip.h"
+#include "train_common.hip.h"
 
 using namespace zett;
 
@@ -32,36 +33,6 @@ constexpr int kOnceMaxVec = 8;                // float4 per lane the read-once p
 constexpr int kMaxGrid = 2048;
 constexpr float kMaskFill = -100000.f;        // NEGATIVE_INF_FILL_VALUE, zett/utils.py:23
 static_assert(kOnceMaxVec * kBlock * 4 == ZETT_CE_ONCE_MAX_COLS, "header and kernel disagree on the read-once limit");
-
-// ---- 16-bit storage -------------------------------------------------------------------------------------------------------
-template <int DT> struct Elem { using type = float; };
-template <> struct Elem<ZETT_F16> { using type = _Float16; };
-template <> struct Elem<ZETT_BF16> { using type = uint16_t; };
-
-template <int DT> __device__ __forceinline__ float load1(const typename Elem<DT>::type* p);
-template <> __device__ __forceinline__ float load1<ZETT_F32>(const float* p) { return *p; }
-template <> __device__ __forceinline__ float load1<ZETT_F16>(const _Float16* p) { return (float)*p; }
-template <> __device__ __forceinline__ float load1<ZETT_BF16>(const uint16_t* p) { return __uint_as_float((uint32_t)*p << 16); }
-
-template <int DT> __device__ __forceinline__ void store1(typename Elem<DT>::type* p, float v);
-template <> __device__ __forceinline__ void store1<ZETT_F32>(float* p, float v) { *p = v; }
-template <> __device__ __forceinline__ void store1<ZETT_F16>(_Float16* p, float v) { *p = (_Float16)v; }
-template <> __device__ __forceinline__ void store1<ZETT_BF16>(uint16_t* p, float v) { *p = __builtin_bit_cast(uint16_t, (__bf16)v); }      // round to nearest even
-
-// four consecutive values, p aligned to four elements: one 16-byte (fp32) or 8-byte (16-bit) store
-template <int DT> __device__ __forceinline__ void store4(typename Elem<DT>::type* p, float4 v);
-template <> __device__ __forceinline__ void store4<ZETT_F32>(float* p, float4 v) { *(float4*)p = v; }
-template <> __device__ __forceinline__ void store4<ZETT_F16>(_Float16* p, float4 v) {
-    typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-    const half4 h = {(_Float16)v.x, (_Float16)v.y, (_Float16)v.z, (_Float16)v.w};
-    *(half4*)p = h;
-}
-template <> __device__ __forceinline__ void store4<ZETT_BF16>(uint16_t* p, float4 v) {
-    typedef float f32x4_t __attribute__((ext_vector_type(4)));
-    typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
-    const f32x4_t f = {v.x, v.y, v.z, v.w};
-    *(uint2*)p = __builtin_bit_cast(uint2, __builtin_convertvector(f, bf16x4_t));
-}
 
 // ---- the running statistics of a softmax row ---------------------------------------------------------------------------------
 struct RowStat {
@@ -148,7 +119,7 @@ __global__ __launch_bounds__(kBlock) void ce_rows_kernel(float* logits, int64_t 
                                                          float* __restrict__ lse_out, int32_t* __restrict__ argmax_out) {
     constexpr int GD = GT < 0 ? ZETT_F32 : GT;
     constexpr int kUnroll = 4;                         // vectors per lane in flight in the loops of the two-read path
-    using G = typename Elem<GD>::type;
+    using G = elem_t<GD>;
     __shared__ float sm[kWaves], ss[kWaves];
     __shared__ int si[kWaves];
     const int tid = threadIdx.x;
@@ -192,7 +163,7 @@ __global__ __launch_bounds__(kBlock) void ce_rows_kernel(float* logits, int64_t 
 #pragma unroll
                 for (int i = 0; i < NV; ++i) {
                     const int q = i * kBlock + tid;
-                    if (q < nvec) store4<GD>(g + 4 * q, o[i]);
+                    if (q < nvec) store4(g + 4 * q, o[i]);
                 }
             } else {
                 for (int q0 = tid; q0 < nvec; q0 += kUnroll * kBlock) {
@@ -204,25 +175,13 @@ __global__ __launch_bounds__(kBlock) void ce_rows_kernel(float* logits, int64_t 
 #pragma unroll
                     for (int j = 0; j < kUnroll; ++j) {
                         const int q = q0 + j * kBlock;
-                        if (q < nvec) store4<GD>(g + 4 * q, zz[j]);
+                        if (q < nvec) store4(g + 4 * q, zz[j]);
                     }
                 }
             }
         }
         __syncthreads();          // the next row reuses the LDS words
     }
-}
-
-__device__ __forceinline__ double block_sum_f64(double v, double* red /* [256] */) {
-    red[threadIdx.x] = v;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-        __syncthreads();
-    }
-    const double s = red[0];
-    __syncthreads();
-    return s;
 }
 
 // record = { loss, sum w, 1 / sum w, int32 n_correct, int32 n_counted, 0, 0, 0 }: one workgroup, double sums in a fixed order
@@ -270,75 +229,81 @@ __global__ __launch_bounds__(256) void ce_addend_kernel(const float* __restrict_
 }
 
 // out[c] (+)= sum_r g[r, c]: a workgroup takes 64 columns, its four waves every fourth row; the four partial sums are added in a fixed order
-template <int GT>
-__global__ __launch_bounds__(256) void ce_colsum_kernel(const void* __restrict__ gin, int64_t ld_g, int64_t rows, int v, float* __restrict__ out, int accumulate) {
-    using G = typename Elem<GT>::type;
+// (the column sum of zett_op_colsum_f32 too: launch_colsum)
+template <typename G>
+__global__ __launch_bounds__(256) void colsum_kernel(const G* __restrict__ g, int64_t ld_g, int64_t rows, int v, float* __restrict__ out, int accumulate) {
     __shared__ float part[4][64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int c = blockIdx.x * 64 + lane;
     float s = 0.f;
     if (c < v)
-        for (int64_t r = wave; r < rows; r += 4) s += load1<GT>((const G*)gin + r * ld_g + c);
+        for (int64_t r = wave; r < rows; r += 4) s += load1(g + r * ld_g + c);
     part[wave][lane] = s;
     __syncthreads();
     if (wave == 0 && c < v) {
-#pragma clang fp contract(off)
         const float t = (part[0][lane] + part[1][lane]) + (part[2][lane] + part[3][lane]);
         out[c] = accumulate ? out[c] + t : t;
     }
 }
 
-// out[i] = in[i] * (upstream[0] * record[2]), written as OT
-template <int OT>
+// out[i] = in[i] * (upstream[0] * record[2]), written as O
+template <typename O>
 __global__ __launch_bounds__(256) void ce_scale_kernel(const float* __restrict__ in, int64_t n, const float* __restrict__ record, const float* __restrict__ upstream,
-                                                       void* __restrict__ out, int vec_ok) {
-    using O = typename Elem<OT>::type;
+                                                       O* __restrict__ o, int vec_ok) {
     const float f = upstream[0] * record[2];
-    O* o = (O*)out;
     const int64_t stride = (int64_t)gridDim.x * 256, t0 = (int64_t)blockIdx.x * 256 + threadIdx.x;
     int64_t tail = 0;
     if (vec_ok) {
         tail = n & ~(int64_t)3;
         for (int64_t i = t0 * 4; i < tail; i += stride * 4) {
             const float4 x = *(const float4*)(in + i);
-            store4<OT>(o + i, make_float4(x.x * f, x.y * f, x.z * f, x.w * f));
+            store4(o + i, make_float4(x.x * f, x.y * f, x.z * f, x.w * f));
         }
     }
-    for (int64_t i = tail + t0; i < n; i += stride) store1<OT>(o + i, in[i] * f);
+    for (int64_t i = tail + t0; i < n; i += stride) store1(o + i, in[i] * f);
 }
 
-// out[r, c] = (OT) in[r, c] for c < cols, 0 for cols <= c < cols_padded
-template <int IT, int OT>
-__global__ __launch_bounds__(256) void ce_cast_kernel(const void* __restrict__ in, int64_t ld_in, void* __restrict__ out, int64_t ld_out, int64_t rows, int cols,
-                                                      int cols_padded) {
-    using I = typename Elem<IT>::type;
-    using O = typename Elem<OT>::type;
+// out[r, c] = (O) in[r, c] for c < cols, 0 for cols <= c < cols_padded: every pair of types goes through float
+// (the general path of zett_op_convert_lo too: launch_cast)
+template <typename I, typename O>
+__global__ __launch_bounds__(256) void cast_kernel(const I* __restrict__ in, int64_t ld_in, O* __restrict__ out, int64_t ld_out, int64_t rows, int cols, int cols_padded) {
     const int64_t total = rows * cols_padded;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
         const int64_t r = i / cols_padded;
         const int c = (int)(i - r * cols_padded);
-        store1<OT>((O*)out + r * ld_out + c, c < cols ? load1<IT>((const I*)in + r * ld_in + c) : 0.f);
+        store1(out + r * ld_out + c, c < cols ? load1(in + r * ld_in + c) : 0.f);
     }
 }
-
-bool is_dtype(int32_t d) { return d == ZETT_F32 || d == ZETT_F16 || d == ZETT_BF16; }
 
 template <int NV>
 void rows_go(int gt, int grid, hipStream_t st, float* logits, int64_t ld_z, const int32_t* labels, const float* weight, int64_t rows, int v, int v_padded, void* g,
              int64_t ld_g, float* row_loss, float* lse, int32_t* argmax) {
-#define GO(GT) hipLaunchKernelGGL((ce_rows_kernel<NV, GT>), dim3(grid), dim3(kBlock), 0, st, logits, ld_z, labels, weight, rows, v, v_padded, g, ld_g, row_loss, lse, argmax)
-    if (!g) GO(-1); else if (gt == ZETT_F32) GO(ZETT_F32); else if (gt == ZETT_F16) GO(ZETT_F16); else GO(ZETT_BF16);
-#undef GO
-}
-
-template <int IT>
-void cast_go(int ot, int grid, hipStream_t st, const void* in, int64_t ld_in, void* out, int64_t ld_out, int64_t rows, int cols, int cols_padded) {
-#define GO(OT) hipLaunchKernelGGL((ce_cast_kernel<IT, OT>), dim3(grid), dim3(256), 0, st, in, ld_in, out, ld_out, rows, cols, cols_padded)
-    if (ot == ZETT_F32) GO(ZETT_F32); else if (ot == ZETT_F16) GO(ZETT_F16); else GO(ZETT_BF16);
-#undef GO
+    const auto go = [&](auto dt) {
+        hipLaunchKernelGGL((ce_rows_kernel<NV, decltype(dt)::value>), dim3(grid), dim3(kBlock), 0, st, logits, ld_z, labels, weight, rows, v, v_padded, g, ld_g, row_loss, lse, argmax);
+    };
+    if (!g) go(std::integral_constant<int, -1>{});
+    else with_dtype(gt, go);
 }
 
 }  // namespace
+
+void zett::launch_colsum(int32_t dtype, const void* in, int64_t ld, int64_t rows, int cols, float* out, int accumulate, hipStream_t st) {
+    with_dtype(dtype, [&](auto dt) {
+        using G = elem_t<decltype(dt)::value>;
+        hipLaunchKernelGGL(colsum_kernel<G>, dim3((cols + 63) / 64), dim3(256), 0, st, (const G*)in, ld, rows, cols, out, accumulate);
+    });
+}
+
+void zett::launch_cast(int32_t in_dtype, int32_t out_dtype, const void* in, int64_t ld_in, void* out, int64_t ld_out, int64_t rows, int cols, int cols_padded, hipStream_t st) {
+    const int grid = (int)std::min<int64_t>((rows * cols_padded + 255) / 256, kMaxGrid * 4);
+    with_dtype(in_dtype, [&](auto it) {
+        with_dtype(out_dtype, [&](auto ot) {
+            using I = elem_t<decltype(it)::value>;
+            using O = elem_t<decltype(ot)::value>;
+            hipLaunchKernelGGL((cast_kernel<I, O>), dim3(grid), dim3(256), 0, st, (const I*)in, ld_in, (O*)out, ld_out, rows, cols, cols_padded);
+        });
+    });
+}
 
 extern "C" {
 
@@ -369,13 +334,14 @@ int zett_op_ce_rows(float* logits, int64_t ld_z, const int32_t* labels, const fl
     const int grid = (int)std::min<int64_t>(rows, 65536);
     hipStream_t st = (hipStream_t)stream;
     const int per_lane = once ? (v_padded / 4 + kBlock - 1) / kBlock : 0;
-#define GO(NV) rows_go<NV>(g_dtype, grid, st, logits, ld_z, labels, weight, rows, v, v_padded, g, ld_g, row_loss, lse, argmax)
-    if (!once) GO(0);
-    else if (per_lane <= 1) GO(1);
-    else if (per_lane <= 2) GO(2);
-    else if (per_lane <= 4) GO(4);
-    else GO(8);
-#undef GO
+    auto go = rows_go<0>;                              // the two-read path
+    if (once) {
+        if (per_lane <= 1) go = rows_go<1>;
+        else if (per_lane <= 2) go = rows_go<2>;
+        else if (per_lane <= 4) go = rows_go<4>;
+        else go = rows_go<8>;
+    }
+    go(g_dtype, grid, st, logits, ld_z, labels, weight, rows, v, v_padded, g, ld_g, row_loss, lse, argmax);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -392,11 +358,7 @@ int zett_op_ce_colsum(const void* g, int32_t g_dtype, int64_t ld_g, int64_t rows
     if (!g || !out) return fail(ZETT_E_INVALID, "null argument");
     if (!is_dtype(g_dtype)) return fail(ZETT_E_INVALID, "unknown dtype %d of the gradient operand", (int)g_dtype);
     if (v <= 0 || rows < 0 || ld_g < v) return fail(ZETT_E_INVALID, "bad column-sum shape (rows = %lld, v = %d, ld = %lld)", (long long)rows, (int)v, (long long)ld_g);
-    const dim3 grid((v + 63) / 64);
-    hipStream_t st = (hipStream_t)stream;
-    if (g_dtype == ZETT_F32) hipLaunchKernelGGL(ce_colsum_kernel<ZETT_F32>, grid, dim3(256), 0, st, g, ld_g, rows, v, out, accumulate);
-    else if (g_dtype == ZETT_F16) hipLaunchKernelGGL(ce_colsum_kernel<ZETT_F16>, grid, dim3(256), 0, st, g, ld_g, rows, v, out, accumulate);
-    else hipLaunchKernelGGL(ce_colsum_kernel<ZETT_BF16>, grid, dim3(256), 0, st, g, ld_g, rows, v, out, accumulate);
+    launch_colsum(g_dtype, g, ld_g, rows, v, out, accumulate, (hipStream_t)stream);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -408,10 +370,10 @@ int zett_op_ce_scale(const float* in, int64_t n, const float* record, const floa
     if (n == 0) return 0;
     const int vec_ok = ((uintptr_t)in & 15) == 0 && ((uintptr_t)out & (out_dtype == ZETT_F32 ? 15 : 7)) == 0;
     const dim3 grid((unsigned)std::min<int64_t>((n + 1023) / 1024, kMaxGrid));
-    hipStream_t st = (hipStream_t)stream;
-    if (out_dtype == ZETT_F32) hipLaunchKernelGGL(ce_scale_kernel<ZETT_F32>, grid, dim3(256), 0, st, in, n, record, upstream, out, vec_ok);
-    else if (out_dtype == ZETT_F16) hipLaunchKernelGGL(ce_scale_kernel<ZETT_F16>, grid, dim3(256), 0, st, in, n, record, upstream, out, vec_ok);
-    else hipLaunchKernelGGL(ce_scale_kernel<ZETT_BF16>, grid, dim3(256), 0, st, in, n, record, upstream, out, vec_ok);
+    with_dtype(out_dtype, [&](auto dt) {
+        using O = elem_t<decltype(dt)::value>;
+        hipLaunchKernelGGL(ce_scale_kernel<O>, grid, dim3(256), 0, (hipStream_t)stream, in, n, record, upstream, (O*)out, vec_ok);
+    });
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -422,11 +384,7 @@ int zett_op_ce_cast(const void* in, int32_t in_dtype, int64_t ld_in, void* out, 
     if (!is_dtype(in_dtype) || !is_dtype(out_dtype)) return fail(ZETT_E_INVALID, "unknown dtype (%d -> %d)", (int)in_dtype, (int)out_dtype);
     if (rows < 0 || cols <= 0 || cols_padded < cols || ld_in < cols || ld_out < cols_padded) return fail(ZETT_E_INVALID, "bad cast shape");
     if (rows == 0) return 0;
-    const int grid = (int)std::min<int64_t>((rows * cols_padded + 255) / 256, kMaxGrid * 4);
-    hipStream_t st = (hipStream_t)stream;
-    if (in_dtype == ZETT_F32) cast_go<ZETT_F32>(out_dtype, grid, st, in, ld_in, out, ld_out, rows, cols, cols_padded);
-    else if (in_dtype == ZETT_F16) cast_go<ZETT_F16>(out_dtype, grid, st, in, ld_in, out, ld_out, rows, cols, cols_padded);
-    else cast_go<ZETT_BF16>(out_dtype, grid, st, in, ld_in, out, ld_out, rows, cols, cols_padded);
+    launch_cast(in_dtype, out_dtype, in, ld_in, out, ld_out, rows, cols, cols_padded, (hipStream_t)stream);
     HIP_TRY(hipGetLastError());
     return 0;
 }

@@ -22,23 +22,11 @@
 #include "common.hip.h"
 #include "gemm.hip.h"
 #include "gemm_launch.hip.h"
+#include "train_common.hip.h"
 
 using namespace zett;
 
 namespace {
-
-__device__ __forceinline__ float t_wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-__device__ __forceinline__ float t_block_sum(float v, float* red /* [4] */) {      // 256 threads
-    v = t_wave_sum(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return red[0] + red[1] + red[2] + red[3];
-}
 
 // ---- transposes / reductions / element-wise ----------------------------------------------------------------------
 // out[c, r] = in[r, c] for r < R; out[c, r] = 0 for R <= r < Rpad   (ld_out >= Rpad)
@@ -58,29 +46,15 @@ __global__ __launch_bounds__(256) void transpose_kernel(const float* __restrict_
     }
 }
 
-// 16-bit operands of the training GEMMs: out[r, c] = lo(in[r, c]) (columns zero-padded to cols_padded), and the transposed
-// form out[c, r] = lo(in[r, c]) (rows zero-padded to rows_padded): conversion fused with the layout change
-template <typename T>
-__global__ void convert_lo_kernel(const float* __restrict__ in, int ld_in, T* __restrict__ out, int ld_out, int64_t rows, int cols, int cols_padded) {
-    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t n = rows * cols_padded, stride = (int64_t)gridDim.x * blockDim.x;
-    for (; i < n; i += stride) {
-        const int64_t r = i / cols_padded;
-        const int c = (int)(i % cols_padded);
-        out[r * ld_out + c] = to_lo<T>(c < cols ? in[r * ld_in + c] : 0.f);
-    }
-}
-// the common case (no column padding, widths multiples of 4): 16-byte loads, 8-byte stores, one row per workgroup pass
+// 16-bit operands of the training GEMMs: out[r, c] = lo(in[r, c]) (columns zero-padded to cols_padded: launch_cast), and the
+// transposed form out[c, r] = lo(in[r, c]) (rows zero-padded to rows_padded): conversion fused with the layout change.
+// convert_lo4_kernel is the common case of the first (no column padding, widths multiples of 4): 16-byte loads, 8-byte stores, one
+// row per workgroup pass
 template <typename T>
 __global__ __launch_bounds__(256) void convert_lo4_kernel(const float* __restrict__ in, int ld_in, T* __restrict__ out, int ld_out, int64_t rows, int cols) {
     const int c4 = cols >> 2;
     for (int64_t r = blockIdx.x; r < rows; r += gridDim.x) {
-        const float4* src = (const float4*)(in + r * ld_in);
-        uint2* dst = (uint2*)(out + r * ld_out);
-        for (int c = threadIdx.x; c < c4; c += 256) {
-            const float4 v = src[c];
-            dst[c] = make_uint2(pack2_lo<T>(v.x, v.y), pack2_lo<T>(v.z, v.w));
-        }
+        for (int c = threadIdx.x; c < c4; c += 256) store4(out + r * ld_out + 4 * c, load4(in + r * ld_in + 4 * c));
     }
 }
 __device__ __forceinline__ float gelu_fwd1(float x, int kind) { return kind == 1 ? gelu_tanh_f(x) : gelu_erf_f(x); }
@@ -93,36 +67,17 @@ __device__ __forceinline__ float gelu_grad1(float x, int kind) {
     return 0.5f * (1.0f + erff(x * 0.70710678118654752440f)) + x * 0.3989422804014327f * expf(-0.5f * x * x);       // Phi(x) + x phi(x)
 }
 
-// four consecutive values of a row as floats: fp32 (16-byte load) or 16-bit (8-byte load) storage; element-wise tail at the edges
-template <typename TIn>
-__device__ __forceinline__ float4 load4(const TIn* __restrict__ row, int c, int C, bool vec_ok);
-template <>
-__device__ __forceinline__ float4 load4<float>(const float* __restrict__ row, int c, int C, bool vec_ok) {
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (c + 3 < C && vec_ok) return *(const float4*)(row + c);
-    if (c < C) v.x = row[c];
-    if (c + 1 < C) v.y = row[c + 1];
-    if (c + 2 < C) v.z = row[c + 2];
-    if (c + 3 < C) v.w = row[c + 3];
-    return v;
-}
+// four consecutive values of a row as floats: one access where all four exist and the row allows it, element-wise tail at the edges
 template <typename T>
-__device__ __forceinline__ float4 load4_lo(const T* __restrict__ row, int c, int C, bool vec_ok) {
+__device__ __forceinline__ float4 load4_edge(const T* __restrict__ row, int c, int C, bool vec_ok) {
     float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (c + 3 < C && vec_ok) {
-        const uint2 u = *(const uint2*)(row + c);
-        unpack2_lo<T>(u.x, v.x, v.y);
-        unpack2_lo<T>(u.y, v.z, v.w);
-        return v;
-    }
-    if (c < C) v.x = lo_to_f32<T>(row[c]);
-    if (c + 1 < C) v.y = lo_to_f32<T>(row[c + 1]);
-    if (c + 2 < C) v.z = lo_to_f32<T>(row[c + 2]);
-    if (c + 3 < C) v.w = lo_to_f32<T>(row[c + 3]);
+    if (c + 3 < C && vec_ok) return load4(row + c);
+    if (c < C) v.x = load1(row + c);
+    if (c + 1 < C) v.y = load1(row + c + 1);
+    if (c + 2 < C) v.z = load1(row + c + 2);
+    if (c + 3 < C) v.w = load1(row + c + 3);
     return v;
 }
-template <> __device__ __forceinline__ float4 load4<bf16_t>(const bf16_t* __restrict__ row, int c, int C, bool vec_ok) { return load4_lo<bf16_t>(row, c, C, vec_ok); }
-template <> __device__ __forceinline__ float4 load4<f16_t>(const f16_t* __restrict__ row, int c, int C, bool vec_ok) { return load4_lo<f16_t>(row, c, C, vec_ok); }
 
 // 64 x 64 tiles through LDS: wide loads along the input rows (fp32 or, TIn = T, an operand that is already 16-bit), 8-byte stores
 // (four converted values) along the output rows.
@@ -144,13 +99,13 @@ __global__ __launch_bounds__(256) void transpose_lo_kernel(const TIn* __restrict
         const int r = r0 + rr, c = c0 + cc;
         float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
         if (r < R) {
-            v = load4<TIn>(in + (size_t)r * ld_in, c, C, in_vec);
+            v = load4_edge(in + (size_t)r * ld_in, c, C, in_vec);
             if (act_z) {
-                const float4 z = load4<float>(act_z + (size_t)r * ld_z, c, C, z_vec);
+                const float4 z = load4_edge(act_z + (size_t)r * ld_z, c, C, z_vec);
                 v.x *= gelu_grad1(z.x, act_kind); v.y *= gelu_grad1(z.y, act_kind); v.z *= gelu_grad1(z.z, act_kind); v.w *= gelu_grad1(z.w, act_kind);
             }
             if (plain) {
-                if (c + 3 < C && ((ld_plain & 3) == 0)) *(uint2*)(plain + (size_t)r * ld_plain + c) = make_uint2(pack2_lo<T>(v.x, v.y), pack2_lo<T>(v.z, v.w));
+                if (c + 3 < C && ((ld_plain & 3) == 0)) store4(plain + (size_t)r * ld_plain + c, v);
                 else {
                     if (c < C) plain[(size_t)r * ld_plain + c] = to_lo<T>(v.x);
                     if (c + 1 < C) plain[(size_t)r * ld_plain + c + 1] = to_lo<T>(v.y);
@@ -173,24 +128,9 @@ __global__ __launch_bounds__(256) void transpose_lo_kernel(const TIn* __restrict
         const int c = c0 + cc, r = r0 + rr;
         if (c >= C || r >= Rpad) continue;
         if (r + 3 < Rpad && ((ld_out & 3) == 0))
-            *(uint2*)(out + (size_t)c * ld_out + r) = make_uint2(pack2_lo<T>(tile[rr][cc], tile[rr + 1][cc]), pack2_lo<T>(tile[rr + 2][cc], tile[rr + 3][cc]));
+            store4(out + (size_t)c * ld_out + r, make_float4(tile[rr][cc], tile[rr + 1][cc], tile[rr + 2][cc], tile[rr + 3][cc]));
         else
             for (int j = 0; j < 4 && r + j < Rpad; ++j) out[(size_t)c * ld_out + r + j] = to_lo<T>(tile[rr + j][cc]);
-    }
-}
-
-// out[c] (+)= sum_r in[r, c]: one workgroup per 64 columns, rows strided over the four waves
-__global__ __launch_bounds__(256) void colsum_kernel(const float* __restrict__ in, int ld, int R, int C, float* __restrict__ out, int accumulate) {
-    __shared__ float part[4][64];
-    const int c = blockIdx.x * 64 + (threadIdx.x & 63), w = threadIdx.x >> 6;
-    float s = 0.f;
-    if (c < C)
-        for (int r = w; r < R; r += 4) s += in[(size_t)r * ld + c];
-    part[w][threadIdx.x & 63] = s;
-    __syncthreads();
-    if (w == 0 && c < C) {
-        const float t = (part[0][threadIdx.x] + part[1][threadIdx.x]) + (part[2][threadIdx.x] + part[3][threadIdx.x]);
-        out[c] = accumulate ? out[c] + t : t;
     }
 }
 
@@ -238,7 +178,7 @@ __global__ __launch_bounds__(256) void rowdot_kernel(const float* __restrict__ a
     if (r >= R) return;
     float s = 0.f;
     for (int c = threadIdx.x; c < C; c += 256) s += a[(size_t)r * ld + c] * w[c];
-    const float t = t_block_sum(s, red);
+    const float t = block_sum_ltr(s, red);
     if (threadIdx.x == 0) out[r] = t + (b ? b[0] : 0.f);
 }
 
@@ -260,7 +200,7 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ x
             v[j] = c < H ? *(const float4*)(x + (size_t)r * ld + c) : make_float4(0.f, 0.f, 0.f, 0.f);
             s += (v[j].x + v[j].y) + (v[j].z + v[j].w);
         }
-        const float mean = t_block_sum(s, red) / (float)H;
+        const float mean = block_sum_ltr(s, red) / (float)H;
         float q = 0.f;
 #pragma unroll
         for (int j = 0; j < J; ++j) {
@@ -269,7 +209,7 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ x
                 q += (a * a + b * b) + (c * c + d * d);
             }
         }
-        const float rstd = 1.0f / sqrtf(t_block_sum(q, red) / (float)H + eps);
+        const float rstd = 1.0f / sqrtf(block_sum_ltr(q, red) / (float)H + eps);
         if (tid == 0) { stats[2 * (size_t)r] = mean; stats[2 * (size_t)r + 1] = rstd; }
 #pragma unroll
         for (int j = 0; j < J; ++j) {
@@ -279,7 +219,7 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ x
                 const float4 o = make_float4(ln_affine(v[j].x, mean, rstd, g.x, b.x), ln_affine(v[j].y, mean, rstd, g.y, b.y),
                                              ln_affine(v[j].z, mean, rstd, g.z, b.z), ln_affine(v[j].w, mean, rstd, g.w, b.w));
                 *(float4*)(y + (size_t)r * H + c) = o;
-                if (y_lo) *(uint2*)(y_lo + (size_t)r * H + c) = make_uint2(pack2_lo<T>(o.x, o.y), pack2_lo<T>(o.z, o.w));      // the next contraction's operand
+                if (y_lo) store4(y_lo + (size_t)r * H + c, o);      // the next contraction's operand
             }
         }
     }
@@ -328,8 +268,8 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const float* __restrict__ d
                 sgx += (g.x * xh[j].x + g.y * xh[j].y) + (g.z * xh[j].z + g.w * xh[j].w);
             }
         }
-        sg = t_wave_sum(sg);
-        sgx = t_wave_sum(sgx);
+        sg = wave_sum(sg);
+        sgx = wave_sum(sgx);
         if (lane == 0) { red[par][0][wave] = sg; red[par][1][wave] = sgx; }
         __syncthreads();                               // (the other parity's slots are rewritten only after the next barrier)
         const float mg = ((red[par][0][0] + red[par][0][1]) + (red[par][0][2] + red[par][0][3])) / (float)H;
@@ -397,7 +337,7 @@ __global__ __launch_bounds__(256) void gelu_fwd_lo_kernel(const float* __restric
     for (; i < n; i += stride) {
         if (i + 3 < n) {
             const float4 v = *(const float4*)(z + i);
-            *(uint2*)(h + i) = make_uint2(pack2_lo<T>(gelu_fwd1(v.x, kind), gelu_fwd1(v.y, kind)), pack2_lo<T>(gelu_fwd1(v.z, kind), gelu_fwd1(v.w, kind)));
+            store4(h + i, make_float4(gelu_fwd1(v.x, kind), gelu_fwd1(v.y, kind), gelu_fwd1(v.z, kind), gelu_fwd1(v.w, kind)));
         } else {
             for (int64_t j = i; j < n; ++j) h[j] = to_lo<T>(gelu_fwd1(z[j], kind));
         }
@@ -457,7 +397,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const float* __restrict__
                 float p = 0.f;
 #pragma unroll
                 for (int e = 0; e < DV; ++e) p += qr[e] * kr[j][e];
-                sc[j] = t_wave_sum(p) * scaling + bias[j];
+                sc[j] = wave_sum(p) * scaling + bias[j];
                 mx = fmaxf(mx, sc[j]);
             }
         }
@@ -539,7 +479,7 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const float* __restrict__
                 float a = 0.f;
 #pragma unroll
                 for (int e = 0; e < DV; ++e) a += gr[e] * vr[j][e];
-                dp[j] = t_wave_sum(a);
+                dp[j] = wave_sum(a);
                 dot += pr[j] * dp[j];
             }
         }
@@ -586,14 +526,9 @@ __global__ __launch_bounds__(256) void scatter_add_rows_kernel(float* __restrict
 }
 
 // ---- source-embedding gather (A2 + A3) and its backward -----------------------------------------------------------------
-template <int SD> __device__ __forceinline__ float load_src1(const void* base, size_t e);
-template <> __device__ __forceinline__ float load_src1<0>(const void* base, size_t e) { return ((const float*)base)[e]; }
-template <> __device__ __forceinline__ float load_src1<1>(const void* base, size_t e) { return (float)((const _Float16*)base)[e]; }
-template <> __device__ __forceinline__ float load_src1<2>(const void* base, size_t e) { return __uint_as_float(((uint32_t)((const uint16_t*)base)[e]) << 16); }
-
 // x[t] = id < V0 ? sw * src[id] + sb : fallback[id - V0]
-template <int SD>
-__global__ __launch_bounds__(256) void gather_fwd_kernel(const int32_t* __restrict__ ids, int64_t T, const void* __restrict__ src, int e_in, int v0,
+template <typename TS>
+__global__ __launch_bounds__(256) void gather_fwd_kernel(const int32_t* __restrict__ ids, int64_t T, const TS* __restrict__ src, int e_in, int v0,
                                                          const float* __restrict__ fallback, const float* __restrict__ sw, const float* __restrict__ sb,
                                                          float* __restrict__ x) {
     const int64_t t = blockIdx.x;
@@ -602,14 +537,14 @@ __global__ __launch_bounds__(256) void gather_fwd_kernel(const int32_t* __restri
     for (int c = threadIdx.x; c < e_in; c += 256) {
         float v;
         if (id >= v0) v = fallback[(size_t)(id - v0) * e_in + c];
-        else { v = load_src1<SD>(src, (size_t)id * e_in + c); if (sw) v = sw[c] * v + sb[c]; }
+        else { v = load1(src + (size_t)id * e_in + c); if (sw) v = sw[c] * v + sb[c]; }
         x[(size_t)t * e_in + c] = v;
     }
 }
 // dfallback[id - V0] += dx[t] (atomics: few rows); prod[t] = dx[t] * src[id] and keep[t] = dx[t] for source rows, 0 for fallback
 // rows — their column sums are d in_scaler.w and d in_scaler.b
-template <int SD>
-__global__ __launch_bounds__(256) void gather_bwd_kernel(const int32_t* __restrict__ ids, int64_t T, const void* __restrict__ src, int e_in, int v0,
+template <typename TS>
+__global__ __launch_bounds__(256) void gather_bwd_kernel(const int32_t* __restrict__ ids, int64_t T, const TS* __restrict__ src, int e_in, int v0,
                                                          const float* __restrict__ dx, float* __restrict__ dfallback, float* __restrict__ prod,
                                                          float* __restrict__ keep) {
     const int64_t t = blockIdx.x;
@@ -621,7 +556,7 @@ __global__ __launch_bounds__(256) void gather_bwd_kernel(const int32_t* __restri
             atomicAdd(dfallback + (size_t)(id - v0) * e_in + c, g);
             prod[(size_t)t * e_in + c] = 0.f; keep[(size_t)t * e_in + c] = 0.f;
         } else {
-            prod[(size_t)t * e_in + c] = g * load_src1<SD>(src, (size_t)id * e_in + c);
+            prod[(size_t)t * e_in + c] = g * load1(src + (size_t)id * e_in + c);
             keep[(size_t)t * e_in + c] = g;
         }
     }
@@ -741,9 +676,7 @@ int zett_op_convert_lo(int32_t prec, const float* in, int32_t ld_in, void* out, 
         if (prec == ZETT_PREC_F16) hipLaunchKernelGGL(convert_lo4_kernel<f16_t>, dim3(grid), dim3(256), 0, (hipStream_t)stream, in, ld_in, (f16_t*)out, ld_out, rows, cols);
         else hipLaunchKernelGGL(convert_lo4_kernel<bf16_t>, dim3(grid), dim3(256), 0, (hipStream_t)stream, in, ld_in, (bf16_t*)out, ld_out, rows, cols);
     } else {
-        const int grid = grid_for(rows * cols_padded);
-        if (prec == ZETT_PREC_F16) hipLaunchKernelGGL(convert_lo_kernel<f16_t>, dim3(grid), dim3(256), 0, (hipStream_t)stream, in, ld_in, (f16_t*)out, ld_out, rows, cols, cols_padded);
-        else hipLaunchKernelGGL(convert_lo_kernel<bf16_t>, dim3(grid), dim3(256), 0, (hipStream_t)stream, in, ld_in, (bf16_t*)out, ld_out, rows, cols, cols_padded);
+        launch_cast(ZETT_F32, prec == ZETT_PREC_F16 ? ZETT_F16 : ZETT_BF16, in, ld_in, out, ld_out, rows, cols, cols_padded, (hipStream_t)stream);
     }
     HIP_TRY(hipGetLastError());
     return 0;
@@ -798,7 +731,7 @@ int zett_op_transpose_f32(const float* in, int32_t ld_in, float* out, int32_t ld
 int zett_op_colsum_f32(const float* in, int32_t ld, int64_t rows, int32_t cols, float* out, int32_t accumulate, void* stream) {
     if (!in || !out) return fail(ZETT_E_INVALID, "null argument");
     if (cols <= 0) return 0;
-    hipLaunchKernelGGL(colsum_kernel, dim3((cols + 63) / 64), dim3(256), 0, (hipStream_t)stream, in, ld, (int)rows, cols, out, accumulate);
+    launch_colsum(ZETT_F32, in, ld, rows, cols, out, accumulate, (hipStream_t)stream);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -945,26 +878,28 @@ int zett_op_scatter_add_rows_f32(float* dst, int32_t ld_dst, const int32_t* idx,
 
 int zett_op_gather_fwd_f32(const int32_t* ids, int64_t n_tokens, const void* src, int32_t src_dtype, int32_t e_in, int32_t v0, const float* fallback,
                            const float* sw, const float* sb, float* x, void* stream) {
-    if (!ids || !src || !fallback || !x || src_dtype < ZETT_F32 || src_dtype > ZETT_BF16) return fail(ZETT_E_INVALID, "bad gather arguments");
+    if (!ids || !src || !fallback || !x || !is_dtype(src_dtype)) return fail(ZETT_E_INVALID, "bad gather arguments");
     if (n_tokens <= 0) return 0;
     const dim3 grid((unsigned)n_tokens), block(256);
     hipStream_t st = (hipStream_t)stream;
-    if (src_dtype == ZETT_F32) hipLaunchKernelGGL(gather_fwd_kernel<0>, grid, block, 0, st, ids, n_tokens, src, e_in, v0, fallback, sw, sb, x);
-    else if (src_dtype == ZETT_F16) hipLaunchKernelGGL(gather_fwd_kernel<1>, grid, block, 0, st, ids, n_tokens, src, e_in, v0, fallback, sw, sb, x);
-    else hipLaunchKernelGGL(gather_fwd_kernel<2>, grid, block, 0, st, ids, n_tokens, src, e_in, v0, fallback, sw, sb, x);
+    with_dtype(src_dtype, [&](auto dt) {
+        using TS = elem_t<decltype(dt)::value>;
+        hipLaunchKernelGGL(gather_fwd_kernel<TS>, grid, block, 0, st, ids, n_tokens, (const TS*)src, e_in, v0, fallback, sw, sb, x);
+    });
     HIP_TRY(hipGetLastError());
     return 0;
 }
 
 int zett_op_gather_bwd_f32(const int32_t* ids, int64_t n_tokens, const void* src, int32_t src_dtype, int32_t e_in, int32_t v0, const float* dx,
                            float* dfallback, float* prod, float* keep, void* stream) {
-    if (!ids || !src || !dx || !dfallback || !prod || !keep || src_dtype < ZETT_F32 || src_dtype > ZETT_BF16) return fail(ZETT_E_INVALID, "bad gather arguments");
+    if (!ids || !src || !dx || !dfallback || !prod || !keep || !is_dtype(src_dtype)) return fail(ZETT_E_INVALID, "bad gather arguments");
     if (n_tokens <= 0) return 0;
     const dim3 grid((unsigned)n_tokens), block(256);
     hipStream_t st = (hipStream_t)stream;
-    if (src_dtype == ZETT_F32) hipLaunchKernelGGL(gather_bwd_kernel<0>, grid, block, 0, st, ids, n_tokens, src, e_in, v0, dx, dfallback, prod, keep);
-    else if (src_dtype == ZETT_F16) hipLaunchKernelGGL(gather_bwd_kernel<1>, grid, block, 0, st, ids, n_tokens, src, e_in, v0, dx, dfallback, prod, keep);
-    else hipLaunchKernelGGL(gather_bwd_kernel<2>, grid, block, 0, st, ids, n_tokens, src, e_in, v0, dx, dfallback, prod, keep);
+    with_dtype(src_dtype, [&](auto dt) {
+        using TS = elem_t<decltype(dt)::value>;
+        hipLaunchKernelGGL(gather_bwd_kernel<TS>, grid, block, 0, st, ids, n_tokens, (const TS*)src, e_in, v0, dx, dfallback, prod, keep);
+    });
     HIP_TRY(hipGetLastError());
     return 0;
 }

@@ -16,6 +16,7 @@
 
 #include "../../include/zett_hip.h"
 #include "common.hip.h"
+#include "train_common.hip.h"
 
 using namespace zett;
 
@@ -26,55 +27,8 @@ constexpr int64_t kChunk = ZETT_MT_CHUNK;     // elements of one (tensor, chunk)
 constexpr int kGroup = 64;                    // tensors per launch: the lists travel as kernel arguments (< 4 KB)
 constexpr float kHuberDelta = 1e-3f, kHuberCorrection = 30.f;      // train.py:1107-1108
 
-__device__ __forceinline__ float s_wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-__device__ __forceinline__ float s_block_sum(float v, float* red /* [4] */) {      // 256 threads, fixed order
-    v = s_wave_sum(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-}
-__device__ __forceinline__ double s_block_sum_f64(double v, double* red /* [256] */) {
-    red[threadIdx.x] = v;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-        __syncthreads();
-    }
-    const double s = red[0];
-    __syncthreads();
-    return s;
-}
-
-// ---- target rows: fp32 / f16 / bf16 storage, upcast on load -------------------------------------------------------------
-template <int SD> struct SrcElem { using type = float; };
-template <> struct SrcElem<ZETT_F16> { using type = _Float16; };
-template <> struct SrcElem<ZETT_BF16> { using type = uint16_t; };
-
-template <int SD> __device__ __forceinline__ float src1(const typename SrcElem<SD>::type* row, int c);
-template <> __device__ __forceinline__ float src1<ZETT_F32>(const float* row, int c) { return row[c]; }
-template <> __device__ __forceinline__ float src1<ZETT_F16>(const _Float16* row, int c) { return (float)row[c]; }
-template <> __device__ __forceinline__ float src1<ZETT_BF16>(const uint16_t* row, int c) { return __uint_as_float((uint32_t)row[c] << 16); }
-
-// four consecutive elements, c % 4 == 0, the row aligned to four elements: 16 bytes of fp32 or 8 bytes of 16-bit storage
-template <int SD> __device__ __forceinline__ float4 src4(const typename SrcElem<SD>::type* row, int c);
-template <> __device__ __forceinline__ float4 src4<ZETT_F32>(const float* row, int c) { return *(const float4*)(row + c); }
-template <> __device__ __forceinline__ float4 src4<ZETT_F16>(const _Float16* row, int c) {
-    typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-    const half4 h = *(const half4*)(row + c);
-    return make_float4((float)h.x, (float)h.y, (float)h.z, (float)h.w);
-}
-template <> __device__ __forceinline__ float4 src4<ZETT_BF16>(const uint16_t* row, int c) {
-    const uint2 u = *(const uint2*)(row + c);
-    return make_float4(__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xffff0000u), __uint_as_float(u.y << 16), __uint_as_float(u.y & 0xffff0000u));
-}
-
 __device__ __forceinline__ int64_t target_row(const void* ids, int ids64, int64_t ids_stride, int64_t r, int64_t src_rows) {
-    const int64_t id = ids64 ? ((const int64_t*)ids)[r * ids_stride] : (int64_t)((const int32_t*)ids)[r * ids_stride];
+    const int64_t id = load_id(ids, ids64, r * ids_stride);
     return id < 0 ? 0 : (id >= src_rows ? src_rows - 1 : id);          // (JAX's gather rule: out-of-range indices are clamped)
 }
 
@@ -98,7 +52,7 @@ __global__ __launch_bounds__(256) void dist_rows_kernel(const float* __restrict_
                                                         int64_t src_rows, int col0, const void* __restrict__ ids, int ids64, int64_t ids_stride,
                                                         const float* __restrict__ mask, int64_t n, int e, int vec_ok, float* __restrict__ row_dist,
                                                         float* __restrict__ row_tnorm) {
-    using T = typename SrcElem<SD>::type;
+    using T = elem_t<SD>;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     for (int64_t r = (int64_t)blockIdx.x * 4 + wave; r < n; r += (int64_t)gridDim.x * 4) {
         const float* x = pred + r * ld_pred;
@@ -108,18 +62,18 @@ __global__ __launch_bounds__(256) void dist_rows_kernel(const float* __restrict_
         if (vec_ok) {
             tail = e & ~3;
             for (int c = lane * 4; c < tail; c += 256) {
-                const float4 a = *(const float4*)(x + c), b = src4<SD>(y, c);
+                const float4 a = *(const float4*)(x + c), b = load4(y + c);
                 d += (dist_term<KIND>(a.x - b.x) + dist_term<KIND>(a.y - b.y)) + (dist_term<KIND>(a.z - b.z) + dist_term<KIND>(a.w - b.w));
                 t += (b.x * b.x + b.y * b.y) + (b.z * b.z + b.w * b.w);
             }
         }
         for (int c = tail + lane; c < e; c += 64) {
-            const float b = src1<SD>(y, c);
+            const float b = load1(y + c);
             d += dist_term<KIND>(x[c] - b);
             t += b * b;
         }
-        d = s_wave_sum(d);
-        t = s_wave_sum(t);
+        d = wave_sum(d);
+        t = wave_sum(t);
         if (lane == 0) {
             if (KIND == ZETT_DIST_RMSE) d = sqrtf(d);
             if (KIND == ZETT_DIST_HUBER) d = d / kHuberDelta / kHuberCorrection;
@@ -139,9 +93,9 @@ __global__ __launch_bounds__(256) void dist_finalize_kernel(const float* __restr
         st += (double)row_tnorm[i];
         sm += mask ? (double)mask[i] : 1.0;
     }
-    sd = s_block_sum_f64(sd, red);
-    st = s_block_sum_f64(st, red);
-    sm = s_block_sum_f64(sm, red);
+    sd = block_sum_f64(sd, red);
+    st = block_sum_f64(st, red);
+    sm = block_sum_f64(sm, red);
     if (threadIdx.x == 0) {
         // mean: sum / n (train.py:942-946).  lexical: sum / (sum(mask) + EPSILON) / mean ||target|| over ALL rows (train.py:1121-1125)
         const double denom = mode == ZETT_LOSS_LEXICAL ? (sm + 1e-8) * (st / (double)n) : (double)n;
@@ -159,7 +113,7 @@ __global__ __launch_bounds__(256) void dist_grad_kernel(const float* __restrict_
                                                         const float* __restrict__ mask, const float* __restrict__ row_dist, int64_t n, int e, int vec_ok,
                                                         const float* __restrict__ record, const float* __restrict__ upstream, float* __restrict__ dpred,
                                                         int64_t ld_dpred, int accumulate) {
-    using T = typename SrcElem<SD>::type;
+    using T = elem_t<SD>;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const float base = upstream[0] * record[1];
     for (int64_t r = (int64_t)blockIdx.x * 4 + wave; r < n; r += (int64_t)gridDim.x * 4) {
@@ -177,7 +131,7 @@ __global__ __launch_bounds__(256) void dist_grad_kernel(const float* __restrict_
         if (vec_ok) {
             tail = e & ~3;
             for (int c = lane * 4; c < tail; c += 256) {
-                const float4 a = *(const float4*)(x + c), b = src4<SD>(y, c);
+                const float4 a = *(const float4*)(x + c), b = load4(y + c);
                 float4 g = make_float4(f * dist_grad<KIND>(a.x - b.x), f * dist_grad<KIND>(a.y - b.y), f * dist_grad<KIND>(a.z - b.z), f * dist_grad<KIND>(a.w - b.w));
                 if (accumulate) {
 #pragma clang fp contract(off)                          // old + g with g rounded first: accumulating adds exactly what a plain call writes
@@ -188,7 +142,7 @@ __global__ __launch_bounds__(256) void dist_grad_kernel(const float* __restrict_
             }
         }
         for (int c = tail + lane; c < e; c += 64) {
-            float g = f * dist_grad<KIND>(x[c] - src1<SD>(y, c));
+            float g = f * dist_grad<KIND>(x[c] - load1(y + c));
             if (accumulate) {
 #pragma clang fp contract(off)
                 g = o[c] + g;
@@ -204,8 +158,7 @@ __global__ __launch_bounds__(256) void single_token_mask_kernel(const void* __re
     for (int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x; r < n; r += (int64_t)gridDim.x * 256) {
         bool single = true;
         for (int j = 1; j < width; ++j) {
-            const int64_t id = ids64 ? ((const int64_t*)ids)[r * ld + j] : (int64_t)((const int32_t*)ids)[r * ld + j];
-            single = single && id == pad;
+            single = single && load_id(ids, ids64, r * ld + j) == pad;
         }
         mask[r] = single ? 1.f : 0.f;
     }
@@ -261,7 +214,7 @@ __global__ __launch_bounds__(256) void sumsq_kernel(const NormList a, float* __r
             }
         }
         for (int i = tail + threadIdx.x; i < len; i += 256) s0 += g[i] * g[i];       // the ragged end, or a pointer that is only 4-byte aligned
-        const float s = s_block_sum((s0 + s1) + (s2 + s3), red);
+        const float s = block_sum_pairwise((s0 + s1) + (s2 + s3), red);
         if (threadIdx.x == 0) partials[a.partial_base + item] = s;
     }
 }
@@ -273,7 +226,7 @@ __global__ __launch_bounds__(256) void norm_finalize_kernel(const float* __restr
     __shared__ double red[256];
     double s = 0.0;
     for (int64_t i = threadIdx.x; i < total; i += 256) s += (double)partials[i];
-    s = s_block_sum_f64(s, red);
+    s = block_sum_f64(s, red);
     if (threadIdx.x == 0) {
         const double norm = sqrt(s);
         const bool finite = isfinite(norm);
@@ -355,32 +308,12 @@ __global__ __launch_bounds__(256) void adamw_kernel(const AdamList a, const Adam
 
 int64_t items_of(int64_t n) { return (n + kChunk - 1) / kChunk; }
 
-template <int SD>
-int dist_rows_go(int kind, int grid, hipStream_t st, const float* pred, int64_t ld_pred, const void* src, int64_t ld_src, int64_t src_rows, int col0, const void* ids,
-                 int ids64, int64_t ids_stride, const float* mask, int64_t n, int e, int vec_ok, float* row_dist, float* row_tnorm) {
-#define GO(K) hipLaunchKernelGGL((dist_rows_kernel<SD, K>), dim3(grid), dim3(256), 0, st, pred, ld_pred, src, ld_src, src_rows, col0, ids, ids64, ids_stride, mask, n, e, \
-                                 vec_ok, row_dist, row_tnorm)
-    if (kind == ZETT_DIST_MSE) GO(ZETT_DIST_MSE); else if (kind == ZETT_DIST_RMSE) GO(ZETT_DIST_RMSE); else GO(ZETT_DIST_HUBER);
-#undef GO
-    return 0;
-}
-template <int SD>
-int dist_grad_go(int kind, int grid, hipStream_t st, const float* pred, int64_t ld_pred, const void* src, int64_t ld_src, int64_t src_rows, int col0, const void* ids,
-                 int ids64, int64_t ids_stride, const float* mask, const float* row_dist, int64_t n, int e, int vec_ok, const float* record, const float* upstream,
-                 float* dpred, int64_t ld_dpred, int accumulate) {
-#define GO(K) hipLaunchKernelGGL((dist_grad_kernel<SD, K>), dim3(grid), dim3(256), 0, st, pred, ld_pred, src, ld_src, src_rows, col0, ids, ids64, ids_stride, mask, row_dist, \
-                                 n, e, vec_ok, record, upstream, dpred, ld_dpred, accumulate)
-    if (kind == ZETT_DIST_MSE) GO(ZETT_DIST_MSE); else if (kind == ZETT_DIST_RMSE) GO(ZETT_DIST_RMSE); else GO(ZETT_DIST_HUBER);
-#undef GO
-    return 0;
-}
-
 // what both passes check: shapes, the dtype, and whether every row start allows the 4-element accesses
 int dist_args(const float* pred, int64_t ld_pred, const void* src, int32_t src_dtype, int64_t ld_src, int64_t src_rows, int32_t col0, const void* ids, int32_t ids_bytes,
               int64_t n, int32_t e, int32_t kind, int* vec_ok) {
     if (!pred || !src || !ids) return fail(ZETT_E_INVALID, "null argument");
     if (n <= 0 || e <= 0) return fail(ZETT_E_INVALID, "the loss needs at least one row and one column (n = %lld, e = %d)", (long long)n, (int)e);
-    if (src_dtype != ZETT_F32 && src_dtype != ZETT_F16 && src_dtype != ZETT_BF16) return fail(ZETT_E_INVALID, "unknown source dtype %d", (int)src_dtype);
+    if (!is_dtype(src_dtype)) return fail(ZETT_E_INVALID, "unknown source dtype %d", (int)src_dtype);
     if (ids_bytes != 4 && ids_bytes != 8) return fail(ZETT_E_INVALID, "ids must be int32 or int64");
     if (kind != ZETT_DIST_MSE && kind != ZETT_DIST_RMSE && kind != ZETT_DIST_HUBER) return fail(ZETT_E_INVALID, "unknown distance kind %d", (int)kind);
     if (src_rows <= 0 || col0 < 0 || (int64_t)col0 + e > ld_src || ld_pred < e) return fail(ZETT_E_INVALID, "columns [%d, %d) do not fit the leading dimensions", (int)col0, (int)(col0 + e));
@@ -412,9 +345,11 @@ int zett_op_embed_dist_rows(const float* pred, int64_t ld_pred, const void* src,
     if (!row_dist || !row_tnorm) return fail(ZETT_E_INVALID, "null argument");
     const int grid = (int)std::min<int64_t>((n + 3) / 4, kMaxGrid);
     hipStream_t st = (hipStream_t)stream;
-    if (src_dtype == ZETT_F32) dist_rows_go<ZETT_F32>(kind, grid, st, pred, ld_pred, src, ld_src, src_rows, col0, ids, ids_bytes == 8, ids_stride, mask, n, e, vec_ok, row_dist, row_tnorm);
-    else if (src_dtype == ZETT_F16) dist_rows_go<ZETT_F16>(kind, grid, st, pred, ld_pred, src, ld_src, src_rows, col0, ids, ids_bytes == 8, ids_stride, mask, n, e, vec_ok, row_dist, row_tnorm);
-    else dist_rows_go<ZETT_BF16>(kind, grid, st, pred, ld_pred, src, ld_src, src_rows, col0, ids, ids_bytes == 8, ids_stride, mask, n, e, vec_ok, row_dist, row_tnorm);
+    with_dtype(src_dtype, [&](auto dt) {
+        constexpr int SD = decltype(dt)::value;
+        const auto kernel = kind == ZETT_DIST_MSE ? dist_rows_kernel<SD, ZETT_DIST_MSE> : kind == ZETT_DIST_RMSE ? dist_rows_kernel<SD, ZETT_DIST_RMSE> : dist_rows_kernel<SD, ZETT_DIST_HUBER>;
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, st, pred, ld_pred, src, ld_src, src_rows, col0, ids, ids_bytes == 8, ids_stride, mask, n, e, vec_ok, row_dist, row_tnorm);
+    });
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -438,9 +373,12 @@ int zett_op_embed_dist_grad(const float* pred, int64_t ld_pred, const void* src,
     vec_ok = vec_ok && ((uintptr_t)dpred & 15) == 0 && ld_dpred % 4 == 0;
     const int grid = (int)std::min<int64_t>((n + 3) / 4, kMaxGrid);
     hipStream_t st = (hipStream_t)stream;
-    if (src_dtype == ZETT_F32) dist_grad_go<ZETT_F32>(kind, grid, st, pred, ld_pred, src, ld_src, src_rows, col0, ids, ids_bytes == 8, ids_stride, mask, row_dist, n, e, vec_ok, record, upstream, dpred, ld_dpred, accumulate);
-    else if (src_dtype == ZETT_F16) dist_grad_go<ZETT_F16>(kind, grid, st, pred, ld_pred, src, ld_src, src_rows, col0, ids, ids_bytes == 8, ids_stride, mask, row_dist, n, e, vec_ok, record, upstream, dpred, ld_dpred, accumulate);
-    else dist_grad_go<ZETT_BF16>(kind, grid, st, pred, ld_pred, src, ld_src, src_rows, col0, ids, ids_bytes == 8, ids_stride, mask, row_dist, n, e, vec_ok, record, upstream, dpred, ld_dpred, accumulate);
+    with_dtype(src_dtype, [&](auto dt) {
+        constexpr int SD = decltype(dt)::value;
+        const auto kernel = kind == ZETT_DIST_MSE ? dist_grad_kernel<SD, ZETT_DIST_MSE> : kind == ZETT_DIST_RMSE ? dist_grad_kernel<SD, ZETT_DIST_RMSE> : dist_grad_kernel<SD, ZETT_DIST_HUBER>;
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, st, pred, ld_pred, src, ld_src, src_rows, col0, ids, ids_bytes == 8, ids_stride, mask, row_dist, n, e, vec_ok, record, upstream,
+                           dpred, ld_dpred, accumulate);
+    });
     HIP_TRY(hipGetLastError());
     return 0;
 }
