@@ -673,6 +673,43 @@ int zett_op_embed_lookup_plan(const void* ids, int32_t ids_bytes, int64_t t, int
 int zett_op_embed_lookup_bwd(const void* g, int32_t g_dtype, int64_t t, int64_t v, int32_t e, const void* plan, int64_t plan_bytes, float* partials,
                              int64_t partial_bytes, float* d_table, int64_t ld_d, void* stream);
 
+/* ---- the batch's sub-vocabulary (zett_amd/training.py subsample_batch_vocabulary) --------------------------------------------------
+ * The n_token_subsample branch of the reference's collator (collator.py:207-282) on arrays that are already on the device
+ * (csrc/train_batch.hip).  With S = special_ids in the given order and N = n:
+ *   positives       = ascending, the ids of [0, v) that occur in input_ids or in labels != -100 and are not in S
+ *   tokens_in_batch = S ++ positives;   *n_positive = their number (> n: ZETT_BATCH_OVERFLOW)
+ *   negatives       = n - *n_positive ids: ZETT_BATCH_POSITIVES_ONLY: id 0 repeated;  ZETT_BATCH_RANDOM: the first entries of
+ *                     negative_order (a permutation of [0, v)) that are not in tokens_in_batch, in negative_order's order
+ *   ids_to_embed    = tokens_in_batch ++ negatives, then move m = 0 .. n_special - 1 in turn: the row move_from[m] is taken out and
+ *                     inserted at row move_to[m] (Python's del / insert; the collator's "for special in sorted(all_special_ids)" loop —
+ *                     the moves depend on special_ids and n alone and are computed by the caller)
+ *   inv[id]         = the LARGEST row r with ids_to_embed[r] == id
+ *   out_input_ids   = inv[input_ids];   out_labels = labels == -100 ? -100 : inv[labels]
+ *   out_surface_forms[r, 0:l] = surface_forms[ids_to_embed[r], 0:l];  out_priors[r] = priors[ids_to_embed[r]];  mask[r] = 1
+ * input_ids / labels: t elements of ids_bytes / labels_bytes (4 or 8), the outputs have the widths of their inputs and ids_to_embed
+ * that of input_ids; surface_forms: [v, l] of sf_bytes (4 or 8) with leading dimension ld_sf >= l elements, out_surface_forms [n, l]
+ * contiguous; negative_order: v elements of order_bytes, read in ZETT_BATCH_RANDOM only.  special_ids / move_from / move_to are
+ * HOST arrays of n_special <= ZETT_SPLICE_MAX_ROWS entries (distinct ids of [0, v), rows of [0, n)), validated before any launch;
+ * they travel to the kernels as launch arguments.
+ * *status (device) is written by the call: an OR of zett_batch_status bits, 0 when all is well.  With a bit set the outputs are
+ * unspecified, but every write stays inside the output buffers and no id outside [0, v) is ever used as an address.
+ * Integers only; the only atomics are integer OR and max, so the same inputs give the same bits.  Asynchronous on `stream`, no
+ * allocation: `workspace` (device, 4-byte aligned, zett_op_batch_vocab_workspace_bytes) is free once the call's work is done. */
+enum zett_batch_mode { ZETT_BATCH_POSITIVES_ONLY = 0, ZETT_BATCH_RANDOM = 1 };
+enum zett_batch_status {
+    ZETT_BATCH_BAD_ID = 1,         /* an id of input_ids / labels (other than a label of -100) is outside [0, v) */
+    ZETT_BATCH_OVERFLOW = 2,       /* *n_positive > n */
+    ZETT_BATCH_BAD_ORDER = 4,      /* an entry of negative_order is outside [0, v) */
+    ZETT_BATCH_REPEAT = 8          /* ZETT_BATCH_RANDOM: an id is listed twice (inv saw a previous owner), or negative_order holds fewer
+                                    * absent ids than rows to fill: negative_order is not a permutation */
+};
+int zett_op_batch_vocab_workspace_bytes(int64_t t, int64_t v, int64_t n, int64_t* bytes);
+int zett_op_batch_vocab(const void* input_ids, int32_t ids_bytes, const void* labels, int32_t labels_bytes, int64_t t, int64_t v, int64_t n, const void* surface_forms,
+                        int32_t sf_bytes, int64_t ld_sf, int32_t l, const float* priors, const void* negative_order, int32_t order_bytes, int32_t mode,
+                        const int32_t* special_ids, const int32_t* move_from, const int32_t* move_to, int32_t n_special, void* out_input_ids, void* out_labels,
+                        void* ids_to_embed, void* out_surface_forms, float* out_priors, uint8_t* mask, int32_t* n_positive, int32_t* status, void* workspace,
+                        int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -27,6 +27,8 @@ CE_AUTO, CE_ONCE, CE_TWICE = 0, 1, 2                 # zett_ce_path
 CE_ONCE_MAX_COLS = 32768                             # ZETT_CE_ONCE_MAX_COLS
 SPLICE_MAX_ROWS = 256                                # ZETT_SPLICE_MAX_ROWS
 EMBED_BWD_CHUNK = 64                                 # ZETT_EMBED_BWD_CHUNK
+BATCH_POSITIVES_ONLY, BATCH_RANDOM = 0, 1            # zett_batch_mode
+BATCH_BAD_ID, BATCH_OVERFLOW, BATCH_BAD_ORDER, BATCH_REPEAT = 1, 2, 4, 8      # zett_batch_status
 
 ABI_SYMBOLS = (
     "zett_last_error", "zett_abi_version", "zett_create", "zett_destroy", "zett_load_weight",
@@ -48,6 +50,8 @@ ABI_SYMBOLS = (
     "zett_op_ce_addend", "zett_op_ce_rows", "zett_op_ce_finalize", "zett_op_ce_colsum", "zett_op_ce_scale", "zett_op_ce_cast",
     # the input side of a training step (zett_amd/training.py splice_special_rows, token_embeddings)
     "zett_op_splice_rows", "zett_op_embed_lookup", "zett_op_embed_lookup_workspace_bytes", "zett_op_embed_lookup_plan", "zett_op_embed_lookup_bwd",
+    # the batch's sub-vocabulary (zett_amd/training.py subsample_batch_vocabulary)
+    "zett_op_batch_vocab_workspace_bytes", "zett_op_batch_vocab",
 )
 
 
@@ -196,6 +200,8 @@ def load():
         lib.zett_op_embed_lookup_workspace_bytes.argtypes = [I64, I64, I32, C.POINTER(I64), C.POINTER(I64), C.POINTER(I64)]
         lib.zett_op_embed_lookup_plan.argtypes = [P, I32, I64, I64, P, I64, P, I64, P]
         lib.zett_op_embed_lookup_bwd.argtypes = [P, I32, I64, I64, I32, P, I64, P, I64, P, I64, P]
+        lib.zett_op_batch_vocab_workspace_bytes.argtypes = [I64, I64, I64, C.POINTER(I64)]
+        lib.zett_op_batch_vocab.argtypes = [P, I32, P, I32, I64, I64, I64, P, I32, I64, I32, P, P, I32, I32, P, P, P, I32, P, P, P, P, P, P, P, P, P, I64, P]
         for name in ABI_SYMBOLS:
             fn = getattr(lib, name)
             if name != "zett_last_error":

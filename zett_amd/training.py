@@ -13,15 +13,17 @@ warm-up loss (train.py:914-975), the lexical loss (train.py:1074-1141) and the p
     pred_in, pred_out = splice_special_rows(pred_in, pred_out, src, special_indices, special_indices_in_reference, inplace=True)      # train.py:1014-1030
     inputs_embeds = token_embeddings(pred_in, input_ids, dtype=torch.bfloat16)      # for a backbone that takes inputs_embeds; d pred_in comes back through it
 
-Losses, update, splice and lookup are HIP kernels (csrc/train_step.hip, csrc/train_loss.hip, csrc/train_embed.hip); torch holds the tensors and the tape.  Nothing in this module waits for
-the host except ``last_step_stats()``, ``state_dict()`` and ``token_embeddings(check_ids=True)`` (the model's forward in front of it still reads its id range back once per
+    bv = subsample_batch_vocabulary(input_ids, labels, special_ids, n_token_subsample, surface_forms, priors, negative_order=perm)      # collator.py:207-282: what feeds all of the above
+
+Losses, update, splice, lookup and the batch's sub-vocabulary are HIP kernels (csrc/train_step.hip, csrc/train_loss.hip, csrc/train_embed.hip, csrc/train_batch.hip); torch holds the tensors and the tape.  Nothing in this module waits for
+the host except ``last_step_stats()``, ``state_dict()``, ``token_embeddings(check_ids=True)`` and ``subsample_batch_vocabulary(check=True)`` (the model's forward in front of it still reads its id range back once per
 step).  Results are bit-reproducible from run to run.
 """
 from __future__ import annotations
 
 import ctypes as C
 import math
-from typing import Callable, Dict, Mapping, Optional, Union
+from typing import Callable, Dict, List, Mapping, NamedTuple, Optional, Sequence, Tuple, Union
 
 import torch
 from torch.autograd.function import once_differentiable
@@ -684,6 +686,166 @@ def token_embeddings(pred_in, input_ids, *, dtype=None, check_ids=True):
             raise ValueError("the gradient of token_embeddings is defined for an fp32 pred_in; a 16-bit pred_in must not require grad")
         return _TokenEmbeddings.apply(pred_in, ids, dtype, bool(check_ids))
     return _lookup(pred_in.detach(), ids, dtype, bool(check_ids))
+
+
+# ---- the batch's sub-vocabulary (collator.py:207-282) ------------------------------------------------------------------------
+class BatchVocabulary(NamedTuple):
+    """What subsample_batch_vocabulary returns: the collator's arrays, on the device."""
+    input_ids: torch.Tensor                  # remapped to rows of ids_to_embed; shape and dtype as given
+    labels: torch.Tensor                     # likewise, -100 kept
+    ids_to_embed: torch.Tensor               # [N], dtype of input_ids
+    target_surface_forms: torch.Tensor       # [N, L]
+    target_priors: torch.Tensor              # [N] fp32
+    mask: torch.Tensor                       # [N] bool, all true
+    special_indices: List[int]               # host list: the row of each special id, in special_ids' order (what splice_special_rows takes)
+    n_positive: torch.Tensor                 # device int32 scalar: specials + distinct other ids of the batch
+    status: torch.Tensor                     # device int32 scalar: 0, or an OR of the BATCH_* bits
+
+
+BATCH_BAD_ID, BATCH_OVERFLOW, BATCH_BAD_ORDER, BATCH_REPEAT = _lib.BATCH_BAD_ID, _lib.BATCH_OVERFLOW, _lib.BATCH_BAD_ORDER, _lib.BATCH_REPEAT
+_BATCH_MODES = {"positives_only": _lib.BATCH_POSITIVES_ONLY, "random": _lib.BATCH_RANDOM}
+
+
+def special_row_moves(special_ids: Sequence[int], n: int) -> Tuple[List[Tuple[int, int]], List[int]]:
+    """The collator's "try to preserve special token indices" loop (collator.py:251-254) as data: ``(moves, special_indices)``.
+
+    The list starts with ``special_ids`` in their own order in rows ``0 .. len - 1``.  For each special id in ASCENDING order its row is
+    deleted and the id inserted at row ``min(id, n - 1)`` (Python's ``del`` / ``insert`` on a list of n entries); ``moves[m] = (from, to)``
+    is that step for the m-th smallest id, and ``special_indices[i]`` the final row of ``special_ids[i]``.  Both depend on nothing but
+    ``special_ids`` and n: only the specials' own rows have to be followed, O(len^2).  ValueError for a negative or repeated id or
+    more ids than rows."""
+    ids = [int(s) for s in special_ids]
+    n = int(n)
+    if len(set(ids)) != len(ids):
+        raise ValueError("special_ids holds an id twice")
+    if any(s < 0 for s in ids):
+        raise ValueError("special_ids holds a negative id")
+    if len(ids) > n:
+        raise ValueError(f"{len(ids)} special ids do not fit n_token_subsample = {n} rows")
+    row = {s: i for i, s in enumerate(ids)}
+    moves = []
+    for s in sorted(ids):
+        frm, to = row[s], min(s, n - 1)
+        for other, r in row.items():
+            r -= 1 if r > frm else 0
+            r += 1 if r >= to else 0
+            row[other] = r
+        row[s] = to
+        moves.append((frm, to))
+    return moves, [row[s] for s in ids]
+
+
+def batch_vocab_workspace(t: int, v: int, n: int) -> int:
+    """bytes of the scratch buffer of subsample_batch_vocabulary for t positions, v ids, n rows"""
+    out = C.c_int64(0)
+    _lib.check(_lib.load().zett_op_batch_vocab_workspace_bytes(int(t), int(v), int(n), C.byref(out)), "batch_vocab_workspace_bytes")
+    return out.value
+
+
+def subsample_batch_vocabulary(input_ids, labels, special_ids, n_token_subsample, target_surface_forms, target_priors, *, mode="random", negative_order=None,
+                               check=True) -> BatchVocabulary:
+    """The ``n_token_subsample`` branch of the reference's collator (collator.py:207-282) on the device: from a batch of token ids to
+    the N ids the hypernetwork embeds this step, with the batch remapped to rows of that list.
+
+        bv = subsample_batch_vocabulary(input_ids, labels, tokenizer.all_special_ids, N, surface_forms, priors, negative_order=torch.randperm(V, device=dev))
+        pred_in, pred_out, _ = model(bv.target_surface_forms, ...)
+        pred_in, pred_out = splice_special_rows(pred_in, pred_out, src, bv.special_indices, special_indices_in_reference, inplace=True)
+        hidden = backbone(token_embeddings(pred_in, bv.input_ids))
+        loss, _ = lm_head_loss(hidden, pred_out, bv.labels, priors=bv.target_priors, ...)
+
+    input_ids, labels: ``[B, S]`` or ``[T]`` int32 / int64 device tensors of one shape; a label of -100 is "no label".  special_ids: a host
+    list, the tokenizer's ``all_special_ids`` in ITS order, at most 256 distinct ids of ``[0, V)``.  target_surface_forms: ``[V, L]`` int32 /
+    int64, unit column stride, any row stride >= L.  target_priors: ``[V]`` fp32.  N = n_token_subsample <= V.  negative_order: ``[V]`` int32 /
+    int64 on the device, a permutation of ``range(V)`` — the randomness of ``mode="random"``, taken as an argument so that the result is
+    a pure function of its inputs.
+
+    1. positives: ascending, the ids that occur in input_ids or in ``labels != -100`` and are not special.  ``tokens_in_batch =
+       special_ids ++ positives``, ``n_positive`` its length; ``n_positive > N`` is an error (the reference asserts).
+    2. ``N - n_positive`` negatives.  "positives_only": id 0 repeated.  "random": the first entries of negative_order that are not in
+       tokens_in_batch, in negative_order's order — the reference's shuffle-then-truncate when negative_order is a uniform permutation.
+    3. ``tokens_in_batch ++ negatives``, then the moves of ``special_row_moves(special_ids, N)``: each special id, ascending, goes to row
+       ``min(id, N - 1)``.  ``special_indices`` is where each ended up.
+    4. ``inv[id]`` = the LARGEST row that holds id (numpy's last write wins for "positives_only"'s repeated id 0); input_ids and the
+       labels other than -100 become ``inv[.]``.
+    5. target_surface_forms / target_priors: the rows of ids_to_embed; mask: ones.
+
+    Deviations from the reference: a label of -100 is not an id (the reference lets -100 into ``np.unique`` under MLM); in "random" mode
+    the negatives exclude ALL of tokens_in_batch (the reference excludes only ``unique(input_ids)``, so it can list a special or label-only
+    id twice) — ids_to_embed has no duplicate in "random" mode.  Wherever the reference's own list has no duplicate and no -100 among its
+    ids, every output equals the reference's element for element.
+
+    ``status``: 0, or an OR of BATCH_BAD_ID (1: an id of input_ids / labels outside ``[0, V)``), BATCH_OVERFLOW (2: n_positive > N),
+    BATCH_BAD_ORDER (4: an entry of negative_order outside ``[0, V)``), BATCH_REPEAT (8, "random": an id listed twice, or too few absent
+    ids in negative_order — it is not a permutation).  An id outside ``[0, V)`` is never used as an address; with a bit set the outputs
+    are unspecified but every write stays inside them.  check=True reads the word once (the one host read of this call) and raises
+    IndexError for bits 1 and 4, ValueError for bits 2 and 8; check=False never waits for the host.
+
+    Integers and a gather of constants: no gradient flows anywhere.  Seven small launches on the current stream (csrc/train_batch.hip), the only
+    atomics integer OR and max: the same inputs give the same bits."""
+    if mode not in _BATCH_MODES:
+        raise ValueError(f"mode must be one of {sorted(_BATCH_MODES)}, got {mode!r} (the reference's \"highest_scores\" is not implemented there either)")
+    ints = (torch.int32, torch.int64)
+    for name, x in (("input_ids", input_ids), ("labels", labels)):
+        if not isinstance(x, torch.Tensor) or x.dtype not in ints or x.dim() not in (1, 2):
+            raise ValueError(f"{name} must be a [B, S] or [T] int32 / int64 tensor")
+    if input_ids.shape != labels.shape:
+        raise ValueError(f"input_ids {tuple(input_ids.shape)} and labels {tuple(labels.shape)} must have the same shape")
+    sf, priors = target_surface_forms, target_priors
+    if sf.dim() != 2 or sf.dtype not in ints or sf.shape[0] == 0 or sf.shape[1] == 0 or sf.stride(1) != 1 or sf.stride(0) < sf.shape[1]:
+        raise ValueError("target_surface_forms must be a non-empty [V, L] int32 / int64 tensor with unit column stride")
+    v, l = sf.shape
+    if priors.dtype != torch.float32 or priors.shape != (v,):
+        raise ValueError(f"target_priors must be an fp32 [{v}] tensor")
+    n = int(n_token_subsample)
+    if n <= 0 or n > v:
+        raise ValueError(f"n_token_subsample = {n} must be in [1, V = {v}]")
+    special = [int(s) for s in special_ids]
+    if len(special) > _lib.SPLICE_MAX_ROWS:
+        raise ValueError(f"special_ids holds {len(special)} entries, at most {_lib.SPLICE_MAX_ROWS} travel with a launch")
+    bad = [s for s in special if s < 0 or s >= v]
+    if bad:
+        raise IndexError(f"special id {bad[0]} is outside [0, {v})")
+    moves, special_indices = special_row_moves(special, n)
+    if mode == "random":
+        if negative_order is None:
+            raise ValueError("mode=\"random\" needs negative_order: a permutation of range(V) on the device (torch.randperm)")
+        if negative_order.dtype not in ints or negative_order.shape != (v,):
+            raise ValueError(f"negative_order must be an int32 / int64 [{v}] tensor")
+    device = input_ids.device
+    if not input_ids.is_cuda:
+        raise ValueError("zett_amd computes on the GPU only: input_ids must be a cuda (ROCm) tensor; there is no CPU path")
+    for name, x in (("labels", labels), ("target_surface_forms", sf), ("target_priors", priors), ("negative_order", negative_order if mode == "random" else None)):
+        if x is not None and x.device != device:
+            raise ValueError(f"{name} must be on the device of input_ids")
+    lib = _lib.load()
+    ids, lab = input_ids.detach().contiguous(), labels.detach().contiguous()
+    priors = priors.detach().contiguous()
+    order = negative_order.detach().contiguous() if mode == "random" else None
+    t, k = ids.numel(), len(special)
+    arrays = [(C.c_int32 * max(k, 1))(*x) for x in (special, [m[0] for m in moves], [m[1] for m in moves])]
+    with torch.cuda.device(device):
+        out_ids, out_lab = torch.empty_like(ids), torch.empty_like(lab)
+        ids_to_embed = torch.empty(n, dtype=ids.dtype, device=device)
+        out_sf = torch.empty((n, l), dtype=sf.dtype, device=device)
+        out_priors = torch.empty(n, dtype=torch.float32, device=device)
+        mask = torch.empty(n, dtype=torch.bool, device=device)
+        words = torch.empty(2, dtype=torch.int32, device=device)          # n_positive, status: both written by the call
+        work = torch.empty(batch_vocab_workspace(t, v, n) // 4, dtype=torch.int32, device=device)          # (released on return: the allocator reuses it in stream order)
+        _lib.check(lib.zett_op_batch_vocab(_ptr(ids), ids.element_size(), _ptr(lab), lab.element_size(), t, v, n, _ptr(sf), sf.element_size(), sf.stride(0), l,
+                                           _ptr(priors), _ptr(order), 0 if order is None else order.element_size(), _BATCH_MODES[mode], *arrays, k, _ptr(out_ids),
+                                           _ptr(out_lab), _ptr(ids_to_embed), _ptr(out_sf), _ptr(out_priors), _ptr(mask), _ptr(words[0]), _ptr(words[1]), _ptr(work),
+                                           work.numel() * 4, _stream(device)), "batch_vocab")
+    if check:
+        bits = int(words[1].item())          # (the one host read of this call)
+        if bits & BATCH_BAD_ID:
+            raise IndexError(f"subsample_batch_vocabulary: an id of input_ids / labels is outside [0, {v})")
+        if bits & BATCH_BAD_ORDER:
+            raise IndexError(f"subsample_batch_vocabulary: an entry of negative_order is outside [0, {v})")
+        if bits & BATCH_OVERFLOW:
+            raise ValueError(f"subsample_batch_vocabulary: the batch holds {int(words[0].item())} ids with the specials, more than n_token_subsample = {n}")
+        if bits & BATCH_REPEAT:
+            raise ValueError("subsample_batch_vocabulary: ids_to_embed lists an id twice: negative_order is not a permutation of range(V)")
+    return BatchVocabulary(out_ids, out_lab, ids_to_embed, out_sf, out_priors, mask, special_indices, words[0], words[1])
 
 
 # ---- which parameters train, and which decay -------------------------------------------------------------------------------
