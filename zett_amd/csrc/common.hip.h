@@ -1,4 +1,4 @@
-// common.hip.h — error reporting and device-buffer helpers shared by the C ABI sources.
+// common.hip.h — error reporting, device-buffer helpers and the dtype / precision dispatch shared by the C ABI sources.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -6,8 +6,10 @@
 #include <cstdarg>
 #include <cstdio>
 #include <string>
+#include <type_traits>
 
 #include "../../include/zett_hip.h"
+#include "gemm.hip.h"
 
 namespace zett {
 
@@ -62,5 +64,32 @@ struct DevBuf {   // grow-only device allocation
     void release() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
     template <typename U> U* as() const { return (U*)p; }
 };
+
+// ---- runtime type codes as compile-time types --------------------------------------------------------------------------------
+// zett_dtype -> storage type
+template <int DT> struct Elem;
+template <> struct Elem<ZETT_F32> { using type = float; };
+template <> struct Elem<ZETT_F16> { using type = f16_t; };
+template <> struct Elem<ZETT_BF16> { using type = bf16_t; };
+template <int DT> using elem_t = typename Elem<DT>::type;
+
+inline bool is_dtype(int32_t d) { return d == ZETT_F32 || d == ZETT_F16 || d == ZETT_BF16; }
+
+// f(std::integral_constant<int, dtype>{}): a checked (is_dtype) runtime dtype code as a compile-time constant, e.g.
+//     with_dtype(d, [&](auto dt) { hipLaunchKernelGGL((kernel<decltype(dt)::value>), ...); });
+template <typename F> inline void with_dtype(int32_t dtype, F&& f) {
+    if (dtype == ZETT_F32) f(std::integral_constant<int, ZETT_F32>{});
+    else if (dtype == ZETT_F16) f(std::integral_constant<int, ZETT_F16>{});
+    else f(std::integral_constant<int, ZETT_BF16>{});
+}
+
+// f(Arith<T>{}) with T the operand type of a zett_precision (checked by zett_create); returns what f returns, e.g.
+//     return with_precision(h->precision, [&](auto a) { return do_forward<typename decltype(a)::type>(...); });
+template <typename T> struct Arith { using type = T; };
+template <typename F> inline auto with_precision(int precision, F&& f) {
+    if (precision == ZETT_PREC_F16) return f(Arith<f16_t>{});
+    if (precision == ZETT_PREC_BF16) return f(Arith<bf16_t>{});
+    return f(Arith<float>{});
+}
 
 }  // namespace zett

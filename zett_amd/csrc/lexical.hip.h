@@ -181,14 +181,6 @@ inline void launch_lexical_rows(const int32_t* ids, const int32_t* count, int64_
                            (OT*)dst, ld_dst, rows, strips);
 }
 
-template <int SRC_DTYPE>
-inline void launch_lexical_rows_dst(int dst_dtype, const int32_t* ids, const int32_t* count, int64_t n_tokens, int width, const void* src, int64_t ld_src,
-                                    int cols, int64_t fallback_id, void* dst, int64_t ld_dst, const int64_t* rows, hipStream_t st) {
-    if (dst_dtype == ZETT_F32) launch_lexical_rows<SRC_DTYPE, float>(ids, count, n_tokens, width, src, ld_src, cols, fallback_id, dst, ld_dst, rows, st);
-    else if (dst_dtype == ZETT_F16) launch_lexical_rows<SRC_DTYPE, f16_t>(ids, count, n_tokens, width, src, ld_src, cols, fallback_id, dst, ld_dst, rows, st);
-    else launch_lexical_rows<SRC_DTYPE, bf16_t>(ids, count, n_tokens, width, src, ld_src, cols, fallback_id, dst, ld_dst, rows, st);
-}
-
 }  // namespace zett
 
 extern "C" {
@@ -271,8 +263,8 @@ int zett_lexical_rows_into(zett_lexical* h, const int32_t* ids, const int32_t* c
     using namespace zett;
     if (!h || !dest) return fail(ZETT_E_INVALID, "null argument");
     if (n_tokens < 0 || width < 1 || n_source_rows < 0 || n_embd < 1) return fail(ZETT_E_INVALID, "bad shape");
-    if (src_dtype != ZETT_F32 && src_dtype != ZETT_F16 && src_dtype != ZETT_BF16) return fail(ZETT_E_INVALID, "unknown source dtype %d", src_dtype);
-    if (dest->dtype != ZETT_F32 && dest->dtype != ZETT_F16 && dest->dtype != ZETT_BF16) return fail(ZETT_E_INVALID, "unknown destination dtype %d", dest->dtype);
+    if (!is_dtype(src_dtype)) return fail(ZETT_E_INVALID, "unknown source dtype %d", src_dtype);
+    if (!is_dtype(dest->dtype)) return fail(ZETT_E_INVALID, "unknown destination dtype %d", dest->dtype);
     if (dest->bias) return fail(ZETT_E_INVALID, "zett_dest.bias must be NULL: the lexical transfer has no bias");
     if (!src_in || !dest->in) return fail(ZETT_E_INVALID, "null source or destination matrix");
     if ((src_out == nullptr) != (dest->out == nullptr)) return fail(ZETT_E_INVALID, "source and destination must both have, or both lack, the output-embedding matrix");
@@ -303,9 +295,12 @@ int zett_lexical_rows_into(zett_lexical* h, const int32_t* ids, const int32_t* c
         const int64_t ld_src = part ? ld_src_out : ld_src_in;
         void* dst = part ? dest->out : dest->in;
         const int64_t ld_dst = part ? dest->ld_out : dest->ld_in;
-        if (src_dtype == ZETT_F32) launch_lexical_rows_dst<0>(dest->dtype, ids, count, n_tokens, width, src, ld_src, n_embd, fallback_id, dst, ld_dst, dest->rows, st);
-        else if (src_dtype == ZETT_F16) launch_lexical_rows_dst<1>(dest->dtype, ids, count, n_tokens, width, src, ld_src, n_embd, fallback_id, dst, ld_dst, dest->rows, st);
-        else launch_lexical_rows_dst<2>(dest->dtype, ids, count, n_tokens, width, src, ld_src, n_embd, fallback_id, dst, ld_dst, dest->rows, st);
+        with_dtype(src_dtype, [&](auto sd) {
+            with_dtype(dest->dtype, [&](auto dd) {
+                launch_lexical_rows<decltype(sd)::value, elem_t<decltype(dd)::value>>(ids, count, n_tokens, width, src, ld_src, n_embd, fallback_id, dst, ld_dst,
+                                                                                      dest->rows, st);
+            });
+        });
     }
     HIP_TRY(hipGetLastError());
     return 0;

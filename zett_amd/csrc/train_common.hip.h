@@ -1,8 +1,9 @@
 // train_common.hip.h — the small device / host layer the four training units (train_ops.hip, train_step.hip, train_loss.hip,
-// train_embed.hip) share: the zett_dtype -> storage-type map, element accessors over gemm.hip.h's conversions (to_lo, lo_to_f32,
-// pack2_lo, unpack2_lo: widen on load — bf16 by the 16-bit left shift —, round to nearest even on store), the reductions, the id
-// read and the dtype dispatch of the launches.  The device helpers here hold only conversions and additions, so a caller's
-// `#pragma clang fp contract(off)` keeps its meaning.  Training only (zett_amd/build.py TRAINING_ONLY): no forward source includes it.
+// train_embed.hip) share: element accessors over gemm.hip.h's conversions (to_lo, lo_to_f32, pack2_lo, unpack2_lo: widen on load —
+// bf16 by the 16-bit left shift —, round to nearest even on store), the reductions and the id read.  (The zett_dtype ->
+// storage-type map and the dtype dispatch of the launches — elem_t, is_dtype, with_dtype — are common.hip.h's: the forward uses
+// them too.)  The device helpers here hold only conversions and additions, so a caller's `#pragma clang fp contract(off)` keeps
+// its meaning.  Training only (zett_amd/build.py TRAINING_ONLY): no forward source includes it.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -11,17 +12,12 @@
 #include <type_traits>
 
 #include "../../include/zett_hip.h"
+#include "common.hip.h"
 #include "gemm.hip.h"
 
 namespace zett {
 
-// ---- element types: fp32 / f16 / bf16 storage ----------------------------------------------------------------------------------
-template <int DT> struct Elem;
-template <> struct Elem<ZETT_F32> { using type = float; };
-template <> struct Elem<ZETT_F16> { using type = f16_t; };
-template <> struct Elem<ZETT_BF16> { using type = bf16_t; };
-template <int DT> using elem_t = typename Elem<DT>::type;
-
+// ---- element accessors (fp32 / f16 / bf16 storage: elem_t, common.hip.h) -----------------------------------------------------------
 template <typename T> __device__ __forceinline__ float load1(const T* p) { return lo_to_f32<T>(*p); }
 template <typename T> __device__ __forceinline__ void store1(T* p, float v) { *p = to_lo<T>(v); }
 
@@ -90,16 +86,6 @@ __device__ __forceinline__ double block_sum_f64(double v, double* red /* [256] *
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------------
-inline bool is_dtype(int32_t d) { return d == ZETT_F32 || d == ZETT_F16 || d == ZETT_BF16; }
-
-// f(std::integral_constant<int, dtype>{}): a checked (is_dtype) runtime dtype code as a compile-time constant, e.g.
-//     with_dtype(d, [&](auto dt) { hipLaunchKernelGGL((kernel<decltype(dt)::value>), ...); });
-template <typename F> inline void with_dtype(int32_t dtype, F&& f) {
-    if (dtype == ZETT_F32) f(std::integral_constant<int, ZETT_F32>{});
-    else if (dtype == ZETT_F16) f(std::integral_constant<int, ZETT_F16>{});
-    else f(std::integral_constant<int, ZETT_BF16>{});
-}
-
 // Declared here, DEFINED in train_loss.hip, which holds the one column-sum kernel and the one converting-copy kernel of the training
 // units: out[c] (+)= sum_r in[r, c], and out[r, c] = convert(in[r, c]) with columns [cols, cols_padded) zero.  train_ops.hip
 // (zett_op_colsum_f32, the general path of zett_op_convert_lo) links against them; they are internal to the library (hidden).

@@ -16,7 +16,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <array>
 #include <cstdlib>
 #include <cmath>
 #include <cstdarg>
@@ -132,9 +131,7 @@ struct zett_hypernet {
     hipEvent_t dest_checked = nullptr;
     std::vector<hipEvent_t> ev;
     size_t ev_used = 0;
-    std::vector<double> ev_flops;
-    std::vector<std::array<int, 4>> ev_shape;   // M, N, K, variant of each timed launch
-    std::vector<zett_gemm_record> gemm_log;     // every GEMM launch of the last forward (zett_get_gemm_log)
+    std::vector<zett_gemm_record> gemm_log;     // every GEMM launch of the last forward (zett_get_gemm_log); "time_gemm": launch k has the event pair ev[2k], ev[2k + 1]
     zett_stats stats{};
 };
 
@@ -215,25 +212,15 @@ int validate_config(const zett_config& c, int precision) {
 }
 
 // Device bytes zett_forward reserves, as a function of what the plan found (packed positions
-// Ttot, distinct ids D).  One definition shared by do_forward and zett_workspace_bytes.
+// Ttot, distinct ids D).  One definition shared by the forward, zett_table_rows and zett_workspace_bytes.
 struct WorkspaceSizes {
     int64_t chunk_tokens;
-    size_t table, x0, f32_rows, lo_rows, big, stats;
-    size_t total() const { return table + x0 + 3 * f32_rows + 3 * lo_rows + big + stats; }
+    size_t table, x0, f32_rows, lo_rows, big, stats, parts;
+    size_t total() const { return table + x0 + 3 * f32_rows + 3 * lo_rows + big + stats + parts; }
 };
 
 static int64_t pair_keys(const zett_config& c, int seq) {
     return ((int64_t)c.original_vocab_size + c.n_extra + 1) * (int64_t)(seq + (c.embed_lang ? 1 : 0));
-}
-
-static size_t plan_i32_bytes(const zett_config& c, int64_t N, int seq) {
-    const int64_t V = (int64_t)c.original_vocab_size + c.n_extra;
-    const int64_t max_tok = N * (int64_t)(seq + (c.embed_lang ? 1 : 0));
-    // row_count[N] row_offset[N+1] id_flag[V] id_slot[V+1] id_list[V] tok_slot[T] tok_pos[T] tok_row[T] err[1] scan scratch
-    // + the pair plan: tok_pkey[T] tok_pair[T] pair_tslot[T] pair_pos[T] pair_flag[K] pair_slot[K+1], K = (V+1)(L+lang)
-    const int64_t K = pair_keys(c, seq);
-    const size_t scan_scratch = 2 * ((size_t)std::max<int64_t>(std::max<int64_t>(N, V), K) / SCAN_CHUNK + 2) + 1;
-    return ((size_t)N + (N + 1) + 3 + V + (V + 1) + V + 7 * (size_t)max_tok + 2 * (size_t)K + 2 + scan_scratch) * 4;
 }
 
 // Packed positions per encoder chunk when the caller has not set "max_chunk_tokens": 12 GiB of per-position workspace,
@@ -259,6 +246,7 @@ static WorkspaceSizes workspace_sizes(const zett_config& c, size_t es, int seq, 
     w.lo_rows = MCS * c.hidden * es;
     w.big = MCS * wide * es;
     w.stats = 2 * MCS * 2 * sizeof(float);         // (mean, rstd) per row: two LayerNorms in flight
+    w.parts = c.hidden % 128 == 0 ? (size_t)(c.hidden / 128) * MCS * sizeof(float2) : 0;      // LayerNorm-fold partials (reserved when ForwardMode::fold)
     return w;
 }
 
@@ -272,45 +260,44 @@ struct PlanLayout {
     bool pair_plan = false;
     int64_t PK = 0;
     size_t n_clear = 0;          // int32 words at the head of the arena that a plan starts from zero
+    size_t words = 0;            // int32 words of the whole arena, scan scratch included
 };
-static PlanLayout plan_layout(const zett_hypernet* h, const zett_hypernet::PlanSlot& s, int64_t N, int seq) {
+// s == null: sizes only (every pointer null).  worst_case: the arena of a plan WITH the pair plan, whatever the options say now.
+static PlanLayout plan_layout(const zett_hypernet* h, const zett_hypernet::PlanSlot* s, int64_t N, int seq, bool worst_case = false) {
     const zett_config& c = h->cfg;
     const int lam = c.embed_lang ? 1 : 0;
-    const int V = c.original_vocab_size + c.n_extra;
+    const int64_t V = (int64_t)c.original_vocab_size + c.n_extra;
     const int64_t max_tok = N * (int64_t)(seq + lam);
     PlanLayout L;
     PlanArrays& p = L.p;
-    // int32 arena: what a plan clears first, in one piece — id_flag[V] pair_flag[PK] err[1] — then row_count[N] row_offset[N+1]
-    // counters[3] (read by the host in one copy with the row offsets) id_slot[V+1] id_list[V] tok_slot[T] tok_pos[T] tok_row[T]
-    // [pair plan] scan scratch
-    L.PK = pair_keys(c, seq);
-    L.pair_plan = h->pair_dedupe && c.layers >= 2 && L.PK <= std::max<int64_t>(4 * max_tok, (int64_t)1 << 23) && L.PK < (int64_t)0x7fffffff;
-    int32_t* base = s.i32.as<int32_t>();
-    p.id_flag = base; base += V;
-    if (L.pair_plan) { p.pair_flag = base; base += L.PK; }
-    p.err = base; base += 1;
-    L.n_clear = (size_t)(base - s.i32.as<int32_t>());
-    p.row_count = base; base += N;
-    p.row_offset = base; base += N + 1;
-    p.counters = base; base += 3;
-    p.id_slot = base; base += V + 1;
-    p.id_list = base; base += V;
-    p.tok_slot = base; base += max_tok;
-    p.tok_pos = base; base += max_tok;
-    p.tok_row = base; base += max_tok;
+    L.PK = pair_keys(c, seq);          // K = (V+1)(L+lang)
+    L.pair_plan = worst_case || (h->pair_dedupe && c.layers >= 2 && L.PK <= std::max<int64_t>(4 * max_tok, (int64_t)1 << 23) && L.PK < (int64_t)0x7fffffff);
+    int32_t* const base = s ? s->i32.as<int32_t>() : nullptr;
+    auto take = [&](int32_t*& array, int64_t n) { array = base ? base + L.words : nullptr; L.words += (size_t)n; };
+    // int32 arena, the one list of its arrays: what a plan clears first, in one piece — id_flag[V] pair_flag[PK] err[1] — then
+    // row_count[N] row_offset[N+1] counters[3] (read by the host in one copy with the row offsets) id_slot[V+1] id_list[V]
+    // tok_slot[T] tok_pos[T] tok_row[T] [pair plan: tok_pkey[T] tok_pair[T] pair_tslot[T] pair_pos[T] pair_slot[PK+1]] scan scratch
+    take(p.id_flag, V);
+    if (L.pair_plan) take(p.pair_flag, L.PK);
+    take(p.err, 1);
+    L.n_clear = L.words;
+    take(p.row_count, N); take(p.row_offset, N + 1); take(p.counters, 3);
+    take(p.id_slot, V + 1); take(p.id_list, V);
+    take(p.tok_slot, max_tok); take(p.tok_pos, max_tok); take(p.tok_row, max_tok);
     p.n_pair_keys = L.pair_plan ? (int32_t)L.PK : 0;
     if (L.pair_plan) {
-        p.tok_pkey = base; base += max_tok;
-        p.tok_pair = base; base += max_tok;
-        p.pair_tslot = base; base += max_tok;
-        p.pair_pos = base; base += max_tok;
-        p.pair_slot = base; base += L.PK + 1;
+        take(p.tok_pkey, max_tok); take(p.tok_pair, max_tok); take(p.pair_tslot, max_tok); take(p.pair_pos, max_tok);
+        take(p.pair_slot, L.PK + 1);
     }
-    L.scan_tmp = base;
-    p.row_uniform = s.u8.as<uint8_t>();
-    p.tok_key = p.row_uniform + N;
+    take(L.scan_tmp, 2 * (std::max<int64_t>(std::max<int64_t>(N, V), L.PK) / SCAN_CHUNK + 2) + 1);
+    if (s) {
+        p.row_uniform = s->u8.as<uint8_t>();
+        p.tok_key = p.row_uniform + N;
+    }
     return L;
 }
+// worst case of a slot's int32 arena for [N, seq] surface forms: what enqueue_plan reserves and zett_workspace_bytes counts
+static size_t plan_i32_bytes(const zett_hypernet* h, int64_t N, int seq) { return plan_layout(h, nullptr, N, seq, true).words * 4; }
 
 // The plan of one forward into slot s, on stream st: six small kernels, three scans, and the copy of the row offsets and the
 // three counters to pinned memory; s.done is recorded behind them.
@@ -319,7 +306,7 @@ static int enqueue_plan(zett_hypernet* h, zett_hypernet::PlanSlot& s, const int3
     const int lam = c.embed_lang ? 1 : 0;
     const int V = c.original_vocab_size + c.n_extra;
     const int64_t max_tok = N * (int64_t)(seq + lam);
-    if (int rc = s.i32.reserve(plan_i32_bytes(c, N, seq))) return rc;
+    if (int rc = s.i32.reserve(plan_i32_bytes(h, N, seq))) return rc;
     if (int rc = s.u8.reserve((size_t)N + (size_t)max_tok)) return rc;
     const size_t need_ints = (size_t)N + 1 + 3;
     if (s.host_ints < need_ints) {
@@ -330,7 +317,7 @@ static int enqueue_plan(zett_hypernet* h, zett_hypernet::PlanSlot& s, const int3
     }
     if (!s.done) HIP_TRY(hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
     if (!s.released) HIP_TRY(hipEventCreateWithFlags(&s.released, hipEventDisableTiming));
-    const PlanLayout L = plan_layout(h, s, N, seq);
+    const PlanLayout L = plan_layout(h, &s, N, seq);
     const PlanArrays& p = L.p;
     HIP_TRY(hipMemsetAsync(s.i32.p, 0, L.n_clear * 4, st));          // id_flag, pair_flag, err: one piece of the arena
     const int rb = (int)((N + 255) / 256);
@@ -358,9 +345,45 @@ static int enqueue_plan(zett_hypernet* h, zett_hypernet::PlanSlot& s, const int3
 
 template <typename T>
 int do_forward(zett_hypernet* h, const int32_t* sfm, int64_t N, int seq, const void* src, int src_dtype, const zett_dest* dest,
-               int64_t v_src, int lang_index, float* out_in, float* out_out, float* out_bias, hipStream_t st);
+               int lang_index, float* out_in, float* out_out, float* out_bias, hipStream_t st);
 template <typename T>
 int do_table_rows(zett_hypernet* h, const int32_t* id_list, int first, int count, const void* src, int src_dtype, void* table_out, float* stats_out, hipStream_t st);
+
+// What the entry points of the forward family (zett_forward[_into], zett_forward_table[_into], zett_forward_prepare, zett_table_plan,
+// zett_table_rows) check before they touch the device, in the one order in which they report it.  An entry point fills in what it
+// has; the fields say where the entry points differ.  Returns 0, an error code, or CALL_EMPTY: a valid call on no rows.
+constexpr int CALL_EMPTY = 1;
+struct CallCheck {
+    int64_t n_rows = 0; int32_t seq = 1;
+    bool shape = true;                  // [n_rows, seq] surface forms (zett_table_rows has a table range of its own instead)
+    bool empty_ok = false;              // n_rows == 0 is a call that does nothing, not a bad shape
+    bool null_arg = false, null_first = false;      // a required pointer is null; reported before the shape (zett_table_plan)
+    const char* null_text = "null tensor argument";
+    bool encoder = false, need_out_out = false; int32_t lang_index = 0;      // the call runs the encoder: positions, outputs, language
+    bool source = false; int src_dtype = ZETT_F32; int64_t v_src = 0;        // the call reads source embeddings
+    const char* table_mode = nullptr;   // the entry point's name when it needs the folded table, i.e. a 16-bit precision
+};
+int check_call(const zett_hypernet* h, const CallCheck& k) {
+    if (!h) return fail(ZETT_E_INVALID, "null handle");
+    if (!h->finalized) return fail(ZETT_E_STATE, "zett_finalize has not been called");
+    const zett_config& c = h->cfg;
+    if (k.null_first && k.null_arg) return fail(ZETT_E_INVALID, "%s", k.null_text);
+    if (k.shape && (k.n_rows < (k.empty_ok ? 0 : 1) || k.seq < 1)) return fail(ZETT_E_INVALID, "bad surface-form shape [%lld, %d]", (long long)k.n_rows, k.seq);
+    if (k.encoder && k.seq + (c.embed_lang ? 1 : 0) > c.max_positions)
+        return fail(ZETT_E_INDEX, "sequence %d exceeds position_embeddings (%d rows)", k.seq, c.max_positions);
+    if (k.shape && k.n_rows == 0) return CALL_EMPTY;
+    if (k.null_arg) return fail(ZETT_E_INVALID, "%s", k.null_text);
+    if (k.need_out_out) return fail(ZETT_E_INVALID, "out_out is required when separate_out_embeddings is set");
+    if (k.source) {
+        if (!is_dtype(k.src_dtype)) return fail(ZETT_E_INVALID, "unknown source dtype %d", k.src_dtype);
+        if (k.v_src < c.original_vocab_size)
+            return fail(ZETT_E_INDEX, "source_embeddings has %lld rows, config.original_vocab_size is %d", (long long)k.v_src, c.original_vocab_size);
+    }
+    if (k.encoder && c.embed_lang && (k.lang_index < 0 || k.lang_index >= c.n_langs)) return fail(ZETT_E_INDEX, "lang_index %d outside [0,%d)", k.lang_index, c.n_langs);
+    if (k.shape && k.n_rows * (int64_t)(k.seq + 1) >= (int64_t)0x7fffffff) return fail(ZETT_E_INVALID, "too many positions for one call");
+    if (k.table_mode && h->precision == ZETT_PREC_F32) return fail(ZETT_E_INVALID, "%s: the folded 16-bit table exists in the 16-bit modes only", k.table_mode);
+    return 0;
+}
 
 }  // namespace
 
@@ -484,10 +507,11 @@ int zett_finalize(zett_hypernet* h) {
         if (h->precision == ZETT_PREC_F32) { t.lo = t.f32; continue; }
         HIP_TRY(hipMalloc(&t.lo, t.numel * 2));
         const int blocks = (int)std::min<size_t>((t.numel / 4 + 255) / 256 + 1, 65535);
-        if (h->precision == ZETT_PREC_F16)
-            hipLaunchKernelGGL(convert_f32_to_lo_kernel<f16_t>, dim3(blocks), dim3(256), 0, 0, t.f32, (f16_t*)t.lo, t.numel, h->range_word);
-        else
-            hipLaunchKernelGGL(convert_f32_to_lo_kernel<bf16_t>, dim3(blocks), dim3(256), 0, 0, t.f32, (bf16_t*)t.lo, t.numel, h->range_word);
+        with_precision(h->precision, [&](auto a) {
+            using T = typename decltype(a)::type;
+            if constexpr (sizeof(T) == 2)       // (the fp32 mode left the loop above: no fp32 instantiation of the kernel exists)
+                hipLaunchKernelGGL(convert_f32_to_lo_kernel<T>, dim3(blocks), dim3(256), 0, 0, t.f32, (T*)t.lo, t.numel, h->range_word);
+        });
     }
     HIP_TRY(hipDeviceSynchronize());
     // fused QKV operand per layer: rows [q | k | v]
@@ -517,10 +541,11 @@ int zett_finalize(zett_hypernet* h) {
             HIP_TRY(hipMalloc((void**)&f.c, N * 4));
             HIP_TRY(hipMalloc((void**)&f.b, N * 4));
             h->owned.push_back(f.w); h->owned.push_back(f.c); h->owned.push_back(f.b);
-            if (h->precision == ZETT_PREC_F16)
-                hipLaunchKernelGGL(fold_weight_kernel<f16_t>, dim3((unsigned)N), dim3(256), 0, 0, w32, (int)K, gamma, beta, bias, (f16_t*)f.w, f.c, f.b, h->range_word);
-            else
-                hipLaunchKernelGGL(fold_weight_kernel<bf16_t>, dim3((unsigned)N), dim3(256), 0, 0, w32, (int)K, gamma, beta, bias, (bf16_t*)f.w, f.c, f.b, h->range_word);
+            with_precision(h->precision, [&](auto a) {
+                using T = typename decltype(a)::type;
+                if constexpr (sizeof(T) == 2)
+                    hipLaunchKernelGGL(fold_weight_kernel<T>, dim3((unsigned)N), dim3(256), 0, 0, w32, (int)K, gamma, beta, bias, (T*)f.w, f.c, f.b, h->range_word);
+            });
             return 0;
         };
         h->fold_qkv.resize(c.layers); h->fold_up.resize(c.layers);
@@ -648,8 +673,7 @@ int zett_workspace_bytes(const zett_hypernet* h, int64_t n_rows, int32_t seq, in
     const int64_t max_tok = n_rows * (int64_t)(seq + (c.embed_lang ? 1 : 0));
     // worst case of the plan: no pad position, every position a different source id
     const WorkspaceSizes w = workspace_sizes(c, elt_size(h->precision), seq, max_tok, std::min<int64_t>(V, max_tok), h->max_chunk_tokens);
-    const size_t parts = c.hidden % 128 == 0 ? (size_t)(c.hidden / 128) * ((size_t)w.chunk_tokens + 768) * 8 : 0;      // LayerNorm-fold partials
-    *out_bytes = (int64_t)(w.total() + parts + plan_i32_bytes(c, n_rows, seq) + (size_t)n_rows + (size_t)max_tok);
+    *out_bytes = (int64_t)(w.total() + plan_i32_bytes(h, n_rows, seq) + (size_t)n_rows + (size_t)max_tok);
     return 0;
 }
 
@@ -753,14 +777,9 @@ int zett_scatter_rows(const void* src, void* dst, const int64_t* order, int64_t 
 }
 
 int zett_forward_prepare(zett_hypernet* h, const int32_t* surface_forms, int64_t n_rows, int32_t seq, void* input_stream) {
-    if (!h) return fail(ZETT_E_INVALID, "null handle");
-    if (!h->finalized) return fail(ZETT_E_STATE, "zett_finalize has not been called");
-    const zett_config& c = h->cfg;
-    if (n_rows < 0 || seq < 1) return fail(ZETT_E_INVALID, "bad surface-form shape [%lld, %d]", (long long)n_rows, seq);
-    if (n_rows == 0) return 0;
-    if (!surface_forms) return fail(ZETT_E_INVALID, "null tensor argument");
-    if (n_rows * (int64_t)(seq + 1) >= (int64_t)0x7fffffff) return fail(ZETT_E_INVALID, "too many positions for one call");
-    (void)c;
+    CallCheck k;
+    k.n_rows = n_rows; k.seq = seq; k.empty_ok = true; k.null_arg = !surface_forms;
+    if (int rc = check_call(h, k)) return rc == CALL_EMPTY ? 0 : rc;
     ZETT_ON_DEVICE(h->device);
     if (!h->plan_stream) {      // highest priority: the plan's small workgroups must get CUs while a forward's GEMM tiles own the chip
         int least = 0, greatest = 0;
@@ -802,36 +821,28 @@ int check_dest(const zett_hypernet* h, const zett_dest* d, int64_t n_rows) {
 
 int forward_entry(zett_hypernet* h, const int32_t* surface_forms, int64_t n_rows, int32_t seq, const void* source_embeddings, int src_dtype,
                   int64_t v_src, int32_t lang_index, const zett_dest* dest, float* out_in, float* out_out, float* out_bias, void* stream) {
-    if (!h) return fail(ZETT_E_INVALID, "null handle");
-    if (!h->finalized) return fail(ZETT_E_STATE, "zett_finalize has not been called");
-    const zett_config& c = h->cfg;
-    if (n_rows < 0 || seq < 1) return fail(ZETT_E_INVALID, "bad surface-form shape [%lld, %d]", (long long)n_rows, seq);
-    if (seq + (c.embed_lang ? 1 : 0) > c.max_positions) return fail(ZETT_E_INDEX, "sequence %d exceeds position_embeddings (%d rows)", seq, c.max_positions);
-    if (n_rows == 0) {
+    CallCheck k;
+    k.n_rows = n_rows; k.seq = seq; k.empty_ok = true; k.encoder = true; k.lang_index = lang_index;
+    k.null_arg = !surface_forms || !source_embeddings || (!dest && (!out_in || !out_bias));
+    k.need_out_out = h && !dest && h->cfg.separate_out && !out_out;
+    k.source = true; k.src_dtype = src_dtype; k.v_src = v_src;
+    const int checked = check_call(h, k);
+    if (checked != 0 && checked != CALL_EMPTY) return checked;
+    ZETT_ON_DEVICE(h->device);
+    hipStream_t st = (hipStream_t)stream;
+    if (checked == CALL_EMPTY) {
         h->stats = zett_stats{};
-        ZETT_ON_DEVICE(h->device);
-        if (!h->range_accumulate) HIP_TRY(hipMemsetAsync(h->range_word, 0, 4, (hipStream_t)stream));
+        if (!h->range_accumulate) HIP_TRY(hipMemsetAsync(h->range_word, 0, 4, st));
         for (hipEvent_t& e : h->out_ready) {
             if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-            HIP_TRY(hipEventRecord(e, (hipStream_t)stream));
+            HIP_TRY(hipEventRecord(e, st));
         }
         h->out_recorded = true;
         return 0;
     }
-    if (!surface_forms || !source_embeddings || (!dest && (!out_in || !out_bias))) return fail(ZETT_E_INVALID, "null tensor argument");
-    const bool has_out = c.separate_out;
-    if (!dest && has_out && !out_out) return fail(ZETT_E_INVALID, "out_out is required when separate_out_embeddings is set");
-    if (src_dtype < ZETT_F32 || src_dtype > ZETT_BF16) return fail(ZETT_E_INVALID, "unknown source dtype %d", src_dtype);
-    if (v_src < c.original_vocab_size) return fail(ZETT_E_INDEX, "source_embeddings has %lld rows, config.original_vocab_size is %d", (long long)v_src, c.original_vocab_size);
-    if (c.embed_lang && (lang_index < 0 || lang_index >= c.n_langs)) return fail(ZETT_E_INDEX, "lang_index %d outside [0,%d)", lang_index, c.n_langs);
-    if (n_rows * (int64_t)(seq + 1) >= (int64_t)0x7fffffff) return fail(ZETT_E_INVALID, "too many positions for one call");
-    ZETT_ON_DEVICE(h->device);
-    hipStream_t st = (hipStream_t)stream;
-    if (h->precision == ZETT_PREC_F16)
-        return do_forward<f16_t>(h, surface_forms, n_rows, seq, source_embeddings, src_dtype, dest, v_src, lang_index, out_in, out_out, out_bias, st);
-    if (h->precision == ZETT_PREC_BF16)
-        return do_forward<bf16_t>(h, surface_forms, n_rows, seq, source_embeddings, src_dtype, dest, v_src, lang_index, out_in, out_out, out_bias, st);
-    return do_forward<float>(h, surface_forms, n_rows, seq, source_embeddings, src_dtype, dest, v_src, lang_index, out_in, out_out, out_bias, st);
+    return with_precision(h->precision, [&](auto a) {
+        return do_forward<typename decltype(a)::type>(h, surface_forms, n_rows, seq, source_embeddings, src_dtype, dest, lang_index, out_in, out_out, out_bias, st);
+    });
 }
 
 }  // namespace
@@ -854,11 +865,10 @@ int zett_forward_into(zett_hypernet* h, const int32_t* surface_forms, int64_t n_
 // ---- (ABI 8) the hoisted table shared between ranks: SURVEY 8e's optional second exchange ---------------------------------
 int zett_table_plan(zett_hypernet* h, const int32_t* surface_forms, int64_t n_rows, int32_t seq, int32_t* id_slot_out, int32_t* id_list_out,
                     int64_t* n_ids_out, void* stream) {
-    if (!h) return fail(ZETT_E_INVALID, "null handle");
-    if (!h->finalized) return fail(ZETT_E_STATE, "zett_finalize has not been called");
-    if (!surface_forms || !id_slot_out || !id_list_out || !n_ids_out) return fail(ZETT_E_INVALID, "null argument");
-    if (n_rows < 1 || seq < 1) return fail(ZETT_E_INVALID, "bad surface-form shape [%lld, %d]", (long long)n_rows, seq);
-    if (n_rows * (int64_t)(seq + 1) >= (int64_t)0x7fffffff) return fail(ZETT_E_INVALID, "too many positions for one call");
+    CallCheck k;
+    k.n_rows = n_rows; k.seq = seq;
+    k.null_arg = !surface_forms || !id_slot_out || !id_list_out || !n_ids_out; k.null_text = "null argument"; k.null_first = true;
+    if (int rc = check_call(h, k)) return rc;
     const zett_config& c = h->cfg;
     const int V = c.original_vocab_size + c.n_extra;
     ZETT_ON_DEVICE(h->device);
@@ -875,7 +885,7 @@ int zett_table_plan(zett_hypernet* h, const int32_t* surface_forms, int64_t n_ro
         return fail(ZETT_E_INDEX, "surface-form row %d holds an id outside [0, %d) (original_vocab_size %d + %d fallback rows)",
                     hoff[n_rows + 2] - 1, V, c.original_vocab_size, c.n_extra);
     const int D = hoff[n_rows + 1];
-    const PlanLayout L = plan_layout(h, ps, n_rows, seq);
+    const PlanLayout L = plan_layout(h, &ps, n_rows, seq);
     HIP_TRY(hipMemcpyAsync(id_slot_out, L.p.id_slot, ((size_t)V + 1) * 4, hipMemcpyDeviceToDevice, st));
     if (D > 0) HIP_TRY(hipMemcpyAsync(id_list_out, L.p.id_list, (size_t)D * 4, hipMemcpyDeviceToDevice, st));
     *n_ids_out = D;
@@ -884,18 +894,21 @@ int zett_table_plan(zett_hypernet* h, const int32_t* surface_forms, int64_t n_ro
 
 int zett_table_rows(zett_hypernet* h, const int32_t* id_list, int64_t first, int64_t count, const void* source_embeddings, int src_dtype,
                     int64_t v_src, void* table_out, float* stats_out, void* stream) {
-    if (!h) return fail(ZETT_E_INVALID, "null handle");
-    if (!h->finalized) return fail(ZETT_E_STATE, "zett_finalize has not been called");
+    CallCheck k;
+    k.shape = false;                    // (a range of table rows instead of surface forms: checked here, between the handle and the tensors)
+    if (int rc = check_call(h, k)) return rc;
     if (first < 0 || count < 0 || first + count >= (int64_t)0x7fffffff) return fail(ZETT_E_INVALID, "bad table range [%lld, +%lld)", (long long)first, (long long)count);
     if (count == 0) return 0;
-    if (!id_list || !source_embeddings || !table_out || !stats_out) return fail(ZETT_E_INVALID, "null tensor argument");
-    if (src_dtype < ZETT_F32 || src_dtype > ZETT_BF16) return fail(ZETT_E_INVALID, "unknown source dtype %d", src_dtype);
-    if (v_src < h->cfg.original_vocab_size) return fail(ZETT_E_INDEX, "source_embeddings has %lld rows, config.original_vocab_size is %d", (long long)v_src, h->cfg.original_vocab_size);
+    k.null_arg = !id_list || !source_embeddings || !table_out || !stats_out;
+    k.source = true; k.src_dtype = src_dtype; k.v_src = v_src;
+    if (int rc = check_call(h, k)) return rc;
     ZETT_ON_DEVICE(h->device);
     hipStream_t st = (hipStream_t)stream;
-    if (h->precision == ZETT_PREC_F16) return do_table_rows<f16_t>(h, id_list, (int)first, (int)count, source_embeddings, src_dtype, table_out, stats_out, st);
-    if (h->precision == ZETT_PREC_BF16) return do_table_rows<bf16_t>(h, id_list, (int)first, (int)count, source_embeddings, src_dtype, table_out, stats_out, st);
-    return fail(ZETT_E_INVALID, "zett_table_rows: the folded 16-bit table exists in the 16-bit modes only");
+    return with_precision(h->precision, [&](auto a) {
+        using T = typename decltype(a)::type;
+        if constexpr (std::is_same<T, float>::value) return fail(ZETT_E_INVALID, "zett_table_rows: the folded 16-bit table exists in the 16-bit modes only");
+        else return do_table_rows<T>(h, id_list, (int)first, (int)count, source_embeddings, src_dtype, table_out, stats_out, st);
+    });
 }
 
 }  // extern "C"
@@ -903,24 +916,17 @@ int zett_table_rows(zett_hypernet* h, const int32_t* id_list, int64_t first, int
 namespace {
 int forward_table_entry(zett_hypernet* h, const int32_t* surface_forms, int64_t n_rows, int32_t seq, const void* table, const float* table_stats,
                         const int32_t* id_slot, int32_t lang_index, const zett_dest* dest, float* out_in, float* out_out, float* out_bias, void* stream) {
-    if (!h) return fail(ZETT_E_INVALID, "null handle");
-    if (!h->finalized) return fail(ZETT_E_STATE, "zett_finalize has not been called");
-    const zett_config& c = h->cfg;
-    if (n_rows < 1 || seq < 1) return fail(ZETT_E_INVALID, "bad surface-form shape [%lld, %d]", (long long)n_rows, seq);
-    if (seq + (c.embed_lang ? 1 : 0) > c.max_positions) return fail(ZETT_E_INDEX, "sequence %d exceeds position_embeddings (%d rows)", seq, c.max_positions);
-    if (!surface_forms || !table || !table_stats || !id_slot || (!dest && (!out_in || !out_bias))) return fail(ZETT_E_INVALID, "null tensor argument");
-    if (!dest && c.separate_out && !out_out) return fail(ZETT_E_INVALID, "out_out is required when separate_out_embeddings is set");
-    if (c.embed_lang && (lang_index < 0 || lang_index >= c.n_langs)) return fail(ZETT_E_INDEX, "lang_index %d outside [0,%d)", lang_index, c.n_langs);
-    if (n_rows * (int64_t)(seq + 1) >= (int64_t)0x7fffffff) return fail(ZETT_E_INVALID, "too many positions for one call");
-    if (h->precision == ZETT_PREC_F32) return fail(ZETT_E_INVALID, "zett_forward_table: the folded 16-bit table exists in the 16-bit modes only");
+    CallCheck k;
+    k.n_rows = n_rows; k.seq = seq; k.encoder = true; k.lang_index = lang_index; k.table_mode = "zett_forward_table";
+    k.null_arg = !surface_forms || !table || !table_stats || !id_slot || (!dest && (!out_in || !out_bias));
+    k.need_out_out = h && !dest && h->cfg.separate_out && !out_out;
+    if (int rc = check_call(h, k)) return rc;
     ZETT_ON_DEVICE(h->device);
     hipStream_t st = (hipStream_t)stream;
     h->ext.table = table; h->ext.stats = table_stats; h->ext.id_slot = id_slot;
-    int rc;
-    if (h->precision == ZETT_PREC_F16)
-        rc = do_forward<f16_t>(h, surface_forms, n_rows, seq, nullptr, ZETT_F32, dest, 0, lang_index, out_in, out_out, out_bias, st);
-    else
-        rc = do_forward<bf16_t>(h, surface_forms, n_rows, seq, nullptr, ZETT_F32, dest, 0, lang_index, out_in, out_out, out_bias, st);
+    const int rc = with_precision(h->precision, [&](auto a) {
+        return do_forward<typename decltype(a)::type>(h, surface_forms, n_rows, seq, nullptr, ZETT_F32, dest, lang_index, out_in, out_out, out_bias, st);
+    });
     h->ext = zett_hypernet::ExtTable{};
     return rc;
 }
@@ -952,7 +958,6 @@ struct Runner {
     hipStream_t st;
     int rc = 0;
 
-    const Tensor& W(const std::string& n) { return h->w.at(n); }
     const T* Wlo(const std::string& n) { return (const T*)h->w.at(n).lo; }
     const float* Wf(const std::string& n) { return h->w.at(n).f32; }
 
@@ -969,40 +974,36 @@ struct Runner {
 
     // the tile variant a launch takes
     int variant_for(int M, int N, int K, const GemmEpilogue<T>& e) const {
-    // Tile choice.  Small problems: 128x128.  Otherwise the 256x256 register-staged eight-wave
-    // kernel (gemm8r), unless the 384x256 LDS-DMA tile needs fewer rounds over the 256 CUs (it
-    // runs ~1.7x as long per tile): wave quantisation decides, e.g. M = 5 111 at N = 4096.
-    // The 384-row kernel has no registers to spare for a residual or scale/shift epilogue
-    // (168 per wave: it would spill to scratch, and no kernel with scratch is ever launched)
-    // and does not clamp rows, so A must have
-    // `a_rows_readable` >= tiles*384 rows (every A operand here is a workspace buffer with
-    // that slack) and N must be a multiple of 256.  (The kernels that led to gemm8r and gemm4d
-    // -- four-wave register-staged, eight-wave LDS-DMA, gemm8r on 16x16x32 MFMAs -- live in
-    // tools/experiments/ with tools/gemm_bench on the `experiments` branch.)
-    constexpr bool is_f32 = std::is_same<T, float>::value;
-    int variant = h->gemm_variant;
-    if (variant == 0) {
-        variant = (M > 128 && N > 128) ? 2 : 1;
-        if (variant != 1 && N % 256 == 0 && !e.scale && !e.residual) {
-            const long t256 = (long)((M + 255) / 256) * (N / 256), t384 = (long)((M + 383) / 384) * (N / 256);
-            const double c256 = (double)((t256 + 255) / 256), c384 = 1.7 * (double)((t384 + 255) / 256);
-            if (c384 < c256) variant = 3;
+        // Tile choice.  Small problems: 128x128.  Otherwise the 256x256 register-staged eight-wave kernel (gemm8r), unless the 384x256
+        // LDS-DMA tile needs fewer rounds over the 256 CUs (it runs ~1.7x as long per tile): wave quantisation decides, e.g. M = 5 111
+        // at N = 4096.  The 384-row kernel has no registers to spare for a residual or scale/shift epilogue (168 per wave: it would
+        // spill to scratch, and no kernel with scratch is ever launched) and does not clamp rows, so A must have `a_rows_readable` >=
+        // tiles*384 rows (every A operand here is a workspace buffer with that slack) and N must be a multiple of 256.  (The kernels
+        // that led to gemm8r and gemm4d -- four-wave register-staged, eight-wave LDS-DMA, gemm8r on 16x16x32 MFMAs -- live in
+        // tools/experiments/ with tools/gemm_bench on the `experiments` branch.)
+        constexpr bool is_f32 = std::is_same<T, float>::value;
+        int variant = h->gemm_variant;
+        if (variant == 0) {
+            variant = (M > 128 && N > 128) ? 2 : 1;
+            if (variant != 1 && N % 256 == 0 && !e.scale && !e.residual) {
+                const long t256 = (long)((M + 255) / 256) * (N / 256), t384 = (long)((M + 383) / 384) * (N / 256);
+                const double c256 = (double)((t256 + 255) / 256), c384 = 1.7 * (double)((t384 + 255) / 256);
+                if (c384 < c256) variant = 3;
+            }
         }
-    }
-    if (variant == 3 && (N % 256 != 0 || (long)((M + 383) / 384) * 384 > a_rows_readable || e.scale || e.shift || e.residual || e.range_final)) variant = 2;
-    // 16-bit operands, K >= 2048: the four-wave direct-to-LDS tile on 16x16x32 MFMAs (4-8 % ahead of the
-    // register-staged eight-wave kernels on the launches of the benchmark step; identical bits).
-    if (h->gemm_variant == 0 && variant == 2 && !is_f32 && K >= h->gemm4d_min_k) variant = 7;
-    if ((variant == 7 || variant == 8) && is_f32) variant = 2;
-    // the large tiles drain eight columns per lane with 16-byte accesses
-    const bool wide_ok = N % 8 == 0 && (!e.out_lo || e.ld_lo % 8 == 0) && e.ld_f32 % 4 == 0 && (!e.residual || e.ld_res % 4 == 0) &&
-                         (e.split_col >= N || e.split_col % 8 == 0);
-    if (variant != 1 && !wide_ok) variant = 1;
-    if (e.residual && (e.scale || e.shift)) variant = 1;      // the large tiles compile their residual epilogues without the Rescaler
-    if (e.stats_part || e.fold_stats) variant = 7;       // LayerNorm-fold launches exist in gemm4d only (any M)
+        if (variant == 3 && (N % 256 != 0 || (long)((M + 383) / 384) * 384 > a_rows_readable || e.scale || e.shift || e.residual || e.range_final)) variant = 2;
+        // 16-bit operands, K >= 2048: the four-wave direct-to-LDS tile on 16x16x32 MFMAs (4-8 % ahead of the
+        // register-staged eight-wave kernels on the launches of the benchmark step; identical bits).
+        if (h->gemm_variant == 0 && variant == 2 && !is_f32 && K >= h->gemm4d_min_k) variant = 7;
+        if ((variant == 7 || variant == 8) && is_f32) variant = 2;
+        // the large tiles drain eight columns per lane with 16-byte accesses
+        const bool wide_ok = N % 8 == 0 && (!e.out_lo || e.ld_lo % 8 == 0) && e.ld_f32 % 4 == 0 && (!e.residual || e.ld_res % 4 == 0) &&
+                             (e.split_col >= N || e.split_col % 8 == 0);
+        if (variant != 1 && !wide_ok) variant = 1;
+        if (e.residual && (e.scale || e.shift)) variant = 1;      // the large tiles compile their residual epilogues without the Rescaler
+        if (e.stats_part || e.fold_stats) variant = 7;       // LayerNorm-fold launches exist in gemm4d only (any M)
         return variant;
     }
-
 
     void gemm(const T* A, int lda, const T* Wp, int ldw, int M, int N, int K, const GemmEpilogue<T>& e) {
         if (rc || M <= 0) return;
@@ -1020,12 +1021,9 @@ struct Runner {
             }
             e0 = h->ev[h->ev_used++];
             e1 = h->ev[h->ev_used++];
-            h->ev_flops.push_back(fl);
-            h->ev_shape.push_back({M, N, K, 0});
             (void)hipEventRecord(e0, st);
         }
         const int variant = variant_for(M, N, K, e);
-        if (h->time_gemm && !h->ev_shape.empty()) h->ev_shape.back()[3] = variant;
         {
             zett_gemm_record r{};
             r.m = M; r.n = N; r.k = K; r.variant = variant;
@@ -1081,32 +1079,12 @@ struct Runner {
         if (rc || rows <= 0) return;
         const bool vec = cols % 4 == 0 && ld_s % 4 == 0 && d.ld % 4 == 0 && (uintptr_t)S % 16 == 0 && (uintptr_t)d.p % (d.dtype == ZETT_F32 ? 16 : 8) == 0;
         const dim3 grid((unsigned)std::min<int64_t>(rows, 65535 * 16));
-#define ZETT_DEST_STORE(OT) do { if (vec) hipLaunchKernelGGL((dest_store_rows_kernel<OT, true>), grid, dim3(256), 0, st, S, ld_s, (OT*)d.p, d.ld, d.rows, (int64_t)rows, cols, h->range_word); \
-                                 else hipLaunchKernelGGL((dest_store_rows_kernel<OT, false>), grid, dim3(256), 0, st, S, ld_s, (OT*)d.p, d.ld, d.rows, (int64_t)rows, cols, h->range_word); } while (0)
-        if (d.dtype == ZETT_F16) ZETT_DEST_STORE(f16_t);
-        else if (d.dtype == ZETT_BF16) ZETT_DEST_STORE(bf16_t);
-        else ZETT_DEST_STORE(float);
-#undef ZETT_DEST_STORE
+        with_dtype(d.dtype, [&](auto dt) {
+            using OT = elem_t<decltype(dt)::value>;
+            if (vec) hipLaunchKernelGGL((dest_store_rows_kernel<OT, true>), grid, dim3(256), 0, st, S, ld_s, (OT*)d.p, d.ld, d.rows, (int64_t)rows, cols, h->range_word);
+            else hipLaunchKernelGGL((dest_store_rows_kernel<OT, false>), grid, dim3(256), 0, st, S, ld_s, (OT*)d.p, d.ld, d.rows, (int64_t)rows, cols, h->range_word);
+        });
         check("dest_store");
-    }
-
-    // the position-0 readout with the bias stored into the caller's destination of type BT (layernorm_rows{,8}_kernel with a destination type)
-    template <typename BT>
-    void readout_dst(const float* in, int rows, const float* gamma, const float* beta, float eps, float* of, T* ol, const LnReadout& readout) {
-        const int H = h->cfg.hidden;
-        if constexpr (sizeof(T) == 2) {
-            const int tpr8 = h->ln_rows8 ? ln_rows8_tpr(H) : 0;
-            if (tpr8) {
-                const dim3 grid8((rows + 256 / tpr8 - 1) / (256 / tpr8));
-                if (tpr8 == 32) hipLaunchKernelGGL((layernorm_rows8_kernel<T, false, 32, true, BT>), grid8, dim3(256), 0, st, in, H, rows, H, gamma, beta, eps, of, ol, (float*)nullptr, (float*)nullptr, LnEmbed{}, 0, readout);
-                else hipLaunchKernelGGL((layernorm_rows8_kernel<T, false, 64, true, BT>), grid8, dim3(256), 0, st, in, H, rows, H, gamma, beta, eps, of, ol, (float*)nullptr, (float*)nullptr, LnEmbed{}, 0, readout);
-                check("readout");
-                return;
-            }
-        }
-        if (H <= 2048) hipLaunchKernelGGL((layernorm_rows_kernel<T, false, 64, true, BT>), dim3((rows + 3) / 4), dim3(256), 0, st, in, H, rows, H, gamma, beta, eps, of, ol, (float*)nullptr, (float*)nullptr, LnEmbed{}, 0, readout);
-        else hipLaunchKernelGGL((layernorm_rows_kernel<T, false, 256, true, BT>), dim3(rows), dim3(256), 0, st, in, H, rows, H, gamma, beta, eps, of, ol, (float*)nullptr, (float*)nullptr, LnEmbed{}, 0, readout);
-        check("readout");
     }
 
     void check(const char* what) {
@@ -1115,36 +1093,48 @@ struct Runner {
         if (e != hipSuccess) rc = fail(ZETT_E_HIP, "%s launch failed: %s", what, hipGetErrorString(e));
     }
 
-    void layernorm(const float* in, int rows, const float* gamma, const float* beta, float eps, float* of, T* ol, float* stats = nullptr,
-                   LnReadout readout = LnReadout{}, const T* in_lo = nullptr, int bias_dtype = -1) {
-        if (rc || rows <= 0) return;
-        readout.in_lo = in_lo;          // (16-bit residual stream: the rows are read from the 16-bit copy of the sum; READOUT instantiations only)
-        if (bias_dtype >= 0 && readout.out_bias) {          // (zett_forward_into: the bias goes to the caller's destination; no statistics are asked for)
-            if (bias_dtype == ZETT_F16) readout_dst<f16_t>(in, rows, gamma, beta, eps, of, ol, readout);
-            else if (bias_dtype == ZETT_BF16) readout_dst<bf16_t>(in, rows, gamma, beta, eps, of, ol, readout);
-            else readout_dst<float>(in, rows, gamma, beta, eps, of, ol, readout);
-            return;
-        }
+    // One LayerNorm launch of the instantiation (EMBED, READOUT, BT): kernel, lanes per row and grid from (H, ln_rows8, sizeof(T)).
+    // (r6) 16-bit modes, narrow rows: layernorm_rows8_kernel, eight columns per lane, 32 lanes per row up to H = 1024 (two rows per
+    // wave), 64 up to 2048.  Otherwise layernorm_rows_kernel: H <= 2048 a wave per row, four rows per workgroup; wider, a workgroup per row.
+    template <bool EMBED, bool READOUT, typename BT>
+    void ln_launch(const char* what, const float* in, int rows, const float* gamma, const float* beta, float eps, float* of, T* ol, float* stats,
+                   float* sum, const LnEmbed& embed, int t0, const LnReadout& readout) {
         const int H = h->cfg.hidden;
-        // (r6) 16-bit modes, narrow rows: eight columns per lane, 32 lanes per row up to H = 1024 (two rows per wave), 64 up to 2048
+        auto go = [&](auto kernel, dim3 grid) {
+            hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, in, H, rows, H, gamma, beta, eps, of, ol, stats, sum, embed, t0, readout);
+            check(what);
+        };
         if constexpr (sizeof(T) == 2) {
-            const int tpr8 = h->ln_rows8 ? ln_rows8_tpr(H) : 0;
-            if (tpr8) {
+            if (const int tpr8 = h->ln_rows8 ? ln_rows8_tpr(H) : 0) {
                 const dim3 grid8((rows + 256 / tpr8 - 1) / (256 / tpr8));
-#define ZETT_LN8_LAUNCH(TPR, RO) hipLaunchKernelGGL((layernorm_rows8_kernel<T, false, TPR, RO>), grid8, dim3(256), 0, st, in, H, rows, H, gamma, beta, eps, of, ol, stats, (float*)nullptr, LnEmbed{}, 0, readout)
-                if (readout.out_bias) { if (tpr8 == 32) ZETT_LN8_LAUNCH(32, true); else ZETT_LN8_LAUNCH(64, true); }
-                else { if (tpr8 == 32) ZETT_LN8_LAUNCH(32, false); else ZETT_LN8_LAUNCH(64, false); }
-#undef ZETT_LN8_LAUNCH
-                check("layernorm");
+                if (tpr8 == 32) go(layernorm_rows8_kernel<T, EMBED, 32, READOUT, BT>, grid8);
+                else go(layernorm_rows8_kernel<T, EMBED, 64, READOUT, BT>, grid8);
                 return;
             }
         }
-        const dim3 grid = H <= 2048 ? dim3((rows + 3) / 4) : dim3(rows);      // H <= 2048: a wave per row, four rows per workgroup
-#define ZETT_LN_LAUNCH(TPR, RO) hipLaunchKernelGGL((layernorm_rows_kernel<T, false, TPR, RO>), grid, dim3(256), 0, st, in, H, rows, H, gamma, beta, eps, of, ol, stats, (float*)nullptr, LnEmbed{}, 0, readout)
-        if (readout.out_bias) { if (H <= 2048) ZETT_LN_LAUNCH(64, true); else ZETT_LN_LAUNCH(256, true); }
-        else { if (H <= 2048) ZETT_LN_LAUNCH(64, false); else ZETT_LN_LAUNCH(256, false); }
-#undef ZETT_LN_LAUNCH
-        check("layernorm");
+        if (H <= 2048) go(layernorm_rows_kernel<T, EMBED, 64, READOUT, BT>, dim3((rows + 3) / 4));
+        else go(layernorm_rows_kernel<T, EMBED, 256, READOUT, BT>, dim3(rows));
+    }
+
+    // Every LayerNorm launch of the forward.  Rows `in` (or, embed != null, the embeddings' sum of buffer rows [t0, t0 + rows), also
+    // written to `sum` unless null) -> fp32 `of` / operand copy `ol` / (mean, rstd) `stats`, each unless null.  readout.out_bias != null:
+    // the position-0 readout with the bias head; bias_dtype >= 0 (zett_forward_into): the bias goes to the caller's destination of that
+    // zett_dtype (no statistics are asked for).  Only these six instantiations exist: the embeddings never read out, a destination
+    // type needs a readout.
+    void layernorm(const float* in, int rows, const float* gamma, const float* beta, float eps, float* of, T* ol, float* stats = nullptr,
+                   const LnReadout& readout = LnReadout{}, int bias_dtype = -1, const LnEmbed* embed = nullptr, int t0 = 0, float* sum = nullptr) {
+        if (rc || rows <= 0) return;
+        if (embed) {
+            ln_launch<true, false, void>("embed_layernorm", nullptr, rows, gamma, beta, eps, nullptr, ol, stats, sum, *embed, t0, LnReadout{});
+        } else if (!readout.out_bias) {
+            ln_launch<false, false, void>("layernorm", in, rows, gamma, beta, eps, of, ol, stats, nullptr, LnEmbed{}, 0, readout);
+        } else if (bias_dtype < 0) {
+            ln_launch<false, true, void>("layernorm", in, rows, gamma, beta, eps, of, ol, stats, nullptr, LnEmbed{}, 0, readout);
+        } else {
+            with_dtype(bias_dtype, [&](auto dt) {
+                ln_launch<false, true, elem_t<decltype(dt)::value>>("readout", in, rows, gamma, beta, eps, of, ol, nullptr, nullptr, LnEmbed{}, 0, readout);
+            });
+        }
     }
 
     // LayerNorm fold: (mean, rstd) per row from the partials the producer GEMM wrote
@@ -1177,229 +1167,278 @@ struct Runner {
     }
 };
 
-template <typename T, int SD>
-void launch_gather(hipStream_t st, const int32_t* id_list, int s0, int m, const void* src, const zett_config& c,
-                   const float* fallback, const float* sw, const float* sb, T* out, int32_t* range_flag) {
-    hipLaunchKernelGGL((gather_src_kernel<T, SD>), dim3(m), dim3(256), 0, st, id_list, s0, m, src, c.n_in_embd,
-                       c.original_vocab_size, fallback, sw, sb, out, range_flag);
+// ---- what a forward does with this handle, decided once --------------------------------------------------------------------------
+// fold — LayerNorm fold: in the 16-bit modes the LayerNorms inside the encoder are not launches — the residual GEMM
+//   in front writes the 16-bit copy of its fp32 rows and per-row partial statistics, the GEMM behind runs on gamma-folded
+//   weights and normalises in its epilogue.  gemm4d only: off when a tile variant is forced.
+// lo_stream — 16-bit residual stream (r4): with the fold on, the encoder's hidden state travels ONLY as the 16-bit copy of the
+//   pre-LayerNorm sum (+ statistics): the producers read their residual rows from it (LN16 epilogue: 4 instead of 10 bytes
+//   per element, 16-byte accesses on both sides) and no fp32 sum is written; Zt and Ct alternate as its buffers (Ct is free
+//   until the readout).  f16 only by default: the rounding of the stream is 2^-11 per layer there (rel-L2 of the outputs
+//   0.8e-3 -> 1.0e-3 against a tolerance of 2.5e-3), in bf16 2^-8 would leave the tolerance.
+// table_lo — 16-bit hoisted table (r6; with the 16-bit residual stream, i.e. f16 by default): the ProjectorBlock of the input projection
+//   ends in the LayerNorm-fold PRODUCER the output heads use (dense2 writes the 16-bit copy of its pre-LayerNorm sum + partial row
+//   statistics; ln_stats makes (mean, rstd)), and the embeddings' kernel normalises a table row as it reads it: the block's
+//   LayerNorm launch is gone (0.40 ms on the headline, 0.16 of XLM-R's 7.3), a table element is 2 bytes on both sides, and a
+//   table exchanged between ranks (SURVEY 8e's optional second exchange) would be 239 instead of 478 MB.  One 16-bit rounding of
+//   the pre-LayerNorm sum replaces none: the same step the encoder's stream takes per layer.  The buffer keeps its fp32 size:
+//   [D, H] 16-bit values, then [D] (mean, rstd).  zett_table_rows / zett_forward_table exist in this mode only.
+// fold_heads — LayerNorm fold of the heads (r3): the ProjectorBlock's LayerNorm in front of each final Linear is not a launch either.
+// (zett_workspace_bytes does not ask: it is an upper bound over the options, so workspace_sizes counts the fold's partials whenever
+// H % 128 == 0 — the part of `fold` no option can change — and the forward reserves them only when `fold` holds.)
+struct ForwardMode { bool fold, lo_stream, table_lo, fold_heads; };
+template <typename T>
+ForwardMode forward_mode(const zett_hypernet* h) {
+    const zett_config& c = h->cfg;
+    ForwardMode m{};
+    m.fold = h->ln_fold && !std::is_same<T, float>::value && h->gemm_variant == 0 && c.hidden % 128 == 0 && c.hidden >= 512 && (int)h->fold_up.size() == c.layers;
+    m.lo_stream = m.fold && c.layers >= 1 && sizeof(T) == 2 && (h->residual_lo == 2 || (h->residual_lo == 1 && std::is_same<T, f16_t>::value));
+    m.table_lo = m.lo_stream && h->table_lo != 0;
+    m.fold_heads = m.fold && h->ln_fold == 1 && h->fold_head_in.w != nullptr;
+    return m;
+}
+int needs_folded_table(const char* entry) {
+    return fail(ZETT_E_INVALID, "%s needs the folded 16-bit table: f16 arithmetic with the LayerNorm fold, the 16-bit residual stream and table_lo on", entry);
+}
+
+// ---- workspace ---------------------------------------------------------------------------------------------------------------------
+// The buffers behind WorkspaceSizes.  encoder = false: what the table phase alone touches (zett_table_rows reserves no more).
+int reserve_workspace(zett_hypernet* h, const WorkspaceSizes& ws, bool fold, bool encoder) {
+    const struct { DevBuf* buf; size_t bytes; bool encoder_only; } list[] = {
+        {&h->table, ws.table, true}, {&h->x0, ws.x0, false}, {&h->yf, ws.f32_rows, false}, {&h->yt, ws.lo_rows, false}, {&h->big, ws.big, false},
+        {&h->pre, ws.f32_rows, false}, {&h->ctx, ws.lo_rows, true}, {&h->cf, ws.f32_rows, true}, {&h->ct, ws.lo_rows, true},
+        {&h->lnstats, ws.stats, true}, {&h->lnparts, fold ? ws.parts : 0, false}};
+    for (const auto& r : list)
+        if (encoder || !r.encoder_only)
+            if (int rc = r.buf->reserve(r.bytes)) return rc;
+    return 0;
+}
+
+// The workspace as one lane sees it: every buffer `off` rows in (lane 0, the table phase and zett_table_rows: off = 0), MCS rows each.
+// LayerNorm statistics: the encoder keeps its hidden state as (pre-LayerNorm sum, statistics, gamma, beta): the LayerNorm kernel
+// writes the 16-bit GEMM operand and the two statistics, and whoever needs the fp32 LayerNorm output (the next residual epilogue)
+// recomputes it with ln_affine from the sum it reads anyway.  Zf and PRE alternate as the sum buffers, STa and STb as their statistics.
+template <typename T>
+struct Workspace {
+    T* X0; float* Zf; T* Zt; T* BIG; float* PRE; T* CTX; float* Cf; T* Ct; float* STa; float* STb; float2* PARTS;
+    int ld_parts;
+    long a_rows;          // rows every A operand buffer can be read for: the 384-row GEMM tile reads whole tiles of A
+};
+template <typename U> U* buf_at(const DevBuf& b, size_t n) { return b.p ? (U*)b.p + n : nullptr; }      // (null: a buffer the call did not reserve)
+template <typename T>
+Workspace<T> lane_workspace(const zett_hypernet* h, size_t off, size_t MCS) {
+    const size_t H = h->cfg.hidden, wide = (size_t)std::max(h->cfg.intermediate, 3 * h->cfg.hidden);
+    Workspace<T> w{};
+    w.X0 = buf_at<T>(h->x0, 0);                   // (the table phase only)
+    w.Zf = buf_at<float>(h->yf, off * H); w.Zt = buf_at<T>(h->yt, off * H);
+    w.BIG = buf_at<T>(h->big, off * wide); w.PRE = buf_at<float>(h->pre, off * H);
+    w.CTX = buf_at<T>(h->ctx, off * H); w.Cf = buf_at<float>(h->cf, off * H); w.Ct = buf_at<T>(h->ct, off * H);
+    w.STa = buf_at<float>(h->lnstats, 2 * off); w.STb = buf_at<float>(h->lnstats, 2 * off + 2 * MCS);
+    w.PARTS = buf_at<float2>(h->lnparts, off);
+    w.ld_parts = (int)MCS;
+    w.a_rows = (long)(MCS - off);
+    return w;
 }
 
 // The hoisted table (A2-A4): input_projection once per distinct source id — rows id_list[first .. first + count) into table rows
 // [first, first + count) (the fp32 table `tbl32`, or — folded — the 16-bit pre-LayerNorm sums `tbl16` with (mean, rstd) in
 // `tblst`), in chunks of MC rows through the caller's workspace.  Errors land in R.rc.
 template <typename T>
-void table_phase(Runner<T>& R, const int32_t* id_list, int first, int count, const void* src, int src_dtype, int64_t MC, size_t MCS,
-                 T* X0, float* Zf, T* Zt, T* BIG, float* PRE, float2* PARTS, bool table_lo, T* tbl16, float* tblst, float* tbl32) {
+void table_phase(Runner<T>& R, const Workspace<T>& w, const int32_t* id_list, int first, int count, const void* src, int src_dtype, int64_t MC,
+                 bool table_lo, T* tbl16, float* tblst, float* tbl32) {
     zett_hypernet* h = R.h;
     const zett_config& c = h->cfg;
     const int H = c.hidden, EIN = c.n_in_embd;
-    hipStream_t st = R.st;
     const float* in_w = c.rescale ? R.Wf("in_scaler.w") : nullptr;
     const float* in_b = c.rescale ? R.Wf("in_scaler.b") : nullptr;
     for (int s0 = first; s0 < first + count && !R.rc; s0 += (int)MC) {
         const int m = (int)std::min<int64_t>(MC, first + count - s0);
         const float* fb = R.Wf("fallback_embeddings.weight");
-        if (src_dtype == ZETT_F32) launch_gather<T, 0>(st, id_list, s0, m, src, c, fb, in_w, in_b, X0, h->range_word);
-        else if (src_dtype == ZETT_F16) launch_gather<T, 1>(st, id_list, s0, m, src, c, fb, in_w, in_b, X0, h->range_word);
-        else launch_gather<T, 2>(st, id_list, s0, m, src, c, fb, in_w, in_b, X0, h->range_word);
+        with_dtype(src_dtype, [&](auto sd) {
+            hipLaunchKernelGGL((gather_src_kernel<T, decltype(sd)::value>), dim3(m), dim3(256), 0, R.st, id_list, s0, m, src, c.n_in_embd,
+                               c.original_vocab_size, fb, in_w, in_b, w.X0, h->range_word);
+        });
         R.check("gather_src");
         GemmEpilogue<T> e0 = R.epi();
-        e0.bias = R.Wf("input_projection.0.bias"); e0.out_f32 = Zf; e0.ld_f32 = H; e0.out_lo = Zt; e0.ld_lo = H;
-        R.gemm(X0, EIN, R.Wlo("input_projection.0.weight"), EIN, m, H, EIN, e0);
-        if (table_lo) R.projector("input_projection.1.", Zt, Zf, m, BIG, PRE, nullptr, tbl16 + (size_t)s0 * H, PARTS, (int)MCS, tblst + 2 * (size_t)s0);
-        else R.projector("input_projection.1.", Zt, Zf, m, BIG, PRE, tbl32 + (size_t)s0 * H, nullptr);
+        e0.bias = R.Wf("input_projection.0.bias"); e0.out_f32 = w.Zf; e0.ld_f32 = H; e0.out_lo = w.Zt; e0.ld_lo = H;
+        R.gemm(w.X0, EIN, R.Wlo("input_projection.0.weight"), EIN, m, H, EIN, e0);
+        if (table_lo) R.projector("input_projection.1.", w.Zt, w.Zf, m, w.BIG, w.PRE, nullptr, tbl16 + (size_t)s0 * H, w.PARTS, w.ld_parts, tblst + 2 * (size_t)s0);
+        else R.projector("input_projection.1.", w.Zt, w.Zf, m, w.BIG, w.PRE, tbl32 + (size_t)s0 * H, nullptr);
     }
-}
-
-// true when this handle's forward keeps the hoisted table folded (16-bit pre-LayerNorm sums + statistics): the predicate of do_forward
-template <typename T>
-bool folded_table_mode(const zett_hypernet* h) {
-    const zett_config& c = h->cfg;
-    const int H = c.hidden;
-    const bool fold = h->ln_fold && !std::is_same<T, float>::value && h->gemm_variant == 0 && H % 128 == 0 && H >= 512 && (int)h->fold_up.size() == c.layers;
-    const bool lo_stream = fold && c.layers >= 1 && sizeof(T) == 2 && (h->residual_lo == 2 || (h->residual_lo == 1 && std::is_same<T, f16_t>::value));
-    return lo_stream && h->table_lo != 0;
 }
 
 // (ABI 8) zett_table_rows: rows [first, first + count) of the folded table of the distinct-id list `id_list` into the caller's buffers
 template <typename T>
 int do_table_rows(zett_hypernet* h, const int32_t* id_list, int first, int count, const void* src, int src_dtype, void* table_out, float* stats_out, hipStream_t st) {
-    const zett_config& c = h->cfg;
-    if (!folded_table_mode<T>(h))
-        return fail(ZETT_E_INVALID, "zett_table_rows needs the folded 16-bit table: f16 arithmetic with the LayerNorm fold, the 16-bit residual stream and table_lo on");
-    const WorkspaceSizes ws = workspace_sizes(c, sizeof(T), 1, count, count, h->max_chunk_tokens);
-    const int64_t MC = ws.chunk_tokens;
-    const size_t MCS = (size_t)MC + 768;
-    if (int rc = h->x0.reserve(ws.x0)) return rc;
-    if (int rc = h->yf.reserve(ws.f32_rows)) return rc;
-    if (int rc = h->yt.reserve(ws.lo_rows)) return rc;
-    if (int rc = h->big.reserve(ws.big)) return rc;
-    if (int rc = h->pre.reserve(ws.f32_rows)) return rc;
-    if (int rc = h->lnparts.reserve((size_t)(c.hidden / 128) * MCS * sizeof(float2))) return rc;
+    const ForwardMode mode = forward_mode<T>(h);
+    if (!mode.table_lo) return needs_folded_table("zett_table_rows");
+    const WorkspaceSizes ws = workspace_sizes(h->cfg, sizeof(T), 1, count, count, h->max_chunk_tokens);
+    const size_t MCS = (size_t)ws.chunk_tokens + 768;
+    if (int rc = reserve_workspace(h, ws, mode.fold, false)) return rc;
     Runner<T> R{h, st};
     R.a_rows_readable = (long)MCS;
     // (per-launch events and the launch log belong to a forward: zett_forward resets both when it starts)
     struct NoTiming { zett_hypernet* h; int saved; ~NoTiming() { h->time_gemm = saved; } } no_timing{h, h->time_gemm};
     h->time_gemm = 0;
-    table_phase<T>(R, id_list, first, count, src, src_dtype, MC, MCS, h->x0.as<T>(), h->yf.as<float>(), h->yt.as<T>(), h->big.as<T>(), h->pre.as<float>(),
-                   h->lnparts.as<float2>(), true, (T*)table_out, stats_out, nullptr);
+    table_phase<T>(R, lane_workspace<T>(h, 0, MCS), id_list, first, count, src, src_dtype, ws.chunk_tokens, true, (T*)table_out, stats_out, nullptr);
     return R.rc;
 }
 
+// From the moment a forward has taken its plan slot, kernels that read the slot (and the pinned host words) may be enqueued: whatever
+// way the forward is left — a failed launch, a failed workspace reservation, a lane that fails after the other one was launched — the
+// second lane is joined to `st` and ps.released is recorded behind everything, so that a later zett_forward_prepare / zett_forward
+// never rewrites the plan under kernels still in flight.
+struct SlotGuard {
+    zett_hypernet* h; zett_hypernet::PlanSlot* ps; hipStream_t st; bool lane_forked = false;
+    ~SlotGuard() {
+        if (lane_forked && h->lane_stream && h->lane_ev[3]) {
+            (void)hipEventRecord(h->lane_ev[3], h->lane_stream);
+            (void)hipStreamWaitEvent(st, h->lane_ev[3], 0);
+        }
+        if (ps->released) (void)hipEventRecord(ps->released, st);
+    }
+};
+
+// "time_gemm": the HIP-event pairs of the forward's GEMM launches, read back once the stream has drained
+int read_gemm_timing(zett_hypernet* h, hipStream_t st) {
+    HIP_TRY(hipStreamSynchronize(st));
+    const bool print = getenv("ZETT_GEMM_LOG") != nullptr;
+    double ms = 0.0, fl = 0.0;
+    for (size_t k = 0; 2 * k + 1 < h->ev_used && k < h->gemm_log.size(); ++k) {
+        zett_gemm_record& r = h->gemm_log[k];
+        float t = 0.f;
+        if (hipEventElapsedTime(&t, h->ev[2 * k], h->ev[2 * k + 1]) == hipSuccess) { ms += t; fl += r.flops; r.ms = t; }
+        if (print)
+            fprintf(stderr, "[zett gemm] M=%6d N=%6d K=%5d tile=%s %8.3f ms %7.1f TF\n", r.m, r.n, r.k,
+                    r.variant == 7 ? "4d " : r.variant == 8 ? "4dg" : r.variant == 3 ? "384" : r.variant == 2 ? "8r " : "128", t, r.flops / (t * 1e9));
+    }
+    h->stats.gemm_ms = ms;
+    h->stats.gemm_flops_timed = fl;
+    return 0;
+}
+
+// One forward (zett_forward / _into / _table / _table_into), in stages: run() names them in order.
 template <typename T>
-int do_forward(zett_hypernet* h, const int32_t* sfm, int64_t N, int seq, const void* src, int src_dtype, const zett_dest* dest,
-               int64_t v_src, int lang_index, float* out_in, float* out_out, float* out_bias, hipStream_t st) {
-    (void)v_src;
+struct Forward {
+    using DestOut = typename Runner<T>::DestOut;
+    // the call
+    zett_hypernet* h; const int32_t* sfm; int64_t N; int seq; const void* src; int src_dtype; const zett_dest* dest; int lang_index;
+    float* out_in; float* out_out; float* out_bias; hipStream_t st;
+    // what the stages find
+    Runner<T> R{h, st};
     const zett_config& c = h->cfg;
-    const int H = c.hidden, I = c.intermediate, E = c.n_embd, EIN = c.n_in_embd;
-    const int lam = c.embed_lang ? 1 : 0;
-    const int V = c.original_vocab_size + c.n_extra;
-    const int64_t max_tok = N * (int64_t)(seq + lam);
-    h->stats = zett_stats{};
-    h->stats.rows = N;
-    h->ev_used = 0;
-    h->ev_flops.clear();
-    h->ev_shape.clear();
-    h->gemm_log.clear();
+    const int H = c.hidden, I = c.intermediate, E = c.n_embd;
+    const ForwardMode mode = forward_mode<T>(h);
+    zett_hypernet::PlanSlot* ps = nullptr;
+    PlanArrays p{};
+    bool pair_plan = false;
+    const int32_t* hoff = nullptr;        // pinned: row offsets [N + 1], then distinct ids, error word, distinct pairs
+    int64_t Ttot = 0;                     // packed positions of the call
+    int D = 0;                            // distinct source ids
+    int64_t MC = 0; size_t MCS = 0;       // packed positions per chunk, and rows of every workspace buffer (MC + slack)
+    float* TBL = nullptr; T* TBL16 = nullptr; float* TBLST = nullptr;      // the hoisted table: fp32, or folded (16-bit sums + statistics)
+    const float* lang_vec = nullptr;
+    const float scaling = 1.0f / std::sqrt((float)(H / c.heads));
+
+    int run() {
+        h->stats = zett_stats{};
+        h->stats.rows = N;
+        h->ev_used = 0;
+        h->gemm_log.clear();
+        if (int rc = take_plan()) return rc;
+        SlotGuard guard{h, ps, st};
+        if (int rc = read_plan()) return rc;
+        if (int rc = reserve()) return rc;
+        // ---- table: input_projection once per distinct source id (A2-A4) -----------------
+        if (!h->ext.table)
+            table_phase<T>(R, lane_workspace<T>(h, 0, MCS), p.id_list, 0, D, src, src_dtype, MC, mode.table_lo, TBL16, TBLST, TBL);
+        if (R.rc) return R.rc;
+        if (int rc = run_chunks(guard)) return rc;
+        h->out_recorded = true;          // (ps.released — the plan slot may be rewritten behind it, zett_forward_prepare — is recorded by the guard)
+        return h->time_gemm ? read_gemm_timing(h, st) : 0;
+    }
 
     // ---- plan ---------------------------------------------------------------------
     // The slot the previous forward did not use.  Prepared for exactly this call (zett_forward_prepare): its plan ran on the
     // plan stream, the host waits for THAT (not for earlier work on st) and st is ordered behind it.  Otherwise the plan is
     // made here, on st, and the host waits for it — and so for whatever was enqueued on st before.
-    zett_hypernet::PlanSlot& ps = h->plan[h->plan_cur ^ 1];
-    if (ps.pending && ps.sfm == sfm && ps.n_rows == N && ps.seq == seq && ps.pair_plan == plan_layout(h, ps, N, seq).pair_plan &&
-        ps.ext_id_slot == h->ext.id_slot) {
-        HIP_TRY(hipStreamWaitEvent(st, ps.done, 0));
-    } else {
-        if (ps.pending) HIP_TRY(hipEventSynchronize(ps.done));       // a prepared plan nobody took: let it finish before the slot is reused
-        if (ps.released) HIP_TRY(hipStreamWaitEvent(st, ps.released, 0));      // (the forward before the previous one read this slot)
-        if (int rc = enqueue_plan(h, ps, sfm, N, seq, st)) return rc;
-    }
-    ps.pending = false;
-    h->plan_cur ^= 1;
-    // From here on kernels that read the slot (and the pinned host words) may be enqueued: whatever way this function is left —
-    // a failed launch, a failed workspace reservation, a lane that fails after the other one was launched — the second lane is
-    // joined to `st` and ps.released is recorded behind everything, so that a later zett_forward_prepare / zett_forward never
-    // rewrites the plan under kernels still in flight.
-    struct SlotGuard {
-        zett_hypernet* h; zett_hypernet::PlanSlot* ps; hipStream_t st; bool lane_forked = false;
-        ~SlotGuard() {
-            if (lane_forked && h->lane_stream && h->lane_ev[3]) {
-                (void)hipEventRecord(h->lane_ev[3], h->lane_stream);
-                (void)hipStreamWaitEvent(st, h->lane_ev[3], 0);
-            }
-            if (ps->released) (void)hipEventRecord(ps->released, st);
+    int take_plan() {
+        zett_hypernet::PlanSlot& s = h->plan[h->plan_cur ^ 1];
+        if (s.pending && s.sfm == sfm && s.n_rows == N && s.seq == seq && s.pair_plan == plan_layout(h, &s, N, seq).pair_plan &&
+            s.ext_id_slot == h->ext.id_slot) {
+            HIP_TRY(hipStreamWaitEvent(st, s.done, 0));
+        } else {
+            if (s.pending) HIP_TRY(hipEventSynchronize(s.done));       // a prepared plan nobody took: let it finish before the slot is reused
+            if (s.released) HIP_TRY(hipStreamWaitEvent(st, s.released, 0));      // (the forward before the previous one read this slot)
+            if (int rc = enqueue_plan(h, s, sfm, N, seq, st)) return rc;
         }
-    } slot_guard{h, &ps, st};
-    const PlanLayout PL = plan_layout(h, ps, N, seq);
-    const PlanArrays& p = PL.p;
-    const bool pair_plan = PL.pair_plan;
-    if (!h->range_accumulate) HIP_TRY(hipMemsetAsync(h->range_word, 0, 4, st));          // range guard: the word of THIS forward (zett_check_range)
-    for (hipEvent_t& e : h->out_ready)
-        if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    // (zett_forward_into) the row map against the destination, answered with the plan's error word: on `stream`, behind whatever wrote
-    // the map (with a prepared plan the host therefore waits for `stream` too)
-    const bool dest_check = dest && dest->rows;
-    if (dest_check) {
-        if (int rc = h->dest_word.reserve(4)) return rc;
-        if (!h->dest_host) HIP_TRY(hipHostMalloc((void**)&h->dest_host, 4, hipHostMallocDefault));
-        if (!h->dest_checked) HIP_TRY(hipEventCreateWithFlags(&h->dest_checked, hipEventDisableTiming));
-        HIP_TRY(hipMemsetAsync(h->dest_word.p, 0, 4, st));
-        hipLaunchKernelGGL(dest_rows_check_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, dest->rows, N, dest->n_dest_rows, h->dest_word.as<int32_t>());
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(h->dest_host, h->dest_word.p, 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipEventRecord(h->dest_checked, st));
+        s.pending = false;
+        h->plan_cur ^= 1;
+        ps = &s;
+        return 0;
     }
-    HIP_TRY(hipEventSynchronize(ps.done));
-    int32_t* hoff = ps.host;
-    if (hoff[N + 2] != 0)
-        return fail(ZETT_E_INDEX, "surface-form row %d holds an id outside [0, %d) (original_vocab_size %d + %d fallback rows)",
-                    hoff[N + 2] - 1, V, c.original_vocab_size, c.n_extra);
-    if (dest_check) {
-        HIP_TRY(hipEventSynchronize(h->dest_checked));
-        if (h->dest_host[0] != 0)
-            return fail(ZETT_E_INDEX, "destination row map: rows[%d] is outside the destination's %lld rows", h->dest_host[0] - 1, (long long)dest->n_dest_rows);
+
+    // The host's one wait: the plan's counters and error word, and — (zett_forward_into) — the row map against the destination,
+    // answered with the plan's error word: on `stream`, behind whatever wrote the map (with a prepared plan the host therefore
+    // waits for `stream` too).
+    int read_plan() {
+        const PlanLayout PL = plan_layout(h, ps, N, seq);
+        p = PL.p;
+        pair_plan = PL.pair_plan;
+        if (!h->range_accumulate) HIP_TRY(hipMemsetAsync(h->range_word, 0, 4, st));          // range guard: the word of THIS forward (zett_check_range)
+        for (hipEvent_t& e : h->out_ready)
+            if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        const bool dest_check = dest && dest->rows;
+        if (dest_check) {
+            if (int rc = h->dest_word.reserve(4)) return rc;
+            if (!h->dest_host) HIP_TRY(hipHostMalloc((void**)&h->dest_host, 4, hipHostMallocDefault));
+            if (!h->dest_checked) HIP_TRY(hipEventCreateWithFlags(&h->dest_checked, hipEventDisableTiming));
+            HIP_TRY(hipMemsetAsync(h->dest_word.p, 0, 4, st));
+            hipLaunchKernelGGL(dest_rows_check_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, dest->rows, N, dest->n_dest_rows, h->dest_word.as<int32_t>());
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpyAsync(h->dest_host, h->dest_word.p, 4, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipEventRecord(h->dest_checked, st));
+        }
+        HIP_TRY(hipEventSynchronize(ps->done));
+        hoff = ps->host;
+        if (hoff[N + 2] != 0)
+            return fail(ZETT_E_INDEX, "surface-form row %d holds an id outside [0, %d) (original_vocab_size %d + %d fallback rows)",
+                        hoff[N + 2] - 1, c.original_vocab_size + c.n_extra, c.original_vocab_size, c.n_extra);
+        if (dest_check) {
+            HIP_TRY(hipEventSynchronize(h->dest_checked));
+            if (h->dest_host[0] != 0)
+                return fail(ZETT_E_INDEX, "destination row map: rows[%d] is outside the destination's %lld rows", h->dest_host[0] - 1, (long long)dest->n_dest_rows);
+        }
+        Ttot = hoff[N];
+        D = hoff[N + 1];
+        h->stats.packed_tokens = Ttot;
+        h->stats.distinct_ids = D;
+        h->stats.distinct_positions = Ttot;
+        return 0;
     }
-    const int64_t Ttot = hoff[N];
-    const int D = hoff[N + 1];
-    h->stats.packed_tokens = Ttot;
-    h->stats.distinct_ids = D;
-    h->stats.distinct_positions = Ttot;
 
     // ---- workspace ------------------------------------------------------------------
-    const WorkspaceSizes ws = workspace_sizes(c, sizeof(T), seq, Ttot, D, h->max_chunk_tokens);
-    const int64_t MC = ws.chunk_tokens;
-    const size_t MCS = (size_t)MC + 768;      // slack rows: the 384-row GEMM tile reads whole tiles of A (per lane, two lanes)
-    if (int rc = h->table.reserve(ws.table)) return rc;
-    if (int rc = h->x0.reserve(ws.x0)) return rc;
-    if (int rc = h->yf.reserve(ws.f32_rows)) return rc;
-    if (int rc = h->yt.reserve(ws.lo_rows)) return rc;
-    if (int rc = h->big.reserve(ws.big)) return rc;
-    if (int rc = h->pre.reserve(ws.f32_rows)) return rc;
-    if (int rc = h->ctx.reserve(ws.lo_rows)) return rc;
-    if (int rc = h->cf.reserve(ws.f32_rows)) return rc;
-    if (int rc = h->ct.reserve(ws.lo_rows)) return rc;
-    if (int rc = h->lnstats.reserve(ws.stats)) return rc;
-    // LayerNorm fold: in the 16-bit modes the LayerNorms inside the encoder are not launches — the residual GEMM
-    // in front writes the 16-bit copy of its fp32 rows and per-row partial statistics, the GEMM behind runs on gamma-folded
-    // weights and normalises in its epilogue.  gemm4d only: off when a tile variant is forced.
-    const bool fold = h->ln_fold && !std::is_same<T, float>::value && h->gemm_variant == 0 && H % 128 == 0 && H >= 512 &&
-                      (int)h->fold_up.size() == c.layers;
-    // 16-bit residual stream (r4): with the fold on, the encoder's hidden state travels ONLY as the 16-bit copy of the
-    // pre-LayerNorm sum (+ statistics): the producers read their residual rows from it (LN16 epilogue: 4 instead of 10 bytes
-    // per element, 16-byte accesses on both sides) and no fp32 sum is written; Zt and Ct alternate as its buffers (Ct is free
-    // until the readout).  f16 only by default: the rounding of the stream is 2^-11 per layer there (rel-L2 of the outputs
-    // 0.8e-3 -> 1.0e-3 against a tolerance of 2.5e-3), in bf16 2^-8 would leave the tolerance.
-    const bool lo_stream = fold && c.layers >= 1 && sizeof(T) == 2 &&
-                           (h->residual_lo == 2 || (h->residual_lo == 1 && std::is_same<T, f16_t>::value));
-    const size_t ws_parts = fold ? (size_t)(H / 128) * MCS * sizeof(float2) : 0;
-    if (int rc = h->lnparts.reserve(ws_parts)) return rc;
-    float2* PARTS = h->lnparts.as<float2>();
-    float* TBL = h->table.as<float>();
-    // 16-bit hoisted table (r6; with the 16-bit residual stream, i.e. f16 by default): the ProjectorBlock of the input projection ends
-    // in the LayerNorm-fold PRODUCER the output heads use (dense2 writes the 16-bit copy of its pre-LayerNorm sum + partial row
-    // statistics; ln_stats makes (mean, rstd)), and the embeddings' kernel normalises a table row as it reads it: the block's
-    // LayerNorm launch is gone (0.40 ms on the headline, 0.16 of XLM-R's 7.3), a table element is 2 bytes on both sides, and a
-    // table exchanged between ranks (SURVEY 8e's optional second exchange) would be 239 instead of 478 MB.  One 16-bit rounding of
-    // the pre-LayerNorm sum replaces none: the same step the encoder's stream takes per layer.  The buffer keeps its fp32 size:
-    // [D, H] 16-bit values, then [D] (mean, rstd).
-    const bool table_lo = lo_stream && h->table_lo != 0;
-    // (ABI 8) zett_forward_table: the table is the caller's — rows of the GLOBAL distinct-id list in the folded 16-bit layout,
-    // computed by zett_table_rows here and on the peer ranks; tok_slot already holds global slots (enqueue_plan)
-    const bool ext_table = h->ext.table != nullptr;
-    if (ext_table && !table_lo)
-        return fail(ZETT_E_INVALID, "zett_forward_table needs the folded 16-bit table: f16 arithmetic with the LayerNorm fold, the 16-bit residual stream and table_lo on");
-    T* TBL16 = ext_table ? (T*)const_cast<void*>(h->ext.table) : (T*)h->table.as<float>();
-    float* TBLST = ext_table ? const_cast<float*>(h->ext.stats) : (float*)((char*)h->table.as<float>() + (((size_t)D * H * sizeof(T) + 15) / 16) * 16);
-    T* X0 = h->x0.as<T>();
-    float* Zf = h->yf.as<float>();
-    T* Zt = h->yt.as<T>();
-    T* BIG = h->big.as<T>();
-    float* PRE = h->pre.as<float>();
-    T* CTX = h->ctx.as<T>();
-    float* Cf = h->cf.as<float>();
-    T* Ct = h->ct.as<T>();
-    // LayerNorm statistics.  The encoder keeps its hidden state as (pre-LayerNorm sum, statistics, gamma, beta):
-    // the LayerNorm kernel writes the 16-bit GEMM operand and the two statistics, and whoever needs the fp32
-    // LayerNorm output (the next residual epilogue) recomputes it with ln_affine from the sum it reads anyway.
-    // Zf and PRE alternate as the sum buffers, STa and STb as their statistics.
-    float* STa = h->lnstats.as<float>();
-    float* STb = STa + 2 * MCS;
-
-    Runner<T> R{h, st};
-    R.a_rows_readable = (long)MCS;
-
-    // ---- table: input_projection once per distinct source id (A2-A4) -----------------
-    if (!ext_table)
-        table_phase<T>(R, p.id_list, 0, D, src, src_dtype, MC, MCS, X0, Zf, Zt, BIG, PRE, PARTS, table_lo, TBL16, TBLST, TBL);
-    if (R.rc) return R.rc;
+    int reserve() {
+        const WorkspaceSizes ws = workspace_sizes(c, sizeof(T), seq, Ttot, D, h->max_chunk_tokens);
+        MC = ws.chunk_tokens;
+        MCS = (size_t)MC + 768;      // slack rows: the 384-row GEMM tile reads whole tiles of A (per lane, two lanes)
+        if (int rc = reserve_workspace(h, ws, mode.fold, true)) return rc;
+        R.a_rows_readable = (long)MCS;
+        // (ABI 8) zett_forward_table: the table is the caller's — rows of the GLOBAL distinct-id list in the folded 16-bit layout,
+        // computed by zett_table_rows here and on the peer ranks; tok_slot already holds global slots (enqueue_plan)
+        const bool ext_table = h->ext.table != nullptr;
+        if (ext_table && !mode.table_lo) return needs_folded_table("zett_forward_table");
+        TBL = h->table.as<float>();
+        TBL16 = ext_table ? (T*)const_cast<void*>(h->ext.table) : (T*)h->table.as<float>();
+        TBLST = ext_table ? const_cast<float*>(h->ext.stats) : (float*)((char*)h->table.as<float>() + (((size_t)D * H * sizeof(T) + 15) / 16) * 16);
+        lang_vec = c.embed_lang ? R.Wf("lang_embeddings.weight") + (size_t)lang_index * H : nullptr;
+        return 0;
+    }
 
     // ---- encoder + heads over row chunks -----------------------------------------------
     // Buffer rows of a chunk are ordered POSITION 0 FIRST (rowops.hip.h chunk_row): rows [0, rows) are position 0 of the
     // chunk's vocabulary rows, the other packed positions follow.  What the last layer and the heads consume — position 0
     // only (modeling_hypernet.py:234) — is then the first `rows` rows of every buffer, with no gather in between.
-    const float* lang_vec = lam ? R.Wf("lang_embeddings.weight") + (size_t)lang_index * H : nullptr;
-    const float scaling = 1.0f / std::sqrt((float)(H / c.heads));
     // One chunk = vocabulary rows [r0, r1) on one LANE: a stream and a slice of every workspace buffer starting `off` rows in.
     // Normally there is one lane (the caller's stream, offset 0) and the chunks follow each other.  A call that is ONE chunk
     // can instead run as two half-vocabulary chunks on two lanes at once (r4, "concurrent_lanes"): rows are independent, so the
@@ -1408,274 +1447,248 @@ int do_forward(zett_hypernet* h, const int32_t* sfm, int64_t N, int seq, const v
     // a 4 096-row shard of 8 GPUs needs: its N = 4096 launches are 608 tiles = 2.375 rounds.  (Same bits: a row's arithmetic
     // does not depend on the chunk it is in.)  ev_mode: 0 = no completion events, 1 = record out_ready on this lane's stream,
     // 2 = lane 1 of a pair (records lane_ev[1..3]), 3 = lane 0 of a pair (out_ready follows lane 1's events).
-    struct Lane { hipStream_t st; size_t off; };
-    // (zett_forward_into) a destination matrix as the heads of the chunk starting at vocabulary row r0 see it
-    auto dest_out = [&](void* base, int64_t ld, int64_t r0) {
-        const size_t es = dest->dtype == ZETT_F32 ? 4 : 2;
-        return typename Runner<T>::DestOut{dest->rows ? base : (void*)((char*)base + (size_t)r0 * (size_t)ld * es), dest->rows ? dest->rows + r0 : nullptr, ld, dest->dtype};
-    };
-    const size_t ld_parts = MCS;
-    auto run_chunk = [&](int64_t r0, int64_t r1, const Lane& lane, int ev_mode) -> int {
-        const int rows = (int)(r1 - r0);
-        const int tok0 = hoff[r0];
-        const int m = hoff[r1] - tok0;
-        h->stats.chunks += 1;
-        hipStream_t st = lane.st;
-        R.st = lane.st;
-        R.stage_lane = ev_mode == 2 ? 1 : 0;      // (the staged fallback of the destination store: each lane of a pair has its own buffer)
-        R.a_rows_readable = (long)(MCS - lane.off);
-        float* const Zf = h->yf.as<float>() + lane.off * H;
-        T* const Zt = h->yt.as<T>() + lane.off * H;
-        T* const BIG = h->big.as<T>() + lane.off * (size_t)std::max(I, 3 * H);
-        float* const PRE = h->pre.as<float>() + lane.off * H;
-        T* const CTX = h->ctx.as<T>() + lane.off * H;
-        float* const Cf = h->cf.as<float>() + lane.off * H;
-        T* const Ct = h->ct.as<T>() + lane.off * H;
-        float* const STa = h->lnstats.as<float>() + 2 * lane.off;
-        float* const STb = STa + 2 * MCS;
-        float2* const PARTS = h->lnparts.as<float2>() + lane.off;
-
-        LnEmbed emb{TBL, p.tok_slot, p.tok_pos, R.Wf("model.embeddings.token_type_embeddings.weight"),
-                    R.Wf("model.embeddings.position_embeddings.weight"), lang_vec, seq, p.tok_row, p.row_offset, r0, rows,
-                    table_lo ? (const void*)TBL16 : nullptr, TBLST, R.Wf("input_projection.1.ln.weight"), R.Wf("input_projection.1.ln.bias")};
+    struct Chunk {
+        int64_t r0; int rows, tok0, m; hipStream_t st; int ev_mode; Workspace<T> w;
         // hidden state = (sum buffer, statistics, gamma, beta); the embeddings' LayerNorm starts it in (Zf, STb)
-        float* hs_sum = Zf;
-        float* hs_stats = STb;
-        const float* hs_gamma = R.Wf("model.embeddings.LayerNorm.weight");
-        const float* hs_beta = R.Wf("model.embeddings.LayerNorm.bias");
-        auto embed_ln = [&](const LnEmbed& e, int n, int t0, T* lo, float* stats, float* sum) {
-            if constexpr (sizeof(T) == 2) {
-                const int tpr8 = h->ln_rows8 ? ln_rows8_tpr(H) : 0;
-                if (tpr8) {
-                    const dim3 grid8((n + 256 / tpr8 - 1) / (256 / tpr8));
-                    if (tpr8 == 32)
-                        hipLaunchKernelGGL((layernorm_rows8_kernel<T, true, 32, false>), grid8, dim3(256), 0, st, (const float*)nullptr, H, n, H,
-                                           hs_gamma, hs_beta, c.ln_eps_encoder, (float*)nullptr, lo, stats, sum, e, t0, LnReadout{});
-                    else
-                        hipLaunchKernelGGL((layernorm_rows8_kernel<T, true, 64, false>), grid8, dim3(256), 0, st, (const float*)nullptr, H, n, H,
-                                           hs_gamma, hs_beta, c.ln_eps_encoder, (float*)nullptr, lo, stats, sum, e, t0, LnReadout{});
-                    R.check("embed_layernorm");
-                    return;
-                }
-            }
-            if (H <= 2048)
-                hipLaunchKernelGGL((layernorm_rows_kernel<T, true, 64>), dim3((n + 3) / 4), dim3(256), 0, st, (const float*)nullptr, H, n, H,
-                                   hs_gamma, hs_beta, c.ln_eps_encoder, (float*)nullptr, lo, stats, sum, e, t0, LnReadout{});
-            else
-                hipLaunchKernelGGL((layernorm_rows_kernel<T, true, 256>), dim3(n), dim3(256), 0, st, (const float*)nullptr, H, n, H,
-                                   hs_gamma, hs_beta, c.ln_eps_encoder, (float*)nullptr, lo, stats, sum, e, t0, LnReadout{});
-            R.check("embed_layernorm");
-        };
-        // Lever 4: the embeddings' output depends on (source id, position) only, so the embeddings' LayerNorm and layer 0's
-        // Q/K/V are computed once per DISTINCT pair (P rows instead of m).  The attention kernel reads a packed position's
-        // q / k / v through tok_pair, and layer 0's attention-output epilogue adds the residual row of the position's pair
-        // (GemmEpilogue::res_index = pair slot per buffer row): until that GEMM has run, the hidden state (operand, sum,
-        // statistics) exists per pair only.  Same values, same bits.  Taken when the call is one chunk and at least 15 % of
-        // the positions repeat a pair.
-        const int P = pair_plan ? hoff[N + 3] : 0;
-        const bool pairs = pair_plan && rows == N && P > 0 && (int64_t)P * 100 <= (int64_t)m * 85;
-        int32_t* brow_pair = p.tok_pkey;       // (the keys are dead once plan_pairs_kernel has run)
-        if (pairs) {
-            LnEmbed pe = emb;
-            pe.tok_slot = p.pair_tslot; pe.tok_pos = p.pair_pos; pe.tok_row = nullptr;
-            embed_ln(pe, P, 0, Zt, hs_stats, lo_stream ? (float*)nullptr : hs_sum);
-            hipLaunchKernelGGL(pair_rows_kernel, dim3((m + 255) / 256), dim3(256), 0, st, m, tok0, r0, rows, p, brow_pair);
-            R.check("pair_rows");
-            h->stats.distinct_positions = P;
-        } else {
-            embed_ln(emb, m, tok0, Zt, hs_stats, lo_stream ? (float*)nullptr : hs_sum);
-        }
-
-        int zrows = m;            // rows of the current hidden state: m, or `rows` (position 0 only) in a position-0-only last layer
+        float* hs_sum; float* hs_stats; const float* hs_gamma; const float* hs_beta;
+        int zrows;                // rows of the current hidden state: m, or `rows` (position 0 only) in a position-0-only last layer
         bool raw = false;         // Zt = 16-bit copy of the un-normalised sum (LayerNorm fold) instead of the LayerNorm output
-        auto other = [&](float* b) { return b == Zf ? PRE : Zf; };
-        auto other_stats = [&](float* b) { return b == STa ? STb : STa; };
+        bool pairs = false;       // lever 4 taken: until layer 0's attention output the hidden state exists per distinct pair only
+        int P = 0;                // distinct (source id, position) pairs of the call
+        float* other(float* b) const { return b == w.Zf ? w.PRE : w.Zf; }
+        float* other_stats(float* b) const { return b == w.STa ? w.STb : w.STa; }
+    };
+
+    int run_chunk(int64_t r0, int64_t r1, hipStream_t lane_st, size_t off, int ev_mode) {
+        Chunk k{r0, (int)(r1 - r0), hoff[r0], hoff[r1] - hoff[r0], lane_st, ev_mode, lane_workspace<T>(h, off, MCS)};
+        h->stats.chunks += 1;
+        R.st = lane_st;
+        R.stage_lane = ev_mode == 2 ? 1 : 0;      // (the staged fallback of the destination store: each lane of a pair has its own buffer)
+        R.a_rows_readable = k.w.a_rows;
+        embeddings(k);
         for (int l = 0; l < c.layers && !R.rc; ++l) {
             const std::string lp = "model.encoder.layer." + std::to_string(l) + ".";
-            const bool last = l == c.layers - 1;
-            const bool cls_only = h->cls_only_last && last;
-            // raw: Zt holds the 16-bit copy of the pre-LayerNorm sum (LayerNorm fold: the previous layer's FFN-down wrote it
-            // with the statistics in hs_stats) instead of the normalised operand — then this layer's QKV runs on the folded weight
-            const T* wqkv = raw ? (const T*)h->fold_qkv[l].w : (const T*)h->qkv_w[l];
-            const float* bqkv = raw ? h->fold_qkv[l].b : h->qkv_b[l];
-            const float* cqkv = raw ? h->fold_qkv[l].c : nullptr;
-            const int64_t waves = attention_waves(rows, H, h->attention_pack != 0).total;
-            const int att_flags = (h->attention_fast ? 2 : 0) | (h->attention_pack ? 4 : 0);
-            if (!cls_only) {
-                const bool by_pair = pairs && l == 0;       // Zt holds the P pair rows; BIG gets their Q/K/V
-                GemmEpilogue<T> eq = R.epi();
-                eq.bias = bqkv; eq.out_lo = BIG; eq.ld_lo = 3 * H;
-                if (raw) { eq.fold_stats = hs_stats; eq.fold_c = cqkv; }
-                R.gemm(Zt, H, wqkv, H, by_pair ? P : m, 3 * H, H, eq);
-                hipLaunchKernelGGL((attention_rows_kernel<T>), dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st,
-                                   (const T*)BIG, (size_t)3 * H, (const T*)BIG + H, (const T*)BIG + 2 * H, (size_t)3 * H,
-                                   H, H / c.heads, p.row_offset, p.row_uniform, p.tok_key, r0, rows, tok0, scaling, 0 | att_flags,
-                                   by_pair ? (const int32_t*)p.tok_pair : (const int32_t*)nullptr, CTX);
-                R.check("attention");
-            } else {
-                // Only hidden[:,0] is consumed after this layer (modeling_hypernet.py:234): keys and values for every
-                // position, the query (and everything downstream) for position 0 = the first `rows` rows of the
-                // hidden state (sum, statistics and 16-bit operand alike).
-                T* KV = BIG;                              // [m, 2H]
-                T* Q = BIG + (size_t)m * 2 * H;           // [rows, H]  (rows <= m, BIG holds >= m x 3H)
-                GemmEpilogue<T> ekv = R.epi();
-                ekv.bias = bqkv + H; ekv.out_lo = KV; ekv.ld_lo = 2 * H;
-                if (raw) { ekv.fold_stats = hs_stats; ekv.fold_c = cqkv + H; }
-                R.gemm(Zt, H, wqkv + (size_t)H * H, H, m, 2 * H, H, ekv);
-                GemmEpilogue<T> eq = R.epi();
-                eq.bias = bqkv; eq.out_lo = Q; eq.ld_lo = H;
-                if (raw) { eq.fold_stats = hs_stats; eq.fold_c = cqkv; }
-                R.gemm(Zt, H, wqkv, H, rows, H, H, eq);
-                hipLaunchKernelGGL((attention_rows_kernel<T>), dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st,
-                                   (const T*)Q, (size_t)H, (const T*)KV, (const T*)KV + H, (size_t)2 * H,
-                                   H, H / c.heads, p.row_offset, p.row_uniform, p.tok_key, r0, rows, tok0, scaling, 1 | att_flags,
-                                   (const int32_t*)nullptr, CTX);
-                R.check("attention(position 0)");
-                zrows = rows;
-            }
-            // attention output: sum = dense(ctx) + LN(hidden)   (the residual is the LayerNorm of hs_sum, recomputed)
-            float* s1 = other(hs_sum);
-            float* st1 = other_stats(hs_stats);
-            GemmEpilogue<T> eo = R.epi();
-            eo.bias = R.Wf(lp + "attention.output.dense.bias");
-            if (pairs && l == 0) eo.res_index = brow_pair;       // hs_sum / hs_stats are still per pair here
-            if (lo_stream) {
-                // the hidden state is Zt: the embeddings' LayerNorm output itself (layer 0: used as stored), or the raw 16-bit
-                // sum of the previous layer with its statistics; the new sum goes to Ct
-                eo.residual_lo = Zt; eo.ld_res_lo = H;
-                if (raw) { eo.res_stats = hs_stats; eo.res_gamma = hs_gamma; eo.res_beta = hs_beta; }
-                eo.out_lo = Ct; eo.ld_lo = H; eo.stats_part = PARTS; eo.ld_part = (int)ld_parts;
-            } else {
-                eo.residual = hs_sum; eo.ld_res = H;
-                eo.res_stats = hs_stats; eo.res_gamma = hs_gamma; eo.res_beta = hs_beta;
-                eo.out_f32 = s1; eo.ld_f32 = H;
-                if (fold) { eo.out_lo = Zt; eo.ld_lo = H; eo.stats_part = PARTS; eo.ld_part = (int)ld_parts; }
-            }
-            R.gemm(CTX, H, R.Wlo(lp + "attention.output.dense.weight"), H, zrows, H, H, eo);
-            const float* g1 = R.Wf(lp + "attention.output.LayerNorm.weight");
-            const float* b1 = R.Wf(lp + "attention.output.LayerNorm.bias");
-            const T* mid = lo_stream ? Ct : Zt;                  // 16-bit operand of intermediate.dense
-            GemmEpilogue<T> ei = R.epi();
-            ei.act = ACT_GELU_ERF; ei.out_lo = BIG; ei.ld_lo = I;
-            if (fold) {          // the attention-output LayerNorm is folded into intermediate.dense
-                R.ln_stats(PARTS, (int)ld_parts, zrows, c.ln_eps_encoder, st1);
-                ei.bias = h->fold_up[l].b; ei.fold_stats = st1; ei.fold_c = h->fold_up[l].c;
-                R.gemm(mid, H, (const T*)h->fold_up[l].w, H, zrows, I, H, ei);
-            } else {
-                R.layernorm(s1, zrows, g1, b1, c.ln_eps_encoder, nullptr, Zt, st1);
-                ei.bias = R.Wf(lp + "intermediate.dense.bias");
-                R.gemm(Zt, H, R.Wlo(lp + "intermediate.dense.weight"), H, zrows, I, H, ei);
-            }
-            // FFN output: sum = dense(gelu) + LN(s1)
-            float* s2 = other(s1);
-            float* st2 = other_stats(st1);
-            GemmEpilogue<T> ef = R.epi();
-            ef.bias = R.Wf(lp + "output.dense.bias");
-            if (lo_stream) {      // (also in the last layer: the readout takes the 16-bit sum)
-                ef.residual_lo = Ct; ef.ld_res_lo = H; ef.res_stats = st1; ef.res_gamma = g1; ef.res_beta = b1;
-                ef.out_lo = Zt; ef.ld_lo = H; ef.stats_part = PARTS; ef.ld_part = (int)ld_parts;
-            } else {
-                ef.residual = s1; ef.ld_res = H;
-                ef.res_stats = st1; ef.res_gamma = g1; ef.res_beta = b1;
-                ef.out_f32 = s2; ef.ld_f32 = H;
-                if (fold && !last) { ef.out_lo = Zt; ef.ld_lo = H; ef.stats_part = PARTS; ef.ld_part = (int)ld_parts; }
-            }
-            R.gemm(BIG, I, R.Wlo(lp + "output.dense.weight"), I, zrows, H, I, ef);
-            hs_gamma = R.Wf(lp + "output.LayerNorm.weight");
-            hs_beta = R.Wf(lp + "output.LayerNorm.bias");
-            hs_sum = s2; hs_stats = st2;
-            // (the last layer's output LayerNorm is the readout below: position 0 only, whatever the layer computed)
-            if (!last) {
-                if (fold) { R.ln_stats(PARTS, (int)ld_parts, zrows, c.ln_eps_encoder, st2); raw = true; }
-                else R.layernorm(s2, zrows, hs_gamma, hs_beta, c.ln_eps_encoder, nullptr, Zt, st2);
-            }
+            attention(k, l);
+            feed_forward(k, l, lp);
         }
         if (R.rc) return R.rc;
+        if (int rc = readout(k)) return rc;
+        return heads(k);
+    }
 
-        // position-0 readout + bias head (modeling_hypernet.py:231-234, 260-265) = the last LayerNorm, on the first `rows`
-        // buffer rows: Cf = fp32 hidden[:,0] (residual of the heads' ProjectorBlocks), Ct its operand copy, bias head fused.
-        // (no encoder layer: the embeddings' LayerNorm is simply taken again for those rows)
-        // (zett_forward_into: the bias goes to the destination's bias vector — row map offset to the chunk, or the identity from r0 on.
-        //  A destination without one still takes the READOUT instantiation — only it reads the 16-bit residual stream — into a
-        //  workspace vector that nothing reads)
-        float* bias_out = out_bias ? out_bias + r0 : nullptr;
-        const int64_t* bias_rows = nullptr;
+    // RobertaEmbeddings: table row + position (+ language) + token type, LayerNorm.
+    // Lever 4: the embeddings' output depends on (source id, position) only, so the embeddings' LayerNorm and layer 0's
+    // Q/K/V are computed once per DISTINCT pair (P rows instead of m).  The attention kernel reads a packed position's
+    // q / k / v through tok_pair, and layer 0's attention-output epilogue adds the residual row of the position's pair
+    // (GemmEpilogue::res_index = pair slot per buffer row): until that GEMM has run, the hidden state (operand, sum,
+    // statistics) exists per pair only.  Same values, same bits.  Taken when the call is one chunk and at least 15 % of
+    // the positions repeat a pair.
+    void embeddings(Chunk& k) {
+        LnEmbed emb{TBL, p.tok_slot, p.tok_pos, R.Wf("model.embeddings.token_type_embeddings.weight"),
+                    R.Wf("model.embeddings.position_embeddings.weight"), lang_vec, seq, p.tok_row, p.row_offset, k.r0, k.rows,
+                    mode.table_lo ? (const void*)TBL16 : nullptr, TBLST, R.Wf("input_projection.1.ln.weight"), R.Wf("input_projection.1.ln.bias")};
+        k.hs_sum = k.w.Zf;
+        k.hs_stats = k.w.STb;
+        k.hs_gamma = R.Wf("model.embeddings.LayerNorm.weight");
+        k.hs_beta = R.Wf("model.embeddings.LayerNorm.bias");
+        k.zrows = k.m;
+        k.P = pair_plan ? hoff[N + 3] : 0;
+        k.pairs = pair_plan && k.rows == N && k.P > 0 && (int64_t)k.P * 100 <= (int64_t)k.m * 85;
+        float* sum = mode.lo_stream ? (float*)nullptr : k.hs_sum;
+        if (k.pairs) {
+            emb.tok_slot = p.pair_tslot; emb.tok_pos = p.pair_pos; emb.tok_row = nullptr;
+            R.layernorm(nullptr, k.P, k.hs_gamma, k.hs_beta, c.ln_eps_encoder, nullptr, k.w.Zt, k.hs_stats, LnReadout{}, -1, &emb, 0, sum);
+            // p.tok_pkey becomes the pair slot of every buffer row (the keys are dead once plan_pairs_kernel has run)
+            hipLaunchKernelGGL(pair_rows_kernel, dim3((k.m + 255) / 256), dim3(256), 0, k.st, k.m, k.tok0, k.r0, k.rows, p, p.tok_pkey);
+            R.check("pair_rows");
+            h->stats.distinct_positions = k.P;
+        } else {
+            R.layernorm(nullptr, k.m, k.hs_gamma, k.hs_beta, c.ln_eps_encoder, nullptr, k.w.Zt, k.hs_stats, LnReadout{}, -1, &emb, k.tok0, sum);
+        }
+    }
+
+    // Self-attention of layer l: fused QKV (per distinct pair in layer 0 under lever 4), attention_rows_kernel into CTX.
+    void attention(Chunk& k, int l) {
+        const Workspace<T>& w = k.w;
+        const bool cls_only = h->cls_only_last && l == c.layers - 1;
+        // raw: Zt holds the 16-bit copy of the pre-LayerNorm sum (LayerNorm fold: the previous layer's FFN-down wrote it
+        // with the statistics in hs_stats) instead of the normalised operand — then this layer's QKV runs on the folded weight
+        const T* wqkv = k.raw ? (const T*)h->fold_qkv[l].w : (const T*)h->qkv_w[l];
+        const float* bqkv = k.raw ? h->fold_qkv[l].b : h->qkv_b[l];
+        const float* cqkv = k.raw ? h->fold_qkv[l].c : nullptr;
+        const int64_t waves = attention_waves(k.rows, H, h->attention_pack != 0).total;
+        const int att_flags = (h->attention_fast ? 2 : 0) | (h->attention_pack ? 4 : 0);
+        auto qkv = [&](int col0, int cols, int M, T* out) {       // columns [col0, col0 + cols) of [q | k | v] for the first M buffer rows
+            GemmEpilogue<T> e = R.epi();
+            e.bias = bqkv + col0; e.out_lo = out; e.ld_lo = cols;
+            if (k.raw) { e.fold_stats = k.hs_stats; e.fold_c = cqkv + col0; }
+            R.gemm(w.Zt, H, wqkv + (size_t)col0 * H, H, M, cols, H, e);
+        };
+        const bool by_pair = !cls_only && k.pairs && l == 0;       // Zt holds the P pair rows; BIG gets their Q/K/V
+        const T* Q = w.BIG;                               // [m | P, 3H]: q | k | v
+        const T* KV = w.BIG + H;
+        size_t ld_q = (size_t)3 * H, ld_kv = (size_t)3 * H;
+        if (!cls_only) {
+            qkv(0, 3 * H, by_pair ? k.P : k.m, w.BIG);
+        } else {
+            // Only hidden[:,0] is consumed after this layer (modeling_hypernet.py:234): keys and values for every
+            // position, the query (and everything downstream) for position 0 = the first `rows` rows of the
+            // hidden state (sum, statistics and 16-bit operand alike).
+            qkv(H, 2 * H, k.m, w.BIG);                                   // KV [m, 2H]
+            qkv(0, H, k.rows, w.BIG + (size_t)k.m * 2 * H);              // Q [rows, H]  (rows <= m, BIG holds >= m x 3H)
+            KV = w.BIG; Q = w.BIG + (size_t)k.m * 2 * H;
+            ld_q = (size_t)H; ld_kv = (size_t)2 * H;
+            k.zrows = k.rows;
+        }
+        hipLaunchKernelGGL((attention_rows_kernel<T>), dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, k.st, Q, ld_q, KV, KV + H, ld_kv,
+                           H, H / c.heads, p.row_offset, p.row_uniform, p.tok_key, k.r0, k.rows, k.tok0, scaling, (cls_only ? 1 : 0) | att_flags,
+                           by_pair ? (const int32_t*)p.tok_pair : (const int32_t*)nullptr, w.CTX);
+        R.check(cls_only ? "attention(position 0)" : "attention");
+    }
+
+    // The rest of layer l on CTX: attention output + residual, intermediate, FFN output + residual; the LayerNorms in between are
+    // launches (fp32 modes), or folded into the GEMMs around them.
+    void feed_forward(Chunk& k, int l, const std::string& lp) {
+        const Workspace<T>& w = k.w;
+        const bool last = l == c.layers - 1, fold = mode.fold, lo_stream = mode.lo_stream;
+        const int zrows = k.zrows;
+        // attention output: sum = dense(ctx) + LN(hidden)   (the residual is the LayerNorm of hs_sum, recomputed)
+        float* s1 = k.other(k.hs_sum);
+        float* st1 = k.other_stats(k.hs_stats);
+        GemmEpilogue<T> eo = R.epi();
+        eo.bias = R.Wf(lp + "attention.output.dense.bias");
+        if (k.pairs && l == 0) eo.res_index = p.tok_pkey;       // hs_sum / hs_stats are still per pair here
+        if (lo_stream) {
+            // the hidden state is Zt: the embeddings' LayerNorm output itself (layer 0: used as stored), or the raw 16-bit
+            // sum of the previous layer with its statistics; the new sum goes to Ct
+            eo.residual_lo = w.Zt; eo.ld_res_lo = H;
+            if (k.raw) { eo.res_stats = k.hs_stats; eo.res_gamma = k.hs_gamma; eo.res_beta = k.hs_beta; }
+            eo.out_lo = w.Ct; eo.ld_lo = H; eo.stats_part = w.PARTS; eo.ld_part = w.ld_parts;
+        } else {
+            eo.residual = k.hs_sum; eo.ld_res = H;
+            eo.res_stats = k.hs_stats; eo.res_gamma = k.hs_gamma; eo.res_beta = k.hs_beta;
+            eo.out_f32 = s1; eo.ld_f32 = H;
+            if (fold) { eo.out_lo = w.Zt; eo.ld_lo = H; eo.stats_part = w.PARTS; eo.ld_part = w.ld_parts; }
+        }
+        R.gemm(w.CTX, H, R.Wlo(lp + "attention.output.dense.weight"), H, zrows, H, H, eo);
+        const float* g1 = R.Wf(lp + "attention.output.LayerNorm.weight");
+        const float* b1 = R.Wf(lp + "attention.output.LayerNorm.bias");
+        const T* mid = lo_stream ? w.Ct : w.Zt;                  // 16-bit operand of intermediate.dense
+        GemmEpilogue<T> ei = R.epi();
+        ei.act = ACT_GELU_ERF; ei.out_lo = w.BIG; ei.ld_lo = I;
+        if (fold) {          // the attention-output LayerNorm is folded into intermediate.dense
+            R.ln_stats(w.PARTS, w.ld_parts, zrows, c.ln_eps_encoder, st1);
+            ei.bias = h->fold_up[l].b; ei.fold_stats = st1; ei.fold_c = h->fold_up[l].c;
+            R.gemm(mid, H, (const T*)h->fold_up[l].w, H, zrows, I, H, ei);
+        } else {
+            R.layernorm(s1, zrows, g1, b1, c.ln_eps_encoder, nullptr, w.Zt, st1);
+            ei.bias = R.Wf(lp + "intermediate.dense.bias");
+            R.gemm(w.Zt, H, R.Wlo(lp + "intermediate.dense.weight"), H, zrows, I, H, ei);
+        }
+        // FFN output: sum = dense(gelu) + LN(s1)
+        float* s2 = k.other(s1);
+        float* st2 = k.other_stats(st1);
+        GemmEpilogue<T> ef = R.epi();
+        ef.bias = R.Wf(lp + "output.dense.bias");
+        if (lo_stream) {      // (also in the last layer: the readout takes the 16-bit sum)
+            ef.residual_lo = w.Ct; ef.ld_res_lo = H; ef.res_stats = st1; ef.res_gamma = g1; ef.res_beta = b1;
+            ef.out_lo = w.Zt; ef.ld_lo = H; ef.stats_part = w.PARTS; ef.ld_part = w.ld_parts;
+        } else {
+            ef.residual = s1; ef.ld_res = H;
+            ef.res_stats = st1; ef.res_gamma = g1; ef.res_beta = b1;
+            ef.out_f32 = s2; ef.ld_f32 = H;
+            if (fold && !last) { ef.out_lo = w.Zt; ef.ld_lo = H; ef.stats_part = w.PARTS; ef.ld_part = w.ld_parts; }
+        }
+        R.gemm(w.BIG, I, R.Wlo(lp + "output.dense.weight"), I, zrows, H, I, ef);
+        k.hs_gamma = R.Wf(lp + "output.LayerNorm.weight");
+        k.hs_beta = R.Wf(lp + "output.LayerNorm.bias");
+        k.hs_sum = s2; k.hs_stats = st2;
+        // (the last layer's output LayerNorm is the readout: position 0 only, whatever the layer computed)
+        if (!last) {
+            if (fold) { R.ln_stats(w.PARTS, w.ld_parts, zrows, c.ln_eps_encoder, st2); k.raw = true; }
+            else R.layernorm(s2, zrows, k.hs_gamma, k.hs_beta, c.ln_eps_encoder, nullptr, w.Zt, st2);
+        }
+    }
+
+    // an output of the chunk is complete (zett_stream_wait_output): lane 1 of a pair records `lane_ev`, lane 0 waits for it first
+    int output_ready(const Chunk& k, int which, hipEvent_t lane_ev) {
+        if (k.ev_mode == 2) HIP_TRY(hipEventRecord(lane_ev, k.st));
+        if (k.ev_mode == 3) HIP_TRY(hipStreamWaitEvent(k.st, lane_ev, 0));
+        if (k.ev_mode == 1 || k.ev_mode == 3) HIP_TRY(hipEventRecord(h->out_ready[which], k.st));
+        return 0;
+    }
+
+    // position-0 readout + bias head (modeling_hypernet.py:231-234, 260-265) = the last LayerNorm, on the first `rows`
+    // buffer rows: Cf = fp32 hidden[:,0] (residual of the heads' ProjectorBlocks), Ct its operand copy, bias head fused.
+    // (no encoder layer: the embeddings' LayerNorm is simply taken again for those rows)
+    // (zett_forward_into: the bias goes to the destination's bias vector — row map offset to the chunk, or the identity from r0 on.
+    //  A destination without one still takes the READOUT instantiation — only it reads the 16-bit residual stream — into a
+    //  workspace vector that nothing reads)
+    int readout(Chunk& k) {
+        LnReadout ro{c.predict_bias ? R.Wf("bias_projection.weight") : (const float*)nullptr,
+                     c.predict_bias ? R.Wf("bias_projection.bias") : (const float*)nullptr, out_bias ? out_bias + k.r0 : nullptr};
         int bias_dtype = -1;
         if (dest && dest->bias) {
             const size_t bes = dest->bias_dtype == ZETT_F32 ? 4 : 2;
-            bias_rows = dest->rows ? dest->rows + r0 : nullptr;
-            bias_out = (float*)((char*)dest->bias + (dest->rows ? 0 : (size_t)r0 * bes));
+            ro.bias_rows = dest->rows ? dest->rows + k.r0 : nullptr;
+            ro.out_bias = (float*)((char*)dest->bias + (dest->rows ? 0 : (size_t)k.r0 * bes));
             bias_dtype = dest->bias_dtype;
         } else if (dest) {
             if (int rc = h->dest_sink.reserve((size_t)N * sizeof(float))) return rc;      // (the whole call: both lanes of a pair share it)
-            bias_out = h->dest_sink.as<float>() + r0;
+            ro.out_bias = h->dest_sink.as<float>() + k.r0;
         }
-        LnReadout ro{c.predict_bias ? R.Wf("bias_projection.weight") : (const float*)nullptr,
-                     c.predict_bias ? R.Wf("bias_projection.bias") : (const float*)nullptr, bias_out};
-        ro.bias_rows = bias_rows;
         ro.range_flag = h->range_word;
-        R.layernorm(hs_sum, rows, hs_gamma, hs_beta, c.ln_eps_encoder, Cf, Ct, nullptr, ro,
-                    lo_stream ? (const T*)Zt : (const T*)nullptr, bias_dtype);
-        R.check("readout");
-        if (!R.rc) {          // out_bias complete (zett_stream_wait_output)
-            if (ev_mode == 2) HIP_TRY(hipEventRecord(h->lane_ev[1], st));
-            if (ev_mode == 3) HIP_TRY(hipStreamWaitEvent(st, h->lane_ev[1], 0));
-            if (ev_mode == 1 || ev_mode == 3) HIP_TRY(hipEventRecord(h->out_ready[ZETT_OUT_BIAS], st));
-        }
+        ro.in_lo = mode.lo_stream ? (const T*)k.w.Zt : (const T*)nullptr;       // (16-bit residual stream: the rows are read from the 16-bit copy of the sum)
+        R.layernorm(k.hs_sum, k.rows, k.hs_gamma, k.hs_beta, c.ln_eps_encoder, k.w.Cf, k.w.Ct, nullptr, ro, bias_dtype);
+        return R.rc ? 0 : output_ready(k, ZETT_OUT_BIAS, h->lane_ev[1]);      // out_bias complete
+    }
 
-        // output heads (modeling_hypernet.py:236-258)
-        // LayerNorm fold of the heads (r3): the ProjectorBlock's LayerNorm in front of each final Linear is not a launch either
-        const bool fold_heads = fold && h->ln_fold == 1 && h->fold_head_in.w != nullptr;
-        {
-            if (fold_heads) R.projector("output_projection.0.", Ct, Cf, rows, BIG, PRE, nullptr, CTX, PARTS, (int)ld_parts, STa);
-            else R.projector("output_projection.0.", Ct, Cf, rows, BIG, PRE, nullptr, CTX);
-            GemmEpilogue<T> e = R.epi();
-            e.bias = fold_heads ? h->fold_head_in.b : R.Wf("output_projection.1.bias");
-            e.scale = c.rescale ? h->head_scale : (fold_heads ? h->head_one : nullptr);
-            e.shift = c.rescale ? h->head_shift : (fold_heads ? h->head_zero : nullptr);
-            if (fold_heads) { e.fold_stats = STa; e.fold_c = h->fold_head_in.c; }
-            e.ld_f32 = E; e.range_final = 1;
-            const int width = c.single_head ? EIN : E;
-            const bool split = c.single_head && c.separate_out;
-            if (!dest) {
-                e.out_f32 = out_in + (size_t)r0 * E;
-                if (split) { e.split_col = E; e.out_f32_b = out_out + (size_t)r0 * E; }
-            } else if (split) {
-                e.split_col = E;
-            }
-            const T* w1 = fold_heads ? (const T*)h->fold_head_in.w : R.Wlo("output_projection.1.weight");
-            if (dest) {
-                const typename Runner<T>::DestOut din = dest_out(dest->in, dest->ld_in, r0), dout = dest_out(dest->out, dest->ld_out, r0);
-                R.head_gemm(CTX, w1, rows, width, H, e, &din, split ? &dout : nullptr, E);
-            } else {
-                R.gemm(CTX, H, w1, H, rows, width, H, e);
-            }
-            if (!R.rc) {      // out_in complete: the second head runs behind it
-                if (ev_mode == 2) HIP_TRY(hipEventRecord(h->lane_ev[2], st));
-                if (ev_mode == 3) HIP_TRY(hipStreamWaitEvent(st, h->lane_ev[2], 0));
-                if (ev_mode == 1 || ev_mode == 3) HIP_TRY(hipEventRecord(h->out_ready[ZETT_OUT_IN], st));
-            }
+    // (zett_forward_into) a destination matrix as the heads of the chunk starting at vocabulary row r0 see it
+    DestOut dest_out(void* base, int64_t ld, int64_t r0) const {
+        const size_t es = dest->dtype == ZETT_F32 ? 4 : 2;
+        return DestOut{dest->rows ? base : (void*)((char*)base + (size_t)r0 * (size_t)ld * es), dest->rows ? dest->rows + r0 : nullptr, ld, dest->dtype};
+    }
+
+    // One output head (modeling_hypernet.py:236-258): ProjectorBlock `name`.0 on hidden[:,0], Linear `name`.1, Rescaler (scale, shift),
+    // into rows [r0, r0 + rows) of zett_forward's fp32 matrix `out` or of the destination's `dst`.  out_b / dst_b: the split single
+    // head, whose columns from n_embd on are a second matrix.  mode.fold_heads: the block's LayerNorm is folded into the Linear (f).
+    void head(const Chunk& k, const std::string& name, const zett_hypernet::Folded& f, const float* scale, const float* shift, bool split,
+              float* out, float* out_b, void* dst, int64_t ld_dst, void* dst_b, int64_t ld_dst_b) {
+        const Workspace<T>& w = k.w;
+        const bool fold = mode.fold_heads;
+        if (fold) R.projector(name + ".0.", w.Ct, w.Cf, k.rows, w.BIG, w.PRE, nullptr, w.CTX, w.PARTS, w.ld_parts, w.STa);
+        else R.projector(name + ".0.", w.Ct, w.Cf, k.rows, w.BIG, w.PRE, nullptr, w.CTX);
+        GemmEpilogue<T> e = R.epi();
+        e.bias = fold ? f.b : R.Wf(name + ".1.bias");
+        e.scale = c.rescale ? scale : (fold ? h->head_one : nullptr);
+        e.shift = c.rescale ? shift : (fold ? h->head_zero : nullptr);
+        if (fold) { e.fold_stats = w.STa; e.fold_c = f.c; }
+        e.ld_f32 = E; e.range_final = 1;
+        if (split) e.split_col = E;
+        const int width = split ? 2 * E : E;
+        const T* wl = fold ? (const T*)f.w : R.Wlo(name + ".1.weight");
+        if (dest) {
+            const DestOut d = dest_out(dst, ld_dst, k.r0), d_b = split ? dest_out(dst_b, ld_dst_b, k.r0) : DestOut{};
+            R.head_gemm(w.CTX, wl, k.rows, width, H, e, &d, split ? &d_b : nullptr, E);
+        } else {
+            e.out_f32 = out + (size_t)k.r0 * E;
+            if (split) e.out_f32_b = out_b + (size_t)k.r0 * E;
+            R.gemm(w.CTX, H, wl, H, k.rows, width, H, e);
         }
-        if (c.separate_out && !c.single_head) {
-            if (fold_heads) R.projector("output_projection_out.0.", Ct, Cf, rows, BIG, PRE, nullptr, CTX, PARTS, (int)ld_parts, STa);
-            else R.projector("output_projection_out.0.", Ct, Cf, rows, BIG, PRE, nullptr, CTX);
-            GemmEpilogue<T> e = R.epi();
-            e.bias = fold_heads ? h->fold_head_out.b : R.Wf("output_projection_out.1.bias");
-            e.scale = c.rescale ? R.Wf("out_scaler.w") : (fold_heads ? h->head_one : nullptr);
-            e.shift = c.rescale ? R.Wf("out_scaler.b") : (fold_heads ? h->head_zero : nullptr);
-            if (fold_heads) { e.fold_stats = STa; e.fold_c = h->fold_head_out.c; }
-            e.ld_f32 = E; e.range_final = 1;
-            const T* w2 = fold_heads ? (const T*)h->fold_head_out.w : R.Wlo("output_projection_out.1.weight");
-            if (dest) {
-                const typename Runner<T>::DestOut dout = dest_out(dest->out, dest->ld_out, r0);
-                R.head_gemm(CTX, w2, rows, E, H, e, &dout, nullptr, E);
-            } else {
-                e.out_f32 = out_out + (size_t)r0 * E;
-                R.gemm(CTX, H, w2, H, rows, E, H, e);
-            }
-        }
+    }
+
+    int heads(const Chunk& k) {
+        const bool split = c.single_head && c.separate_out;      // one head of 2 * n_embd columns: [in | out]
+        head(k, "output_projection", h->fold_head_in, h->head_scale, h->head_shift, split, out_in, out_out,
+             dest ? dest->in : nullptr, dest ? dest->ld_in : 0, dest ? dest->out : nullptr, dest ? dest->ld_out : 0);
+        if (!R.rc)           // out_in complete: the second head runs behind it
+            if (int rc = output_ready(k, ZETT_OUT_IN, h->lane_ev[2])) return rc;
+        if (c.separate_out && !c.single_head)
+            head(k, "output_projection_out", h->fold_head_out, c.rescale ? R.Wf("out_scaler.w") : nullptr, c.rescale ? R.Wf("out_scaler.b") : nullptr, false,
+                 out_out, nullptr, dest ? dest->out : nullptr, dest ? dest->ld_out : 0, nullptr, 0);
         return R.rc;
-    };
+    }
+
     // two lanes?  Only a call that is one chunk and would not take the pair lever (which needs the whole call in one chunk and is
     // worth more).  auto = the launches of width H (attention output, FFN down: the fewest tiles) would leave more than 8 % of the
     // CU-rounds they occupy idle, on a hypernet wide enough for that to be the cost (H >= 1024), and per-launch timing is off
@@ -1683,69 +1696,54 @@ int do_forward(zett_hypernet* h, const int32_t* sfm, int64_t N, int seq, const v
     // Measured (r4, same box, Mistral shape): 4 096 rows 9.25 -> 9.11 ms; 8 192 rows 16.14 -> 16.12; 16 384 rows and every full
     // vocabulary slower (28.9 -> 29.8; headline 53.1 -> 55.2 with the pair lever lost): the dispatcher interleaves the two
     // chains' workgroups, but each 256x256 tile still owns its CU, so only the partial last rounds gain.
-    bool two_lanes = false;
-    if (h->concurrent_lanes && Ttot <= MC && N >= 512) {
+    bool two_lanes() const {
+        if (!h->concurrent_lanes || Ttot > MC || N < 512) return false;
         const int Pn = pair_plan ? hoff[N + 3] : 0;
         const bool pairs_taken = pair_plan && Pn > 0 && (int64_t)Pn * 100 <= Ttot * 85;
         const double r = (double)((Ttot + 255) / 256) * (double)((H + 255) / 256) / 256.0;
-        two_lanes = h->concurrent_lanes == 2 ||
-                    (!pairs_taken && !h->time_gemm && H >= 1024 && r < 4.0 && (std::ceil(r) - r) / std::ceil(r) > 0.08);
+        return h->concurrent_lanes == 2 || (!pairs_taken && !h->time_gemm && H >= 1024 && r < 4.0 && (std::ceil(r) - r) / std::ceil(r) > 0.08);
     }
-    if (two_lanes) {
-        if (!h->lane_stream) HIP_TRY(hipStreamCreateWithFlags(&h->lane_stream, hipStreamNonBlocking));
-        for (hipEvent_t& e : h->lane_ev)
-            if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        // the split is a multiple of 256 rows (the position-0-only last layer and the heads keep their number of row tiles)
-        int64_t ra = ((N / 2 + 128) / 256) * 256;
-        ra = std::min<int64_t>(std::max<int64_t>(ra, 256), N - 1);
-        const size_t off1 = (size_t)(hoff[ra] - hoff[0]) + 384;
-        HIP_TRY(hipEventRecord(h->lane_ev[0], st));                       // fork: the plan and the table are complete
-        HIP_TRY(hipStreamWaitEvent(h->lane_stream, h->lane_ev[0], 0));
-        slot_guard.lane_forked = true;                                    // (joined by the guard on every exit path)
-        if (int rc = run_chunk(ra, N, Lane{h->lane_stream, off1}, 2)) return rc;
-        if (int rc = run_chunk(0, ra, Lane{st, 0}, 3)) return rc;
-    } else {
-        int64_t r0 = 0;
-        while (r0 < N) {
-            int64_t r1 = r0 + 1;
-            while (r1 < N && (int64_t)hoff[r1 + 1] - hoff[r0] <= MC) ++r1;
-            if (int rc = run_chunk(r0, r1, Lane{st, 0}, r1 == N ? 1 : 0)) return rc;
-            r0 = r1;
-        }
-    }
-    R.st = st;
-    if (R.rc) return R.rc;
-    if (slot_guard.lane_forked) {                      // join now (the guard then has nothing left to join)
-        HIP_TRY(hipEventRecord(h->lane_ev[3], h->lane_stream));
-        HIP_TRY(hipStreamWaitEvent(st, h->lane_ev[3], 0));
-        slot_guard.lane_forked = false;
-    }
-    h->out_recorded = true;          // (ps.released — the plan slot may be rewritten behind it, zett_forward_prepare — is recorded by the guard)
 
-    if (h->time_gemm) {
-        HIP_TRY(hipStreamSynchronize(st));
-        double ms = 0.0, fl = 0.0;
-        for (size_t i = 0; i + 1 < h->ev_used; i += 2) {
-            float t = 0.f;
-            if (hipEventElapsedTime(&t, h->ev[i], h->ev[i + 1]) == hipSuccess) { ms += t; fl += h->ev_flops[i / 2]; }
-        }
-        h->stats.gemm_ms = ms;
-        h->stats.gemm_flops_timed = fl;
-        for (size_t i = 0; i + 1 < h->ev_used && i / 2 < h->gemm_log.size(); i += 2) {
-            float t = 0.f;
-            if (hipEventElapsedTime(&t, h->ev[i], h->ev[i + 1]) == hipSuccess) h->gemm_log[i / 2].ms = t;
-        }
-        if (getenv("ZETT_GEMM_LOG")) {
-            for (size_t i = 0; i + 1 < h->ev_used; i += 2) {
-                float t = 0.f;
-                (void)hipEventElapsedTime(&t, h->ev[i], h->ev[i + 1]);
-                const auto& sh = h->ev_shape[i / 2];
-                fprintf(stderr, "[zett gemm] M=%6d N=%6d K=%5d tile=%s %8.3f ms %7.1f TF\n", sh[0], sh[1], sh[2],
-                        sh[3] == 7 ? "4d " : sh[3] == 8 ? "4dg" : sh[3] == 3 ? "384" : sh[3] == 2 ? "8r " : "128", t, h->ev_flops[i / 2] / (t * 1e9));
+    // lane selection and the join
+    int run_chunks(SlotGuard& guard) {
+        if (two_lanes()) {
+            if (!h->lane_stream) HIP_TRY(hipStreamCreateWithFlags(&h->lane_stream, hipStreamNonBlocking));
+            for (hipEvent_t& e : h->lane_ev)
+                if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+            // the split is a multiple of 256 rows (the position-0-only last layer and the heads keep their number of row tiles)
+            int64_t ra = ((N / 2 + 128) / 256) * 256;
+            ra = std::min<int64_t>(std::max<int64_t>(ra, 256), N - 1);
+            const size_t off1 = (size_t)(hoff[ra] - hoff[0]) + 384;       // (the second lane's slice starts 384 rows behind the first one's rows)
+            HIP_TRY(hipEventRecord(h->lane_ev[0], st));                       // fork: the plan and the table are complete
+            HIP_TRY(hipStreamWaitEvent(h->lane_stream, h->lane_ev[0], 0));
+            guard.lane_forked = true;                                         // (joined by the guard on every exit path)
+            if (int rc = run_chunk(ra, N, h->lane_stream, off1, 2)) return rc;
+            if (int rc = run_chunk(0, ra, st, 0, 3)) return rc;
+        } else {
+            int64_t r0 = 0;
+            while (r0 < N) {
+                int64_t r1 = r0 + 1;
+                while (r1 < N && (int64_t)hoff[r1 + 1] - hoff[r0] <= MC) ++r1;
+                if (int rc = run_chunk(r0, r1, st, 0, r1 == N ? 1 : 0)) return rc;
+                r0 = r1;
             }
         }
+        R.st = st;
+        if (R.rc) return R.rc;
+        if (guard.lane_forked) {                      // join now (the guard then has nothing left to join)
+            HIP_TRY(hipEventRecord(h->lane_ev[3], h->lane_stream));
+            HIP_TRY(hipStreamWaitEvent(st, h->lane_ev[3], 0));
+            guard.lane_forked = false;
+        }
+        return 0;
     }
-    return 0;
+};
+
+template <typename T>
+int do_forward(zett_hypernet* h, const int32_t* sfm, int64_t N, int seq, const void* src, int src_dtype, const zett_dest* dest,
+               int lang_index, float* out_in, float* out_out, float* out_bias, hipStream_t st) {
+    Forward<T> f{h, sfm, N, seq, src, src_dtype, dest, lang_index, out_in, out_out, out_bias, st};
+    return f.run();
 }
 
 }  // namespace
