@@ -497,6 +497,10 @@ int zett_op_gemm_f32(const float* a, int32_t lda, const float* w, int32_t ldw, i
  * zero-padded to rows_padded): the conversion is fused with the layout change dgrad / wgrad need anyway. */
 int zett_op_gemm_lo(int32_t prec, const void* a, int32_t lda, const void* w, int32_t ldw, int64_t m, int32_t n, int32_t k, const float* bias, int32_t act,
                     const float* residual, int32_t ld_res, float* out, int32_t ld_out, void* stream);
+/* Alignment of the conversions and 16-bit transposes: `in` of zett_op_transpose_lo / zett_op_grad_operands_lo (and act_z) 16-byte aligned,
+ * 16-bit buffers (out, dy_lo, dy_t, a 16-bit `in`) 8-byte aligned, or ZETT_E_INVALID; zett_op_convert_lo takes any pointer.  Leading
+ * dimensions may be any value >= the width (ld_out >= rows_padded / cols_padded): multiples of 4 elements move four values per access, any
+ * other value one value at a time, with the same bits.  zett_op_transpose_f32 has no alignment requirement. */
 int zett_op_convert_lo(int32_t prec, const float* in, int32_t ld_in, void* out, int32_t ld_out, int64_t rows, int32_t cols, int32_t cols_padded, void* stream);
 int zett_op_transpose_lo(int32_t prec, const float* in, int32_t ld_in, void* out, int32_t ld_out, int64_t rows, int32_t cols, int64_t rows_padded, void* stream);
 /* The transposed operand of an activation that is already stored as a 16-bit operand of type prec (no conversion). */
@@ -512,18 +516,22 @@ int zett_op_grad_operands_lo(int32_t prec, const float* dy, int32_t ld, const fl
 int zett_op_transpose_f32(const float* in, int32_t ld_in, float* out, int32_t ld_out, int64_t rows, int32_t cols, int64_t rows_padded, void* stream);
 /* out[c] (+)= sum_r in[r, c] */
 int zett_op_colsum_f32(const float* in, int32_t ld, int64_t rows, int32_t cols, float* out, int32_t accumulate, void* stream);
-/* op 0: a + b; 1: a * b; 2: a * vec[col] + vec2[col] (vec NULL: 1, vec2 NULL: 0); 3: a + s[row] * vec[col]; 4: a * s[row] (a NULL: s[row] * vec[col]) */
+/* op 0: a + b; 1: a * b; 2: a * vec[col] + vec2[col] (vec NULL: 1, vec2 NULL: 0); 3: a + s[row] * vec[col]; 4: a * s[row] (a NULL: s[row] * vec[col]).
+ * a, b, out are [n / cols, cols] without padding; any 4-byte aligned pointers (16-byte aligned with cols % 4 == 0: four values per access, same bits).
+ * The GELU entry points below likewise. */
 int zett_op_elementwise_f32(int32_t op, const float* a, const float* b, const float* vec, const float* vec2, const float* s, float* out,
                             int64_t n, int32_t cols, void* stream);
 /* out[r] = a[r, :] . w + b[0] (b nullable) */
 int zett_op_rowdot_f32(const float* a, int32_t ld, const float* w, const float* b, float* out, int64_t rows, int32_t cols, void* stream);
 /* y = LayerNorm(x) (two-pass variance); stats[r] = (mean, rstd); y_lo (nullable, type prec): the same values as the 16-bit
- * operand of the next contraction.  4 <= h <= 8192, h % 4 == 0. */
+ * operand of the next contraction.  4 <= h <= 8192, h % 4 == 0.  x has leading dimension ld (ld % 4 == 0: x may be a column slice of a
+ * wider matrix); y, y_lo (and dy, dy2, dx of the backward) have leading dimension h.  x, gamma, beta, y 16-byte aligned, y_lo 8-byte. */
 int zett_op_layernorm_fwd_f32(const float* x, int32_t ld, const float* gamma, const float* beta, float eps, float* y, float* stats,
                               int64_t rows, int32_t h, void* y_lo, int32_t prec, void* stream);
 /* dx for the gradient dy (+ dy2, nullable: the part arriving over the residual branch), and the parameter gradients as
  * n_part partial sums: partials [n_part, 2, h] — partials[:, 0].sum(0) = dgamma, partials[:, 1].sum(0) = dbeta (workgroup b
- * walks rows b, b + n_part, ...: deterministic for a given n_part).  4 <= h <= 8192, h % 4 == 0. */
+ * walks rows b, b + n_part, ...: deterministic for a given n_part; any n_part >= 1, a workgroup without rows writes zeros).
+ * 4 <= h <= 8192, h % 4 == 0; dy, dy2, x, gamma, dx and partials 16-byte aligned. */
 int zett_op_layernorm_bwd_f32(const float* dy, const float* dy2, const float* x, int32_t ld, const float* stats, const float* gamma, float* dx,
                               float* partials, int32_t n_part, int64_t rows, int32_t h, void* stream);
 int zett_op_gelu_fwd_f32(const float* z, float* h, int64_t n, int32_t kind, void* stream);
@@ -534,7 +542,10 @@ int zett_op_gelu_fwd_lo(int32_t prec, const float* z, void* h_lo, int64_t n, int
  * masked attends uniformly).  The positions of row n are rows [row_offset[n], row_offset[n+1]) of k / v (packed: only the
  * positions the row keeps) or [n*seq, (n+1)*seq) when row_offset is NULL (the reference's dense layout); at most seq <= 32
  * positions per row; mask[t] = position t is visible as a key.  cls_only: one query per row (position 0), q and ctx hold
- * one row per vocabulary row (the position-0-only last layer).  probs [n_rows, heads, seq, seq] is kept for the backward.
+ * one row per vocabulary row (the position-0-only last layer).  probs [n_rows, heads, seq, seq] is kept for the backward: of a row with
+ * L positions only the [L, L] block (cls_only: its first line) is written and read, the rest of the buffer is unspecified; a masked key
+ * holds exactly 0 unless every key of the row is masked.  ld_ctx, ld_dq, ld_d may be any value >= heads * head_dim; no alignment beyond
+ * the element's.
  * ctx_lo (nullable, type prec, same leading dimension): the context is written as the 16-bit operand of the contraction behind it
  * INSTEAD of fp32 (ctx may then be NULL).
  * Head dims up to 256 (the backward: above 128 for rows of up to 16 positions — the row's keys, values and their gradients
@@ -545,10 +556,13 @@ int zett_op_attention_fwd_f32(const float* q, int32_t ldq, const float* k, const
 int zett_op_attention_bwd_f32(const float* dctx, int32_t ld_ctx, const float* q, int32_t ldq, const float* k, const float* v, int32_t ld, const float* probs,
                               const int32_t* row_offset, int64_t n_rows, int32_t seq, int32_t heads, int32_t head_dim, int32_t cls_only, float* dq, int32_t ld_dq,
                               float* dk, float* dv, int32_t ld_d, void* stream);
-/* out[r, :] = a[r, :] + src[idx[r], :] (a NULL: 0);   dst[idx[r], :] += src[r, :] (atomic) */
+/* out[r, :] = a[r, :] + src[idx[r], :] (a NULL: 0);   dst[idx[r], :] += src[r, :] (float atomics: a sum in NO fixed order, a row hit three
+ * or more times can differ in its last bits from run to run).  a, out and scatter's src are [rows, cols] without padding. */
 int zett_op_gather_rows_f32(const float* a, const float* src, int32_t ld_src, const int32_t* idx, float* out, int64_t rows, int32_t cols, void* stream);
 int zett_op_scatter_add_rows_f32(float* dst, int32_t ld_dst, const int32_t* idx, const float* src, int64_t rows, int32_t cols, void* stream);
-/* A2 + A3 (modeling_hypernet.py:170-188) per position, and its backward: dfallback accumulated in place (zero it first),
+/* A2 + A3 (modeling_hypernet.py:170-188) per position (ids < v0: source rows, v0 <= id < v0 + fallback rows: fallback[id - v0]; sw NULL: no
+ * rescaler, sb is then not read), and its backward: dfallback accumulated in place with float atomics (zero it first; like
+ * zett_op_scatter_add_rows_f32 a sum in no fixed order),
  * prod = dx * source row and keep = dx on source rows (0 on fallback rows): their column sums are d in_scaler.w / d in_scaler.b */
 int zett_op_gather_fwd_f32(const int32_t* ids, int64_t n_tokens, const void* src, int32_t src_dtype, int32_t e_in, int32_t v0, const float* fallback,
                            const float* sw, const float* sb, float* x, void* stream);
