@@ -724,6 +724,46 @@ int zett_op_batch_vocab(const void* input_ids, int32_t ids_bytes, const void* la
                         void* ids_to_embed, void* out_surface_forms, float* out_priors, uint8_t* mask, int32_t* n_positive, int32_t* status, void* workspace,
                         int64_t workspace_bytes, void* stream);
 
+/* ---- text encoding (zett_amd/text_encode.py DeviceTextEncoder, training.encode_texts; additive, ABI 8) ----------------------------
+ * The tokenizer call of the reference's Collator.encode (collator.py:166-175: tokenizer(texts, max_length=block_size, truncation=True,
+ * padding="max_length", add_special_tokens=True)) and its special_ids_map patch (collator.py:177-178), on UTF-8 text that is already on
+ * the device (csrc/text_encode.hip).  `r` holds the tokenizer's bare model (BPE or Unigram; WordPiece is ZETT_E_NOT_IMPLEMENTED).
+ *   text          n_text bytes: the UTF-8 of the n_texts texts back to back;  text_offsets: DEVICE, n_texts + 1 int64, non-decreasing from 0
+ *                 to n_text (anything else sets ZETT_ENCODE_BAD_OFFSETS; every offset is clamped before it is used)
+ *   prefix        zett_encode_prefix: a U+0020 in front of a NON-EMPTY text — always (normalizers.Prepend(" ")), or unless the text
+ *                 starts with one (pre_tokenizers.ByteLevel(add_prefix_space=True)).  An empty text gets none in any mode.
+ *   words         the leftmost-first matches of 's|'t|'re|'ve|'m|'ll|'d| ?\p{L}+| ?\p{N}+| ?[^\s\p{L}\p{N}]+|\s+(?!\S)|\s+ (zett/utils.py:29;
+ *                 with ZETT_ENCODE_MARKS_ARE_LETTERS the letter class is [\p{L}\p{M}]), per text.  class_table: DEVICE, 4 bits per code
+ *                 point (code point c in bits 4 * (c & 1) .. of byte c >> 1), n_code_points <= 0x110000 of them: 0 other, 1 \p{L},
+ *                 2 \p{M}, 3 \p{N}, 4 \s; a code point beyond the table and a byte sequence that is not UTF-8 are class 0.
+ *   ids of a word what stage 2 of zett_retokenize gives for the word's bytes as raw bytes (no special-token lookup)
+ *   row           prefix_ids ++ the text's ids cut to block_size - n_prefix - n_suffix from the right ++ suffix_ids ++ pad_id ...;
+ *                 attention_mask 1 on everything but the pads; then for m = 0 .. n_map - 1 in turn every id equal to map_from[m]
+ *                 becomes map_to[m].  input_ids / attention_mask: [n_texts, block_size] of out_bytes (4 or 8) with leading
+ *                 dimension ld_out >= block_size elements.
+ * prefix_ids / suffix_ids (at most ZETT_ENCODE_MAX_TEMPLATE each, n_prefix + n_suffix < block_size <= 8192) and map_from / map_to (at
+ * most ZETT_SPLICE_MAX_ROWS pairs) are HOST arrays, validated before any launch; they travel to the kernels as launch arguments.
+ * *status (device) is written by the call: an OR of zett_encode_status bits, 0 when all is well.  With a bit set the outputs are
+ * unspecified, but every write stays inside them.  Integers only, the only atomic is the OR into *status: the same inputs give the same
+ * bits.  Asynchronous on `stream`, no allocation: `workspace` (device, 16-byte aligned, zett_encode_workspace_bytes: about 180 bytes per
+ * byte of text, most of it the worst-case state of words too long for LDS) is free once the call's work is done.  n_texts == 0 is a no-op. */
+#define ZETT_ENCODE_MAX_TEMPLATE 8
+enum zett_encode_flags {
+    ZETT_ENCODE_MARKS_ARE_LETTERS = 1,   /* the letter class is [\p{L}\p{M}] (zett/utils.py:29) */
+    ZETT_ENCODE_RESPLIT = 2              /* every word is split once more, on its own, with the pattern WITHOUT \p{M}: what a ByteLevel with use_regex behind
+                                          * the Split of collator.py:408-411 does to it ("e" + U+0301 becomes two words; U+0301 + "." stays two) */
+};
+enum zett_encode_prefix { ZETT_ENCODE_PREFIX_NONE = 0, ZETT_ENCODE_PREFIX_ALWAYS = 1, ZETT_ENCODE_PREFIX_UNLESS_SPACE = 2 };
+enum zett_encode_status {
+    ZETT_ENCODE_NO_UNK = 1,        /* a word needs an unk id the model does not have (the library raises) */
+    ZETT_ENCODE_BAD_OFFSETS = 2    /* text_offsets is not non-decreasing from 0 to n_text */
+};
+int zett_encode_workspace_bytes(int64_t n_text, int64_t n_texts, int64_t* bytes);
+int zett_encode_texts(zett_retok* r, const uint8_t* text, const int64_t* text_offsets, int64_t n_texts, int64_t n_text, const uint8_t* class_table,
+                      int64_t n_code_points, int32_t flags, int32_t prefix_mode, int32_t block_size, const int32_t* prefix_ids, int32_t n_prefix,
+                      const int32_t* suffix_ids, int32_t n_suffix, const int32_t* map_from, const int32_t* map_to, int32_t n_map, int32_t pad_id, void* input_ids,
+                      void* attention_mask, int32_t out_bytes, int64_t ld_out, void* workspace, int64_t workspace_bytes, int32_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -36,7 +36,11 @@
 #include <vector>
 
 #include "common.hip.h"
+// text_encode.hip shares the tables, the device functions and the handle of this header (it defines ZETT_RETOK_DEVICE_FUNCTIONS_ONLY): the kernels and
+// the entry points — and rowops.hip.h, which only they need — are compiled once, into zett_hip.hip
+#ifndef ZETT_RETOK_DEVICE_FUNCTIONS_ONLY
 #include "rowops.hip.h"
+#endif
 
 namespace zett {
 
@@ -287,6 +291,7 @@ __global__ __launch_bounds__(256) void chars_to_bytes_kernel(const uint8_t* __re
     }
 }
 
+#ifndef ZETT_RETOK_DEVICE_FUNCTIONS_ONLY
 __global__ void token_raw_offsets_kernel(const int32_t* __restrict__ offsets, int64_t n_tokens, int64_t n_text,
                                          const uint32_t* __restrict__ raw_pos, const int32_t* __restrict__ blk_scan,
                                          int n_blocks, int32_t* __restrict__ raw_off) {
@@ -301,6 +306,7 @@ __global__ void fill_i32_kernel(int32_t* __restrict__ p, int64_t n, int32_t v) {
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (; i < n; i += stride) p[i] = v;
 }
+#endif  // ZETT_RETOK_DEVICE_FUNCTIONS_ONLY
 
 // ---------------------------------------------------------------------------------------
 // stage 2: a wave per 64 tokens, one lane per token; the tokens' bytes and their working state live in LDS
@@ -685,6 +691,7 @@ __device__ inline bool segment_token(const RetokTables& t, const RetokLds& L, ty
     return wordpiece_token<M>(t, s, len, w, pad_id);
 }
 
+#ifndef ZETT_RETOK_DEVICE_FUNCTIONS_ONLY
 __global__ __launch_bounds__(64) void retok_tokens_kernel(RetokTables t, const uint8_t* __restrict__ raw,
                                                           const int32_t* __restrict__ raw_off, int64_t n_tokens,
                                                           int maxlen, int32_t pad_id, int32_t* __restrict__ out, int32_t* __restrict__ scratch,
@@ -761,6 +768,7 @@ __global__ __launch_bounds__(64) void retok_tokens_kernel(RetokTables t, const u
     }
     if (lex.counts && live) lex.counts[tok] = exact ? 1 : lex.count_of(w);
 }
+#endif  // ZETT_RETOK_DEVICE_FUNCTIONS_ONLY
 
 // ---------------------------------------------------------------------------------------
 // stage 2 for Unigram models (r6): a WORKGROUP per 64 tokens — the piece lookups by all four waves, the Viterbi walk by lane
@@ -782,6 +790,7 @@ constexpr int UG_THREADS = 256;
 constexpr int UG_TOKENS = 64;
 constexpr int UG_PCAP = 4096;
 
+#ifndef ZETT_RETOK_DEVICE_FUNCTIONS_ONLY
 __global__ __launch_bounds__(UG_THREADS) void retok_unigram_kernel(RetokTables t, const uint8_t* __restrict__ raw,
                                                                    const int32_t* __restrict__ raw_off, int64_t n_tokens,
                                                                    int maxlen, int32_t pad_id, int32_t* __restrict__ out, int32_t* __restrict__ scratch,
@@ -921,6 +930,7 @@ __global__ __launch_bounds__(UG_THREADS) void retok_unigram_kernel(RetokTables t
         tb = te;
     }
 }
+#endif  // ZETT_RETOK_DEVICE_FUNCTIONS_ONLY
 
 }  // namespace zett
 
@@ -1013,6 +1023,7 @@ inline int upload(zett_retok* r, const std::vector<U>& v, const U** dev) {
 
 }  // namespace zett
 
+#ifndef ZETT_RETOK_DEVICE_FUNCTIONS_ONLY
 extern "C" {
 
 int zett_retok_create(const zett_retok_model* m, int device, zett_retok** out) {
@@ -1284,3 +1295,4 @@ int zett_retokenize(zett_retok* r, const uint8_t* token_chars, const int32_t* of
 }
 
 }  // extern "C"
+#endif  // ZETT_RETOK_DEVICE_FUNCTIONS_ONLY

@@ -1,0 +1,527 @@
+// text_encode.hip — a batch of texts to padded input_ids on the device (include/zett_hip.h, "text encoding"; the tokenizer call of the
+// reference's Collator.encode, zett/collator.py:166-178).
+//
+// Positions.  Text t occupies bytes [off[t], off[t + 1]) of `text`; on the device every text gets one SLOT in front of it, so byte i of
+// text t sits at position p = i + t + 1 of a space of nP = n_text + B positions and the slot of text t at off[t] + t.  The slot holds
+// the prefix space (U+0020) when the prefix mode gives text t one, and is a dead word otherwise: either way it is a word boundary, so
+// no word ever crosses from one text into the next, and a word's bytes (prefix included) are one contiguous range of `raw`.
+//
+//   classify   a thread per byte / slot: the byte into `raw`, and for a character start its class (the 4-bit class table) and what the
+//              contractions and ` ?` need to know about it (apostrophe, U+0020, s t m d r v l e) into one code byte; flags zeroed
+//   walk       a lane per text: the leftmost-first matches of the split pattern as a state machine over the code bytes; a flag at
+//              every match start (ZETT_ENCODE_RESPLIT: every match is matched again, on its own, with the plain pattern).  Sequential by
+//              definition: where a match starts depends on where the previous one ended
+//   count / scan / place   the flags into the word list woff[] — the multi-workgroup scan of train_batch.hip: a wave owns 1024
+//              positions, one workgroup scans the segment counts
+//   words      a lane per word: retok.hip.h's stage 2 (BPE merge / Unigram Viterbi) on the word's raw bytes, state in LDS or — a wave
+//              with more than 4 KiB of text, a lane beyond the arena — in the global scratch.  A word of b bytes gives at most 2b ids
+//              (a byte is at least one symbol, byte fallback makes at most two ids of it), so word w writes at ids[2 * woff[w]]: no
+//              second pass, no compaction, and the count per word is all the pack needs
+//   pack       a wave per text: scan of the word counts, the row staged in LDS (prefix, ids up to the cut, suffix, pads), the id map,
+//              then the row and its mask written with 16-byte stores where the output allows
+//
+// Integers only; the only atomic is the OR into the status word.  Every index derived from text_offsets is clamped before it is used.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdint>
+
+#include "../../include/zett_hip.h"
+#define ZETT_RETOK_DEVICE_FUNCTIONS_ONLY
+#include "retok.hip.h"
+
+using namespace zett;
+
+namespace {
+
+constexpr int kSeg = 1024;                  // positions of one wave's segment: 16 per lane
+constexpr int kMaxGrid = 1 << 16;
+constexpr int kMaxBlock = 8192;             // block_size: the row is staged in LDS
+constexpr int kMaxTemplate = ZETT_ENCODE_MAX_TEMPLATE;
+constexpr int kMaxMap = ZETT_SPLICE_MAX_ROWS;
+constexpr int64_t kMaxPositions = 1 << 30;
+constexpr int kScrPerByte = SCR_PER_BYTE + SCR_FIXED;      // a word starts at or behind its index: one factor covers both terms of the retokenizer's bound
+
+// code byte of a position: class in bits 0-2, what the pattern asks about the character itself in bits 3-7
+enum : int { C_O = 0, C_L = 1, C_M = 2, C_N = 3, C_S = 4, C_SKIP = 7 };
+enum : int { A_NONE = 0, A_SPACE, A_APOS, A_s, A_t, A_m, A_d, A_r, A_v, A_l, A_e };
+
+struct Lists {
+    int32_t n_prefix, n_suffix, n_map, pad_id;
+    int32_t prefix[kMaxTemplate], suffix[kMaxTemplate];
+    int32_t map_from[kMaxMap], map_to[kMaxMap];
+};
+static_assert(sizeof(Lists) < 4096 - 512, "the lists must fit the kernel-argument limit");
+
+// workspace, in bytes (every array starts on a 16-byte boundary)
+struct Layout {
+    int64_t codes, flags, raw, woff, counts, segcnt, segoff, totals, ids, scratch, bytes;
+    int64_t np, nseg;
+};
+Layout layout(int64_t n_text, int64_t b) {
+    Layout L{};
+    L.np = n_text + b;
+    L.nseg = (L.np + kSeg - 1) / kSeg;
+    int64_t w = 0;
+    auto take = [&](int64_t bytes) { const int64_t at = w; w += (bytes + 15) & ~(int64_t)15; return at; };
+    L.codes = take(L.np + 16);
+    L.flags = take(L.np + 16);
+    L.raw = take(L.np + 32);                        // 16 bytes of slack for the staging loads of the last wave
+    L.woff = take((L.np + 1) * 4);
+    L.counts = take(L.np * 4);
+    L.segcnt = take(L.nseg * 4);
+    L.segoff = take(L.nseg * 4);
+    L.totals = take(16);
+    L.ids = take(L.np * 8);                         // 2 ids per position
+    L.scratch = take((L.np * kScrPerByte + 64) * 4);
+    L.bytes = w;
+    return L;
+}
+
+__device__ __forceinline__ int wave_index() { return __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); }
+__device__ __forceinline__ int64_t clamp_off(int64_t o, int64_t n_text) { return o < 0 ? 0 : (o > n_text ? n_text : o); }
+
+__global__ __launch_bounds__(256) void encode_classify_kernel(const uint8_t* __restrict__ text, const int64_t* __restrict__ off, int64_t b, int64_t n_text,
+                                                              const uint8_t* __restrict__ table, int64_t n_cp, int prefix_mode, uint8_t* __restrict__ codes,
+                                                              uint8_t* __restrict__ flags, uint8_t* __restrict__ raw, int* __restrict__ status) {
+    const int64_t item = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (item >= n_text + b) return;
+    if (item >= n_text) {                                             // the slot of text t
+        const int64_t t = item - n_text;
+        const int64_t lo = clamp_off(off[t], n_text), hi = clamp_off(off[t + 1], n_text);
+        if (off[t] < 0 || off[t] > n_text || off[t + 1] < off[t] || (t == 0 && off[0] != 0) || (t == b - 1 && off[b] != n_text)) atomicOr(status, ZETT_ENCODE_BAD_OFFSETS);
+        const bool prefixed = hi > lo && (prefix_mode == ZETT_ENCODE_PREFIX_ALWAYS || (prefix_mode == ZETT_ENCODE_PREFIX_UNLESS_SPACE && text[lo] != 0x20));
+        const int64_t p = lo + t;
+        raw[p] = 0x20;
+        codes[p] = prefixed ? (uint8_t)(C_S | (A_SPACE << 3)) : (uint8_t)C_SKIP;
+        flags[p] = prefixed ? 0 : 2;                                   // 2: a dead word (the walk marks the live slot itself)
+        return;
+    }
+    int64_t lo = 0, hi = b - 1;                                       // the last text whose offset is <= item
+    while (lo < hi) {
+        const int64_t mid = (lo + hi + 1) >> 1;
+        if (off[mid] <= item) lo = mid; else hi = mid - 1;
+    }
+    const int64_t p = item + lo + 1;
+    const int c = text[item];
+    raw[p] = (uint8_t)c;
+    flags[p] = 0;
+    if ((c & 0xC0) == 0x80) { codes[p] = C_SKIP; return; }          // continuation byte
+    int need = c < 0x80 ? 0 : (c >= 0xF0 ? 3 : (c >= 0xE0 ? 2 : 1));
+    int64_t cp = c < 0x80 ? c : (c >= 0xF0 ? (c & 0x07) : (c >= 0xE0 ? (c & 0x0F) : (c & 0x1F)));
+    for (int k = 1; k <= need; ++k) {
+        const int nb = item + k < n_text ? text[item + k] : 0;
+        if ((nb & 0xC0) != 0x80) { cp = -1; break; }                  // not UTF-8: class O
+        cp = (cp << 6) | (nb & 0x3F);
+    }
+    int cls = C_O;
+    if (cp >= 0 && cp < n_cp) cls = (table[cp >> 1] >> ((cp & 1) * 4)) & 7;
+    if (cls > C_S) cls = C_O;
+    int a = A_NONE;
+    switch (c) {
+        case ' ': a = A_SPACE; break;
+        case '\'': a = A_APOS; break;
+        case 's': a = A_s; break;
+        case 't': a = A_t; break;
+        case 'm': a = A_m; break;
+        case 'd': a = A_d; break;
+        case 'r': a = A_r; break;
+        case 'v': a = A_v; break;
+        case 'l': a = A_l; break;
+        case 'e': a = A_e; break;
+        default: break;
+    }
+    codes[p] = (uint8_t)(cls | (a << 3));
+}
+
+// the next character start behind position i (hi: none)
+__device__ __forceinline__ int64_t next_char(const uint8_t* __restrict__ codes, int64_t i, int64_t hi) {
+    ++i;
+    while (i < hi && (codes[i] & 7) == C_SKIP) ++i;
+    return i;
+}
+
+// The end of the match that starts at i < hi (always > i).  The alternatives of the pattern in their order: a contraction; ` ?` and a
+// run of letters (marks too if `marks`), of digits, or of anything that is not whitespace, letter or digit (marks always); whitespace
+// not followed by non-whitespace (a run gives up its last character to the next match unless it ends the text); whitespace.
+__device__ inline int64_t match_end(const uint8_t* __restrict__ codes, int64_t i, int64_t hi, int marks) {
+    const int c = codes[i];
+    if ((c >> 3) == A_APOS) {
+        const int64_t j = next_char(codes, i, hi);
+        if (j < hi) {
+            const int a1 = codes[j] >> 3;
+            if (a1 == A_s || a1 == A_t || a1 == A_m || a1 == A_d) return next_char(codes, j, hi);
+            if (a1 == A_r || a1 == A_v || a1 == A_l) {
+                const int64_t k = next_char(codes, j, hi);
+                if (k < hi) {
+                    const int a2 = codes[k] >> 3;
+                    if (a2 == (a1 == A_l ? A_l : A_e)) return next_char(codes, k, hi);
+                }
+            }
+        }
+    }
+    int64_t s = i;                                                   // where the run starts: behind an optional U+0020
+    int cls = c & 7;
+    if ((c >> 3) == A_SPACE) {
+        const int64_t j = next_char(codes, i, hi);
+        if (j < hi && (codes[j] & 7) != C_S) { s = j; cls = codes[j] & 7; }
+    }
+    if (cls == C_S) {
+        int64_t last = s, j = next_char(codes, s, hi);
+        while (j < hi && (codes[j] & 7) == C_S) { last = j; j = next_char(codes, j, hi); }
+        if (j >= hi || last == s) return j;                            // the run ends the text, or is one character
+        return last;
+    }
+    const int run = (cls == C_L || (cls == C_M && marks)) ? 0 : (cls == C_N ? 1 : 2);
+    int64_t j = next_char(codes, s, hi);
+    while (j < hi) {
+        const int k = codes[j] & 7;
+        const bool in = run == 0 ? (k == C_L || (k == C_M && marks)) : (run == 1 ? k == C_N : (k == C_O || k == C_M));
+        if (!in) break;
+        j = next_char(codes, j, hi);
+    }
+    return j;
+}
+
+__global__ __launch_bounds__(64) void encode_walk_kernel(const int64_t* __restrict__ off, int64_t b, int64_t n_text, const uint8_t* __restrict__ codes,
+                                                         uint8_t* __restrict__ flags, int marks, int resplit) {
+    const int64_t t = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    if (t >= b) return;
+    const int64_t lo = clamp_off(off[t], n_text), end = std::max(lo, clamp_off(off[t + 1], n_text));
+    int64_t i = lo + t;
+    const int64_t hi = end + t + 1;
+    if (codes[i] == C_SKIP) ++i;                                      // no prefix: the slot is a dead word
+    while (i < hi) {
+        const int64_t e = match_end(codes, i, hi, marks);
+        if (resplit) {                                                 // the word once more, on its own, with the plain pattern
+            for (int64_t j = i; j < e; j = match_end(codes, j, e, 0)) flags[j] = 1;
+        } else {
+            flags[i] = 1;
+        }
+        i = e;
+    }
+}
+
+// the flags of a lane's 16 positions of segment seg, as a bit mask
+__device__ __forceinline__ uint32_t lane_flags(const uint8_t* __restrict__ flags, int64_t np, int64_t seg, int lane) {
+    const int64_t base = seg * kSeg + lane * 16;
+    uint32_t bits = 0;
+    if (base + 16 <= np) {
+        const uint4 v = *(const uint4*)(flags + base);
+        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int j = 0; j < 16; ++j) bits |= (uint32_t)(((w[j >> 2] >> ((j & 3) * 8)) & 0xff) != 0) << j;
+    } else {
+#pragma unroll
+        for (int j = 0; j < 16; ++j) bits |= (uint32_t)(base + j < np && flags[base + j] != 0) << j;
+    }
+    return bits;
+}
+
+__global__ __launch_bounds__(256) void encode_count_kernel(const uint8_t* __restrict__ flags, int64_t np, int64_t nseg, int* __restrict__ segcnt) {
+    const int lane = threadIdx.x & 63;
+    for (int64_t seg = (int64_t)blockIdx.x * 4 + wave_index(); seg < nseg; seg += (int64_t)gridDim.x * 4) {
+        int a = __popc(lane_flags(flags, np, seg, lane));
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
+        if (lane == 0) segcnt[seg] = a;
+    }
+}
+
+// exclusive scan of the segment counts: one workgroup, 1024 segments (2^20 positions) per round, the carry in registers
+__global__ __launch_bounds__(1024) void encode_scan_kernel(const int* __restrict__ segcnt, int64_t nseg, int* __restrict__ segoff, int* __restrict__ totals,
+                                                           int* __restrict__ woff, int64_t np) {
+    __shared__ int s0[1024];
+    const int tid = threadIdx.x;
+    int carry = 0;
+    for (int64_t base = 0; base < nseg; base += 1024) {
+        const int64_t i = base + tid;
+        const int a = i < nseg ? segcnt[i] : 0;
+        s0[tid] = a;
+        __syncthreads();
+        for (int o = 1; o < 1024; o <<= 1) {
+            const int x = tid >= o ? s0[tid - o] : 0;
+            __syncthreads();
+            s0[tid] += x;
+            __syncthreads();
+        }
+        if (i < nseg) segoff[i] = carry + s0[tid] - a;
+        carry += s0[1023];
+        __syncthreads();
+    }
+    if (tid == 0) {
+        totals[0] = carry;                 // the number of words (dead slots included)
+        woff[carry] = (int)np;             // the end of the last word
+    }
+}
+
+__global__ __launch_bounds__(256) void encode_place_kernel(const uint8_t* __restrict__ flags, int64_t np, int64_t nseg, const int* __restrict__ segoff,
+                                                           int* __restrict__ woff) {
+    const int lane = threadIdx.x & 63;
+    for (int64_t seg = (int64_t)blockIdx.x * 4 + wave_index(); seg < nseg; seg += (int64_t)gridDim.x * 4) {
+        const uint32_t bits = lane_flags(flags, np, seg, lane);
+        const int n = __popc(bits);
+        int inc = n;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const int v = __shfl_up(inc, o, 64);
+            if (lane >= o) inc += v;
+        }
+        int at = segoff[seg] + inc - n;
+        const int64_t base = seg * kSeg + lane * 16;
+#pragma unroll
+        for (int j = 0; j < 16; ++j)
+            if ((bits >> j) & 1) woff[at++] = (int)(base + j);
+    }
+}
+
+// Stage 2 of the retokenizer, a lane per word (retok_tokens_kernel's shape): no special-token lookup, no byte table — the word's bytes
+// are the text's bytes.  ids of word w at ids[2 * woff[w] ...), its count in counts[w].
+__global__ __launch_bounds__(64) void encode_words_kernel(RetokTables t, const uint8_t* __restrict__ raw, const uint8_t* __restrict__ flags,
+                                                          const int32_t* __restrict__ woff, const int32_t* __restrict__ totals, int32_t* __restrict__ ids,
+                                                          int32_t* __restrict__ counts, int32_t* __restrict__ scratch, int* __restrict__ status) {
+    __shared__ RetokLds L;
+    __shared__ __attribute__((aligned(16))) uint8_t s_text[RT_TEXT_BYTES + 16];
+    __shared__ __attribute__((aligned(8))) int32_t s_arena[RT_ARENA_WORDS];
+    const int64_t n_words = totals[0];
+    const int64_t tok0 = (int64_t)blockIdx.x * 64;
+    if (tok0 >= n_words) return;                                       // (uniform) the grid is sized for a word per position
+    const int lane = threadIdx.x;
+    for (int i = lane; i < 256; i += 64) { L.single_id[i] = t.single_id[i]; L.bf_ids[i] = t.bf_ids[i]; }
+    const int64_t tok = tok0 + lane;
+    const bool live = tok < n_words;
+    const int o0 = live ? woff[tok] : 0;
+    const int len = live ? woff[tok + 1] - o0 : 0;
+    const int w_lo = woff[tok0];
+    const int w_hi = woff[tok0 + 64 < n_words ? tok0 + 64 : n_words];
+    const int mis = w_lo & 15;
+    const bool text_lds = (w_hi - w_lo) + mis <= RT_TEXT_BYTES;
+    if (text_lds)
+        for (int i = lane * 16; i < (w_hi - w_lo) + mis; i += 64 * 16) *(uint4*)(s_text + i) = *(const uint4*)(raw + (w_lo - mis) + i);
+    __syncthreads();
+    const lds_u8* sl = (const lds_u8*)s_text + mis + (o0 - w_lo);
+    const uint8_t* sg = raw + o0;
+    RowWriter w{ids + 2 * (int64_t)o0, 2 * len, 0};
+    bool todo = live && len > 0 && !(flags[o0] & 2);
+    if (todo && t.kind == ZETT_RETOK_BPE && t.ignore_merges) {
+        const int id = text_lds ? whole_token_id<LdsMem>(t.pieces, t.piece_mask, t.piece_blob, sl, len)
+                                : whole_token_id<GlobalMem>(t.pieces, t.piece_mask, t.piece_blob, sg, len);
+        if (id >= 0) { w.push(id); todo = false; }
+    }
+    int n_sym = 0, need = 0;
+    if (todo) {
+        if (t.kind == ZETT_RETOK_BPE) {
+            n_sym = text_lds ? bpe_symbols<false, LdsMem>(t, L, sl, len, (lds_i32*)nullptr) : bpe_symbols<false, GlobalMem>(t, L, sg, len, (int32_t*)nullptr);
+            need = bpe_state_words(n_sym);
+        } else {
+            need = unigram_state_words(len);
+        }
+        need = (need + 1) & ~1;                                        // regions start on 8-byte boundaries
+    }
+    int inc = need;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int v = __shfl_up(inc, o, 64);
+        if (lane >= o) inc += v;
+    }
+    const int a0 = inc - need;
+    if (todo) {
+        bool ok;
+        if (text_lds && a0 + need <= RT_ARENA_WORDS) {
+            ok = segment_token<LdsMem>(t, L, sl, len, n_sym, (lds_i32*)s_arena + a0, w, 0);
+        } else {
+            int32_t* scr = scratch + (int64_t)o0 * kScrPerByte;
+            ok = segment_token<GlobalMem>(t, L, sg, len, n_sym, scr, w, 0);
+        }
+        if (!ok) {                                                     // the library raises: an unknown piece and no unk id
+            atomicOr(status, ZETT_ENCODE_NO_UNK);
+            w.n = 0;
+        }
+    }
+    if (live) counts[tok] = w.n < 2 * len ? w.n : 2 * len;
+}
+
+// the first word that starts at or behind position p
+__device__ __forceinline__ int64_t first_word_at(const int32_t* __restrict__ woff, int64_t n_words, int64_t p) {
+    int64_t lo = 0, hi = n_words;
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (woff[mid] < p) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+__device__ __forceinline__ int32_t map_id(const Lists& ls, int32_t v) {
+    for (int m = 0; m < ls.n_map; ++m)                                 // in order, as the reference's loop of assignments
+        if (v == ls.map_from[m]) v = ls.map_to[m];
+    return v;
+}
+
+// A wave per text.  WIDE: int64 outputs.  VEC: 16-byte stores (the launcher checked the row length, the row stride and the pointers).
+template <bool WIDE, bool VEC>
+__global__ __launch_bounds__(64) void encode_pack_kernel(const int64_t* __restrict__ off, int64_t b, int64_t n_text, const int32_t* __restrict__ woff,
+                                                         const int32_t* __restrict__ totals, const int32_t* __restrict__ counts, const int32_t* __restrict__ ids,
+                                                         int block, const Lists ls, void* __restrict__ out_ids, void* __restrict__ out_mask, int64_t ld_out) {
+    extern __shared__ int32_t s_row[];
+    const int lane = threadIdx.x;
+    const int64_t n_words = totals[0];
+    const int cap = block - ls.n_prefix - ls.n_suffix;
+    for (int64_t t = blockIdx.x; t < b; t += gridDim.x) {
+        const int64_t p0 = clamp_off(off[t], n_text) + t;
+        const int64_t p1 = t + 1 < b ? clamp_off(off[t + 1], n_text) + t + 1 : n_text + b;
+        const int64_t w0 = first_word_at(woff, n_words, p0), w1 = first_word_at(woff, n_words, p1);
+        for (int j = lane; j < block; j += 64) s_row[j] = ls.pad_id;
+        __syncthreads();
+        int64_t base = 0;                                              // ids of the words before this round
+        for (int64_t wb = w0; wb < w1 && base < cap; wb += 64) {
+            const int64_t w = wb + lane;
+            int k = 0, at = 0;
+            if (w < w1) {
+                at = woff[w];
+                k = std::max(0, std::min(counts[w], 2 * (woff[w + 1] - at)));
+            }
+            int inc = k;
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) {
+                const int v = __shfl_up(inc, o, 64);
+                if (lane >= o) inc += v;
+            }
+            const int64_t e = base + inc - k;
+            const int32_t* src = ids + 2 * (int64_t)at;
+            for (int q = 0; q < k && e + q < cap; ++q) s_row[ls.n_prefix + e + q] = src[q];      // (a word may be cut in the middle)
+            base += __shfl(inc, 63, 64);
+        }
+        const int total = (int)std::min<int64_t>(base, cap);
+        __syncthreads();
+        if (lane == 0) {
+            for (int i = 0; i < ls.n_prefix; ++i) s_row[i] = ls.prefix[i];
+            for (int i = 0; i < ls.n_suffix; ++i) s_row[ls.n_prefix + total + i] = ls.suffix[i];
+        }
+        __syncthreads();
+        const int n_real = ls.n_prefix + total + ls.n_suffix;
+        if (VEC) {
+            constexpr int per = WIDE ? 2 : 4;
+            uint4* oi = (uint4*)((char*)out_ids + t * ld_out * (WIDE ? 8 : 4));
+            uint4* om = (uint4*)((char*)out_mask + t * ld_out * (WIDE ? 8 : 4));
+            for (int u = lane; u < block / per; u += 64) {
+                int32_t v[per], m[per];
+#pragma unroll
+                for (int k = 0; k < per; ++k) { v[k] = map_id(ls, s_row[u * per + k]); m[k] = u * per + k < n_real; }
+                if (WIDE) {
+                    oi[u] = make_uint4((uint32_t)v[0], (uint32_t)(v[0] >> 31), (uint32_t)v[per - 1], (uint32_t)(v[per - 1] >> 31));
+                    om[u] = make_uint4((uint32_t)m[0], 0u, (uint32_t)m[per - 1], 0u);
+                } else {
+                    oi[u] = make_uint4((uint32_t)v[0], (uint32_t)v[1 % per], (uint32_t)v[2 % per], (uint32_t)v[3 % per]);
+                    om[u] = make_uint4((uint32_t)m[0], (uint32_t)m[1 % per], (uint32_t)m[2 % per], (uint32_t)m[3 % per]);
+                }
+            }
+        } else {
+            for (int j = lane; j < block; j += 64) {
+                const int32_t v = map_id(ls, s_row[j]);
+                if (WIDE) {
+                    ((int64_t*)out_ids)[t * ld_out + j] = v;
+                    ((int64_t*)out_mask)[t * ld_out + j] = j < n_real;
+                } else {
+                    ((int32_t*)out_ids)[t * ld_out + j] = v;
+                    ((int32_t*)out_mask)[t * ld_out + j] = j < n_real;
+                }
+            }
+        }
+        __syncthreads();
+    }
+}
+
+bool aligned(const void* p, size_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
+int grid_for(int64_t workgroups) { return (int)std::max<int64_t>(1, std::min<int64_t>(workgroups, kMaxGrid)); }
+
+int shape_args(int64_t n_text, int64_t n_texts) {
+    if (n_text < 0 || n_texts < 0) return fail(ZETT_E_INVALID, "text encoding needs n_text >= 0 bytes and n_texts >= 0 texts (n_text = %lld, n_texts = %lld)", (long long)n_text, (long long)n_texts);
+    if (n_text + n_texts >= kMaxPositions) return fail(ZETT_E_INVALID, "n_text + n_texts = %lld: a call takes fewer than 2^30 positions", (long long)(n_text + n_texts));
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int zett_encode_workspace_bytes(int64_t n_text, int64_t n_texts, int64_t* bytes) {
+    if (int rc = shape_args(n_text, n_texts)) return rc;
+    if (!bytes) return fail(ZETT_E_INVALID, "null argument");
+    *bytes = layout(n_text, n_texts).bytes;
+    return 0;
+}
+
+int zett_encode_texts(zett_retok* r, const uint8_t* text, const int64_t* text_offsets, int64_t n_texts, int64_t n_text, const uint8_t* class_table,
+                      int64_t n_code_points, int32_t flags, int32_t prefix_mode, int32_t block_size, const int32_t* prefix_ids, int32_t n_prefix,
+                      const int32_t* suffix_ids, int32_t n_suffix, const int32_t* map_from, const int32_t* map_to, int32_t n_map, int32_t pad_id, void* input_ids,
+                      void* attention_mask, int32_t out_bytes, int64_t ld_out, void* workspace, int64_t workspace_bytes, int32_t* status, void* stream) {
+    if (!r) return fail(ZETT_E_INVALID, "null argument");
+    if (r->t.kind != ZETT_RETOK_BPE && r->t.kind != ZETT_RETOK_UNIGRAM)
+        return fail(ZETT_E_NOT_IMPLEMENTED, "text encoding segments with a BPE or a Unigram model (WordPiece targets need another pre-tokenizer)");
+    if (int rc = shape_args(n_text, n_texts)) return rc;
+    if (flags & ~(ZETT_ENCODE_MARKS_ARE_LETTERS | ZETT_ENCODE_RESPLIT)) return fail(ZETT_E_INVALID, "unknown flags 0x%x", (unsigned)flags);
+    if (prefix_mode != ZETT_ENCODE_PREFIX_NONE && prefix_mode != ZETT_ENCODE_PREFIX_ALWAYS && prefix_mode != ZETT_ENCODE_PREFIX_UNLESS_SPACE)
+        return fail(ZETT_E_INVALID, "unknown prefix mode %d", (int)prefix_mode);
+    if (block_size < 1 || block_size > kMaxBlock) return fail(ZETT_E_INVALID, "block_size = %d must be in [1, %d]", (int)block_size, kMaxBlock);
+    if (n_prefix < 0 || n_prefix > kMaxTemplate || n_suffix < 0 || n_suffix > kMaxTemplate)
+        return fail(ZETT_E_INVALID, "%d prefix and %d suffix ids: at most %d each travel with a launch", (int)n_prefix, (int)n_suffix, kMaxTemplate);
+    if (block_size <= n_prefix + n_suffix)
+        return fail(ZETT_E_INVALID, "block_size = %d leaves no room for the text behind %d template ids", (int)block_size, (int)(n_prefix + n_suffix));
+    if (n_map < 0 || n_map > kMaxMap) return fail(ZETT_E_INVALID, "%d id pairs are listed, at most %d travel with a launch", (int)n_map, kMaxMap);
+    if ((n_prefix && !prefix_ids) || (n_suffix && !suffix_ids) || (n_map && (!map_from || !map_to))) return fail(ZETT_E_INVALID, "null argument");
+    if (out_bytes != 4 && out_bytes != 8) return fail(ZETT_E_INVALID, "input_ids and attention_mask must be int32 or int64");
+    if (ld_out < block_size) return fail(ZETT_E_INVALID, "ld_out = %lld must be at least block_size = %d", (long long)ld_out, (int)block_size);
+    if (!status || !class_table || n_code_points <= 0 || n_code_points > 0x110000) return fail(ZETT_E_INVALID, "null status or class table, or a table of more than 0x110000 code points");
+    if (n_texts && (!text_offsets || !input_ids || !attention_mask || (n_text && !text))) return fail(ZETT_E_INVALID, "null argument");
+    if (n_texts && (!aligned(input_ids, out_bytes) || !aligned(attention_mask, out_bytes))) return fail(ZETT_E_INVALID, "misaligned output");
+    Lists ls{};
+    ls.n_prefix = n_prefix; ls.n_suffix = n_suffix; ls.n_map = n_map; ls.pad_id = pad_id;
+    for (int i = 0; i < n_prefix; ++i) ls.prefix[i] = prefix_ids[i];
+    for (int i = 0; i < n_suffix; ++i) ls.suffix[i] = suffix_ids[i];
+    for (int i = 0; i < n_map; ++i) { ls.map_from[i] = map_from[i]; ls.map_to[i] = map_to[i]; }
+    const Layout L = layout(n_text, n_texts);
+    if (n_texts) {
+        if (!workspace || !aligned(workspace, 16)) return fail(ZETT_E_INVALID, "null or misaligned workspace (16 bytes)");
+        if (workspace_bytes < L.bytes) return fail(ZETT_E_INVALID, "the workspace holds %lld bytes, %lld are needed", (long long)workspace_bytes, (long long)L.bytes);
+    }
+    ZETT_ON_DEVICE(r->device);
+    hipStream_t st = (hipStream_t)stream;
+    HIP_TRY(hipMemsetAsync(status, 0, 4, st));
+    if (n_texts == 0) return 0;
+
+    char* w = (char*)workspace;
+    uint8_t* codes = (uint8_t*)(w + L.codes);
+    uint8_t* wflags = (uint8_t*)(w + L.flags);
+    uint8_t* raw = (uint8_t*)(w + L.raw);
+    int* woff = (int*)(w + L.woff);
+    int* counts = (int*)(w + L.counts);
+    int* segcnt = (int*)(w + L.segcnt);
+    int* segoff = (int*)(w + L.segoff);
+    int* totals = (int*)(w + L.totals);
+    int* ids = (int*)(w + L.ids);
+    int* scratch = (int*)(w + L.scratch);
+    const int marks = (flags & ZETT_ENCODE_MARKS_ARE_LETTERS) != 0;
+    hipLaunchKernelGGL(encode_classify_kernel, dim3((unsigned)((L.np + 255) / 256)), dim3(256), 0, st, text, text_offsets, n_texts, n_text, class_table, n_code_points,
+                       (int)prefix_mode, codes, wflags, raw, status);
+    hipLaunchKernelGGL(encode_walk_kernel, dim3((unsigned)((n_texts + 63) / 64)), dim3(64), 0, st, text_offsets, n_texts, n_text, (const uint8_t*)codes, wflags, marks,
+                       (int)((flags & ZETT_ENCODE_RESPLIT) != 0));
+    const int seg_grid = grid_for((L.nseg + 3) / 4);
+    hipLaunchKernelGGL(encode_count_kernel, dim3(seg_grid), dim3(256), 0, st, (const uint8_t*)wflags, L.np, L.nseg, segcnt);
+    hipLaunchKernelGGL(encode_scan_kernel, dim3(1), dim3(1024), 0, st, (const int*)segcnt, L.nseg, segoff, totals, woff, L.np);
+    hipLaunchKernelGGL(encode_place_kernel, dim3(seg_grid), dim3(256), 0, st, (const uint8_t*)wflags, L.np, L.nseg, (const int*)segoff, woff);
+    hipLaunchKernelGGL(encode_words_kernel, dim3((unsigned)((L.np + 63) / 64)), dim3(64), 0, st, r->t, (const uint8_t*)raw, (const uint8_t*)wflags, (const int32_t*)woff,
+                       (const int32_t*)totals, ids, counts, scratch, status);
+    const int per = out_bytes == 8 ? 2 : 4;
+    const bool vec = block_size % per == 0 && ld_out % per == 0 && aligned(input_ids, 16) && aligned(attention_mask, 16);
+    const size_t lds = (size_t)block_size * 4;
+#define ZETT_PACK(WIDE, VEC)                                                                                                                                       \
+    hipLaunchKernelGGL((encode_pack_kernel<WIDE, VEC>), dim3(grid_for(n_texts)), dim3(64), lds, st, text_offsets, n_texts, n_text, (const int32_t*)woff,          \
+                       (const int32_t*)totals, (const int32_t*)counts, (const int32_t*)ids, (int)block_size, ls, input_ids, attention_mask, ld_out)
+    if (out_bytes == 8) { if (vec) ZETT_PACK(true, true); else ZETT_PACK(true, false); }
+    else { if (vec) ZETT_PACK(false, true); else ZETT_PACK(false, false); }
+#undef ZETT_PACK
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+}  // extern "C"

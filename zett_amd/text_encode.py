@@ -1,0 +1,347 @@
+"""A batch of texts to padded ``input_ids`` on the device — the tokenizer call of the reference's ``Collator.encode``
+(zett/collator.py:166-178) without the ``tokenizers`` library on the step's path.
+
+    enc = DeviceTextEncoder.from_tokenizer(tokenizer)                 # once per tokenizer: tables to the device
+    batch = enc(texts, block_size=128, special_ids_map={3: 1})        # {"input_ids", "attention_mask"}: [B, block_size] device tensors
+
+What the kernels do (csrc/text_encode.hip): the optional prefix space, the split of every text into words with
+the GPT-2 style pattern (zett/utils.py:29) as a state machine over five character classes, the retokenizer's stage 2 (BPE merge / Unigram
+Viterbi) on every word's raw bytes, and the packing into rows: template ids, truncation from the right, padding, attention mask, the
+``special_ids_map`` substitution.  Per call the host joins and encodes the texts once, takes their byte lengths and looks for the
+strings of added tokens; nothing is done per word.
+
+The character classes are DATA and come from the installed ``tokenizers``: its regex engine knows a newer Unicode than Python's
+``unicodedata`` (code points unassigned in one are letters in the other), so the table is built by probing the library's own
+pre-tokenizers, once per process (``class_table()``).
+
+Everything the kernels do not reproduce is refused here, on the host, with NotImplementedError / ValueError: another normalizer,
+pre-tokenizer, post-processor, padding or truncation side; WordPiece models; ``block_size <= n_prefix + n_suffix``; a text that holds the
+string of an added or special token (the library would split it out).  There is no CPU path.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import json
+from dataclasses import dataclass
+from typing import Dict, List, Mapping, Optional, Sequence, Tuple
+
+import numpy as np
+
+from . import _lib
+
+# the split pattern of the sampled tokenizers (zett/utils.py:29) and, without \p{M} in the letter class, of pre_tokenizers.ByteLevel(use_regex=True)
+SPLIT_PATTERN_MARKS = r"'s|'t|'re|'ve|'m|'ll|'d| ?[\p{L}\p{M}]+| ?\p{N}+| ?[^\s\p{L}\p{N}]+|\s+(?!\S)|\s+"
+SPLIT_PATTERN_PLAIN = r"'s|'t|'re|'ve|'m|'ll|'d| ?\p{L}+| ?\p{N}+| ?[^\s\p{L}\p{N}]+|\s+(?!\S)|\s+"
+
+CLASS_O, CLASS_L, CLASS_M, CLASS_N, CLASS_S = 0, 1, 2, 3, 4
+N_CODE_POINTS = 0x110000
+PREFIX_NONE, PREFIX_ALWAYS, PREFIX_UNLESS_SPACE = _lib.ENCODE_PREFIX_NONE, _lib.ENCODE_PREFIX_ALWAYS, _lib.ENCODE_PREFIX_UNLESS_SPACE
+ENCODE_NO_UNK, ENCODE_BAD_OFFSETS = _lib.ENCODE_NO_UNK, _lib.ENCODE_BAD_OFFSETS
+MAX_BLOCK_SIZE = 8192
+_CHUNK = 256          # probes per call of a pre-tokenizer: its cost grows faster than the text
+
+
+# ---- the class table ----------------------------------------------------------------------------------------------------------
+def _pre_tokenizers():
+    import tokenizers
+    from tokenizers import pre_tokenizers
+    marks = pre_tokenizers.Split(tokenizers.Regex(SPLIT_PATTERN_MARKS), "removed", invert=True)
+    plain = pre_tokenizers.ByteLevel(add_prefix_space=False, use_regex=True)
+    return marks, plain
+
+
+def _joined(pre, first: str, code_points: np.ndarray) -> np.ndarray:
+    """For every code point c: does the pre-tokenizer keep ``first + chr(c)`` in one word?  One call for the whole array: the probes
+    stand on lines of their own (a line feed is whitespace to the pattern and joins nothing)."""
+    text = "".join(first + chr(c) + "\n" for c in code_points.tolist())
+    starts = np.fromiter((s for _, (s, e) in pre.pre_tokenize_str(text) if e - s == 2), dtype=np.int64)
+    hit = np.zeros(len(code_points), dtype=bool)
+    starts = starts[starts % 3 == 0]
+    hit[starts // 3] = True
+    return hit
+
+
+def classify_code_points(code_points: Sequence[int]) -> np.ndarray:
+    """The class (CLASS_*) of each code point, from four probes of the library's pre-tokenizers: behind a letter under both patterns,
+    behind a digit, behind a full stop.  The four character sets of the pattern — whitespace, letters, digits, everything else —
+    partition the code space, and marks are what joins a letter only when the pattern says so.  Surrogates cannot stand in a str:
+    class O."""
+    cps = np.asarray(code_points, dtype=np.int64)
+    out = np.zeros(len(cps), dtype=np.uint8)
+    ok = (cps < 0xD800) | (cps > 0xDFFF)
+    marks, plain = _pre_tokenizers()
+    for a in range(0, len(cps), _CHUNK):
+        idx = np.flatnonzero(ok[a:a + _CHUNK]) + a
+        if not len(idx):
+            continue
+        c = cps[idx]
+        letter = _joined(plain, "a", c)
+        mark = _joined(marks, "a", c) & ~letter
+        digit = _joined(plain, "1", c)
+        other = _joined(plain, ".", c)
+        cls = np.full(len(c), CLASS_S, dtype=np.uint8)
+        cls[other] = CLASS_O
+        cls[digit] = CLASS_N
+        cls[mark] = CLASS_M
+        cls[letter] = CLASS_L
+        out[idx] = cls
+    return out
+
+
+_CLASS_TABLE: Optional[np.ndarray] = None
+
+
+def class_table() -> np.ndarray:
+    """uint8 [0x110000]: the class of every code point as the installed ``tokenizers`` sees it, built once per process (a few
+    seconds).  One sweep of the whole code space with the library's regex engine (the engine of both pre-tokenizers) finds the
+    code points that are whitespace, letter, mark or digit to it; ``classify_code_points`` — the pre-tokenizers themselves —
+    classifies those, and a seeded sample of the others, which must come out as class O."""
+    global _CLASS_TABLE
+    if _CLASS_TABLE is not None:
+        return _CLASS_TABLE
+    import tokenizers
+    from tokenizers import pre_tokenizers
+    cps = np.concatenate([np.arange(0, 0xD800), np.arange(0xE000, N_CODE_POINTS)])
+    sweep = pre_tokenizers.Split(tokenizers.Regex(r"[\s\p{L}\p{M}\p{N}]+"), "removed", invert=True)
+    found = np.zeros(N_CODE_POINTS, dtype=bool)
+    for _, (lo, hi) in sweep.pre_tokenize_str("".join(map(chr, cps.tolist()))):
+        found[cps[lo:hi]] = True
+    found[:0x80] = True
+    rest = cps[~found[cps]]
+    todo = np.concatenate([np.flatnonzero(found), np.random.default_rng(0).choice(rest, size=1024, replace=False)])
+    table = np.zeros(N_CODE_POINTS, dtype=np.uint8)
+    table[todo] = classify_code_points(todo)
+    if table[todo[-1024:]].any():
+        raise RuntimeError("the pre-tokenizers give a class to a code point the regex engine's classes do not hold")
+    table.setflags(write=False)
+    _CLASS_TABLE = table
+    return table
+
+
+def pack_class_table(table: np.ndarray) -> np.ndarray:
+    """4 bits per code point, code point c in bits 4 * (c & 1) .. of byte c >> 1: what zett_encode_texts takes."""
+    t = np.asarray(table, dtype=np.uint8)
+    if len(t) % 2:
+        t = np.concatenate([t, np.zeros(1, dtype=np.uint8)])
+    return (t[0::2] | (t[1::2] << 4)).astype(np.uint8)
+
+
+# ---- what the kernels need to know about a tokenizer -------------------------------------------------------------------------------
+@dataclass
+class EncodeSpec:
+    """Normalizer, pre-tokenizer, post-processor and padding of a tokenizer, as the arguments of zett_encode_texts."""
+    prefix_mode: int
+    marks_are_letters: bool
+    resplit: bool                             # every word is split again with the plain pattern (the Sequence's ByteLevel has use_regex)
+    prefix_ids: Tuple[int, ...]
+    suffix_ids: Tuple[int, ...]
+    pad_id: int
+    special_strings: Tuple[str, ...]          # contents of the added tokens: a text that holds one is refused
+
+    @staticmethod
+    def _template(post: Optional[dict]) -> Tuple[Tuple[int, ...], Tuple[int, ...]]:
+        if post is None or post.get("type") == "ByteLevel":
+            return (), ()
+        if post.get("type") == "RobertaProcessing":
+            return (int(post["cls"][1]),), (int(post["sep"][1]),)
+        if post.get("type") == "TemplateProcessing":
+            prefix: List[int] = []
+            suffix: List[int] = []
+            seen = False
+            for item in post["single"]:
+                if "Sequence" in item:
+                    if seen or item["Sequence"]["id"] != "A":
+                        raise NotImplementedError("a TemplateProcessing whose single template is not specials, $A, specials")
+                    seen = True
+                elif "SpecialToken" in item:
+                    ids = post["special_tokens"][item["SpecialToken"]["id"]]["ids"]
+                    (suffix if seen else prefix).extend(int(i) for i in ids)
+                else:
+                    raise NotImplementedError(f"template item {item!r}")
+            if not seen:
+                raise NotImplementedError("a TemplateProcessing without $A")
+            return tuple(prefix), tuple(suffix)
+        raise NotImplementedError(f"post-processor {post.get('type')!r} (TemplateProcessing, RobertaProcessing, ByteLevel or none)")
+
+    @classmethod
+    def from_tokenizer_json(cls, data: Mapping, pad_id: Optional[int], padding_side: str = "right", truncation_side: str = "right") -> "EncodeSpec":
+        if padding_side != "right" or truncation_side != "right":
+            raise NotImplementedError(f"padding_side = {padding_side!r}, truncation_side = {truncation_side!r}: rows are cut and padded on the right")
+        for key in ("padding", "truncation"):          # what an earlier call left switched on in the backend
+            if (data.get(key) or {}).get("direction", "Right") != "Right":
+                raise NotImplementedError(f"{key} direction {data[key]['direction']!r}: rows are cut and padded on the right")
+        if pad_id is None:
+            raise ValueError("the tokenizer has no pad token: padding=\"max_length\" needs one")
+        model = data.get("model") or {}
+        kind = model.get("type") or ("BPE" if "merges" in model else None)
+        if kind not in ("BPE", "Unigram"):
+            raise NotImplementedError(f"text encoding with a {kind!r} model (BPE and Unigram; WordPiece targets need another pre-tokenizer)")
+        norm, pre = data.get("normalizer"), data.get("pre_tokenizer")
+        prefix_mode = PREFIX_NONE
+        if norm is not None:
+            if norm.get("type") != "Prepend" or norm.get("prepend") != " ":
+                raise NotImplementedError(f"normalizer {norm!r} (none or Prepend(\" \"))")
+            prefix_mode = PREFIX_ALWAYS
+        if pre is None:
+            raise NotImplementedError("a tokenizer without a pre-tokenizer")
+        if pre.get("type") == "ByteLevel":
+            if not pre.get("use_regex", True):
+                raise NotImplementedError("ByteLevel(use_regex=False) alone: the text is not split into words")
+            marks, resplit = False, False
+            if pre.get("add_prefix_space"):
+                if norm is not None:
+                    raise NotImplementedError("Prepend(\" \") together with ByteLevel(add_prefix_space=True)")
+                prefix_mode = PREFIX_UNLESS_SPACE
+        elif pre.get("type") == "Sequence":
+            steps = pre.get("pretokenizers") or []
+            ok = (len(steps) == 2 and steps[0].get("type") == "Split" and steps[0].get("pattern") == {"Regex": SPLIT_PATTERN_MARKS}
+                  and steps[0].get("behavior") == "Removed" and steps[0].get("invert") is True and steps[1].get("type") == "ByteLevel"
+                  and not steps[1].get("add_prefix_space"))
+            if not ok:
+                raise NotImplementedError(f"pre-tokenizer {pre!r} (Split(the split pattern, removed, invert) then ByteLevel(add_prefix_space=False), or ByteLevel(use_regex=True))")
+            marks, resplit = True, bool(steps[1].get("use_regex", True))
+        else:
+            raise NotImplementedError(f"pre-tokenizer {pre.get('type')!r}")
+        prefix, suffix = cls._template(data.get("post_processor"))
+        if len(prefix) > _lib.ENCODE_MAX_TEMPLATE or len(suffix) > _lib.ENCODE_MAX_TEMPLATE:
+            raise NotImplementedError(f"more than {_lib.ENCODE_MAX_TEMPLATE} template ids on one side")
+        strings = tuple(a["content"] for a in data.get("added_tokens") or [] if a.get("content"))
+        return cls(prefix_mode, marks, resplit, prefix, suffix, int(pad_id), strings)
+
+    @classmethod
+    def from_tokenizer(cls, tokenizer) -> "EncodeSpec":
+        """From a transformers fast tokenizer (what ``Collator.sample_tokenizer`` returns, zett/collator.py:414-431)."""
+        data = json.loads(tokenizer._tokenizer.to_str())
+        strings = {a["content"] for a in data.get("added_tokens") or []} | set(getattr(tokenizer, "all_special_tokens", ()))
+        spec = cls.from_tokenizer_json(data, tokenizer.pad_token_id, getattr(tokenizer, "padding_side", "right"), getattr(tokenizer, "truncation_side", "right"))
+        spec.special_strings = tuple(sorted(s for s in strings if s))
+        return spec
+
+    @property
+    def flags(self) -> int:
+        return (_lib.ENCODE_MARKS_ARE_LETTERS if self.marks_are_letters else 0) | (_lib.ENCODE_RESPLIT if self.resplit else 0)
+
+    def check_call(self, texts: Sequence[str], block_size: int, special_ids_map) -> Tuple[str, List[Tuple[int, int]]]:
+        """The host's part of a call: the joined text and the id pairs; raises for what the kernels would answer differently."""
+        t = int(block_size)
+        if t <= len(self.prefix_ids) + len(self.suffix_ids):
+            raise ValueError(f"block_size = {t} leaves no room for the text behind {len(self.prefix_ids) + len(self.suffix_ids)} template ids")
+        if t > MAX_BLOCK_SIZE:
+            raise ValueError(f"block_size = {t} is more than {MAX_BLOCK_SIZE}")
+        pairs = [(int(k), int(v)) for k, v in (special_ids_map or {}).items()]
+        if len(pairs) > _lib.SPLICE_MAX_ROWS:
+            raise ValueError(f"special_ids_map holds {len(pairs)} pairs, at most {_lib.SPLICE_MAX_ROWS} travel with a launch")
+        if any(not -2 ** 31 <= x < 2 ** 31 for p in pairs for x in p):
+            raise ValueError("special_ids_map holds an id outside int32")
+        joined = "".join(texts)
+        for s in self.special_strings:          # one str.find per special; the texts themselves only where the joined text has a hit
+            if joined.find(s) >= 0 and any(s in x for x in texts):
+                raise NotImplementedError(f"a text holds the added token {s!r}: the library would split it out")
+        return joined, pairs
+
+
+class DeviceTextEncoder:
+    """``tokenizer(texts, max_length=block_size, truncation=True, padding="max_length", add_special_tokens=True)`` on one GPU."""
+
+    def __init__(self, model_spec, encode_spec: EncodeSpec, device=None, table: Optional[np.ndarray] = None):
+        import torch
+
+        from .surface_forms import DeviceRetokenizer
+        if device is None:
+            if not torch.cuda.is_available():
+                raise RuntimeError("zett_amd computes on MI355X only: no cuda (ROCm) device is visible; there is no CPU path")
+            device = torch.device("cuda", torch.cuda.current_device())
+        self.device = torch.device(device)
+        if model_spec.kind not in (_lib.RETOK_BPE, _lib.RETOK_UNIGRAM):
+            raise NotImplementedError("text encoding with a WordPiece model")
+        self.spec = encode_spec
+        self.retok = DeviceRetokenizer(model_spec, self.device)
+        self.lib = self.retok.lib
+        self.table = class_table() if table is None else np.asarray(table, dtype=np.uint8)          # (cached on the encoder)
+        self._d_table = torch.from_numpy(pack_class_table(self.table)).to(self.device)
+        k = _lib.ENCODE_MAX_TEMPLATE
+        self._prefix = (C.c_int32 * k)(*encode_spec.prefix_ids)
+        self._suffix = (C.c_int32 * k)(*encode_spec.suffix_ids)
+
+    @classmethod
+    def from_tokenizer(cls, tokenizer, device=None) -> "DeviceTextEncoder":
+        from .surface_forms import HnTokenizerSpec
+        encode_spec = EncodeSpec.from_tokenizer(tokenizer)          # (refusals first: no device work for a tokenizer that is not carried)
+        return cls(HnTokenizerSpec.from_tokenizer(tokenizer), encode_spec, device)
+
+    @classmethod
+    def from_tokenizer_json(cls, data: Mapping, pad_token_id: int, special_tokens: Sequence[str] = (), special_ids: Sequence[int] = (), padding_side: str = "right",
+                            truncation_side: str = "right", device=None) -> "DeviceTextEncoder":
+        """From a ``tokenizer.json`` dict and what transformers adds to it: the pad id, ``all_special_tokens`` / ``all_special_ids``, the sides."""
+        from .surface_forms import HnTokenizerSpec
+        encode_spec = EncodeSpec.from_tokenizer_json(data, pad_token_id, padding_side, truncation_side)
+        encode_spec.special_strings = tuple(sorted(set(encode_spec.special_strings) | {s for s in special_tokens if s}))
+        return cls(HnTokenizerSpec.from_model_json(data["model"], list(special_tokens), list(special_ids), pad_token_id), encode_spec, device)
+
+    def workspace_bytes(self, n_text: int, n_texts: int) -> int:
+        out = C.c_int64(0)
+        _lib.check(self.lib.zett_encode_workspace_bytes(int(n_text), int(n_texts), C.byref(out)), "zett_encode_workspace_bytes")
+        return out.value
+
+    def __call__(self, texts: Sequence[str], block_size: int, special_ids_map: Optional[Dict[int, int]] = None, dtype=None, check: bool = True, out=None):
+        """{"input_ids", "attention_mask"}: ``[len(texts), block_size]`` device tensors of ``dtype`` (int64, or int32).  ``out``: a pair
+        of preallocated tensors of that shape (any row stride).  check=True reads the status word once and raises what the library
+        raises (an unknown piece and no unk id: Exception); check=False never waits for the host."""
+        import torch
+        dtype = torch.int64 if dtype is None else dtype
+        if dtype not in (torch.int32, torch.int64):
+            raise ValueError("dtype must be torch.int32 or torch.int64")
+        texts = list(texts)
+        joined, pairs = self.spec.check_call(texts, block_size, special_ids_map)
+        b, t = len(texts), int(block_size)
+        blob = joined.encode("utf-8")
+        chars = np.zeros(b + 1, dtype=np.int64)          # character offsets of the texts; byte offsets from the character starts of the blob
+        np.cumsum(np.fromiter(map(len, texts), dtype=np.int64, count=b), out=chars[1:])
+        if len(blob) == len(joined):
+            offsets = chars
+        else:
+            raw = np.frombuffer(blob, dtype=np.uint8)
+            offsets = np.append(np.flatnonzero((raw & 0xC0) != 0x80), len(raw))[chars]
+        assert offsets[-1] == len(blob)
+        with torch.cuda.device(self.device):
+            if out is None:
+                ids = torch.empty((b, t), dtype=dtype, device=self.device)
+                mask = torch.empty((b, t), dtype=dtype, device=self.device)
+            else:
+                ids, mask = out
+                for x in (ids, mask):
+                    if x.dtype != dtype or tuple(x.shape) != (b, t) or x.device != self.device or (b and x.stride(1) != 1) or (b > 1 and x.stride(0) != ids.stride(0)):
+                        raise ValueError(f"out must be two [{b}, {t}] tensors of {dtype} on {self.device} with unit column stride and one row stride")
+            status = torch.empty(1, dtype=torch.int32, device=self.device)
+            d_text = self.retok._to_device(np.frombuffer(blob or b"\0", dtype=np.uint8))
+            d_off = self.retok._to_device(offsets)
+            work = torch.empty(max(self.workspace_bytes(len(blob), b), 16), dtype=torch.uint8, device=self.device)          # (released on return: the allocator reuses it in stream order)
+            n_map = len(pairs)
+            m_from = (C.c_int32 * max(n_map, 1))(*[p[0] for p in pairs])
+            m_to = (C.c_int32 * max(n_map, 1))(*[p[1] for p in pairs])
+            ld = ids.stride(0) if b > 1 else t
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            rc = self.lib.zett_encode_texts(self.retok.handle, C.c_void_p(d_text.data_ptr()), C.c_void_p(d_off.data_ptr()), b, len(blob),
+                                            C.c_void_p(self._d_table.data_ptr()), len(self.table), self.spec.flags, self.spec.prefix_mode, t,
+                                            self._prefix, len(self.spec.prefix_ids), self._suffix, len(self.spec.suffix_ids), m_from, m_to, n_map, self.spec.pad_id,
+                                            C.c_void_p(ids.data_ptr() if b else 0), C.c_void_p(mask.data_ptr() if b else 0), ids.element_size(), ld,
+                                            C.c_void_p(work.data_ptr()), work.numel(), C.c_void_p(status.data_ptr()), C.c_void_p(stream))
+            _lib.check(rc, "zett_encode_texts")
+        if check:
+            bits = int(status.item())          # (the one host read of this call)
+            if bits & ENCODE_BAD_OFFSETS:
+                raise ValueError("encode_texts: the text offsets are not non-decreasing from 0 to the text length")
+            if bits & ENCODE_NO_UNK:
+                raise Exception("Encountered an unknown token but `unk_id` is missing")          # tokenizers raises a bare Exception here
+        self.last_status = status          # device int32 [1]: what a caller with check=False may look at later
+        return {"input_ids": ids, "attention_mask": mask}
+
+    def close(self) -> None:
+        self.retok.close()
+
+
+def encode_texts(tokenizer_or_encoder, texts: Sequence[str], block_size: int, special_ids_map: Optional[Dict[int, int]] = None, dtype=None, check: bool = True,
+                 device=None):
+    """``DeviceTextEncoder.from_tokenizer(tokenizer)(texts, block_size, ...)``; pass the encoder itself to keep its tables."""
+    enc = tokenizer_or_encoder if isinstance(tokenizer_or_encoder, DeviceTextEncoder) else DeviceTextEncoder.from_tokenizer(tokenizer_or_encoder, device)
+    return enc(texts, block_size, special_ids_map, dtype=dtype, check=check)

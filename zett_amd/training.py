@@ -848,6 +848,10 @@ def subsample_batch_vocabulary(input_ids, labels, special_ids, n_token_subsample
     return BatchVocabulary(out_ids, out_lab, ids_to_embed, out_sf, out_priors, mask, special_indices, words[0], words[1])
 
 
+# ---- from texts to the batch's ids (collator.py:166-178): zett_amd/text_encode.py, re-exported beside subsample_batch_vocabulary ---------
+from .text_encode import DeviceTextEncoder, encode_texts  # noqa: E402,F401
+
+
 # ---- which parameters train, and which decay -------------------------------------------------------------------------------
 LABELS = ("decay", "no_decay", "frozen")
 
