@@ -764,6 +764,49 @@ int zett_encode_texts(zett_retok* r, const uint8_t* text, const int64_t* text_of
                       const int32_t* suffix_ids, int32_t n_suffix, const int32_t* map_from, const int32_t* map_to, int32_t n_map, int32_t pad_id, void* input_ids,
                       void* attention_mask, int32_t out_bytes, int64_t ld_out, void* workspace, int64_t workspace_bytes, int32_t* status, void* stream);
 
+/* ---- tokenizer sampling (zett_amd/tokenizer_sampling.py DeviceTokenizerSampler; additive, ABI 8) -----------------------------------
+ * What rust_utils.TokenizerSampler.sample_tokenizer computes for a batch of texts (rust_utils/src/lib.rs:70-249; restated in
+ * tests/sampler_ref.py, the definition this code is tested against), on the device (csrc/tokenizer_sample.hip).
+ * A sampler owns the queue of the earlier batches' substring tables and all scratch that depends on its capacities:
+ *   max_depth       batches the queue may hold            list_capacity   distinct substrings kept of one batch
+ *   table_capacity  slots of the open-addressing table (this call's substrings, then the queue's merged)
+ *   max_pieces      the most pieces of the table one call may ask for (seed_size - 256 - 9 * (max_length - 1))
+ * zett_sampler_sample: text / text_offsets / class_table as zett_encode_texts takes them; the texts must be distinct (the reference
+ * takes them as dictionary keys).  Every text gets a U+0020 in front, the words are the matches of the split pattern without \p{M}.
+ * A key is a run of 1 .. max_length - 1 (max_length <= 16) raw bytes of a word from every stride-th entry of the reference's start
+ * list; its score grows by the UTF-8 length of its byte-level string.  Then, in the reference's order: with pop_prev the oldest batch
+ * leaves the queue; this batch enters at the front; with pop_prev the queue's tables are summed and the outputs written; with
+ * push_current == 0 this batch leaves again and the popped one returns.  Outputs (device; written with pop_prev only, else *n_out = 0):
+ *   pieces [out_capacity, 16] key bytes, zero padded; piece_lengths [out_capacity] (a separate array: the whitespace runs reach 16
+ *   bytes); scores [out_capacity] float64; *n_out.  First the 256 single bytes in byte order at log(min / sum), then for c1 in
+ *   (0x20, 0x0A, 0x09), i in 1 .. max_length - 1, c2 in the same three: c2 c1^i at 0.0, then the max(1, seed_size - those) best keys of
+ *   two or more bytes with fewer than two of the three whitespace bytes, by p = v / sum + noise_std * z(seed, key) descending, shorter
+ *   key first, smaller bytes first; log(p), or -100000.0 for p <= 0 (those keys tie on p).  p is float64 with every operation rounded
+ *   on its own; z is standard normal and a function of seed and key bytes alone.
+ * *status (device): an OR of zett_sample_status bits; with a bit set the outputs are unspecified but every write stays in bounds.
+ * Asynchronous on `stream` (one stream per sampler), no allocation after zett_sampler_create; `workspace` (16-byte aligned,
+ * zett_sampler_workspace_bytes) is free once the call's work is done, and so is the text.  No loop waits for another lane and every
+ * probe loop ends after table_capacity slots.  zett_sampler_table reads out the merged table of the last call with pop_prev, in no
+ * particular order: keys [capacity, 16], key_lengths, counts, z (of that call's seed) and *n (which may exceed capacity: the rest is
+ * dropped); ZETT_E_STATE after a call without pop_prev.  A full queue (pop_prev == 0, push_current != 0 at max_depth): ZETT_E_STATE. */
+typedef struct zett_sampler zett_sampler;
+enum zett_sample_status {
+    ZETT_SAMPLE_BAD_OFFSETS = 2,    /* text_offsets is not non-decreasing from 0 to n_text (the bit of ZETT_ENCODE_BAD_OFFSETS) */
+    ZETT_SAMPLE_TABLE_FULL = 4,     /* a key found no slot within table_capacity probes: it is not counted */
+    ZETT_SAMPLE_LIST_FULL = 8,      /* the batch has more than list_capacity distinct keys: the rest is dropped */
+    ZETT_SAMPLE_SUM_OVERFLOW = 16,  /* the sum of the merged scores reached 2^32, where the reference's u32 wraps (it is held in 64 bits here) */
+    ZETT_SAMPLE_OUT_FULL = 32       /* more pieces than out_capacity: the rest is dropped */
+};
+int zett_sampler_create(int device, int32_t max_depth, int64_t list_capacity, int64_t table_capacity, int64_t max_pieces, zett_sampler** out);
+int zett_sampler_destroy(zett_sampler* s);
+int zett_sampler_depth(const zett_sampler* s, int32_t* depth);
+int zett_sampler_workspace_bytes(int64_t n_text, int64_t n_texts, int64_t* bytes);
+int zett_sampler_sample(zett_sampler* s, const uint8_t* text, const int64_t* text_offsets, int64_t n_texts, int64_t n_text, const uint8_t* class_table,
+                        int64_t n_code_points, int64_t seed_size, int32_t max_length, int32_t stride, double noise_std, uint64_t seed, int32_t pop_prev,
+                        int32_t push_current, uint8_t* pieces, uint8_t* piece_lengths, double* scores, int64_t out_capacity, int32_t* n_out, void* workspace,
+                        int64_t workspace_bytes, int32_t* status, void* stream);
+int zett_sampler_table(zett_sampler* s, uint8_t* keys, uint8_t* key_lengths, uint32_t* counts, double* z, int64_t capacity, int32_t* n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

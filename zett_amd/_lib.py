@@ -33,6 +33,7 @@ ENCODE_MAX_TEMPLATE = 8                              # ZETT_ENCODE_MAX_TEMPLATE
 ENCODE_MARKS_ARE_LETTERS, ENCODE_RESPLIT = 1, 2      # zett_encode_flags
 ENCODE_PREFIX_NONE, ENCODE_PREFIX_ALWAYS, ENCODE_PREFIX_UNLESS_SPACE = 0, 1, 2      # zett_encode_prefix
 ENCODE_NO_UNK, ENCODE_BAD_OFFSETS = 1, 2             # zett_encode_status
+SAMPLE_BAD_OFFSETS, SAMPLE_TABLE_FULL, SAMPLE_LIST_FULL, SAMPLE_SUM_OVERFLOW, SAMPLE_OUT_FULL = 2, 4, 8, 16, 32      # zett_sample_status
 
 ABI_SYMBOLS = (
     "zett_last_error", "zett_abi_version", "zett_create", "zett_destroy", "zett_load_weight",
@@ -58,6 +59,8 @@ ABI_SYMBOLS = (
     "zett_op_batch_vocab_workspace_bytes", "zett_op_batch_vocab",
     # text encoding (zett_amd/text_encode.py DeviceTextEncoder)
     "zett_encode_workspace_bytes", "zett_encode_texts",
+    # tokenizer sampling (zett_amd/tokenizer_sampling.py DeviceTokenizerSampler)
+    "zett_sampler_create", "zett_sampler_destroy", "zett_sampler_depth", "zett_sampler_workspace_bytes", "zett_sampler_sample", "zett_sampler_table",
 )
 
 
@@ -210,6 +213,12 @@ def load():
         lib.zett_op_batch_vocab.argtypes = [P, I32, P, I32, I64, I64, I64, P, I32, I64, I32, P, P, I32, I32, P, P, P, I32, P, P, P, P, P, P, P, P, P, I64, P]
         lib.zett_encode_workspace_bytes.argtypes = [I64, I64, C.POINTER(I64)]
         lib.zett_encode_texts.argtypes = [P, P, P, I64, I64, P, I64, I32, I32, I32, P, I32, P, I32, P, P, I32, I32, P, P, I32, I64, P, I64, P, P]
+        lib.zett_sampler_create.argtypes = [C.c_int, I32, I64, I64, I64, C.POINTER(P)]
+        lib.zett_sampler_destroy.argtypes = [P]
+        lib.zett_sampler_depth.argtypes = [P, C.POINTER(I32)]
+        lib.zett_sampler_workspace_bytes.argtypes = [I64, I64, C.POINTER(I64)]
+        lib.zett_sampler_sample.argtypes = [P, P, P, I64, I64, P, I64, I64, I32, I32, C.c_double, C.c_uint64, I32, I32, P, P, P, I64, P, P, I64, P, P]
+        lib.zett_sampler_table.argtypes = [P, P, P, P, P, I64, P, P]
         for name in ABI_SYMBOLS:
             fn = getattr(lib, name)
             if name != "zett_last_error":

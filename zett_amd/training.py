@@ -850,6 +850,8 @@ def subsample_batch_vocabulary(input_ids, labels, special_ids, n_token_subsample
 
 # ---- from texts to the batch's ids (collator.py:166-178): zett_amd/text_encode.py, re-exported beside subsample_batch_vocabulary ---------
 from .text_encode import DeviceTextEncoder, encode_texts  # noqa: E402,F401
+# ---- a step's tokenizer sampled from the batch (collator.py:341-452): zett_amd/tokenizer_sampling.py ---------------------------------------
+from .tokenizer_sampling import DeviceTokenizerSampler, sample_tokenizer  # noqa: E402,F401
 
 
 # ---- which parameters train, and which decay -------------------------------------------------------------------------------
