@@ -807,6 +807,68 @@ int zett_sampler_sample(zett_sampler* s, const uint8_t* text, const int64_t* tex
                         int64_t workspace_bytes, int32_t* status, void* stream);
 int zett_sampler_table(zett_sampler* s, uint8_t* keys, uint8_t* key_lengths, uint32_t* counts, double* z, int64_t capacity, int32_t* n, void* stream);
 
+/* ---- sampled vocabulary (zett_amd/sampled_vocab.py DeviceSampledVocabulary; additive, ABI 8) ----------------------------------------
+ * From the sampler's piece list, as zett_sampler_sample leaves it on the device, to the step's vocabulary and the tables zett_encode_texts
+ * segments with: what zett/collator.py:371-400 does with Python lists and DeviceTextEncoder.from_tokenizer with a host Tokenizer
+ * (csrc/sampled_vocab.hip; zett_amd/sampled_vocab.py holds the definition the kernels are tested against).
+ * zett_retok_create_unigram_device makes a retokenizer handle whose piece table, bitmap, blob and single-byte ids are allocated for
+ * max_vocab entries and empty: a Unigram model without unk id, byte fallback, merges or special table.  zett_retok_destroy frees it.
+ * zett_sampled_vocab_build fills it.  pieces / piece_lengths / scores / n: the outputs of zett_sampler_sample (pieces 16-byte aligned,
+ * rows [0, min(*n, piece_capacity, seed_size)) are read; seed_size is the caller's upper bound of *n, seed_size + n_special <=
+ * max_vocab).  The reference tokenizer's special tokens, n_special <= ZETT_SPLICE_MAX_ROWS of them SORTED BY ID, are DEVICE arrays:
+ * special_ids (distinct, >= 0), special_raw_offsets [n_special + 1] into special_raw (the raw bytes of the byte-level strings; an
+ * empty range for a string that is not byte-level; at most max_special_raw <= ZETT_SAMPLED_VOCAB_KEY_BYTES bytes each and
+ * special_raw_bytes in all, both known to the host), special_char_lengths (characters of the string) and special_hn_ids (the id to put
+ * into the token's surface-form row, or -1).  With m the number of pieces that equal no special token's raw bytes, special k gets id
+ * min(special_ids[k], m + k) and the kept pieces fill the other ids of [0, m + n_special) in their order.  Outputs (device):
+ *   priors [vocab_capacity] the scores bit for bit, 0.0 for a special;  byte_lengths [vocab_capacity] int64: bytes of a piece,
+ *   characters of a special;  token_text [text_capacity] / text_offsets [vocab_capacity + 1]: the UTF-8 of every id's byte-level
+ *   string back to back, what zett_retokenize_async takes (a special with an hn id has an empty text);
+ *   record: 32 bytes, zett_sampled_vocab_record; status is an OR of zett_vocab_status bits, 0 when all is well.
+ * The table holds every id with raw bytes under its id and score.  With a status bit set the outputs are unspecified, but every write
+ * stays inside them.  Integers and bit copies, and for ZETT_VOCAB_SCORES_THROUGH_JSON one conversion and one correctly rounded division per score: the same inputs give the same bits.  Asynchronous on `stream` (one stream per
+ * handle), no allocation; `workspace` (16-byte aligned, zett_sampled_vocab_workspace_bytes) is free once the call's work is done.
+ * zett_sampled_vocab_commit takes the record as the caller read it back (HOST memory) and sets what the kernels take by value: the
+ * masks, the longest piece and the unknown score table_min_score - 10.  Between build and commit zett_encode_texts and zett_retokenize*
+ * return ZETT_E_STATE; a record whose n_vocab is beyond the build's bound is ZETT_E_INVALID.
+ * zett_sampled_vocab_table reads out the occupied slots in no particular order: keys [capacity, ZETT_SAMPLED_VOCAB_KEY_BYTES] zero
+ * padded, key_lengths, ids, scores, *n (which may exceed capacity: the rest is dropped) and, unless null, single_id [256]: the id of
+ * every one-byte piece or -1.  zett_sampled_vocab_patch_rows writes
+ * surface_forms [n_rows, maxlen] row min(special_ids[k], record.n_vocab - n_special + k) = special_hn_ids[k], pad_id ... for every k
+ * with an hn id (zett/utils.py:671-673); record and the arrays are DEVICE memory. */
+#define ZETT_SAMPLED_VOCAB_KEY_BYTES 64
+enum zett_vocab_status {
+    ZETT_VOCAB_NOT_A_SAMPLE = 1,   /* *n < 256: the list does not hold the alphabet pieces (the reference would prepend the missing characters) */
+    ZETT_VOCAB_DUPLICATE = 2,      /* two ids have the same bytes: the second is not in the table */
+    ZETT_VOCAB_TABLE_FULL = 4,     /* an id found no slot within the capacity: it is not in the table */
+    ZETT_VOCAB_OUT_FULL = 8        /* *n beyond min(piece_capacity, seed_size), or more ids / text than vocab_capacity / text_capacity: the rest is dropped */
+};
+enum zett_vocab_flags {
+    ZETT_VOCAB_SCORES_THROUGH_JSON = 1   /* a slot's score is the sampler's as the tokenizers library reads it back from its own JSON: (double)digits / 10^places
+                                          * of the shortest decimal, one ulp off for about one score in nine.  The model of a tokenizer that transformers
+                                          * rebuilt from JSON holds these values; priors stay the sampler's bit for bit */
+};
+typedef struct zett_sampled_vocab_record {
+    int32_t n_vocab;      /* m + n_special */
+    int32_t n_removed;    /* pieces that were a special token's string */
+    int32_t n_text;       /* bytes of token_text */
+    int32_t status;
+    double min_score;     /* over all n_vocab scores, the specials' 0.0 included */
+    double table_min_score; /* over the scores as the table holds them (zett_vocab_flags): the unknown score is this - 10 */
+} zett_sampled_vocab_record;
+int zett_retok_create_unigram_device(int device, int64_t max_vocab, zett_retok** out);
+int zett_sampled_vocab_workspace_bytes(int64_t max_vocab, int32_t n_special, int64_t* bytes);
+int zett_sampled_vocab_build(zett_retok* r, const uint8_t* pieces, const uint8_t* piece_lengths, const double* scores, const int32_t* n, int64_t piece_capacity,
+                             int64_t seed_size, const int32_t* special_ids, const int32_t* special_raw_offsets, const uint8_t* special_raw,
+                             const int32_t* special_char_lengths, const int32_t* special_hn_ids, int32_t n_special, int32_t special_raw_bytes, int32_t max_special_raw,
+                             double* priors, int64_t* byte_lengths, int32_t* text_offsets, int64_t vocab_capacity, uint8_t* token_text, int64_t text_capacity,
+                             void* record, int32_t flags, void* workspace, int64_t workspace_bytes, void* stream);
+int zett_sampled_vocab_commit(zett_retok* r, const void* host_record);
+int zett_sampled_vocab_table(zett_retok* r, uint8_t* keys, int32_t* key_lengths, int32_t* ids, double* scores, int32_t* single_id, int64_t capacity, int32_t* n,
+                             void* stream);
+int zett_sampled_vocab_patch_rows(zett_retok* r, const void* record, const int32_t* special_ids, const int32_t* special_hn_ids, int32_t n_special,
+                                  int32_t* surface_forms, int64_t n_rows, int32_t maxlen, int32_t pad_id, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -34,6 +34,9 @@ ENCODE_MARKS_ARE_LETTERS, ENCODE_RESPLIT = 1, 2      # zett_encode_flags
 ENCODE_PREFIX_NONE, ENCODE_PREFIX_ALWAYS, ENCODE_PREFIX_UNLESS_SPACE = 0, 1, 2      # zett_encode_prefix
 ENCODE_NO_UNK, ENCODE_BAD_OFFSETS = 1, 2             # zett_encode_status
 SAMPLE_BAD_OFFSETS, SAMPLE_TABLE_FULL, SAMPLE_LIST_FULL, SAMPLE_SUM_OVERFLOW, SAMPLE_OUT_FULL = 2, 4, 8, 16, 32      # zett_sample_status
+VOCAB_NOT_A_SAMPLE, VOCAB_DUPLICATE, VOCAB_TABLE_FULL, VOCAB_OUT_FULL = 1, 2, 4, 8      # zett_vocab_status
+VOCAB_SCORES_THROUGH_JSON = 1                        # zett_vocab_flags
+SAMPLED_VOCAB_KEY_BYTES = 64                         # ZETT_SAMPLED_VOCAB_KEY_BYTES
 
 ABI_SYMBOLS = (
     "zett_last_error", "zett_abi_version", "zett_create", "zett_destroy", "zett_load_weight",
@@ -61,6 +64,9 @@ ABI_SYMBOLS = (
     "zett_encode_workspace_bytes", "zett_encode_texts",
     # tokenizer sampling (zett_amd/tokenizer_sampling.py DeviceTokenizerSampler)
     "zett_sampler_create", "zett_sampler_destroy", "zett_sampler_depth", "zett_sampler_workspace_bytes", "zett_sampler_sample", "zett_sampler_table",
+    # the sampled tokenizer's vocabulary and encoder tables (zett_amd/sampled_vocab.py DeviceSampledVocabulary)
+    "zett_retok_create_unigram_device", "zett_sampled_vocab_workspace_bytes", "zett_sampled_vocab_build", "zett_sampled_vocab_commit", "zett_sampled_vocab_table",
+    "zett_sampled_vocab_patch_rows",
 )
 
 
@@ -90,6 +96,11 @@ class ZettDest(C.Structure):
     """struct zett_dest (zett_forward_into / zett_forward_table_into): where the predicted rows go."""
     _fields_ = [("in_", C.c_void_p), ("out", C.c_void_p), ("bias", C.c_void_p), ("dtype", C.c_int32), ("bias_dtype", C.c_int32),
                 ("ld_in", C.c_int64), ("ld_out", C.c_int64), ("rows", C.c_void_p), ("n_dest_rows", C.c_int64)]
+
+
+class ZettSampledVocabRecord(C.Structure):
+    """struct zett_sampled_vocab_record: the 32 bytes zett_sampled_vocab_build leaves on the device."""
+    _fields_ = [("n_vocab", C.c_int32), ("n_removed", C.c_int32), ("n_text", C.c_int32), ("status", C.c_int32), ("min_score", C.c_double), ("table_min_score", C.c_double)]
 
 
 class ZettRetokModel(C.Structure):
@@ -219,6 +230,12 @@ def load():
         lib.zett_sampler_workspace_bytes.argtypes = [I64, I64, C.POINTER(I64)]
         lib.zett_sampler_sample.argtypes = [P, P, P, I64, I64, P, I64, I64, I32, I32, C.c_double, C.c_uint64, I32, I32, P, P, P, I64, P, P, I64, P, P]
         lib.zett_sampler_table.argtypes = [P, P, P, P, P, I64, P, P]
+        lib.zett_retok_create_unigram_device.argtypes = [C.c_int, I64, C.POINTER(P)]
+        lib.zett_sampled_vocab_workspace_bytes.argtypes = [I64, I32, C.POINTER(I64)]
+        lib.zett_sampled_vocab_build.argtypes = [P, P, P, P, P, I64, I64, P, P, P, P, P, I32, I32, I32, P, P, P, I64, P, I64, P, I32, P, I64, P]
+        lib.zett_sampled_vocab_commit.argtypes = [P, P]
+        lib.zett_sampled_vocab_table.argtypes = [P, P, P, P, P, P, I64, P, P]
+        lib.zett_sampled_vocab_patch_rows.argtypes = [P, P, P, P, I32, P, I64, I32, I32, P]
         for name in ABI_SYMBOLS:
             fn = getattr(lib, name)
             if name != "zett_last_error":

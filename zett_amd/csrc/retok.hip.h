@@ -949,6 +949,20 @@ struct zett_retok {
     std::vector<Call> recent;            // the calls since the last result query (for the token of a KeyError)
     bool words_ready = false;            // the device result words hold their initial values
     int unigram_wg = 1;                  // Unigram models: 1 = the workgroup-per-64-tokens kernel for calls of up to 32 768 tokens, 2 = always, 0 = never (the lane-per-token kernel)
+    // A handle of zett_retok_create_unigram_device (sampled_vocab.hip): its piece table is filled on the device, per step.
+    // state 0: not such a handle; 1: created, empty; 2: built, the record not committed yet; 3: committed — only then does it tokenize.
+    struct SampledVocab {
+        int state = 0;
+        int64_t max_vocab = 0;
+        zett::PieceEntry* slots = nullptr; uint32_t slot_capacity = 0;      // (the allocation: pow2_capacity(max_vocab) slots)
+        uint32_t* bits = nullptr;
+        uint8_t* blob = nullptr; int64_t blob_bytes = 0;
+        int32_t* single_id = nullptr;
+        uint32_t capacity = 0;           // slots of the last build: pow2_capacity(its bound)
+        int64_t bound = 0;               // the last build's upper bound of n_vocab
+        int max_piece_len = 0;
+    } sv;
+    bool tokenizes() const { return sv.state == 0 || sv.state == 3; }
 };
 
 namespace zett {
@@ -1143,6 +1157,7 @@ static int retok_enqueue_call(zett_retok* r, const uint8_t* token_chars, const i
                               int32_t maxlen, int32_t pad_id, int32_t* out, void* stream, zett::LexPlan lex) {
     using namespace zett;
     if (!r) return fail(ZETT_E_INVALID, "null argument");
+    if (!r->tokenizes()) return fail(ZETT_E_STATE, "the handle's tables are built on the device: zett_sampled_vocab_build and zett_sampled_vocab_commit come first");
     if (n_tokens < 0 || maxlen < 1 || n_text < 0 || n_text >= (int64_t)0x7fffffff) return fail(ZETT_E_INVALID, "bad shape");
     if (n_tokens == 0) return 0;
     if (!out) return fail(ZETT_E_INVALID, "null argument");

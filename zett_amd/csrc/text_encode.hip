@@ -252,6 +252,7 @@ int zett_encode_texts(zett_retok* r, const uint8_t* text, const int64_t* text_of
                       const int32_t* suffix_ids, int32_t n_suffix, const int32_t* map_from, const int32_t* map_to, int32_t n_map, int32_t pad_id, void* input_ids,
                       void* attention_mask, int32_t out_bytes, int64_t ld_out, void* workspace, int64_t workspace_bytes, int32_t* status, void* stream) {
     if (!r) return fail(ZETT_E_INVALID, "null argument");
+    if (!r->tokenizes()) return fail(ZETT_E_STATE, "the handle's tables are built on the device: zett_sampled_vocab_build and zett_sampled_vocab_commit come first");
     if (r->t.kind != ZETT_RETOK_BPE && r->t.kind != ZETT_RETOK_UNIGRAM)
         return fail(ZETT_E_NOT_IMPLEMENTED, "text encoding segments with a BPE or a Unigram model (WordPiece targets need another pre-tokenizer)");
     if (int rc = shape_args(n_text, n_texts)) return rc;

@@ -220,6 +220,24 @@ class DeviceRetokenizer:
         self._outstanding = []          # (text, offsets) tensors of the asynchronous calls since the last result()
         self._staging = {}              # element width -> pinned staging buffer + the event of its last transfer (_to_device)
 
+    @classmethod
+    def unigram_on_device(cls, device: torch.device, max_vocab: int) -> "DeviceRetokenizer":
+        """A handle of zett_retok_create_unigram_device: a Unigram model without unk id whose piece table is allocated for ``max_vocab``
+        pieces and empty — zett_sampled_vocab_build fills it on the device (zett_amd/sampled_vocab.py).  It has no ``spec``."""
+        if device.type != "cuda":
+            raise RuntimeError("zett_amd computes on MI355X only: pass a cuda (ROCm) device; there is no CPU path")
+        self = cls.__new__(cls)
+        self.lib = _lib.load()
+        self.spec = None
+        self.device = device
+        self._outstanding = []
+        self._staging = {}
+        handle = C.c_void_p()
+        index = device.index if device.index is not None else torch.cuda.current_device()
+        _lib.check(self.lib.zett_retok_create_unigram_device(index, int(max_vocab), C.byref(handle)), "zett_retok_create_unigram_device")
+        self.handle = handle
+        return self
+
     def set_option(self, key: str, value: int) -> None:
         """zett_retok_set_option: A/B switches of the handle ("unigram_workgroup": which Unigram kernel runs — 1 = by size, the
         default; 2 = the workgroup-per-64-tokens kernel; 0 = the lane-per-token kernel)."""

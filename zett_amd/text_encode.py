@@ -254,14 +254,29 @@ class DeviceTextEncoder:
         self.device = torch.device(device)
         if model_spec.kind not in (_lib.RETOK_BPE, _lib.RETOK_UNIGRAM):
             raise NotImplementedError("text encoding with a WordPiece model")
+        self._adopt(DeviceRetokenizer(model_spec, self.device), encode_spec, table, None, True)
+
+    def _adopt(self, retok, encode_spec: EncodeSpec, table, d_table, owns_handle: bool) -> None:
+        import torch
         self.spec = encode_spec
-        self.retok = DeviceRetokenizer(model_spec, self.device)
-        self.lib = self.retok.lib
+        self.retok = retok
+        self.lib = retok.lib
         self.table = class_table() if table is None else np.asarray(table, dtype=np.uint8)          # (cached on the encoder)
-        self._d_table = torch.from_numpy(pack_class_table(self.table)).to(self.device)
+        self._d_table = torch.from_numpy(pack_class_table(self.table)).to(self.device) if d_table is None else d_table
         k = _lib.ENCODE_MAX_TEMPLATE
         self._prefix = (C.c_int32 * k)(*encode_spec.prefix_ids)
         self._suffix = (C.c_int32 * k)(*encode_spec.suffix_ids)
+        self._owns_handle = owns_handle
+
+    @classmethod
+    def from_handle(cls, retok, encode_spec: EncodeSpec, table: Optional[np.ndarray] = None, d_table=None) -> "DeviceTextEncoder":
+        """On a retokenizer handle that is already there and stays its owner's — ``DeviceSampledVocabulary`` rebuilds the tables of one
+        handle every step (zett_amd/sampled_vocab.py).  ``retok``: a ``DeviceRetokenizer``; ``d_table``: the packed class table on its
+        device, if the caller keeps one.  ``close()`` leaves the handle alone."""
+        self = cls.__new__(cls)
+        self.device = retok.device
+        self._adopt(retok, encode_spec, table, d_table, False)
+        return self
 
     @classmethod
     def from_tokenizer(cls, tokenizer, device=None) -> "DeviceTextEncoder":
@@ -337,7 +352,8 @@ class DeviceTextEncoder:
         return {"input_ids": ids, "attention_mask": mask}
 
     def close(self) -> None:
-        self.retok.close()
+        if self._owns_handle:
+            self.retok.close()
 
 
 def encode_texts(tokenizer_or_encoder, texts: Sequence[str], block_size: int, special_ids_map: Optional[Dict[int, int]] = None, dtype=None, check: bool = True,

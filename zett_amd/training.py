@@ -852,6 +852,8 @@ def subsample_batch_vocabulary(input_ids, labels, special_ids, n_token_subsample
 from .text_encode import DeviceTextEncoder, encode_texts  # noqa: E402,F401
 # ---- a step's tokenizer sampled from the batch (collator.py:341-452): zett_amd/tokenizer_sampling.py ---------------------------------------
 from .tokenizer_sampling import DeviceTokenizerSampler, sample_tokenizer  # noqa: E402,F401
+# ---- that tokenizer's vocabulary and encoder tables without the host Tokenizer: zett_amd/sampled_vocab.py -------------------------------------
+from .sampled_vocab import DeviceSampledVocabulary, SampledVocabulary, sample_tokenizer_device  # noqa: E402,F401
 
 
 # ---- which parameters train, and which decay -------------------------------------------------------------------------------
