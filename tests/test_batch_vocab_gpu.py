@@ -91,6 +91,31 @@ def test_several_scan_segments_a_ragged_tail_and_a_special_beyond_n(mode):
         assert torch.equal(x, y) if isinstance(x, torch.Tensor) else x == y
 
 
+@pytest.mark.parametrize("v", (1023, 1024, 1025))
+@pytest.mark.parametrize("mode", MODES)
+def test_the_edges_of_one_scan_segment(mode, v):
+    """V one short of a segment of 1024 ids (a ragged tail alone), exactly one segment, and one id into a second segment; the last id is
+    special."""
+    a = _case(v, 200, 2, [0, v - 1])
+    _same(_call(a, 256, mode), _ref(a, 256, mode), what=(mode, v))
+
+
+@pytest.mark.parametrize("mode", MODES)
+def test_more_than_1024_scan_segments(mode):
+    """V = 2^20 + 1325 is 1026 segments: the workgroup that scans the segment counts takes a second round of two segments, whose offsets are
+    the first round's total (the carry) and what follows.  Positives in both of those segments — 2^20 + 7 put there by hand, V - 2 and V - 3
+    the recipe's label-only ids — and the special id V - 1 land in the right rows only if the carry is right."""
+    v, t, n = (1 << 20) + 1025 + 300, 3000, 4096
+    a = _case(v, t, 1, [0, 1, v - 1])
+    ids = a["input_ids"].copy()
+    ids[5] = (1 << 20) + 7
+    a = dict(a, input_ids=ids)
+    want = _ref(a, n, mode)
+    beyond = want["ids_to_embed"][:want["n_positive"]]
+    assert ((beyond >= 1 << 20) & (beyond < (1 << 20) + 1024)).any() and ((beyond >= (1 << 20) + 1024) & (beyond < v - 1)).any()
+    _same(_call(a, n, mode, torch.int32, torch.int32, order_dtype=torch.int32), want, torch.int32, torch.int32, what=mode)
+
+
 def test_no_negative_at_all():
     """N = n_positive exactly: K = 0."""
     a = _case(5000, 700, 4, [3, 0])

@@ -77,6 +77,23 @@ def test_long_word_and_many_words(name):
     _same(_encoder(name)(texts, 32, dtype=torch.int32), ids, mask, torch.int32, what=(name, 32))
 
 
+def test_more_than_1024_scan_segments():
+    """2^20 + 1500 texts, all empty but four: 1026 segments of 1024 positions, so the workgroup that scans the segment counts takes a
+    second round, whose offsets start from the first round's total (the carry).  Every empty text is one dead word whatever the carry;
+    the words of the two texts behind position 2^20 come out right only if it is.  The rows of the four distinct texts come from the
+    restatement and are placed with numpy.  The call's workspace is 188 MB (zett_encode_workspace_bytes(31, 2^20 + 1500) = 187 977 744)."""
+    fx = er.load_fixture(UNIGRAM)
+    b, t = (1 << 20) + 1500, 8
+    distinct = ["", "hello world", "it's 12", " x"]
+    which = np.zeros(b, dtype=np.int64)
+    which[[0, (1 << 20) - 1, (1 << 20) + 3, b - 1]] = [1, 2, 3, 1]
+    texts = [distinct[k] for k in which.tolist()]
+    assert sum(map(len, texts)) + b > (1 << 20) + 1024
+    ids, mask = er.encode_with(fx["spec"], fx["segment"], distinct, t)
+    assert len({tuple(r) for r in ids.tolist()}) == 4 and (mask.sum(1)[1:] > mask.sum(1)[0]).all()
+    _same(_encoder(UNIGRAM)(texts, t, dtype=torch.int32), ids[which], mask[which], torch.int32, "2^20 + 1500 texts")
+
+
 def test_no_texts_and_empty_texts():
     enc, fx = _encoder(UNIGRAM), er.load_fixture(UNIGRAM)
     got = enc([], 8)

@@ -1,9 +1,12 @@
-// common.hip.h — error reporting, device-buffer helpers and the dtype / precision dispatch shared by the C ABI sources.
+// common.hip.h — error reporting, device-buffer helpers, launch / workspace arithmetic and the dtype / precision dispatch shared by the
+// C ABI sources.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdarg>
+#include <cstdint>
 #include <cstdio>
 #include <string>
 #include <type_traits>
@@ -63,6 +66,17 @@ struct DevBuf {   // grow-only device allocation
     }
     void release() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
     template <typename U> U* as() const { return (U*)p; }
+};
+
+// ---- launch and workspace arithmetic of the entry points ---------------------------------------------------------------------
+inline bool aligned(const void* p, size_t bytes) { return ((uintptr_t)p & (bytes - 1)) == 0; }          // bytes: a power of two
+// a grid of `workgroups` workgroups, at least 1 and at most `most` (the kernel strides over what a capped grid leaves)
+inline int grid_for(int64_t workgroups, int64_t most) { return (int)std::max<int64_t>(1, std::min<int64_t>(workgroups, most)); }
+inline int grid256(int64_t items, int64_t most) { return grid_for((items + 255) / 256, most); }           // 256 items per workgroup
+// a workspace carved into arrays that each start on a 16-byte boundary: take(n) is the offset of the next n bytes
+struct Carve {
+    int64_t bytes = 0;
+    int64_t take(int64_t n) { const int64_t at = bytes; bytes += (n + 15) & ~(int64_t)15; return at; }
 };
 
 // ---- runtime type codes as compile-time types --------------------------------------------------------------------------------

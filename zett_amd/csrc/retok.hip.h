@@ -6,7 +6,7 @@
 //     (the GPT-2 printable-character alphabet, zett/utils.py:351-609).  A workgroup
 //     takes 4 KiB of text with coalesced 16-byte loads, marks character starts, looks
 //     every character up in the byte table staged in LDS, and compacts the bytes with a
-//     wavefront scan (DPP-free shuffles inside a wave, LDS across the 4 waves); block
+//     wavefront scan (scan.hip.h: shuffles inside a wave, LDS across the 4 waves); block
 //     totals are chained by one tiny scan launch.  A character outside the table is the
 //     reference's KeyError (zett/utils.py:675).
 //
@@ -36,6 +36,7 @@
 #include <vector>
 
 #include "common.hip.h"
+#include "scan.hip.h"
 // text_encode.hip shares the tables, the device functions and the handle of this header (it defines ZETT_RETOK_DEVICE_FUNCTIONS_ONLY): the kernels and
 // the entry points — and rowops.hip.h, which only they need — are compiled once, into zett_hip.hip
 #ifndef ZETT_RETOK_DEVICE_FUNCTIONS_ONLY
@@ -189,23 +190,6 @@ __device__ inline const MergeEntry* merge_find(const RetokTables& t, int32_t a, 
 constexpr int CH_PER_THREAD = 16;
 constexpr int CH_PER_BLOCK = 256 * CH_PER_THREAD;
 
-__device__ inline int block_excl_scan_256(int v, int* total, int* lds /* [4] */) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int inc = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int n = __shfl_up(inc, off, 64);
-        if (lane >= off) inc += n;
-    }
-    __syncthreads();
-    if (lane == 63) lds[wave] = inc;
-    __syncthreads();
-    int base = 0;
-    for (int w = 0; w < wave; ++w) base += lds[w];
-    *total = lds[0] + lds[1] + lds[2] + lds[3];
-    return base + inc - v;
-}
-
 // MODE 0: count character starts per block.  MODE 1: decode + compact.
 // SEP (r5): the text holds the tokens NUL-SEPARATED instead of coming with an offsets array (zett_retokenize_async with
 // offsets == nullptr: what one "\0".join(tokens).encode() on the host produces — no per-token work there at all).  A NUL is
@@ -250,9 +234,9 @@ __global__ __launch_bounds__(256) void chars_to_bytes_kernel(const uint8_t* __re
         if (SEP) nsep += in && b[i] == 0;
     }
     int total = 0, total_sep = 0;
-    const int excl = block_excl_scan_256(cnt, &total, s_red);
+    const int excl = block_exclusive_scan<256>(cnt, s_red, &total);
     int tok = 0;
-    if (SEP) tok = block_excl_scan_256(nsep, &total_sep, s_red2);
+    if (SEP) tok = block_exclusive_scan<256>(nsep, s_red2, &total_sep);
     if (MODE == 0) {
         if (threadIdx.x == 0) { blk_count[blockIdx.x] = total; if (SEP) sep_count[blockIdx.x] = total_sep; }
         return;
@@ -744,13 +728,7 @@ __global__ __launch_bounds__(64) void retok_tokens_kernel(RetokTables t, const u
         }
         need = (need + 1) & ~1;                                // regions start on 8-byte boundaries
     }
-    int inc = need;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int v = __shfl_up(inc, off, 64);
-        if (lane >= off) inc += v;
-    }
-    const int a0 = inc - need;
+    const int a0 = wave_inclusive_scan(need) - need;
     RETOK_STOP(3);
     if (todo) {
         bool ok;
@@ -836,14 +814,8 @@ __global__ __launch_bounds__(UG_THREADS) void retok_unigram_kernel(RetokTables t
     int slots = (todo && text_lds) ? len * W_mine : 0;
     int a0 = 0;
     if (wave0) {
-        int inc = need, inc_s = slots;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const int v = __shfl_up(inc, off, 64), vs = __shfl_up(inc_s, off, 64);
-            if (lane >= off) { inc += v; inc_s += vs; }
-        }
-        a0 = inc - need;
-        s_base[lane + 1] = inc_s;
+        a0 = wave_inclusive_scan(need) - need;
+        s_base[lane + 1] = wave_inclusive_scan(slots);
         if (lane == 0) s_base[0] = 0;
         s_len[lane] = todo ? len : 0;
         s_toff[lane] = mis + (o0 - w_lo);

@@ -16,6 +16,7 @@
 #include <type_traits>
 
 #include "gemm.hip.h"
+#include "scan.hip.h"
 
 namespace zett {
 
@@ -87,23 +88,16 @@ __global__ void plan_rows_kernel(const int32_t* __restrict__ sfm, int64_t n_rows
 // Single-workgroup exclusive scan (n <= a few million): out[i] = sum(in[0..i)), out[n] = total.
 __global__ __launch_bounds__(1024) void exclusive_scan_kernel(const int32_t* __restrict__ in,
                                                               int32_t* __restrict__ out, int64_t n) {
-    __shared__ int32_t part[1024];
+    __shared__ int32_t s_waves[16];
     const int t = threadIdx.x;
     const int64_t per = (n + 1023) / 1024;
     const int64_t b = (int64_t)t * per, e = (b + per < n) ? b + per : n;
     int32_t s = 0;
     for (int64_t i = b; i < e; ++i) s += in[i];
-    part[t] = s;
-    __syncthreads();
-    for (int off = 1; off < 1024; off <<= 1) {
-        int32_t v = (t >= off) ? part[t - off] : 0;
-        __syncthreads();
-        part[t] += v;
-        __syncthreads();
-    }
-    int32_t run = (t == 0) ? 0 : part[t - 1];
+    int32_t total;
+    int32_t run = block_exclusive_scan<1024>(s, s_waves, &total);
     for (int64_t i = b; i < e; ++i) { const int32_t v = in[i]; out[i] = run; run += v; }
-    if (t == 1023) out[n] = part[1023];
+    if (t == 1023) out[n] = total;
 }
 
 // Multi-block exclusive scan for the plan arrays (V can be 250 k source ids, N 262 k rows: the single
@@ -113,40 +107,26 @@ __global__ __launch_bounds__(1024) void exclusive_scan_kernel(const int32_t* __r
 //   (3) scan_apply_kernel: out[i] = offs[c] + exclusive scan inside the chunk; out[n] = total.
 constexpr int SCAN_CHUNK = 4096;          // 256 threads x 16 elements
 
-__device__ __forceinline__ int32_t block_exclusive_scan_256(int32_t v, int32_t* sh /* [256] */, int32_t* total) {
-    const int t = threadIdx.x;
-    sh[t] = v;
-    __syncthreads();
-    for (int off = 1; off < 256; off <<= 1) {
-        const int32_t add = (t >= off) ? sh[t - off] : 0;
-        __syncthreads();
-        sh[t] += add;
-        __syncthreads();
-    }
-    if (total) *total = sh[255];
-    return sh[t] - v;
-}
-
 __global__ __launch_bounds__(256) void scan_chunk_sums_kernel(const int32_t* __restrict__ in, int64_t n, int32_t* __restrict__ sums) {
-    __shared__ int32_t sh[256];
+    __shared__ int32_t s_waves[4];
     const int64_t base = (int64_t)blockIdx.x * SCAN_CHUNK + threadIdx.x * 16;
     int32_t s = 0;
 #pragma unroll
     for (int k = 0; k < 16; ++k) { const int64_t i = base + k; if (i < n) s += in[i]; }
     int32_t total;
-    block_exclusive_scan_256(s, sh, &total);
+    block_exclusive_scan<256>(s, s_waves, &total);
     if (threadIdx.x == 0) sums[blockIdx.x] = total;
 }
 
 __global__ __launch_bounds__(256) void scan_apply_kernel(const int32_t* __restrict__ in, int64_t n, const int32_t* __restrict__ offs,
                                                          int32_t* __restrict__ out) {
-    __shared__ int32_t sh[256];
+    __shared__ int32_t s_waves[4];
     const int64_t base = (int64_t)blockIdx.x * SCAN_CHUNK + threadIdx.x * 16;
     int32_t v[16];
     int32_t s = 0;
 #pragma unroll
     for (int k = 0; k < 16; ++k) { const int64_t i = base + k; v[k] = i < n ? in[i] : 0; s += v[k]; }
-    int32_t run = offs[blockIdx.x] + block_exclusive_scan_256(s, sh, nullptr);
+    int32_t run = offs[blockIdx.x] + block_exclusive_scan<256>(s, s_waves);
 #pragma unroll
     for (int k = 0; k < 16; ++k) { const int64_t i = base + k; if (i < n) out[i] = run; run += v[k]; }
     if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) out[n] = offs[gridDim.x];

@@ -5,7 +5,7 @@
 // The reference's special tokens (string_k, s_k), sorted by s_k, k = 0 .. S - 1; m pieces are left after the removal.
 //
 //   flag       a thread per piece: keep = 0 for a piece whose bytes are a special's raw bytes
-//   count / scan / place   text_words.hip.h: the flags into the list of the kept pieces' indices, and m
+//   compact    scan.hip.h's count / scan / place: the flags into the list of the kept pieces' indices, and m
 //   rows       a thread per final id v.  Special k sits at pos_k = min(s_k, m + k) (strictly increasing in k), everything else is kept
 //              piece v - #{k : pos_k < v}.  The id's raw bytes into the blob (piece v at 16 * v, the specials behind the pieces), its
 //              score and byte length into the outputs, the length of its byte-level text into the workspace; the minimum of the scores
@@ -30,8 +30,8 @@
 #include "../../include/zett_hip.h"
 #define ZETT_RETOK_DEVICE_FUNCTIONS_ONLY
 #include "retok.hip.h"
+#include "scan.hip.h"
 #include "score_json.hip.h"
-#include "text_words.hip.h"
 
 using namespace zett;
 
@@ -41,6 +41,7 @@ constexpr int kMaxSpecials = ZETT_SPLICE_MAX_ROWS;
 constexpr int kMaxSpecialBytes = ZETT_SAMPLED_VOCAB_KEY_BYTES;      // raw bytes of one special token in the table
 constexpr int64_t kMaxVocab = 1 << 22;
 constexpr int kPieceBytes = 16;
+constexpr int64_t kAnyGrid = INT32_MAX;      // the kernels below take one item per thread: no cap on their grids
 
 struct Record {                              // zett_sampled_vocab_record
     int32_t n_vocab, n_removed, n_text, status;
@@ -66,17 +67,16 @@ struct Layout {
 Layout layout(int64_t n_pieces, int64_t n_special) {
     Layout L{};
     L.np = n_pieces;
-    L.nseg = (L.np + kSeg - 1) / kSeg;
-    int64_t w = 0;
-    auto take = [&](int64_t bytes) { const int64_t at = w; w += (bytes + 15) & ~(int64_t)15; return at; };
-    L.flags = take(L.np + 16);
-    L.kidx = take((L.np + 1) * 4);
-    L.segcnt = take(L.nseg * 4);
-    L.segoff = take(L.nseg * 4);
-    L.totals = take(16);
-    L.tlen = take((L.np + n_special) * 4);
-    L.minkey = take(16);
-    L.bytes = w;
+    L.nseg = compact_segments(L.np);
+    Carve w;
+    L.flags = w.take(L.np + 16);
+    L.kidx = w.take((L.np + 1) * 4);
+    L.segcnt = w.take(L.nseg * 4);
+    L.segoff = w.take(L.nseg * 4);
+    L.totals = w.take(16);
+    L.tlen = w.take((L.np + n_special) * 4);
+    L.minkey = w.take(16);
+    L.bytes = w.bytes;
     return L;
 }
 
@@ -186,28 +186,20 @@ __global__ __launch_bounds__(256) void vocab_rows_kernel(const ulonglong2* __res
 __global__ __launch_bounds__(1024) void vocab_offsets_kernel(const int32_t* __restrict__ n, int64_t np, int32_t n_special, const int32_t* __restrict__ totals,
                                                              const int32_t* __restrict__ tlen, int64_t vocab_cap, int64_t text_cap, int32_t* __restrict__ text_offsets,
                                                              const unsigned long long* __restrict__ minkey, Record* __restrict__ rec) {
-    __shared__ long long s0[1024];
+    __shared__ long long s_waves[16];
     const int tid = threadIdx.x;
     const int64_t m = std::min<int64_t>(std::max(totals[0], 0), np);
     const int64_t nv = m + n_special, nout = std::min(nv, vocab_cap);
     const int64_t per = (nout + 1023) / 1024, lo = std::min(tid * per, nout), hi = std::min(lo + per, nout);
     long long mine = 0;
     for (int64_t v = lo; v < hi; ++v) mine += std::max(tlen[v], 0);
-    s0[tid] = mine;
-    __syncthreads();
-    for (int o = 1; o < 1024; o <<= 1) {
-        const long long x = tid >= o ? s0[tid - o] : 0;
-        __syncthreads();
-        s0[tid] += x;
-        __syncthreads();
-    }
-    long long at = s0[tid] - mine;
+    long long total;
+    long long at = block_exclusive_scan<1024>(mine, s_waves, &total);
     for (int64_t v = lo; v < hi; ++v) {
         text_offsets[v] = (int32_t)std::min<long long>(at, text_cap);
         at += std::max(tlen[v], 0);
     }
     if (tid == 0) {
-        const long long total = s0[1023];
         text_offsets[nout] = (int32_t)std::min<long long>(total, text_cap);
         rec->n_vocab = (int32_t)nv;
         rec->n_removed = (int32_t)(pieces_in(n, np) - m);
@@ -315,8 +307,6 @@ __global__ __launch_bounds__(256) void vocab_patch_kernel(const Record* __restri
     const int64_t row = sp_pos(sp, k, m);
     if (sp.hn[k] >= 0 && row < n_rows) sf[row * maxlen + col] = col == 0 ? sp.hn[k] : pad_id;
 }
-
-int grid256(int64_t items) { return (int)std::max<int64_t>(1, (items + 255) / 256); }
 
 int specials_args(const int32_t* ids, const int32_t* raw_offsets, const uint8_t* raw, const int32_t* char_lengths, const int32_t* hn_ids, int32_t n_special,
                   int32_t raw_bytes) {
@@ -447,12 +437,9 @@ int zett_sampled_vocab_build(zett_retok* r, const uint8_t* pieces, const uint8_t
     HIP_TRY(hipMemsetAsync(sv.slots, 0, (size_t)cap * sizeof(PieceEntry), st));
     HIP_TRY(hipMemsetAsync(sv.bits, 0, (size_t)cap * 4 / 8, st));
     HIP_TRY(hipMemsetAsync(sv.single_id, 0xFF, 256 * 4, st));
-    hipLaunchKernelGGL(vocab_flag_kernel, dim3(grid256(np)), dim3(256), 0, st, (const ulonglong2*)pieces, piece_lengths, n, np, sp, keep, rec);
-    const int seg_grid = grid_for((L.nseg + 3) / 4);
-    hipLaunchKernelGGL(encode_count_kernel, dim3(seg_grid), dim3(256), 0, st, (const uint8_t*)keep, L.np, L.nseg, segcnt);
-    hipLaunchKernelGGL(encode_scan_kernel, dim3(1), dim3(1024), 0, st, (const int*)segcnt, L.nseg, segoff, totals, kidx, L.np);
-    hipLaunchKernelGGL(encode_place_kernel, dim3(seg_grid), dim3(256), 0, st, (const uint8_t*)keep, L.np, L.nseg, (const int*)segoff, kidx);
-    const int vgrid = grid256(np + n_special);
+    hipLaunchKernelGGL(vocab_flag_kernel, dim3(grid256(np, kAnyGrid)), dim3(256), 0, st, (const ulonglong2*)pieces, piece_lengths, n, np, sp, keep, rec);
+    launch_compact(keep, L.np, kidx, segcnt, segoff, totals, st);
+    const int vgrid = grid256(np + n_special, kAnyGrid);
     hipLaunchKernelGGL(vocab_rows_kernel, dim3(vgrid), dim3(256), 0, st, (const ulonglong2*)pieces, piece_lengths, (const unsigned long long*)scores, np, sp,
                        (const int32_t*)kidx, (const int32_t*)totals, sv.blob, (unsigned long long*)priors, byte_lengths, vocab_capacity, tlen, minkey, (int)(flags & ZETT_VOCAB_SCORES_THROUGH_JSON));
     hipLaunchKernelGGL(vocab_offsets_kernel, dim3(1), dim3(1024), 0, st, n, np, n_special, (const int32_t*)totals, (const int32_t*)tlen, vocab_capacity, text_capacity,
@@ -488,7 +475,7 @@ int zett_sampled_vocab_table(zett_retok* r, uint8_t* keys, int32_t* key_lengths,
     hipStream_t st = (hipStream_t)stream;
     HIP_TRY(hipMemsetAsync(n, 0, 4, st));
     if (single_id) HIP_TRY(hipMemcpyAsync(single_id, r->sv.single_id, 256 * 4, hipMemcpyDeviceToDevice, st));
-    hipLaunchKernelGGL(vocab_readout_kernel, dim3(std::min(grid256(r->sv.capacity), 4096)), dim3(256), 0, st, (const PieceEntry*)r->sv.slots, r->sv.capacity,
+    hipLaunchKernelGGL(vocab_readout_kernel, dim3(grid256(r->sv.capacity, 4096)), dim3(256), 0, st, (const PieceEntry*)r->sv.slots, r->sv.capacity,
                        (const uint8_t*)r->sv.blob, r->sv.blob_bytes, keys, key_lengths, ids, (unsigned long long*)scores, capacity, n);
     HIP_TRY(hipGetLastError());
     return 0;
@@ -503,7 +490,7 @@ int zett_sampled_vocab_patch_rows(zett_retok* r, const void* record, const int32
     if (!special_ids || !special_hn_ids || !surface_forms) return fail(ZETT_E_INVALID, "null argument");
     ZETT_ON_DEVICE(r->device);
     const Specials sp{special_ids, nullptr, nullptr, nullptr, special_hn_ids, n_special, 0};
-    hipLaunchKernelGGL(vocab_patch_kernel, dim3(grid256((int64_t)n_special * maxlen)), dim3(256), 0, (hipStream_t)stream, (const Record*)record, sp, surface_forms, n_rows,
+    hipLaunchKernelGGL(vocab_patch_kernel, dim3(grid256((int64_t)n_special * maxlen, kAnyGrid)), dim3(256), 0, (hipStream_t)stream, (const Record*)record, sp, surface_forms, n_rows,
                        maxlen, pad_id);
     HIP_TRY(hipGetLastError());
     return 0;

@@ -11,9 +11,9 @@
 //   walk       a lane per text: the leftmost-first matches of the split pattern as a state machine over the code bytes; a flag at
 //              every match start (ZETT_ENCODE_RESPLIT: every match is matched again, on its own, with the plain pattern).  Sequential by
 //              definition: where a match starts depends on where the previous one ended
-//   count / scan / place   the flags into the word list woff[] — the multi-workgroup scan of train_batch.hip: a wave owns 1024
-//              positions, one workgroup scans the segment counts
-//              (classify to place live in text_words.hip.h: tokenizer_sample.hip launches the same kernels)
+//   compact    the flags into the word list woff[] — scan.hip.h's count / scan / place: a wave owns 1024 positions, one workgroup
+//              scans the segment counts
+//              (classify and walk live in text_words.hip.h: tokenizer_sample.hip launches the same kernels)
 //   words      a lane per word: retok.hip.h's stage 2 (BPE merge / Unigram Viterbi) on the word's raw bytes, state in LDS or — a wave
 //              with more than 4 KiB of text, a lane beyond the arena — in the global scratch.  A word of b bytes gives at most 2b ids
 //              (a byte is at least one symbol, byte fallback makes at most two ids of it), so word w writes at ids[2 * woff[w]]: no
@@ -30,6 +30,7 @@
 #include "../../include/zett_hip.h"
 #define ZETT_RETOK_DEVICE_FUNCTIONS_ONLY
 #include "retok.hip.h"
+#include "scan.hip.h"
 #include "text_words.hip.h"
 
 using namespace zett;
@@ -56,20 +57,19 @@ struct Layout {
 Layout layout(int64_t n_text, int64_t b) {
     Layout L{};
     L.np = n_text + b;
-    L.nseg = (L.np + kSeg - 1) / kSeg;
-    int64_t w = 0;
-    auto take = [&](int64_t bytes) { const int64_t at = w; w += (bytes + 15) & ~(int64_t)15; return at; };
-    L.codes = take(L.np + 16);
-    L.flags = take(L.np + 16);
-    L.raw = take(L.np + 32);                        // 16 bytes of slack for the staging loads of the last wave
-    L.woff = take((L.np + 1) * 4);
-    L.counts = take(L.np * 4);
-    L.segcnt = take(L.nseg * 4);
-    L.segoff = take(L.nseg * 4);
-    L.totals = take(16);
-    L.ids = take(L.np * 8);                         // 2 ids per position
-    L.scratch = take((L.np * kScrPerByte + 64) * 4);
-    L.bytes = w;
+    L.nseg = compact_segments(L.np);
+    Carve w;
+    L.codes = w.take(L.np + 16);
+    L.flags = w.take(L.np + 16);
+    L.raw = w.take(L.np + 32);                      // 16 bytes of slack for the staging loads of the last wave
+    L.woff = w.take((L.np + 1) * 4);
+    L.counts = w.take(L.np * 4);
+    L.segcnt = w.take(L.nseg * 4);
+    L.segoff = w.take(L.nseg * 4);
+    L.totals = w.take(16);
+    L.ids = w.take(L.np * 8);                       // 2 ids per position
+    L.scratch = w.take((L.np * kScrPerByte + 64) * 4);
+    L.bytes = w.bytes;
     return L;
 }
 
@@ -116,13 +116,7 @@ __global__ __launch_bounds__(64) void encode_words_kernel(RetokTables t, const u
         }
         need = (need + 1) & ~1;                                        // regions start on 8-byte boundaries
     }
-    int inc = need;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int v = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += v;
-    }
-    const int a0 = inc - need;
+    const int a0 = wave_inclusive_scan(need) - need;
     if (todo) {
         bool ok;
         if (text_lds && a0 + need <= RT_ARENA_WORDS) {
@@ -178,12 +172,7 @@ __global__ __launch_bounds__(64) void encode_pack_kernel(const int64_t* __restri
                 at = woff[w];
                 k = std::max(0, std::min(counts[w], 2 * (woff[w + 1] - at)));
             }
-            int inc = k;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const int v = __shfl_up(inc, o, 64);
-                if (lane >= o) inc += v;
-            }
+            const int inc = wave_inclusive_scan(k);
             const int64_t e = base + inc - k;
             const int32_t* src = ids + 2 * (int64_t)at;
             for (int q = 0; q < k && e + q < cap; ++q) s_row[ls.n_prefix + e + q] = src[q];      // (a word may be cut in the middle)
@@ -302,17 +291,14 @@ int zett_encode_texts(zett_retok* r, const uint8_t* text, const int64_t* text_of
                        (int)prefix_mode, codes, wflags, raw, status);
     hipLaunchKernelGGL(encode_walk_kernel, dim3((unsigned)((n_texts + 63) / 64)), dim3(64), 0, st, text_offsets, n_texts, n_text, (const uint8_t*)codes, wflags, marks,
                        (int)((flags & ZETT_ENCODE_RESPLIT) != 0));
-    const int seg_grid = grid_for((L.nseg + 3) / 4);
-    hipLaunchKernelGGL(encode_count_kernel, dim3(seg_grid), dim3(256), 0, st, (const uint8_t*)wflags, L.np, L.nseg, segcnt);
-    hipLaunchKernelGGL(encode_scan_kernel, dim3(1), dim3(1024), 0, st, (const int*)segcnt, L.nseg, segoff, totals, woff, L.np);
-    hipLaunchKernelGGL(encode_place_kernel, dim3(seg_grid), dim3(256), 0, st, (const uint8_t*)wflags, L.np, L.nseg, (const int*)segoff, woff);
+    launch_compact(wflags, L.np, woff, segcnt, segoff, totals, st);
     hipLaunchKernelGGL(encode_words_kernel, dim3((unsigned)((L.np + 63) / 64)), dim3(64), 0, st, r->t, (const uint8_t*)raw, (const uint8_t*)wflags, (const int32_t*)woff,
                        (const int32_t*)totals, ids, counts, scratch, status);
     const int per = out_bytes == 8 ? 2 : 4;
     const bool vec = block_size % per == 0 && ld_out % per == 0 && aligned(input_ids, 16) && aligned(attention_mask, 16);
     const size_t lds = (size_t)block_size * 4;
 #define ZETT_PACK(WIDE, VEC)                                                                                                                                       \
-    hipLaunchKernelGGL((encode_pack_kernel<WIDE, VEC>), dim3(grid_for(n_texts)), dim3(64), lds, st, text_offsets, n_texts, n_text, (const int32_t*)woff,          \
+    hipLaunchKernelGGL((encode_pack_kernel<WIDE, VEC>), dim3(grid_for(n_texts, 1 << 16)), dim3(64), lds, st, text_offsets, n_texts, n_text, (const int32_t*)woff, \
                        (const int32_t*)totals, (const int32_t*)counts, (const int32_t*)ids, (int)block_size, ls, input_ids, attention_mask, ld_out)
     if (out_bytes == 8) { if (vec) ZETT_PACK(true, true); else ZETT_PACK(true, false); }
     else { if (vec) ZETT_PACK(false, true); else ZETT_PACK(false, false); }

@@ -1,7 +1,7 @@
 // text_words.hip.h — the split of a batch of texts into words, shared by text_encode.hip (zett_encode_texts) and tokenizer_sample.hip
-// (zett_sampler_sample): classify / walk / count / scan / place, from the text bytes to the word list woff[].  Both entry points launch
-// these kernels; the stages are described at the head of text_encode.hip.  Everything here has internal linkage: a translation unit
-// that includes the header gets its own copy.
+// (zett_sampler_sample): classify / walk, from the text bytes to a flag at every word start (scan.hip.h's compaction makes the word
+// list woff[] of them).  Both entry points launch these kernels; the stages are described at the head of text_encode.hip.  Everything
+// here has internal linkage: a translation unit that includes the header gets its own copy.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -12,8 +12,6 @@
 
 namespace {
 
-constexpr int kSeg = 1024;                  // positions of one wave's segment: 16 per lane
-constexpr int kMaxGrid = 1 << 16;
 constexpr int64_t kMaxPositions = 1 << 30;
 // a prefix mode of the sampler alone (zett_encode_texts refuses it): a U+0020 in front of EVERY text, the empty one included
 constexpr int kPrefixEvenEmpty = 3;
@@ -22,7 +20,6 @@ constexpr int kPrefixEvenEmpty = 3;
 enum : int { C_O = 0, C_L = 1, C_M = 2, C_N = 3, C_S = 4, C_SKIP = 7 };
 enum : int { A_NONE = 0, A_SPACE, A_APOS, A_s, A_t, A_m, A_d, A_r, A_v, A_l, A_e };
 
-__device__ __forceinline__ int wave_index() { return __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); }
 __device__ __forceinline__ int64_t clamp_off(int64_t o, int64_t n_text) { return o < 0 ? 0 : (o > n_text ? n_text : o); }
 
 __global__ __launch_bounds__(256) void encode_classify_kernel(const uint8_t* __restrict__ text, const int64_t* __restrict__ off, int64_t b, int64_t n_text,
@@ -145,81 +142,5 @@ __global__ __launch_bounds__(64) void encode_walk_kernel(const int64_t* __restri
         i = e;
     }
 }
-
-// the flags of a lane's 16 positions of segment seg, as a bit mask
-__device__ __forceinline__ uint32_t lane_flags(const uint8_t* __restrict__ flags, int64_t np, int64_t seg, int lane) {
-    const int64_t base = seg * kSeg + lane * 16;
-    uint32_t bits = 0;
-    if (base + 16 <= np) {
-        const uint4 v = *(const uint4*)(flags + base);
-        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int j = 0; j < 16; ++j) bits |= (uint32_t)(((w[j >> 2] >> ((j & 3) * 8)) & 0xff) != 0) << j;
-    } else {
-#pragma unroll
-        for (int j = 0; j < 16; ++j) bits |= (uint32_t)(base + j < np && flags[base + j] != 0) << j;
-    }
-    return bits;
-}
-
-__global__ __launch_bounds__(256) void encode_count_kernel(const uint8_t* __restrict__ flags, int64_t np, int64_t nseg, int* __restrict__ segcnt) {
-    const int lane = threadIdx.x & 63;
-    for (int64_t seg = (int64_t)blockIdx.x * 4 + wave_index(); seg < nseg; seg += (int64_t)gridDim.x * 4) {
-        int a = __popc(lane_flags(flags, np, seg, lane));
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
-        if (lane == 0) segcnt[seg] = a;
-    }
-}
-
-// exclusive scan of the segment counts: one workgroup, 1024 segments (2^20 positions) per round, the carry in registers
-__global__ __launch_bounds__(1024) void encode_scan_kernel(const int* __restrict__ segcnt, int64_t nseg, int* __restrict__ segoff, int* __restrict__ totals,
-                                                           int* __restrict__ woff, int64_t np) {
-    __shared__ int s0[1024];
-    const int tid = threadIdx.x;
-    int carry = 0;
-    for (int64_t base = 0; base < nseg; base += 1024) {
-        const int64_t i = base + tid;
-        const int a = i < nseg ? segcnt[i] : 0;
-        s0[tid] = a;
-        __syncthreads();
-        for (int o = 1; o < 1024; o <<= 1) {
-            const int x = tid >= o ? s0[tid - o] : 0;
-            __syncthreads();
-            s0[tid] += x;
-            __syncthreads();
-        }
-        if (i < nseg) segoff[i] = carry + s0[tid] - a;
-        carry += s0[1023];
-        __syncthreads();
-    }
-    if (tid == 0) {
-        totals[0] = carry;                 // the number of words (dead slots included)
-        woff[carry] = (int)np;             // the end of the last word
-    }
-}
-
-__global__ __launch_bounds__(256) void encode_place_kernel(const uint8_t* __restrict__ flags, int64_t np, int64_t nseg, const int* __restrict__ segoff,
-                                                           int* __restrict__ woff) {
-    const int lane = threadIdx.x & 63;
-    for (int64_t seg = (int64_t)blockIdx.x * 4 + wave_index(); seg < nseg; seg += (int64_t)gridDim.x * 4) {
-        const uint32_t bits = lane_flags(flags, np, seg, lane);
-        const int n = __popc(bits);
-        int inc = n;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int v = __shfl_up(inc, o, 64);
-            if (lane >= o) inc += v;
-        }
-        int at = segoff[seg] + inc - n;
-        const int64_t base = seg * kSeg + lane * 16;
-#pragma unroll
-        for (int j = 0; j < 16; ++j)
-            if ((bits >> j) & 1) woff[at++] = (int)(base + j);
-    }
-}
-
-bool aligned(const void* p, size_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
-int grid_for(int64_t workgroups) { return (int)std::max<int64_t>(1, std::min<int64_t>(workgroups, kMaxGrid)); }
 
 }  // namespace

@@ -1,7 +1,7 @@
 // tokenizer_sample.hip — a step's Unigram seed vocabulary from the batch's texts, on the device (include/zett_hip.h, "tokenizer sampling";
 // what rust_utils.TokenizerSampler.sample_tokenizer computes, restated in tests/sampler_ref.py).
 //
-//   words      text_words.hip.h: classify / walk / count / scan / place with the plain split pattern and a U+0020 in front of EVERY text;
+//   words      text_words.hip.h's classify / walk with the plain split pattern and a U+0020 in front of EVERY text, scan.hip.h's compaction;
 //              the slot of a text is then marked as the start of the text's first word (flag bit 4)
 //   count      a lane per word (lanes of a wave with the same word first sum into one): the word's starts (every stride-th entry of the reference's start list) and from each start the keys
 //              of 1 .. max_length - 1 bytes.  A key is 16 bytes, 15 key bytes and the length; a key of one byte goes into a 256-bin
@@ -12,8 +12,8 @@
 //              either adds to the score or probes on.  The bytes behind a reference were written by an earlier launch, the reference
 //              arrives through the atomic: no lane waits for another lane's store.  Probing is linear, wraps at the capacity and stops
 //              after `capacity` slots (ZETT_SAMPLE_TABLE_FULL)
-//   compact    occupied slots and non-empty bins as flags, the flags to an index list with the count / scan / place of
-//              text_words.hip.h, the list gathered into (key16, score) arrays the queue owns
+//   compact    occupied slots and non-empty bins as flags, the flags to an index list with the compaction of scan.hip.h, the list
+//              gathered into (key16, score) arrays the queue owns
 //   merge      the table again, rebuilt per call from every list of the queue; sum (64 bits), min and the number of keys
 //   candidates p = v / sum + noise_std * z for every kept key, as 24 ordered bytes: ~bits(p) (0 for p <= 0), length, key bytes; a workgroup
 //              packs the candidates of its share of the slots into the same share of the candidate array (its counter is in LDS)
@@ -32,6 +32,7 @@
 
 #include "../../include/zett_hip.h"
 #include "common.hip.h"
+#include "scan.hip.h"
 #include "text_words.hip.h"
 
 using namespace zett;
@@ -64,6 +65,7 @@ namespace {
 
 constexpr uint64_t kLocMask = (1ull << 40) - 1;
 constexpr int kFixedBytes = 256;
+constexpr int kGrid = 4096;                 // workgroups of the other grid-stride passes, at most
 constexpr int kSelGrid = 1024;              // workgroups of the passes over the merged table: each owns a contiguous share of the slots
 
 struct Comp { uint64_t a, b, c; };            // 24 ordered bytes, most significant first
@@ -86,17 +88,16 @@ struct Layout {
 Layout layout(int64_t n_text, int64_t b) {
     Layout L{};
     L.np = n_text + b;
-    L.nseg = (L.np + kSeg - 1) / kSeg;
-    int64_t w = 0;
-    auto take = [&](int64_t bytes) { const int64_t at = w; w += (bytes + 15) & ~(int64_t)15; return at; };
-    L.codes = take(L.np + 16);
-    L.flags = take(L.np + 16);
-    L.raw = take(L.np + 32);
-    L.woff = take((L.np + 1) * 4);
-    L.segcnt = take(L.nseg * 4);
-    L.segoff = take(L.nseg * 4);
-    L.totals = take(16);
-    L.bytes = w;
+    L.nseg = compact_segments(L.np);
+    Carve w;
+    L.codes = w.take(L.np + 16);
+    L.flags = w.take(L.np + 16);
+    L.raw = w.take(L.np + 32);
+    L.woff = w.take((L.np + 1) * 4);
+    L.segcnt = w.take(L.nseg * 4);
+    L.segoff = w.take(L.nseg * 4);
+    L.totals = w.take(16);
+    L.bytes = w.bytes;
     return L;
 }
 
@@ -479,8 +480,6 @@ __global__ __launch_bounds__(256) void sample_table_kernel(const unsigned long l
     }
 }
 
-int grid256(int64_t items, int64_t most = 4096) { return (int)std::max<int64_t>(1, std::min<int64_t>((items + 255) / 256, most)); }
-
 int shape_args(int64_t n_text, int64_t n_texts) {
     if (n_text < 0 || n_texts < 0) return fail(ZETT_E_INVALID, "tokenizer sampling needs n_text >= 0 bytes and n_texts >= 0 texts (n_text = %lld, n_texts = %lld)", (long long)n_text, (long long)n_texts);
     if (n_text + n_texts >= kMaxPositions) return fail(ZETT_E_INVALID, "n_text + n_texts = %lld: a call takes fewer than 2^30 positions", (long long)(n_text + n_texts));
@@ -512,7 +511,7 @@ int zett_sampler_create(int device, int32_t max_depth, int64_t list_capacity, in
     s->sort_cap = 1;
     while (s->sort_cap < max_pieces) s->sort_cap <<= 1;
     s->np_occ = table_capacity + kFixedBytes;
-    s->nseg_occ = (s->np_occ + kSeg - 1) / kSeg;
+    s->nseg_occ = compact_segments(s->np_occ);
     const int64_t slots = max_depth + 1;
     hipError_t e = hipSuccess;
     auto get = [&](auto** p, int64_t bytes) { if (e == hipSuccess) e = hipMalloc((void**)p, (size_t)bytes); };
@@ -610,21 +609,15 @@ int zett_sampler_sample(zett_sampler* s, const uint8_t* text, const int64_t* tex
                            kPrefixEvenEmpty, codes, wflags, raw, status);
         hipLaunchKernelGGL(encode_walk_kernel, dim3((unsigned)((n_texts + 63) / 64)), dim3(64), 0, st, text_offsets, n_texts, n_text, (const uint8_t*)codes, wflags, 0, 0);
         hipLaunchKernelGGL(sample_mark_first_kernel, dim3((unsigned)((n_texts + 255) / 256)), dim3(256), 0, st, text_offsets, n_texts, n_text, wflags);
-        const int seg_grid = grid_for((L.nseg + 3) / 4);
-        hipLaunchKernelGGL(encode_count_kernel, dim3(seg_grid), dim3(256), 0, st, (const uint8_t*)wflags, L.np, L.nseg, segcnt);
-        hipLaunchKernelGGL(encode_scan_kernel, dim3(1), dim3(1024), 0, st, (const int*)segcnt, L.nseg, segoff, totals, woff, L.np);
-        hipLaunchKernelGGL(encode_place_kernel, dim3(seg_grid), dim3(256), 0, st, (const uint8_t*)wflags, L.np, L.nseg, (const int*)segoff, woff);
+        launch_compact(wflags, L.np, woff, segcnt, segoff, totals, st);
         HIP_TRY(hipMemsetAsync(s->refs, 0, (size_t)cap * 8, st));
         HIP_TRY(hipMemsetAsync(s->scores, 0, (size_t)cap * 4, st));
         HIP_TRY(hipMemsetAsync(s->hist1, 0, 256 * 4, st));
         hipLaunchKernelGGL(sample_count_kernel, dim3(grid256((L.np + 3) / 4, 8192)), dim3(256), 0, st, (const uint8_t*)raw, (const uint8_t*)codes, (const uint8_t*)wflags,
                            (const int32_t*)woff, (const int32_t*)totals, L.np, (int)max_length, (int)stride, s->refs, s->scores, cap, s->hist1, status);
-        hipLaunchKernelGGL(sample_occupied_kernel, dim3(grid256(s->np_occ)), dim3(256), 0, st, (const unsigned long long*)s->refs, (const uint32_t*)s->hist1, (int64_t)cap, s->occ);
-        const int occ_grid = grid_for((s->nseg_occ + 3) / 4);
-        hipLaunchKernelGGL(encode_count_kernel, dim3(occ_grid), dim3(256), 0, st, (const uint8_t*)s->occ, s->np_occ, s->nseg_occ, s->segcnt);
-        hipLaunchKernelGGL(encode_scan_kernel, dim3(1), dim3(1024), 0, st, (const int*)s->segcnt, s->nseg_occ, s->segoff, s->totals, s->idx, s->np_occ);
-        hipLaunchKernelGGL(encode_place_kernel, dim3(occ_grid), dim3(256), 0, st, (const uint8_t*)s->occ, s->np_occ, s->nseg_occ, (const int*)s->segoff, s->idx);
-        hipLaunchKernelGGL(sample_gather_kernel, dim3(grid256(s->list_cap)), dim3(256), 0, st, (const unsigned long long*)s->refs, (const uint32_t*)s->scores,
+        hipLaunchKernelGGL(sample_occupied_kernel, dim3(grid256(s->np_occ, kGrid)), dim3(256), 0, st, (const unsigned long long*)s->refs, (const uint32_t*)s->hist1, (int64_t)cap, s->occ);
+        launch_compact(s->occ, s->np_occ, s->idx, s->segcnt, s->segoff, s->totals, st);
+        hipLaunchKernelGGL(sample_gather_kernel, dim3(grid256(s->list_cap, kGrid)), dim3(256), 0, st, (const unsigned long long*)s->refs, (const uint32_t*)s->scores,
                            (const uint32_t*)s->hist1, (int64_t)cap, (const uint8_t*)raw, (const int32_t*)s->idx, (const int32_t*)s->totals, s->list_cap,
                            s->list_keys + (int64_t)cur * s->list_cap, s->list_scores + (int64_t)cur * s->list_cap, s->list_n + cur, status);
     }
@@ -645,7 +638,7 @@ int zett_sampler_sample(zett_sampler* s, const uint8_t* text, const int64_t* tex
         hipLaunchKernelGGL(sample_init_state_kernel, dim3(1), dim3(64), 0, st, state, (long long)k_pieces);
         HIP_TRY(hipMemsetAsync(surv, 0xFF, (size_t)sort_n * sizeof(Comp), st));
         for (int q : s->queue)
-            hipLaunchKernelGGL(sample_merge_kernel, dim3(grid256(s->list_cap)), dim3(256), 0, st, (const ulonglong2*)s->list_keys, (const uint32_t*)s->list_scores,
+            hipLaunchKernelGGL(sample_merge_kernel, dim3(grid256(s->list_cap, kGrid)), dim3(256), 0, st, (const ulonglong2*)s->list_keys, (const uint32_t*)s->list_scores,
                                (const int32_t*)s->list_n, q, s->list_cap, s->refs, s->scores, cap, status);
         const int tgrid = grid256(cap, kSelGrid);          // (the same grid for every pass over `cand`: a workgroup reads what it wrote)
         hipLaunchKernelGGL(sample_stats_kernel, dim3(tgrid), dim3(256), 0, st, (const unsigned long long*)s->refs, (const uint32_t*)s->scores, (int64_t)cap, state);
@@ -659,7 +652,7 @@ int zett_sampler_sample(zett_sampler* s, const uint8_t* text, const int64_t* tex
         for (int64_t k = 2; k <= sort_n; k <<= 1)
             for (int64_t j = k >> 1; j > 0; j >>= 1)
                 hipLaunchKernelGGL(sample_bitonic_kernel, dim3((unsigned)((sort_n + 255) / 256)), dim3(256), 0, st, surv, sort_n, k, j);
-        hipLaunchKernelGGL(sample_emit_kernel, dim3(grid256(fixed + sort_n)), dim3(256), 0, st, (const SelState*)state, (const Comp*)surv, sort_n, (int)max_length, pieces,
+        hipLaunchKernelGGL(sample_emit_kernel, dim3(grid256(fixed + sort_n, kGrid)), dim3(256), 0, st, (const SelState*)state, (const Comp*)surv, sort_n, (int)max_length, pieces,
                            piece_lengths, scores, out_capacity, n_out, status);
         s->merged = true;
         s->seed = seed;
@@ -681,7 +674,7 @@ int zett_sampler_table(zett_sampler* s, uint8_t* keys, uint8_t* key_lengths, uin
     ZETT_ON_DEVICE(s->device);
     hipStream_t st = (hipStream_t)stream;
     HIP_TRY(hipMemsetAsync(n, 0, 4, st));
-    hipLaunchKernelGGL(sample_table_kernel, dim3(grid256(s->table_cap)), dim3(256), 0, st, (const unsigned long long*)s->refs, (const uint32_t*)s->scores, s->table_cap,
+    hipLaunchKernelGGL(sample_table_kernel, dim3(grid256(s->table_cap, kGrid)), dim3(256), 0, st, (const unsigned long long*)s->refs, (const uint32_t*)s->scores, s->table_cap,
                        (const ulonglong2*)s->list_keys, s->seed, keys, key_lengths, counts, z, capacity, n);
     HIP_TRY(hipGetLastError());
     return 0;

@@ -4,7 +4,8 @@
 //
 // Integers only.  Presence flags over V are set with an integer OR; the positives' ranks and the ranks of the absent ids in
 // negative_order's order come from ONE multi-workgroup scan in three launches (count per segment of 1024 ids, one workgroup over the
-// segment counts, place) — every wave owns a contiguous segment, so no launch waits for another workgroup; the inverse table is written
+// segment counts, place: the shape of scan.hip.h's compaction, here with two predicates in one pass and a payload) — every wave owns a
+// contiguous segment, so no launch waits for another workgroup; the inverse table is written
 // with an integer max.  OR and max do not depend on arrival order: the same inputs give the same bits.  An id outside [0, V) is
 // reported in the status word and never becomes an address.
 #include <hip/hip_runtime.h>
@@ -14,6 +15,7 @@
 
 #include "../../include/zett_hip.h"
 #include "common.hip.h"
+#include "scan.hip.h"
 #include "train_common.hip.h"
 
 using namespace zett;
@@ -21,8 +23,7 @@ using namespace zett;
 namespace {
 
 constexpr int kListMax = ZETT_SPLICE_MAX_ROWS;
-constexpr int kSeg = 1024;                            // ids of one wave's segment: 16 per lane (count and place each read them: two launches)
-constexpr int kPerLane = kSeg / 64;
+constexpr int kPerLane = kSeg / 64;                   // ids of a lane in its wave's segment (count and place each read them: two launches)
 constexpr int kMaxGrid = 1 << 16;
 constexpr int kMaxL = 65536;                          // columns of a surface-form row: the copy's indices are 32-bit
 
@@ -44,7 +45,7 @@ struct Layout {
 };
 Layout layout(int64_t v, int64_t n) {
     Layout L{};
-    L.nseg = (v + kSeg - 1) / kSeg;
+    L.nseg = compact_segments(v);
     int64_t w = 0;
     L.flags = w; w += v;                   // bit 0: the id occurs in input_ids / labels; bit 1: it is special
     L.inv = w; w += v;                     // id -> its last row of ids_to_embed, -1: none
@@ -57,8 +58,6 @@ Layout layout(int64_t v, int64_t n) {
     return L;
 }
 
-__device__ __forceinline__ int wave_index() { return __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); }
-__device__ __forceinline__ int lanes_below(uint64_t mask) { return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0)); }
 __device__ __forceinline__ void store_id(void* out, int wide, int64_t i, int64_t x) {
     if (wide) ((int64_t*)out)[i] = x;
     else ((int32_t*)out)[i] = (int32_t)x;
@@ -142,29 +141,20 @@ __global__ __launch_bounds__(256) void batch_count_kernel(const int* __restrict_
 // exclusive scans of the two rows of segment counts: one workgroup, 1024 segments (2^20 ids) per round, the carry in registers
 __global__ __launch_bounds__(1024) void batch_scan_kernel(const int* __restrict__ segcnt, int64_t nseg, int* __restrict__ segoff, int* __restrict__ totals, int64_t n,
                                                           int n_special, int random, int* __restrict__ n_positive, int* __restrict__ status) {
-    __shared__ int s0[1024], s1[1024];
+    __shared__ int s_waves0[16], s_waves1[16];
     const int tid = threadIdx.x;
     int carry0 = 0, carry1 = 0;
     for (int64_t base = 0; base < nseg; base += 1024) {
         const int64_t i = base + tid;
         const int a = i < nseg ? segcnt[i] : 0, b = i < nseg ? segcnt[nseg + i] : 0;
-        s0[tid] = a;
-        s1[tid] = b;
-        __syncthreads();
-        for (int off = 1; off < 1024; off <<= 1) {
-            const int x0 = tid >= off ? s0[tid - off] : 0, x1 = tid >= off ? s1[tid - off] : 0;
-            __syncthreads();
-            s0[tid] += x0;
-            s1[tid] += x1;
-            __syncthreads();
-        }
+        int round0, round1;
+        const int before0 = block_exclusive_scan<1024>(a, s_waves0, &round0), before1 = block_exclusive_scan<1024>(b, s_waves1, &round1);
         if (i < nseg) {
-            segoff[i] = carry0 + s0[tid] - a;
-            segoff[nseg + i] = carry1 + s1[tid] - b;
+            segoff[i] = carry0 + before0;
+            segoff[nseg + i] = carry1 + before1;
         }
-        carry0 += s0[1023];
-        carry1 += s1[1023];
-        __syncthreads();
+        carry0 += round0;
+        carry1 += round1;
     }
     if (tid == 0) {
         totals[0] = carry0;
@@ -270,8 +260,6 @@ __global__ __launch_bounds__(256) void batch_remap_kernel(const void* __restrict
     }
 }
 
-bool aligned(const void* p, size_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
-int grid_for(int64_t workgroups) { return (int)std::max<int64_t>(1, std::min<int64_t>(workgroups, kMaxGrid)); }
 bool width_ok(int32_t b) { return b == 4 || b == 8; }
 
 int shape_args(int64_t t, int64_t v, int64_t n) {
@@ -339,16 +327,16 @@ int zett_op_batch_vocab(const void* input_ids, int32_t ids_bytes, const void* la
     hipStream_t st = (hipStream_t)stream;
     int* w = (int*)workspace;
     const int ids64 = ids_bytes == 8, labels64 = labels_bytes == 8, order64 = order_bytes == 8;
-    hipLaunchKernelGGL(batch_init_kernel, dim3(grid_for((v + 255) / 256)), dim3(256), 0, st, w + L.flags, w + L.inv, v, status);
-    hipLaunchKernelGGL(batch_mark_kernel, dim3(grid_for((t + 255) / 256)), dim3(256), 0, st, input_ids, ids64, labels, labels64, t, v, w + L.flags, status, sp);
-    const int seg_grid = grid_for((L.nseg + 3) / 4);
+    hipLaunchKernelGGL(batch_init_kernel, dim3(grid_for((v + 255) / 256, kMaxGrid)), dim3(256), 0, st, w + L.flags, w + L.inv, v, status);
+    hipLaunchKernelGGL(batch_mark_kernel, dim3(grid_for((t + 255) / 256, kMaxGrid)), dim3(256), 0, st, input_ids, ids64, labels, labels64, t, v, w + L.flags, status, sp);
+    const int seg_grid = grid_for((L.nseg + 3) / 4, kMaxGrid);
     hipLaunchKernelGGL(batch_count_kernel, dim3(seg_grid), dim3(256), 0, st, (const int*)(w + L.flags), negative_order, order64, v, L.nseg, random, w + L.segcnt, status);
     hipLaunchKernelGGL(batch_scan_kernel, dim3(1), dim3(1024), 0, st, (const int*)(w + L.segcnt), L.nseg, w + L.segoff, w + L.totals, n, (int)n_special, random, n_positive,
                        status);
     hipLaunchKernelGGL(batch_place_kernel, dim3(seg_grid), dim3(256), 0, st, (const int*)(w + L.flags), negative_order, order64, v, L.nseg, random,
                        (const int*)(w + L.segoff), n, w + L.pos, w + L.neg);
     const int64_t row_bytes = (int64_t)l * sf_bytes, ld_bytes = ld_sf * sf_bytes;
-    const int rows_grid = grid_for(((n + 63) / 64 + 3) / 4);
+    const int rows_grid = grid_for(((n + 63) / 64 + 3) / 4, kMaxGrid);
     const bool vec = row_bytes % 16 == 0 && ld_bytes % 16 == 0 && aligned(surface_forms, 16) && aligned(out_surface_forms, 16);
 #define ZETT_ROWS(TV)                                                                                                                                                   \
     hipLaunchKernelGGL(batch_rows_kernel<TV>, dim3(rows_grid), dim3(256), 0, st, n, v, random, (const int*)(w + L.totals), (const int*)(w + L.pos), (const int*)(w + L.neg), \
@@ -358,7 +346,7 @@ int zett_op_batch_vocab(const void* input_ids, int32_t ids_bytes, const void* la
     else if (sf_bytes == 8) ZETT_ROWS(uint64_t);
     else ZETT_ROWS(uint32_t);
 #undef ZETT_ROWS
-    if (t) hipLaunchKernelGGL(batch_remap_kernel, dim3(grid_for((t + 255) / 256)), dim3(256), 0, st, input_ids, ids64, labels, labels64, t, v, (const int*)(w + L.inv),
+    if (t) hipLaunchKernelGGL(batch_remap_kernel, dim3(grid_for((t + 255) / 256, kMaxGrid)), dim3(256), 0, st, input_ids, ids64, labels, labels64, t, v, (const int*)(w + L.inv),
                               out_input_ids, out_labels);
     HIP_TRY(hipGetLastError());
     return 0;

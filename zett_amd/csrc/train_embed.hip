@@ -16,6 +16,7 @@
 
 #include "../../include/zett_hip.h"
 #include "common.hip.h"
+#include "scan.hip.h"
 #include "train_common.hip.h"
 
 using namespace zett;
@@ -26,8 +27,6 @@ constexpr int kChunk = ZETT_EMBED_BWD_CHUNK;          // positions of one partia
 constexpr int kListMax = ZETT_SPLICE_MAX_ROWS;        // the longest list: the two lists travel as kernel arguments
 constexpr int kMaxGrid = 1 << 18;
 static_assert(kChunk == 64, "a chunk is one wave of positions: the plan's tile and the sum's position register are 64 lanes wide");
-
-__device__ __forceinline__ int wave_index() { return __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); }
 
 // ---- splice: listed rows from the source (or zero), every other row copied or left alone ----------------------------------------
 struct SpliceList {
@@ -145,7 +144,7 @@ __global__ __launch_bounds__(256) void plan_hist_kernel(const void* __restrict__
 
 // exclusive scans of counts and of the chunk numbers of long lists: one workgroup, every thread a contiguous run of ids
 __global__ __launch_bounds__(1024) void plan_scan_kernel(const int* __restrict__ counts, int64_t v, int* __restrict__ offsets, int* __restrict__ mstart) {
-    __shared__ int s0[1024], s1[1024];
+    __shared__ int s_waves0[16], s_waves1[16];
     const int tid = threadIdx.x;
     const int64_t seg = (v + 1023) / 1024, lo = std::min<int64_t>(tid * seg, v), hi = std::min<int64_t>(lo + seg, v);
     int a = 0, b = 0;
@@ -154,17 +153,7 @@ __global__ __launch_bounds__(1024) void plan_scan_kernel(const int* __restrict__
         a += c;
         b += c > kChunk ? (c + kChunk - 1) / kChunk : 0;
     }
-    s0[tid] = a;
-    s1[tid] = b;
-    __syncthreads();
-    for (int off = 1; off < 1024; off <<= 1) {
-        const int x0 = tid >= off ? s0[tid - off] : 0, x1 = tid >= off ? s1[tid - off] : 0;
-        __syncthreads();
-        s0[tid] += x0;
-        s1[tid] += x1;
-        __syncthreads();
-    }
-    int r0 = s0[tid] - a, r1 = s1[tid] - b;
+    int r0 = block_exclusive_scan<1024>(a, s_waves0), r1 = block_exclusive_scan<1024>(b, s_waves1);
     for (int64_t i = lo; i < hi; ++i) {
         const int c = counts[i];
         offsets[i] = r0;
@@ -344,8 +333,6 @@ __global__ __launch_bounds__(256) void embed_bwd_fin_kernel(const float* __restr
 
 // ---- host side ----------------------------------------------------------------------------------------------------------------------
 int elem_bytes(int32_t d) { return d == ZETT_F32 ? 4 : 2; }
-bool aligned(const void* p, size_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
-int grid_for(int64_t workgroups) { return (int)std::max<int64_t>(1, std::min<int64_t>(workgroups, kMaxGrid)); }
 
 // W elements per access where W is one of the widths the element type takes (8: 16-bit on both sides), one otherwise
 template <typename TI, typename TO>
@@ -353,7 +340,7 @@ void lookup_go(int w, hipStream_t st, const void* table, int64_t ld, int64_t v, 
     const int nvec = e / w;
     int shift = 0;
     while (shift < 8 && (1 << shift) < nvec) ++shift;
-    const int grid = grid_for((t + (256 >> shift) - 1) / (256 >> shift));
+    const int grid = grid_for((t + (256 >> shift) - 1) / (256 >> shift), kMaxGrid);
     auto kernel = embed_lookup_kernel<TI, TO, 1>;
     if (w == 4) kernel = embed_lookup_kernel<TI, TO, 4>;
     if constexpr (sizeof(TI) == 2 && sizeof(TO) == 2) {
@@ -365,7 +352,7 @@ void lookup_go(int w, hipStream_t st, const void* table, int64_t ld, int64_t v, 
 template <typename TG>
 void bwd_sum_go(int w, hipStream_t st, const void* g, int e, int64_t v, const int* plan, const PlanLayout& L, float* partials, float* d, int64_t ld_d) {
     const int nslices = (e + 64 * w - 1) / (64 * w);
-    const int grid = grid_for(((L.maxch + v) * nslices + 3) / 4);
+    const int grid = grid_for(((L.maxch + v) * nslices + 3) / 4, kMaxGrid);
     auto kernel = embed_bwd_sum_kernel<TG, 1>;
     if (w == 4) kernel = embed_bwd_sum_kernel<TG, 4>;
     if constexpr (sizeof(TG) == 2) {
@@ -418,7 +405,7 @@ int zett_op_splice_rows(const float* in, int64_t ld_in, float* out, int64_t ld_o
         list.ref[i] = src ? ref_rows[i] : 0;
     }
     const int copy_all = in != nullptr;
-    const int grid = grid_for(((copy_all ? v : (int64_t)n) + 3) / 4);
+    const int grid = grid_for(((copy_all ? v : (int64_t)n) + 3) / 4, kMaxGrid);
     with_dtype(src ? src_dtype : ZETT_F32, [&](auto dt) {
         using TS = elem_t<decltype(dt)::value>;
         hipLaunchKernelGGL(splice_rows_kernel<TS>, dim3(grid), dim3(256), 0, st, in, ld_in, out, ld_out, v, (int)e, (const TS*)src, ld_src, (int)col0, copy_all, vec_ok, list);
@@ -469,14 +456,14 @@ int zett_op_embed_lookup_plan(const void* ids, int32_t ids_bytes, int64_t t, int
     int* s = (int*)scratch;
     const int ids64 = ids_bytes == 8;
     HIP_TRY(hipMemsetAsync(s + L.counts, 0, (size_t)(2 * v) * 4, st));          // counts and tiles
-    if (t) hipLaunchKernelGGL(plan_hist_kernel, dim3(grid_for((t + 255) / 256)), dim3(256), 0, st, ids, ids64, t, v, s + L.counts);
+    if (t) hipLaunchKernelGGL(plan_hist_kernel, dim3(grid_for((t + 255) / 256, kMaxGrid)), dim3(256), 0, st, ids, ids64, t, v, s + L.counts);
     hipLaunchKernelGGL(plan_scan_kernel, dim3(1), dim3(1024), 0, st, (const int*)(s + L.counts), v, w + L.offsets, w + L.mstart);
     if (t) {
-        hipLaunchKernelGGL(plan_tile_kernel, dim3(grid_for(((t + 63) / 64 + 3) / 4)), dim3(256), 0, st, ids, ids64, t, v, (const int*)(w + L.offsets), s + L.tiles,
+        hipLaunchKernelGGL(plan_tile_kernel, dim3(grid_for(((t + 63) / 64 + 3) / 4, kMaxGrid)), dim3(256), 0, st, ids, ids64, t, v, (const int*)(w + L.offsets), s + L.tiles,
                            s + L.tl_w, s + L.tl_cnt, s + L.info);
-        hipLaunchKernelGGL(plan_base_kernel, dim3(grid_for((v + 3) / 4)), dim3(256), 0, st, v, (const int*)(w + L.offsets), (const int*)(w + L.mstart),
+        hipLaunchKernelGGL(plan_base_kernel, dim3(grid_for((v + 3) / 4, kMaxGrid)), dim3(256), 0, st, v, (const int*)(w + L.offsets), (const int*)(w + L.mstart),
                            (const int*)(s + L.counts), (const int*)(s + L.tiles), (const int*)(s + L.tl_w), (const int*)(s + L.tl_cnt), s + L.tl_base, w + L.mchunk);
-        hipLaunchKernelGGL(plan_place_kernel, dim3(grid_for((t + 255) / 256)), dim3(256), 0, st, ids, ids64, t, v, (const int*)(w + L.offsets), (const int*)(s + L.info),
+        hipLaunchKernelGGL(plan_place_kernel, dim3(grid_for((t + 255) / 256, kMaxGrid)), dim3(256), 0, st, ids, ids64, t, v, (const int*)(w + L.offsets), (const int*)(s + L.info),
                            (const int*)(s + L.tl_base), w + L.pos);
     }
     HIP_TRY(hipGetLastError());
@@ -501,7 +488,7 @@ int zett_op_embed_lookup_bwd(const void* g, int32_t g_dtype, int64_t t, int64_t 
     with_dtype(g_dtype, [&](auto dt) { bwd_sum_go<elem_t<decltype(dt)::value>>(vec, st, g, e, v, w, L, partials, d_table, ld_d); });
     const int wf = vec_out ? 4 : 1;
     const int nslices = (e + 64 * wf - 1) / (64 * wf);
-    const int grid = grid_for((L.maxch * nslices + 3) / 4);
+    const int grid = grid_for((L.maxch * nslices + 3) / 4, kMaxGrid);
     if (vec_out)
         hipLaunchKernelGGL((embed_bwd_fin_kernel<4>), dim3(grid), dim3(256), 0, st, (const float*)partials, (int)e, v, w + L.offsets, w + L.mstart, w + L.mchunk, L.maxch, nslices,
                            d_table, ld_d);

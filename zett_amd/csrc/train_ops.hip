@@ -571,15 +571,14 @@ int grid_for(int64_t n) { return (int)std::min<int64_t>((n + 255) / 256, 65535);
 // `a` and `w` are 16-byte aligned for all three or the call is refused.  bias, residual and out are fp32: 4-byte aligned or
 // refused.  The 128x128 tile reads and writes them one float at a time and takes any such pointer; both 256x256 tiles (gemm8r's
 // and gemm4d's drains, generic and streamlined) move them as float4, so they additionally need 16-byte aligned bases there.
-static inline bool aligned_to(const void* p, uintptr_t bytes) { return ((uintptr_t)p & (bytes - 1)) == 0; }
 static int gemm_pointers_ok(const void* a, const void* w, const float* bias, const float* residual, const float* out) {
-    if (!aligned_to(a, 16) || !aligned_to(w, 16)) return fail(ZETT_E_INVALID, "operand pointers a and w must be 16-byte aligned");
-    if (!aligned_to(bias, 4) || !aligned_to(residual, 4) || !aligned_to(out, 4)) return fail(ZETT_E_INVALID, "bias, residual and out must be 4-byte aligned");
+    if (!aligned(a, 16) || !aligned(w, 16)) return fail(ZETT_E_INVALID, "operand pointers a and w must be 16-byte aligned");
+    if (!aligned(bias, 4) || !aligned(residual, 4) || !aligned(out, 4)) return fail(ZETT_E_INVALID, "bias, residual and out must be 4-byte aligned");
     return 0;
 }
 // what the float4 drains of the 256x256 tiles need beyond the 128x128 tile: eight columns per lane, 16-byte rows and bases
 static inline bool gemm_wide_ok(int n, const float* bias, const float* residual, int ld_res, const float* out, int ld_out) {
-    return n % 8 == 0 && ld_out % 4 == 0 && (!residual || ld_res % 4 == 0) && aligned_to(out, 16) && aligned_to(residual, 16) && aligned_to(bias, 16);
+    return n % 8 == 0 && ld_out % 4 == 0 && (!residual || ld_res % 4 == 0) && aligned(out, 16) && aligned(residual, 16) && aligned(bias, 16);
 }
 
 // 16-bit MFMA operands, fp32 accumulate and output: the tile choice of the inference path (gemm4d from K = 512, gemm8r below,
