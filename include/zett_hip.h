@@ -724,6 +724,46 @@ int zett_op_batch_vocab(const void* input_ids, int32_t ids_bytes, const void* la
                         void* ids_to_embed, void* out_surface_forms, float* out_priors, uint8_t* mask, int32_t* n_positive, int32_t* status, void* workspace,
                         int64_t workspace_bytes, void* stream);
 
+/* ---- labelling a batch (zett_amd/collate.py label_batch; additive, ABI 8) --------------------------------------------------------------
+ * What the reference's Collator.encode does between the tokenizer call and the vocabulary (collator.py:180-205): the inner collator
+ * (MLM: the arithmetic of transformers' DataCollatorForLanguageModeling.numpy_mask_tokens; CLM: labels = input_ids), then byte_lengths
+ * and the two metrics, taken on the ids AFTER masking (csrc/train_batch.hip).  input_ids: [b, s] of ids_bytes (4 or 8) with leading
+ * dimension ld_in >= s; position p = row * s + column is the logical index whatever ld_in is.  "special" = the id is one of special_ids
+ * (HOST array, n_special <= ZETT_SPLICE_MAX_ROWS ids of [0, v)).  byte_lengths_per_token: v elements of table_bytes (4 or 8).
+ * ZETT_LABEL_MLM, with mix64 the finalizer of splitmix64 and all arithmetic mod 2^64:
+ *   key_i  = mix64(seed + (i + 1) * 0x9E3779B97F4A7C15)   i = 0 .. 3;     h_i(p) = mix64(key_i ^ p);     k_i(p) = h_i(p) >> 11   (53 bits)
+ *   masked   = not special and k_0 < t_mask;   replaced = masked and k_1 < t_replace;   random = masked, not replaced and k_2 < t_random
+ *   labels   = masked ? id : -100;   out_input_ids = replaced ? mask_token_id : random ? h_3(p) mod vocab_len : id
+ * A threshold is ceil(probability * 2^53), so that k < t <=> k * 2^-53 < probability; at most 2^53.  1 <= vocab_len <= v.
+ * ZETT_LABEL_CLM: labels = out_input_ids = input_ids; thresholds, seed and mask_token_id are not read.
+ *   byte_lengths[p] = byte_lengths_per_token[out_input_ids[p]]     int64, [b, s] contiguous, like labels (width of input_ids)
+ *   record   = { t, n_non_special, byte_sum_non_special, n_unk, n_masked, n_replaced, n_random, status }   8 int64 on the device;
+ *              non-special and unk (out_input_ids == unk_token_id; -1: none) are counted on out_input_ids
+ *   metrics  = { byte_sum_non_special / n_non_special, n_unk / t }   2 doubles on the device: quotients of exact integers, numpy's
+ *              mean bit for bit; 0 / 0 is NaN
+ * out_input_ids ([b, s], leading dimension ld_out >= s) may be input_ids itself.  An id outside [0, v) sets ZETT_LABEL_BAD_ID in
+ * status; it is never used as an address, is never masked, counts as non-special and has byte length 0.  Integers only, added in a
+ * fixed order (lanes, waves, workgroups): the same inputs give the same bits.  Positions and ids are indexed with 32 bits: b, b * s and v
+ * above 0x7fffff00 are ZETT_E_INVALID.  Two launches on `stream`, no allocation, no host read;
+ * `workspace`: ZETT_LABEL_WORKSPACE_BYTES on the device, 8-byte aligned, free once the call's work is done. */
+#define ZETT_LABEL_WORKSPACE_BYTES 16384
+enum zett_label_mode { ZETT_LABEL_CLM = 0, ZETT_LABEL_MLM = 1 };
+enum zett_label_status { ZETT_LABEL_BAD_ID = 1 };
+int zett_op_label_batch(const void* input_ids, int32_t ids_bytes, int64_t ld_in, int64_t b, int32_t s, const int32_t* special_ids, int32_t n_special,
+                        const void* byte_lengths_per_token, int32_t table_bytes, int64_t v, int64_t vocab_len, int64_t mask_token_id, int64_t unk_token_id, int32_t mode,
+                        uint64_t t_mask, uint64_t t_replace, uint64_t t_random, uint64_t seed, void* out_input_ids, int64_t ld_out, void* labels, int64_t* byte_lengths,
+                        int64_t* record, double* metrics, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ---- the padded vocabulary (zett_amd/collate.py pad_vocabulary; additive, ABI 8) ----------------------------------------------------------
+ * The branch of Collator.encode without n_token_subsample (collator.py:283-337): the whole vocabulary, padded to r >= v rows.
+ *   out_surface_forms[i, 0:l] = i < v ? surface_forms[i, 0:l] : 0        [r, l] contiguous, sf_bytes (4 or 8) like the input (ld_sf >= l)
+ *   out_priors[i] = i < v ? (float)priors[i] : -100000                   priors: v elements of priors_bytes (4: float, 8: double, rounded
+ *                                                                        once to nearest even)
+ *   mask[i] = i < v;     ids_to_embed[i] = i < v ? i : 0                 (int64)
+ * Limits, ZETT_E_INVALID beyond them: 0 < l <= 65536 columns, r <= 0x7fffff00 rows.  One launch on `stream`; nothing is read back. */
+int zett_op_pad_vocabulary(const void* surface_forms, int32_t sf_bytes, int64_t ld_sf, int32_t l, int64_t v, int64_t r, const void* priors, int32_t priors_bytes,
+                           void* out_surface_forms, float* out_priors, uint8_t* mask, int64_t* ids_to_embed, void* stream);
+
 /* ---- text encoding (zett_amd/text_encode.py DeviceTextEncoder, training.encode_texts; additive, ABI 8) ----------------------------
  * The tokenizer call of the reference's Collator.encode (collator.py:166-175: tokenizer(texts, max_length=block_size, truncation=True,
  * padding="max_length", add_special_tokens=True)) and its special_ids_map patch (collator.py:177-178), on UTF-8 text that is already on

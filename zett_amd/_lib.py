@@ -29,6 +29,9 @@ SPLICE_MAX_ROWS = 256                                # ZETT_SPLICE_MAX_ROWS
 EMBED_BWD_CHUNK = 64                                 # ZETT_EMBED_BWD_CHUNK
 BATCH_POSITIVES_ONLY, BATCH_RANDOM = 0, 1            # zett_batch_mode
 BATCH_BAD_ID, BATCH_OVERFLOW, BATCH_BAD_ORDER, BATCH_REPEAT = 1, 2, 4, 8      # zett_batch_status
+LABEL_CLM, LABEL_MLM = 0, 1                          # zett_label_mode
+LABEL_BAD_ID = 1                                     # zett_label_status
+LABEL_WORKSPACE_BYTES = 16384                        # ZETT_LABEL_WORKSPACE_BYTES
 ENCODE_MAX_TEMPLATE = 8                              # ZETT_ENCODE_MAX_TEMPLATE
 ENCODE_MARKS_ARE_LETTERS, ENCODE_RESPLIT = 1, 2      # zett_encode_flags
 ENCODE_PREFIX_NONE, ENCODE_PREFIX_ALWAYS, ENCODE_PREFIX_UNLESS_SPACE = 0, 1, 2      # zett_encode_prefix
@@ -60,6 +63,8 @@ ABI_SYMBOLS = (
     "zett_op_splice_rows", "zett_op_embed_lookup", "zett_op_embed_lookup_workspace_bytes", "zett_op_embed_lookup_plan", "zett_op_embed_lookup_bwd",
     # the batch's sub-vocabulary (zett_amd/training.py subsample_batch_vocabulary)
     "zett_op_batch_vocab_workspace_bytes", "zett_op_batch_vocab",
+    # the rest of the collator (zett_amd/collate.py label_batch, pad_vocabulary)
+    "zett_op_label_batch", "zett_op_pad_vocabulary",
     # text encoding (zett_amd/text_encode.py DeviceTextEncoder)
     "zett_encode_workspace_bytes", "zett_encode_texts",
     # tokenizer sampling (zett_amd/tokenizer_sampling.py DeviceTokenizerSampler)
@@ -222,6 +227,9 @@ def load():
         lib.zett_op_embed_lookup_bwd.argtypes = [P, I32, I64, I64, I32, P, I64, P, I64, P, I64, P]
         lib.zett_op_batch_vocab_workspace_bytes.argtypes = [I64, I64, I64, C.POINTER(I64)]
         lib.zett_op_batch_vocab.argtypes = [P, I32, P, I32, I64, I64, I64, P, I32, I64, I32, P, P, I32, I32, P, P, P, I32, P, P, P, P, P, P, P, P, P, I64, P]
+        U64 = C.c_uint64
+        lib.zett_op_label_batch.argtypes = [P, I32, I64, I64, I32, P, I32, P, I32, I64, I64, I64, I64, I32, U64, U64, U64, U64, P, I64, P, P, P, P, P, I64, P]
+        lib.zett_op_pad_vocabulary.argtypes = [P, I32, I64, I32, I64, I64, P, I32, P, P, P, P, P]
         lib.zett_encode_workspace_bytes.argtypes = [I64, I64, C.POINTER(I64)]
         lib.zett_encode_texts.argtypes = [P, P, P, I64, I64, P, I64, I32, I32, I32, P, I32, P, I32, P, P, I32, I32, P, P, I32, I64, P, I64, P, P]
         lib.zett_sampler_create.argtypes = [C.c_int, I32, I64, I64, I64, C.POINTER(P)]

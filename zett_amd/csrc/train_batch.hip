@@ -8,6 +8,11 @@
 // contiguous segment, so no launch waits for another workgroup; the inverse table is written
 // with an integer max.  OR and max do not depend on arrival order: the same inputs give the same bits.  An id outside [0, V) is
 // reported in the status word and never becomes an address.
+//
+// Two more pieces of the collator live here.  zett_op_label_batch (collator.py:180-205): one streaming pass over the positions writes
+// the MLM (or CLM) labels, the masked ids, byte_lengths and integer counts per workgroup; a one-workgroup finalize adds the counts in
+// workgroup order and forms the two metrics as quotients of exact integers.  zett_op_pad_vocabulary (collator.py:283-337): one launch
+// that copies the vocabulary's rows and fills the rows behind them.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -269,6 +274,119 @@ int shape_args(int64_t t, int64_t v, int64_t n) {
     return 0;
 }
 
+// ---- labels, byte lengths and metrics of a batch (include/zett_hip.h, "labelling a batch"; collator.py:180-205) ----------------------
+constexpr int kLabelGrid = ZETT_LABEL_WORKSPACE_BYTES / 64;          // workgroups of the labelling pass: one row of 8 int64 partials each
+
+struct LabelSpecials {
+    int32_t n;
+    int32_t id[kListMax];
+};
+static_assert(kLabelGrid == 256, "label_finalize_kernel has one thread per workgroup of the labelling pass");
+static_assert(sizeof(LabelSpecials) < 4096 - 256, "the list must fit the kernel-argument limit");
+
+struct LabelKeys { uint64_t key[4]; uint64_t t_mask, t_replace, t_random; };
+
+__device__ __forceinline__ bool is_special(const LabelSpecials& sp, int64_t id) {
+    bool hit = false;
+    for (int i = 0; i < sp.n; ++i) hit |= id == sp.id[i];
+    return hit;
+}
+
+__device__ __forceinline__ int64_t wave_sum_i64(int64_t v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+
+// One pass over the T = b * s positions.  A thread takes positions p, p + grid * 256, ...; p is the LOGICAL index (row * s + column),
+// the addresses use the leading dimensions.  Every count is an integer: lanes, then the four waves (LDS, fixed order), then one row of
+// partials per workgroup, which label_finalize_kernel adds in workgroup order.
+__global__ __launch_bounds__(256) void label_batch_kernel(const void* ids, int wide, int64_t ld_in, int64_t t, int s, int64_t v, const void* __restrict__ table,
+                                                          int table64, int64_t vocab_len, int64_t mask_id, int64_t unk_id, int mlm, const LabelKeys k, void* ids_out,
+                                                          int64_t ld_out, void* __restrict__ labels, int64_t* __restrict__ byte_lengths, int64_t* __restrict__ partials,
+                                                          const LabelSpecials sp) {
+    __shared__ int64_t s_red[4][8];
+    int64_t c[8] = {0, 0, 0, 0, 0, 0, 0, 0};          // -, non-special, their bytes, unk, masked, replaced, random, bad
+    for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < t; p += (int64_t)gridDim.x * 256) {
+        const int64_t row = (uint32_t)p / (uint32_t)s, col = p - row * s;          // (t < 2^31)
+        const int64_t id = load_id(ids, wide, row * ld_in + col);          // (ids_out may be ids: a position is read, then written, by one thread)
+        const bool ok = id >= 0 && id < v;
+        int64_t out = id, label = id;
+        if (mlm) {
+            const bool masked = ok && !is_special(sp, id) && (mix64(k.key[0] ^ (uint64_t)p) >> 11) < k.t_mask;
+            label = masked ? id : -100;
+            if (masked) {
+                const bool replaced = (mix64(k.key[1] ^ (uint64_t)p) >> 11) < k.t_replace;
+                const bool random = !replaced && (mix64(k.key[2] ^ (uint64_t)p) >> 11) < k.t_random;
+                if (replaced) out = mask_id;
+                if (random) out = (int64_t)(mix64(k.key[3] ^ (uint64_t)p) % (uint64_t)vocab_len);
+                c[4] += 1;
+                c[5] += replaced;
+                c[6] += random;
+            }
+        }
+        const int64_t bytes = ok ? load_id(table, table64, out) : 0;          // (a replaced id is mask_id or below vocab_len: both inside the table)
+        const bool plain = !is_special(sp, out);
+        c[1] += plain;
+        c[2] += plain ? bytes : 0;
+        c[3] += unk_id >= 0 && out == unk_id;
+        c[7] |= !ok;
+        store_id(ids_out, wide, row * ld_out + col, out);
+        store_id(labels, wide, p, label);
+        byte_lengths[p] = bytes;
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int i = 1; i < 8; ++i) {
+        const int64_t w = wave_sum_i64(c[i]);
+        if (lane == 0) s_red[wave][i] = w;
+    }
+    __syncthreads();
+    if (threadIdx.x >= 1 && threadIdx.x < 8) partials[(int64_t)blockIdx.x * 8 + threadIdx.x] = s_red[0][threadIdx.x] + s_red[1][threadIdx.x] + s_red[2][threadIdx.x] + s_red[3][threadIdx.x];
+}
+
+// the record and the two quotients: thread g takes the partials of workgroup g (at most kLabelGrid = 256 of them); lanes, then waves
+__global__ __launch_bounds__(256) void label_finalize_kernel(const int64_t* __restrict__ partials, int n_groups, int64_t t, int64_t* __restrict__ record, double* __restrict__ metrics) {
+    __shared__ int64_t s_red[4][8];
+    __shared__ int64_t s_sum[8];
+    const int g = threadIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int i = 1; i < 8; ++i) {
+        const int64_t w = wave_sum_i64(g < n_groups ? partials[(int64_t)g * 8 + i] : 0);
+        if (lane == 0) s_red[wave][i] = w;
+    }
+    __syncthreads();
+    if (g < 8) {
+        int64_t sum = g ? s_red[0][g] + s_red[1][g] + s_red[2][g] + s_red[3][g] : t;
+        if (g == 7) sum = sum ? ZETT_LABEL_BAD_ID : 0;
+        record[g] = sum;
+        s_sum[g] = sum;
+    }
+    __syncthreads();
+    if (g == 0) {
+        metrics[0] = (double)s_sum[2] / (double)s_sum[1];          // 0 / 0: NaN, numpy's mean of nothing
+        metrics[1] = (double)s_sum[3] / (double)t;
+    }
+}
+
+// ---- the padded vocabulary (collator.py:283-337) ------------------------------------------------------------------------------------------
+template <typename TE, typename TP>
+__global__ __launch_bounds__(256) void pad_vocab_kernel(const TE* __restrict__ sf, int64_t ld, int l, int64_t v, int64_t r, const TP* __restrict__ priors, TE* __restrict__ sf_out,
+                                                        float* __restrict__ priors_out, uint8_t* __restrict__ mask, int64_t* __restrict__ ids_to_embed) {
+    const int64_t total = r * l;
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
+        const int64_t row = e / l;
+        const int col = (int)(e - row * l);
+        const bool live = row < v;
+        sf_out[e] = live ? sf[row * ld + col] : (TE)0;
+        if (col == 0) {
+            priors_out[row] = live ? (float)priors[row] : -100000.0f;          // (a float64 prior is rounded once, to nearest even)
+            mask[row] = live;
+            ids_to_embed[row] = live ? row : 0;
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -348,6 +466,69 @@ int zett_op_batch_vocab(const void* input_ids, int32_t ids_bytes, const void* la
 #undef ZETT_ROWS
     if (t) hipLaunchKernelGGL(batch_remap_kernel, dim3(grid_for((t + 255) / 256, kMaxGrid)), dim3(256), 0, st, input_ids, ids64, labels, labels64, t, v, (const int*)(w + L.inv),
                               out_input_ids, out_labels);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int zett_op_label_batch(const void* input_ids, int32_t ids_bytes, int64_t ld_in, int64_t b, int32_t s, const int32_t* special_ids, int32_t n_special,
+                        const void* byte_lengths_per_token, int32_t table_bytes, int64_t v, int64_t vocab_len, int64_t mask_token_id, int64_t unk_token_id, int32_t mode,
+                        uint64_t t_mask, uint64_t t_replace, uint64_t t_random, uint64_t seed, void* out_input_ids, int64_t ld_out, void* labels, int64_t* byte_lengths,
+                        int64_t* record, double* metrics, void* workspace, int64_t workspace_bytes, void* stream) {
+    if (b <= 0 || s <= 0 || v <= 0) return fail(ZETT_E_INVALID, "labelling needs b > 0 rows of s > 0 positions and a table of v > 0 ids (b = %lld, s = %d, v = %lld)", (long long)b, (int)s, (long long)v);
+    const int64_t t = b * (int64_t)s;
+    if (b > 0x7fffff00LL || t > 0x7fffff00LL || v > 0x7fffff00LL) return fail(ZETT_E_INVALID, "positions and ids are indexed with 32 bits (t = %lld, v = %lld)", (long long)t, (long long)v);
+    if (mode != ZETT_LABEL_CLM && mode != ZETT_LABEL_MLM) return fail(ZETT_E_INVALID, "unknown mode %d", (int)mode);
+    if (!width_ok(ids_bytes) || !width_ok(table_bytes)) return fail(ZETT_E_INVALID, "ids and byte lengths must be int32 or int64");
+    if (!input_ids || !byte_lengths_per_token || !out_input_ids || !labels || !byte_lengths || !record || !metrics) return fail(ZETT_E_INVALID, "null argument");
+    if (ld_in < s || ld_out < s) return fail(ZETT_E_INVALID, "a row of %d positions needs leading dimensions >= %d (ld_in = %lld, ld_out = %lld)", (int)s, (int)s, (long long)ld_in, (long long)ld_out);
+    if (n_special < 0 || n_special > kListMax) return fail(ZETT_E_INVALID, "%d special ids are listed, at most %d travel with a launch", (int)n_special, kListMax);
+    if (n_special && !special_ids) return fail(ZETT_E_INVALID, "null argument");
+    if (vocab_len <= 0 || vocab_len > v) return fail(ZETT_E_INVALID, "vocab_len = %lld must be in [1, v = %lld]: a random id is an index of the byte-length table", (long long)vocab_len, (long long)v);
+    if (unk_token_id < -1) return fail(ZETT_E_INVALID, "unk_token_id is an id or -1 for none, got %lld", (long long)unk_token_id);
+    const int mlm = mode == ZETT_LABEL_MLM;
+    if (mlm && (mask_token_id < 0 || mask_token_id >= v)) return fail(ZETT_E_INDEX, "mask_token_id %lld is outside [0, %lld)", (long long)mask_token_id, (long long)v);
+    const uint64_t one = 1ull << 53;
+    if (mlm && (t_mask > one || t_replace > one || t_random > one)) return fail(ZETT_E_INVALID, "a threshold is ceil(probability * 2^53): at most 2^53");
+    LabelSpecials sp{};
+    sp.n = n_special;
+    for (int i = 0; i < n_special; ++i) {
+        if (special_ids[i] < 0 || special_ids[i] >= v) return fail(ZETT_E_INDEX, "special id %d is outside [0, %lld)", (int)special_ids[i], (long long)v);
+        sp.id[i] = special_ids[i];
+    }
+    if (!workspace || !aligned(workspace, 8)) return fail(ZETT_E_INVALID, "null or misaligned workspace");
+    if (workspace_bytes < ZETT_LABEL_WORKSPACE_BYTES) return fail(ZETT_E_INVALID, "the workspace holds %lld bytes, %d are needed", (long long)workspace_bytes, (int)ZETT_LABEL_WORKSPACE_BYTES);
+    LabelKeys k{};
+    for (int i = 0; i < 4; ++i) k.key[i] = mix64(seed + (uint64_t)(i + 1) * 0x9E3779B97F4A7C15ull);
+    k.t_mask = t_mask;
+    k.t_replace = t_replace;
+    k.t_random = t_random;
+    hipStream_t st = (hipStream_t)stream;
+    const int grid = grid256(t, kLabelGrid);
+    hipLaunchKernelGGL(label_batch_kernel, dim3(grid), dim3(256), 0, st, input_ids, (int)(ids_bytes == 8), ld_in, t, (int)s, v, byte_lengths_per_token, (int)(table_bytes == 8),
+                       vocab_len, mask_token_id, unk_token_id, mlm, k, out_input_ids, ld_out, labels, byte_lengths, (int64_t*)workspace, sp);
+    hipLaunchKernelGGL(label_finalize_kernel, dim3(1), dim3(256), 0, st, (const int64_t*)workspace, grid, t, record, metrics);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int zett_op_pad_vocabulary(const void* surface_forms, int32_t sf_bytes, int64_t ld_sf, int32_t l, int64_t v, int64_t r, const void* priors, int32_t priors_bytes,
+                           void* out_surface_forms, float* out_priors, uint8_t* mask, int64_t* ids_to_embed, void* stream) {
+    if (v <= 0 || r < v) return fail(ZETT_E_INVALID, "the padded vocabulary needs v > 0 rows and r >= v (v = %lld, r = %lld)", (long long)v, (long long)r);
+    if (r > 0x7fffff00LL) return fail(ZETT_E_INVALID, "rows are indexed with 32 bits (r = %lld)", (long long)r);
+    if (!width_ok(sf_bytes)) return fail(ZETT_E_INVALID, "surface forms must be int32 or int64");
+    if (!width_ok(priors_bytes)) return fail(ZETT_E_INVALID, "priors must be float32 or float64");
+    if (l <= 0 || l > kMaxL || ld_sf < l) return fail(ZETT_E_INVALID, "surface forms need 0 < l <= %d columns and ld_sf >= l (l = %d, ld_sf = %lld)", kMaxL, (int)l, (long long)ld_sf);
+    if (!surface_forms || !priors || !out_surface_forms || !out_priors || !mask || !ids_to_embed) return fail(ZETT_E_INVALID, "null argument");
+    hipStream_t st = (hipStream_t)stream;
+    const int grid = grid256(r * l, kMaxGrid);
+#define ZETT_PAD(TE, TP)                                                                                                                                          \
+    hipLaunchKernelGGL((pad_vocab_kernel<TE, TP>), dim3(grid), dim3(256), 0, st, (const TE*)surface_forms, ld_sf, (int)l, v, r, (const TP*)priors, (TE*)out_surface_forms, \
+                       out_priors, mask, ids_to_embed)
+    if (sf_bytes == 8 && priors_bytes == 8) ZETT_PAD(int64_t, double);
+    else if (sf_bytes == 8) ZETT_PAD(int64_t, float);
+    else if (priors_bytes == 8) ZETT_PAD(int32_t, double);
+    else ZETT_PAD(int32_t, float);
+#undef ZETT_PAD
     HIP_TRY(hipGetLastError());
     return 0;
 }

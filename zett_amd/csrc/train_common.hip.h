@@ -1,6 +1,6 @@
 // train_common.hip.h — the small device / host layer the four training units (train_ops.hip, train_step.hip, train_loss.hip,
 // train_embed.hip) share: element accessors over gemm.hip.h's conversions (to_lo, lo_to_f32, pack2_lo, unpack2_lo: widen on load —
-// bf16 by the 16-bit left shift —, round to nearest even on store), the reductions and the id read.  (The zett_dtype ->
+// bf16 by the 16-bit left shift —, round to nearest even on store), the reductions, the id read and the splitmix64 finalizer.  (The zett_dtype ->
 // storage-type map and the dtype dispatch of the launches — elem_t, is_dtype, with_dtype — are common.hip.h's: the forward uses
 // them too.)  The device helpers here hold only conversions and additions, so a caller's `#pragma clang fp contract(off)` keeps
 // its meaning.  Training only (zett_amd/build.py TRAINING_ONLY): no forward source includes it.
@@ -46,6 +46,14 @@ template <typename T> struct Convert<T, T> { static __device__ __forceinline__ T
 
 __device__ __forceinline__ int64_t load_id(const void* ids, int ids64, int64_t i) {
     return ids64 ? ((const int64_t*)ids)[i] : (int64_t)((const int32_t*)ids)[i];
+}
+
+// the finalizer of splitmix64, for the host (the keys of a call) and the device (a draw per position): zett_op_label_batch.  (The
+// tokenizer sampler keeps its own device copy in tokenizer_sample.hip: that unit is not a training unit and does not include this header.)
+__host__ __device__ __forceinline__ uint64_t mix64(uint64_t x) {
+    x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull;
+    x ^= x >> 27; x *= 0x94D049BB133111EBull;
+    return x ^ (x >> 31);
 }
 
 // ---- reductions -----------------------------------------------------------------------------------------------------------------

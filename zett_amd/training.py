@@ -854,6 +854,8 @@ from .text_encode import DeviceTextEncoder, encode_texts  # noqa: E402,F401
 from .tokenizer_sampling import DeviceTokenizerSampler, sample_tokenizer  # noqa: E402,F401
 # ---- that tokenizer's vocabulary and encoder tables without the host Tokenizer: zett_amd/sampled_vocab.py -------------------------------------
 from .sampled_vocab import DeviceSampledVocabulary, SampledVocabulary, sample_tokenizer_device  # noqa: E402,F401
+# ---- the rest of the collator (collator.py:180-205, 283-337, 454-537): zett_amd/collate.py --------------------------------------------------------
+from .collate import DeviceCollator, LabelledBatch, PaddedVocabulary, label_batch, mlm_thresholds, pad_vocabulary, padded_rows  # noqa: E402,F401
 
 
 # ---- which parameters train, and which decay -------------------------------------------------------------------------------
