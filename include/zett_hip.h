@@ -568,6 +568,14 @@ int zett_op_gather_fwd_f32(const int32_t* ids, int64_t n_tokens, const void* src
                            const float* sw, const float* sb, float* x, void* stream);
 int zett_op_gather_bwd_f32(const int32_t* ids, int64_t n_tokens, const void* src, int32_t src_dtype, int32_t e_in, int32_t v0, const float* dx,
                            float* dfallback, float* prod, float* keep, void* stream);
+/* The order-stable form of the gather's backward (ZettHypernet.train_deterministic): prod and keep exactly as zett_op_gather_bwd_f32
+ * writes them — the same kernel with the fallback branch compiled out, the same bits for fp32 / f16 / bf16 sources — and NO fallback sum:
+ * no dfallback argument, no atomic.  d fallback is then zett_op_embed_lookup_bwd(g = dx) over the plan
+ * zett_op_embed_lookup_plan_base(ids, id_base = v0, v = fallback rows), i.e. per fallback row the sum that entry point defines
+ * (ascending positions, fp32 partials of ZETT_EMBED_BWD_CHUNK positions added left to right, the partials added in ascending chunk
+ * order, a row with no position zeros).  A null pointer, an unknown dtype, n_tokens < 0, e_in <= 0 or v0 < 0: ZETT_E_INVALID. */
+int zett_op_gather_bwd_rows_f32(const int32_t* ids, int64_t n_tokens, const void* src, int32_t src_dtype, int32_t e_in, int32_t v0, const float* dx, float* prod,
+                                float* keep, void* stream);
 
 /* ---- the losses and the parameter update of a training step (zett_amd/training.py) ----------------------------------------------
  * What the reference's trainer puts around the hypernetwork forward: the squared-error loss of the identity warm-up
@@ -679,6 +687,15 @@ int zett_op_embed_lookup_workspace_bytes(int64_t t, int64_t v, int32_t e, int64_
  * on tile indices and counts alone): the plan is a pure function of ids.  `plan`, `scratch`: device, 4-byte aligned, sizes as queried. */
 int zett_op_embed_lookup_plan(const void* ids, int32_t ids_bytes, int64_t t, int64_t v, void* plan, int64_t plan_bytes, void* scratch, int64_t scratch_bytes,
                               void* stream);
+/* The same plan over SHIFTED ids: the inverted index of ids[p] - id_base over [0, v) — row r lists the positions that hold the id
+ * id_base + r, ascending; an id outside [id_base, id_base + v) is in no list.  The same kernels with one more integer argument;
+ * zett_op_embed_lookup_plan is the id_base = 0 case and writes the same plan words as ever.  Sizes as queried for (t, v).  With
+ * zett_op_embed_lookup_bwd this is "sum the rows of g that share an index" for any index array, in the order defined there: the
+ * fallback rows of the hypernetwork take ids in [v0, v0 + F) to rows [0, F) with id_base = v0.  id_base and id_base + v must be
+ * 32-bit values (rows are indexed with 32 bits): otherwise ZETT_E_INVALID, as for ids_bytes outside {4, 8}, t < 0, v <= 0, a null,
+ * misaligned or too small plan or scratch.  Everything is checked before the first launch. */
+int zett_op_embed_lookup_plan_base(const void* ids, int32_t ids_bytes, int64_t t, int64_t id_base, int64_t v, void* plan, int64_t plan_bytes, void* scratch,
+                                   int64_t scratch_bytes, void* stream);
 /* d_table[id, 0:e] for EVERY id in [0, v), each row written exactly once (no memset, no read-modify-write): with p_0 < p_1 < ... the
  * positions of id and C = ZETT_EMBED_BWD_CHUNK,
  *     partial_j = ((g[p_jC] + g[p_jC+1]) + ...) + g[p_jC+C-1]        fp32, ascending positions, the last chunk ragged

@@ -3,7 +3,7 @@
 the backward to every hypernetwork parameter (what train.py:1007-1013 does once per training step on a sampled
 vocabulary), through zett_amd/autograd.py.
 
-    python tools/train_bench.py [--workload mistral_gpt2_32k] [--rows N] [--steps K] [--dense]
+    python tools/train_bench.py [--workload mistral_gpt2_32k] [--rows N] [--steps K] [--dense] [--deterministic]
 
 Prints one JSON line: rows/s, ms per step (forward / backward split by HIP events), the GEMM FLOPs of a step (counted at
 the C-ABI calls: forward + dgrad + wgrad) and the rate they imply against the fp32-MFMA roof (157.3 TFLOP/s) — a LOWER
@@ -34,6 +34,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--precision", default="f32", choices=["f32", "bf16", "f16"], help="arithmetic of the dense contractions (forward, dgrad, wgrad)")
     ap.add_argument("--dense", action="store_true", help="the reference's dense layout instead of the packed schedule")
+    ap.add_argument("--deterministic", action="store_true", help="model.train_deterministic: the backward's index sums in a fixed order, no float atomics")
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
     cfg, rows, src_dtype, hist = synth.workload(args.workload)
@@ -46,6 +47,8 @@ def main():
     model.requires_grad_(True).train()
     model.train_packed = not args.dense
     model.train_precision = args.precision
+    if args.deterministic:
+        model.train_deterministic = True
     peak = {"f32": 157.3, "bf16": 2500.0, "f16": 2500.0}[args.precision]
     src = torch.from_numpy(synth.make_source_embeddings(cfg, seed=0, dtype=src_dtype)).to(dev)
     ids = torch.from_numpy(synth.make_surface_forms(cfg, rows, seed=0, hist=hist)).to(dev)
@@ -84,13 +87,16 @@ def main():
     t_f = t_b = 0.0
     torch.cuda.synchronize()
     t0 = time.perf_counter()
+    step_ms = []
     for _ in range(args.steps):
+        t1 = time.perf_counter()
         step()
+        step_ms.append((time.perf_counter() - t1) * 1e3)
     dt = time.perf_counter() - t0
     per = flops["n"] / args.steps
     print(json.dumps({"metric": "training step of the embedding-prediction path (forward + backward to every parameter)",
-                      "workload": args.workload, "rows": rows, "schedule": "dense" if args.dense else "packed (levers 1-3)", "dtype": args.precision,
-                      "rows_per_s": rows * args.steps / dt, "ms_per_step": dt / args.steps * 1e3,
+                      "workload": args.workload, "rows": rows, "schedule": "dense" if args.dense else "packed (levers 1-3)", "dtype": args.precision, "deterministic": bool(args.deterministic),
+                      "rows_per_s": rows * args.steps / dt, "ms_per_step": dt / args.steps * 1e3, "ms_per_step_min": min(step_ms), "ms_per_step_max": max(step_ms),
                       "forward_ms": t_f / args.steps, "backward_ms": t_b / args.steps,
                       "gemm_tflop_per_step": per / 1e12, "gemm_tflops_lower_bound": per / (dt / args.steps) / 1e12, "mfma_peak_tflops": peak,
                       "frac_lower_bound": per / (dt / args.steps) / 1e12 / peak,

@@ -72,6 +72,8 @@ ABI_SYMBOLS = (
     # the sampled tokenizer's vocabulary and encoder tables (zett_amd/sampled_vocab.py DeviceSampledVocabulary)
     "zett_retok_create_unigram_device", "zett_sampled_vocab_workspace_bytes", "zett_sampled_vocab_build", "zett_sampled_vocab_commit", "zett_sampled_vocab_table",
     "zett_sampled_vocab_patch_rows",
+    # the order-stable sums of the hypernetwork's backward (zett_amd/autograd.py, deterministic=True)
+    "zett_op_embed_lookup_plan_base", "zett_op_gather_bwd_rows_f32",
 )
 
 
@@ -207,6 +209,7 @@ def load():
         lib.zett_op_scatter_add_rows_f32.argtypes = [P, I32, P, P, I64, I32, P]
         lib.zett_op_gather_fwd_f32.argtypes = [P, I64, P, I32, I32, I32, P, P, P, P, P]
         lib.zett_op_gather_bwd_f32.argtypes = [P, I64, P, I32, I32, I32, P, P, P, P, P]
+        lib.zett_op_gather_bwd_rows_f32.argtypes = [P, I64, P, I32, I32, I32, P, P, P, P]
         D = C.c_double
         lib.zett_op_single_token_mask.argtypes = [P, I32, I64, I32, I64, I64, P, P]
         lib.zett_op_embed_dist_rows.argtypes = [P, I64, P, I32, I64, I64, I32, P, I32, I64, P, I64, I32, I32, P, P, P]
@@ -224,6 +227,7 @@ def load():
         lib.zett_op_embed_lookup.argtypes = [P, I32, I64, I64, I32, P, I32, I64, P, I32, P, P]
         lib.zett_op_embed_lookup_workspace_bytes.argtypes = [I64, I64, I32, C.POINTER(I64), C.POINTER(I64), C.POINTER(I64)]
         lib.zett_op_embed_lookup_plan.argtypes = [P, I32, I64, I64, P, I64, P, I64, P]
+        lib.zett_op_embed_lookup_plan_base.argtypes = [P, I32, I64, I64, I64, P, I64, P, I64, P]
         lib.zett_op_embed_lookup_bwd.argtypes = [P, I32, I64, I64, I32, P, I64, P, I64, P, I64, P]
         lib.zett_op_batch_vocab_workspace_bytes.argtypes = [I64, I64, I64, C.POINTER(I64)]
         lib.zett_op_batch_vocab.argtypes = [P, I32, P, I32, I64, I64, I64, P, I32, I64, I32, P, P, I32, I32, P, P, P, I32, P, P, P, P, P, P, P, P, P, I64, P]

@@ -24,6 +24,10 @@ the headline workload.  The dense contractions run in exact fp32 MFMA (default) 
 ``model.train_precision``; operands converted — and for dgrad / wgrad transposed in the same pass — per launch, fp32
 accumulation, everything else fp32).  bf16 is the 16-bit mode to train in: f16 operands are ~8x more accurate but have the
 half range and there is no loss scaling here — a step whose gradients overflow raises RangeError instead of returning NaNs.
+
+The backward adds rows that share an index (per position, per distinct id, per fallback row) with float atomics by default: sums in no
+fixed order.  ``model.train_deterministic`` / ``deterministic=True`` takes them in the fixed order of ``Ops.index_sum_rows`` instead
+(the inverted-index plan and chunked sum of the token lookup's backward): gradients are then the same bits on every run.
 """
 from __future__ import annotations
 
@@ -304,9 +308,28 @@ class Ops:
                                                    _ptr(x), self._stream()), "zett_op_gather_fwd_f32")
         return x
 
-    def gather_bwd(self, ids, src, v0, dx, n_fallback):
-        """-> dfallback [n_fallback, E_in], d in_scaler.w [E_in], d in_scaler.b [E_in]"""
+    def index_sum_rows(self, idx, src, n_dst, id_base=0):
+        """out[r] = the sum of the rows src[p] with idx[p] - id_base == r, r < n_dst -> [n_dst, cols] fp32, in the fixed order of
+        zett_op_embed_lookup_bwd (ascending p, fp32 partials of 64 rows, the partials in ascending order; no such p: zeros): the
+        inverted index of idx (integers, a pure function of idx) and an output-stationary sum that writes every row once.  An
+        index outside [id_base, id_base + n_dst) is in no sum.  Nothing is read back to the host."""
+        from . import training
+        assert src.dim() == 2 and src.is_contiguous() and idx.is_contiguous() and idx.numel() == src.shape[0] and idx.dtype in (torch.int32, torch.int64)
+        t, cols = src.shape
+        if n_dst == 0 or cols == 0:
+            return self.new(n_dst, cols)
+        return training.embed_lookup_backward(src, training.embed_lookup_plan(idx, n_dst, id_base), t, n_dst, cols)
+
+    def gather_bwd(self, ids, src, v0, dx, n_fallback, deterministic=False):
+        """-> dfallback [n_fallback, E_in], d in_scaler.w [E_in], d in_scaler.b [E_in].  deterministic: the fallback rows' sum in the
+        fixed order of index_sum_rows instead of float atomics; prod / keep, and with them the two column sums, are the same bits"""
         t, e_in = dx.shape
+        if deterministic:
+            assert dx.is_contiguous()
+            prod, keep = self.new(t, e_in), self.new(t, e_in)
+            _lib.check(self.lib.zett_op_gather_bwd_rows_f32(_ptr(ids), t, _ptr(src), _SRC_DTYPES[src.dtype], e_in, v0, _ptr(dx), _ptr(prod), _ptr(keep),
+                                                            self._stream()), "zett_op_gather_bwd_rows_f32")
+            return self.index_sum_rows(ids, dx, n_fallback, id_base=v0), self.colsum(prod), self.colsum(keep)
         dfb = torch.zeros((n_fallback, e_in), dtype=torch.float32, device=self.device)
         prod, keep = self.new(t, e_in), self.new(t, e_in)
         _lib.check(self.lib.zett_op_gather_bwd_f32(_ptr(ids), t, _ptr(src), _SRC_DTYPES[src.dtype], e_in, v0, _ptr(dx), _ptr(dfb), _ptr(prod), _ptr(keep),
@@ -494,8 +517,9 @@ def forward_train(ops: Ops, dims: HypernetDims, ln_eps: float, P: Dict[str, torc
 
 
 def backward_train(ops: Ops, dims: HypernetDims, P: Dict[str, torch.Tensor], S, src: torch.Tensor, lang: int,
-                   d_in: Optional[torch.Tensor], d_out: Optional[torch.Tensor], d_bias: Optional[torch.Tensor]) -> Dict[str, torch.Tensor]:
-    """Gradients of every hypernetwork parameter, given the gradients of the three outputs."""
+                   d_in: Optional[torch.Tensor], d_out: Optional[torch.Tensor], d_bias: Optional[torch.Tensor], deterministic: bool = False) -> Dict[str, torch.Tensor]:
+    """Gradients of every hypernetwork parameter, given the gradients of the three outputs.  deterministic: the fallback rows'
+    gradient — the one sum of this schedule that is otherwise made of float atomics — in the fixed order of Ops.index_sum_rows."""
     G: Dict[str, torch.Tensor] = {}
     n, L = S["ids"].shape
     lam = 1 if dims.embed_lang else 0
@@ -542,7 +566,7 @@ def backward_train(ops: Ops, dims: HypernetDims, P: Dict[str, torch.Tensor], S, 
     # ---- input projection
     dy0 = _projector_bwd(ops, P, G, "input_projection.1.", S["pb_in"], dt)
     dx0, G["input_projection.0.weight"], G["input_projection.0.bias"] = ops.linear_bwd(dy0, S["x0"], P["input_projection.0.weight"])
-    dfb, dsw, dsb = ops.gather_bwd(S["ids"].view(-1), src, dims.original_vocab_size, dx0, P["fallback_embeddings.weight"].shape[0])
+    dfb, dsw, dsb = ops.gather_bwd(S["ids"].view(-1), src, dims.original_vocab_size, dx0, P["fallback_embeddings.weight"].shape[0], deterministic=deterministic)
     G["fallback_embeddings.weight"] = dfb
     if dims.rescale:
         # x = w * src + b on source rows: d w = sum dx * src; gather_bwd's `prod` used the raw source row
@@ -649,7 +673,11 @@ def forward_packed(ops: Ops, dims: HypernetDims, ln_eps: float, P, ids: torch.Te
     return _heads_fwd(ops, dims, P, S, cls, n, ids.device), S
 
 
-def backward_packed(ops: Ops, dims: HypernetDims, P, S, src, lang, d_in, d_out, d_bias):
+def backward_packed(ops: Ops, dims: HypernetDims, P, S, src, lang, d_in, d_out, d_bias, deterministic: bool = False):
+    """deterministic: the two sums over shared indices (per position, per distinct id) in the fixed order of Ops.index_sum_rows
+    instead of float atomics.  Their integer plans are built here, right in front of each sum, from plan["tok_pos"] and S["slot"]:
+    the forward saves nothing more.  The position-0 scatter into dz and gather_bwd over the DISTINCT ids have one addend per
+    destination and stay as they are."""
     G: Dict[str, torch.Tensor] = {}
     ids = S["ids"]
     n, L = ids.shape
@@ -711,15 +739,21 @@ def backward_packed(ops: Ops, dims: HypernetDims, P, S, src, lang, d_in, d_out, 
         A.clear()                                                               # this layer's activations are not needed again
     demb, G["model.embeddings.LayerNorm.weight"], G["model.embeddings.LayerNorm.bias"] = \
         ops.layernorm_bwd(dz, S["emb"], S["emb_st"], P["model.embeddings.LayerNorm.weight"], dy2=dz_res)
-    per_pos = torch.zeros((Lp, H), dtype=torch.float32, device=dev)
-    ops.scatter_add_rows(per_pos, plan["tok_pos"], demb)
+    if deterministic:
+        per_pos = ops.index_sum_rows(plan["tok_pos"], demb, Lp)
+    else:
+        per_pos = torch.zeros((Lp, H), dtype=torch.float32, device=dev)
+        ops.scatter_add_rows(per_pos, plan["tok_pos"], demb)
     dpos = torch.zeros_like(P["model.embeddings.position_embeddings.weight"])
     dpos[:L] = per_pos[:L]                                                     # (the language token's type / position terms cancel)
     G["model.embeddings.position_embeddings.weight"] = dpos
     G["model.embeddings.token_type_embeddings.weight"] = ops.colsum(per_pos[:L].contiguous()).reshape(1, -1)
     d_ids = S["uniq"].numel()
-    dtable = torch.zeros((d_ids + lam, H), dtype=torch.float32, device=dev)
-    ops.scatter_add_rows(dtable, S["slot"], demb)                               # lever 2 backwards: the uses of an id add up
+    if deterministic:
+        dtable = ops.index_sum_rows(S["slot"], demb, d_ids + lam)
+    else:
+        dtable = torch.zeros((d_ids + lam, H), dtype=torch.float32, device=dev)
+        ops.scatter_add_rows(dtable, S["slot"], demb)                           # lever 2 backwards: the uses of an id add up
     if lam:
         dlang = torch.zeros_like(P["lang_embeddings.weight"])
         dlang[lang] = dtable[d_ids]
@@ -738,13 +772,13 @@ class HypernetFunction(torch.autograd.Function):
     the parameters only (the reference trains the hypernetwork against frozen source embeddings)."""
 
     @staticmethod
-    def forward(ctx, dims, ln_eps, names, packed, precision, ids, src, lang, *params):
+    def forward(ctx, dims, ln_eps, names, packed, precision, deterministic, ids, src, lang, *params):
         ops = Ops(src.device, precision)
         P = {n: p.detach().float().contiguous() for n, p in zip(names, params)}
         with torch.no_grad(), torch.cuda.device(src.device):          # (the primitives launch on the CURRENT device and stream)
             fwd = forward_packed if packed else forward_train
             (pred_in, pred_out, bias), S = fwd(ops, dims, ln_eps, P, ids, src, int(lang))
-        ctx.dims, ctx.names, ctx.lang, ctx.ops = dims, names, int(lang), ops
+        ctx.dims, ctx.names, ctx.lang, ctx.ops, ctx.deterministic = dims, names, int(lang), ops, bool(deterministic)
         ctx.P, ctx.S, ctx.src = P, S, src
         ctx.has_out = pred_out is not None
         if pred_out is None:
@@ -755,7 +789,7 @@ class HypernetFunction(torch.autograd.Function):
     def backward(ctx, d_in, d_out, d_bias):
         with torch.no_grad(), torch.cuda.device(ctx.src.device):
             bwd = backward_packed if ctx.S.get("packed") else backward_train
-            G = bwd(ctx.ops, ctx.dims, ctx.P, ctx.S, ctx.src, ctx.lang, d_in, d_out if ctx.has_out else None, d_bias)
+            G = bwd(ctx.ops, ctx.dims, ctx.P, ctx.S, ctx.src, ctx.lang, d_in, d_out if ctx.has_out else None, d_bias, deterministic=ctx.deterministic)
         grads = []
         for name, p in zip(ctx.names, ctx.P.values()):
             g = G.get(name)
@@ -769,7 +803,7 @@ class HypernetFunction(torch.autograd.Function):
             if not bool(torch.isfinite(worst)):
                 raise _lib.RangeError("zett_amd: a gradient left the range of f16 MFMA operands (non-finite parameter gradients); scale the loss "
                                       "down or use model.train_precision = 'bf16' (fp32 exponent range)")
-        return (None, None, None, None, None, None, None, None, *grads)
+        return (None, None, None, None, None, None, None, None, None, *grads)
 
 
 def _check_indices(dims: HypernetDims, ids: torch.Tensor, src: torch.Tensor, lang: int) -> None:
@@ -796,12 +830,15 @@ def _check_indices(dims: HypernetDims, ids: torch.Tensor, src: torch.Tensor, lan
 
 
 def differentiable_forward(model, target_surface_forms: torch.Tensor, source_embeddings: torch.Tensor, lang_index: int, packed: bool = True,
-                           precision: str = "f32"):
+                           precision: str = "f32", deterministic: bool = False):
     """The forward of `model` (a zett_amd.hypernet.ZettHypernet) with gradients to its parameters.  packed = True (default):
     the schedule of the inference path (pad skipping, input projection per distinct id, position-0-only last layer);
     False: the reference's dense layout, every position computed — same outputs and gradients to fp32 round-off.
     precision: "f32" (exact fp32 MFMA) or "bf16" / "f16" (16-bit MFMA operands in every forward / dgrad / wgrad contraction,
-    fp32 accumulation, fp32 parameters, activations and gradients)."""
+    fp32 accumulation, fp32 parameters, activations and gradients).
+    deterministic = True: the backward's sums over shared indices — the embedding gradient per position and per distinct id (packed),
+    the fallback rows' gradient (dense) — are taken in a fixed order instead of with float atomics (Ops.index_sum_rows), so the
+    gradients are a pure function of the inputs, bit for bit.  The forward and every other gradient are the same bits in both modes."""
     # (parameters of the checkpoint contract that the forward never reads stay outside the graph: a gradient hook that waits for
     # every input of the Function — DistributedDataParallel's bucket logic — would wait for them for ever)
     _check_indices(model.dims, target_surface_forms, source_embeddings, int(lang_index))
@@ -809,6 +846,6 @@ def differentiable_forward(model, target_surface_forms: torch.Tensor, source_emb
     params = dict(model.named_parameters())
     tensors = [params[n] for n in names]
     src = source_embeddings if source_embeddings.dtype in _SRC_DTYPES else source_embeddings.float()
-    pred_in, pred_out, bias = HypernetFunction.apply(model.dims, model._ln_eps_encoder, tuple(names), bool(packed), str(precision), target_surface_forms, src.contiguous(),
+    pred_in, pred_out, bias = HypernetFunction.apply(model.dims, model._ln_eps_encoder, tuple(names), bool(packed), str(precision), bool(deterministic), target_surface_forms, src.contiguous(),
                                                      int(lang_index), *tensors)
     return pred_in, (pred_out if model.dims.separate_out else None), bias

@@ -135,10 +135,17 @@ PlanLayout plan_layout(int64_t t, int64_t v) {
     return L;
 }
 
-__global__ __launch_bounds__(256) void plan_hist_kernel(const void* __restrict__ ids, int ids64, int64_t t, int64_t v, int* __restrict__ counts) {
+// The row a position refers to: ids[p] - id_base where that lies in [0, v), else -1 (in no list, never an address).  id_base and
+// id_base + v are 32-bit values (checked on the host), so the comparison cannot overflow whatever a 64-bit id holds.
+__device__ __forceinline__ int64_t plan_row(const void* __restrict__ ids, int ids64, int64_t p, int64_t id_base, int64_t v) {
+    const int64_t x = load_id(ids, ids64, p);
+    return (x >= id_base && x < id_base + v) ? x - id_base : -1;
+}
+
+__global__ __launch_bounds__(256) void plan_hist_kernel(const void* __restrict__ ids, int ids64, int64_t t, int64_t id_base, int64_t v, int* __restrict__ counts) {
     for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < t; p += (int64_t)gridDim.x * 256) {
-        const int64_t id = load_id(ids, ids64, p);
-        if (id >= 0 && id < v) atomicAdd(counts + id, 1);
+        const int64_t id = plan_row(ids, ids64, p, id_base, v);
+        if (id >= 0) atomicAdd(counts + id, 1);
     }
 }
 
@@ -170,17 +177,14 @@ __global__ __launch_bounds__(1024) void plan_scan_kernel(const int* __restrict__
 // One wave per tile of 64 positions: a position's rank among the tile's positions of its id (ascending by construction), and one
 // entry (tile, count) per id of the tile in that id's tile list.  The SLOT of the entry is whatever the atomic hands out; what is
 // placed with it (plan_base_kernel, plan_place_kernel) depends on tile indices and counts only.
-__global__ __launch_bounds__(256) void plan_tile_kernel(const void* __restrict__ ids, int ids64, int64_t t, int64_t v, const int* __restrict__ offsets,
+__global__ __launch_bounds__(256) void plan_tile_kernel(const void* __restrict__ ids, int ids64, int64_t t, int64_t id_base, int64_t v, const int* __restrict__ offsets,
                                                         int* __restrict__ tiles, int* __restrict__ tl_w, int* __restrict__ tl_cnt, int* __restrict__ info) {
     const int lane = threadIdx.x & 63;
     const int64_t n_tiles = (t + 63) / 64;
     for (int64_t w = (int64_t)blockIdx.x * 4 + wave_index(); w < n_tiles; w += (int64_t)gridDim.x * 4) {
         const int64_t p = w * 64 + lane;
         int id = -1;
-        if (p < t) {
-            const int64_t x = load_id(ids, ids64, p);
-            if (x >= 0 && x < v) id = (int)x;
-        }
+        if (p < t) id = (int)plan_row(ids, ids64, p, id_base, v);
         int rank = 0, count = 0, first = 64;
 #pragma unroll
         for (int k = 0; k < 64; ++k) {
@@ -223,11 +227,11 @@ __global__ __launch_bounds__(256) void plan_base_kernel(int64_t v, const int* __
     }
 }
 
-__global__ __launch_bounds__(256) void plan_place_kernel(const void* __restrict__ ids, int ids64, int64_t t, int64_t v, const int* __restrict__ offsets,
+__global__ __launch_bounds__(256) void plan_place_kernel(const void* __restrict__ ids, int ids64, int64_t t, int64_t id_base, int64_t v, const int* __restrict__ offsets,
                                                          const int* __restrict__ info, const int* __restrict__ tl_base, int* __restrict__ pos) {
     for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < t; p += (int64_t)gridDim.x * 256) {
-        const int64_t id = load_id(ids, ids64, p);
-        if (id < 0 || id >= v) continue;
+        const int64_t id = plan_row(ids, ids64, p, id_base, v);
+        if (id < 0) continue;
         const int x = info[p];
         const int64_t off = offsets[id];
         pos[off + tl_base[off + (x >> 6)] + (x & 63)] = (int)p;
@@ -446,8 +450,15 @@ int zett_op_embed_lookup_workspace_bytes(int64_t t, int64_t v, int32_t e, int64_
 
 int zett_op_embed_lookup_plan(const void* ids, int32_t ids_bytes, int64_t t, int64_t v, void* plan, int64_t plan_bytes, void* scratch, int64_t scratch_bytes,
                               void* stream) {
+    return zett_op_embed_lookup_plan_base(ids, ids_bytes, t, 0, v, plan, plan_bytes, scratch, scratch_bytes, stream);
+}
+
+int zett_op_embed_lookup_plan_base(const void* ids, int32_t ids_bytes, int64_t t, int64_t id_base, int64_t v, void* plan, int64_t plan_bytes, void* scratch,
+                                   int64_t scratch_bytes, void* stream) {
     PlanLayout L;
     if (int rc = plan_args(t, v, plan, plan_bytes, &L)) return rc;
+    if (id_base < -0x80000000LL || id_base > 0x7fffffffLL || id_base + v > 0x80000000LL)
+        return fail(ZETT_E_INVALID, "the ids of the rows, [id_base, id_base + v), must be 32-bit values (id_base = %lld, v = %lld)", (long long)id_base, (long long)v);
     if (!scratch || !aligned(scratch, 4)) return fail(ZETT_E_INVALID, "null or misaligned scratch");
     if (scratch_bytes < L.scratch_words * 4) return fail(ZETT_E_INVALID, "the scratch holds %lld bytes, %lld are needed", (long long)scratch_bytes, (long long)(L.scratch_words * 4));
     if ((t && !ids) || (ids_bytes != 4 && ids_bytes != 8)) return fail(ZETT_E_INVALID, "ids must be a non-null int32 or int64 array");
@@ -456,14 +467,14 @@ int zett_op_embed_lookup_plan(const void* ids, int32_t ids_bytes, int64_t t, int
     int* s = (int*)scratch;
     const int ids64 = ids_bytes == 8;
     HIP_TRY(hipMemsetAsync(s + L.counts, 0, (size_t)(2 * v) * 4, st));          // counts and tiles
-    if (t) hipLaunchKernelGGL(plan_hist_kernel, dim3(grid_for((t + 255) / 256, kMaxGrid)), dim3(256), 0, st, ids, ids64, t, v, s + L.counts);
+    if (t) hipLaunchKernelGGL(plan_hist_kernel, dim3(grid_for((t + 255) / 256, kMaxGrid)), dim3(256), 0, st, ids, ids64, t, id_base, v, s + L.counts);
     hipLaunchKernelGGL(plan_scan_kernel, dim3(1), dim3(1024), 0, st, (const int*)(s + L.counts), v, w + L.offsets, w + L.mstart);
     if (t) {
-        hipLaunchKernelGGL(plan_tile_kernel, dim3(grid_for(((t + 63) / 64 + 3) / 4, kMaxGrid)), dim3(256), 0, st, ids, ids64, t, v, (const int*)(w + L.offsets), s + L.tiles,
+        hipLaunchKernelGGL(plan_tile_kernel, dim3(grid_for(((t + 63) / 64 + 3) / 4, kMaxGrid)), dim3(256), 0, st, ids, ids64, t, id_base, v, (const int*)(w + L.offsets), s + L.tiles,
                            s + L.tl_w, s + L.tl_cnt, s + L.info);
         hipLaunchKernelGGL(plan_base_kernel, dim3(grid_for((v + 3) / 4, kMaxGrid)), dim3(256), 0, st, v, (const int*)(w + L.offsets), (const int*)(w + L.mstart),
                            (const int*)(s + L.counts), (const int*)(s + L.tiles), (const int*)(s + L.tl_w), (const int*)(s + L.tl_cnt), s + L.tl_base, w + L.mchunk);
-        hipLaunchKernelGGL(plan_place_kernel, dim3(grid_for((t + 255) / 256, kMaxGrid)), dim3(256), 0, st, ids, ids64, t, v, (const int*)(w + L.offsets), (const int*)(s + L.info),
+        hipLaunchKernelGGL(plan_place_kernel, dim3(grid_for((t + 255) / 256, kMaxGrid)), dim3(256), 0, st, ids, ids64, t, id_base, v, (const int*)(w + L.offsets), (const int*)(s + L.info),
                            (const int*)(s + L.tl_base), w + L.pos);
     }
     HIP_TRY(hipGetLastError());

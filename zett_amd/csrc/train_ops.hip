@@ -542,8 +542,9 @@ __global__ __launch_bounds__(256) void gather_fwd_kernel(const int32_t* __restri
     }
 }
 // dfallback[id - V0] += dx[t] (atomics: few rows); prod[t] = dx[t] * src[id] and keep[t] = dx[t] for source rows, 0 for fallback
-// rows — their column sums are d in_scaler.w and d in_scaler.b
-template <typename TS>
+// rows — their column sums are d in_scaler.w and d in_scaler.b.  FB = false: prod and keep only, by the same expressions, no atomic;
+// d fallback is then the fixed-order sum of dx over the plan of ids - v0 (zett_op_embed_lookup_plan_base, zett_op_embed_lookup_bwd)
+template <typename TS, bool FB>
 __global__ __launch_bounds__(256) void gather_bwd_kernel(const int32_t* __restrict__ ids, int64_t T, const TS* __restrict__ src, int e_in, int v0,
                                                          const float* __restrict__ dx, float* __restrict__ dfallback, float* __restrict__ prod,
                                                          float* __restrict__ keep) {
@@ -553,7 +554,7 @@ __global__ __launch_bounds__(256) void gather_bwd_kernel(const int32_t* __restri
     for (int c = threadIdx.x; c < e_in; c += 256) {
         const float g = dx[(size_t)t * e_in + c];
         if (id >= v0) {
-            atomicAdd(dfallback + (size_t)(id - v0) * e_in + c, g);
+            if constexpr (FB) atomicAdd(dfallback + (size_t)(id - v0) * e_in + c, g);
             prod[(size_t)t * e_in + c] = 0.f; keep[(size_t)t * e_in + c] = 0.f;
         } else {
             prod[(size_t)t * e_in + c] = g * load1(src + (size_t)id * e_in + c);
@@ -897,7 +898,25 @@ int zett_op_gather_bwd_f32(const int32_t* ids, int64_t n_tokens, const void* src
     hipStream_t st = (hipStream_t)stream;
     with_dtype(src_dtype, [&](auto dt) {
         using TS = elem_t<decltype(dt)::value>;
-        hipLaunchKernelGGL(gather_bwd_kernel<TS>, grid, block, 0, st, ids, n_tokens, (const TS*)src, e_in, v0, dx, dfallback, prod, keep);
+        hipLaunchKernelGGL((gather_bwd_kernel<TS, true>), grid, block, 0, st, ids, n_tokens, (const TS*)src, e_in, v0, dx, dfallback, prod, keep);
+    });
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int zett_op_gather_bwd_rows_f32(const int32_t* ids, int64_t n_tokens, const void* src, int32_t src_dtype, int32_t e_in, int32_t v0, const float* dx, float* prod,
+                                float* keep, void* stream) {
+    if (!ids || !src || !dx || !prod || !keep) return fail(ZETT_E_INVALID, "null argument");
+    if (!is_dtype(src_dtype)) return fail(ZETT_E_INVALID, "unknown source dtype %d", (int)src_dtype);
+    if (n_tokens < 0 || n_tokens > 0x7fffffffLL || e_in <= 0 || v0 < 0)
+        return fail(ZETT_E_INVALID, "the gather needs 0 <= n_tokens < 2^31 (a workgroup each), e_in > 0 and v0 >= 0 (n_tokens = %lld, e_in = %d, v0 = %d)", (long long)n_tokens,
+                    (int)e_in, (int)v0);
+    if (n_tokens == 0) return 0;
+    const dim3 grid((unsigned)n_tokens), block(256);
+    hipStream_t st = (hipStream_t)stream;
+    with_dtype(src_dtype, [&](auto dt) {
+        using TS = elem_t<decltype(dt)::value>;
+        hipLaunchKernelGGL((gather_bwd_kernel<TS, false>), grid, block, 0, st, ids, n_tokens, (const TS*)src, e_in, v0, dx, (float*)nullptr, prod, keep);
     });
     HIP_TRY(hipGetLastError());
     return 0;

@@ -346,6 +346,17 @@ class HipEngine:
 
 
 class ZettHypernet(PreTrainedModel):
+    """The hypernetwork on the HIP path.  In eval mode (or without grad) a call predicts on the inference engine; in train() mode with
+    parameters that require grad it runs zett_amd/autograd.py, steered by three plain attributes that are read at each call:
+
+    train_packed (default True): the inference path's schedule (pad skipping, the input projection once per distinct id, a
+        position-0-only last layer); False: the reference's dense layout.  Same gradients to fp32 round-off.
+    train_precision (default "f32"): "bf16" / "f16" run every forward / dgrad / wgrad contraction on 16-bit MFMA operands.
+    train_deterministic (default False): True takes the backward's sums over shared indices — the embedding gradient per position
+        and per distinct id (packed), the fallback rows' gradient (dense) — in a fixed order instead of with float atomics, so the
+        gradients of the position, token-type, language and fallback embeddings and of the input projection, and with them a whole
+        training step, are the same bits on every run.  Works with both schedules and every train_precision; the forward and every
+        other gradient are the same bits in both modes."""
     config_class = ZettHypernetConfig
     base_model_prefix = ""
     _no_split_modules = []
@@ -525,7 +536,7 @@ class ZettHypernet(PreTrainedModel):
             # inference path, which builds no graph
             from .autograd import differentiable_forward
             return differentiable_forward(self, target_surface_forms, source_embeddings, lang, packed=getattr(self, "train_packed", True),
-                                          precision=getattr(self, "train_precision", "f32"))
+                                          precision=getattr(self, "train_precision", "f32"), deterministic=getattr(self, "train_deterministic", False))
         return self._guarded_forward(device, target_surface_forms, source_embeddings, lang)
 
     def _guarded_forward(self, device, surface_forms, source_embeddings, lang):

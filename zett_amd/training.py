@@ -605,17 +605,21 @@ def embed_lookup_workspace(t: int, v: int, e: int):
     return plan.value, scratch.value, partial.value
 
 
-def embed_lookup_plan(ids, v: int):
+def embed_lookup_plan(ids, v: int, id_base: int = 0):
     """The inverted index of `ids` over v rows (per id, its positions in ascending order) as an opaque int32 device tensor: a pure
     function of ids, built on the current stream without a host round trip.  What only the building needs (about 4T + 2V words) is a
     scratch tensor that is released on return — the caching allocator reuses it in stream order — so the plan that autograd holds until
-    the backward is T + 2V + T/32 words."""
+    the backward is T + 2V + T/32 words.  id_base != 0: the index of ``ids - id_base`` (row r lists the positions of id_base + r)."""
     plan_bytes, scratch_bytes, _ = embed_lookup_workspace(ids.numel(), v, 1)
     plan = torch.empty(plan_bytes // 4, dtype=torch.int32, device=ids.device)
     scratch = torch.empty(max(scratch_bytes // 4, 1), dtype=torch.int32, device=ids.device)
     with torch.cuda.device(ids.device):
-        _lib.check(_lib.load().zett_op_embed_lookup_plan(_ptr(ids), ids.element_size(), ids.numel(), int(v), _ptr(plan), plan.numel() * 4, _ptr(scratch),
-                                                         scratch.numel() * 4, _stream(ids.device)), "embed_lookup_plan")
+        if id_base:
+            _lib.check(_lib.load().zett_op_embed_lookup_plan_base(_ptr(ids), ids.element_size(), ids.numel(), int(id_base), int(v), _ptr(plan), plan.numel() * 4,
+                                                                  _ptr(scratch), scratch.numel() * 4, _stream(ids.device)), "embed_lookup_plan_base")
+        else:
+            _lib.check(_lib.load().zett_op_embed_lookup_plan(_ptr(ids), ids.element_size(), ids.numel(), int(v), _ptr(plan), plan.numel() * 4, _ptr(scratch),
+                                                             scratch.numel() * 4, _stream(ids.device)), "embed_lookup_plan")
     return plan
 
 
