@@ -153,3 +153,43 @@ def test_chain_into_the_batch_vocabulary():
         assert torch.equal(getattr(got, key), getattr(want, key)), key
     assert got.special_indices == want.special_indices
     assert training.DeviceTextEncoder is DeviceTextEncoder
+
+
+def _texts_of_bytes(n_text):
+    """three ASCII texts of n_text bytes together"""
+    src = "the quick brown fox it's 12 345 times, we'll see. " * (n_text // 50 + 1)
+    a, b = n_text // 3, n_text // 2
+    return [src[:a], src[a:a + b], src[a + b:n_text]]
+
+
+@pytest.mark.parametrize("positions", (15, 16, 17, 1023, 1024, 1025, "empty"))
+def test_c_abi_stays_inside_a_framed_workspace(positions):
+    """Straight through the C ABI with a workspace of exactly zett_encode_workspace_bytes between two 4096-byte guards: n_text + n_texts
+    at the rounding edges of the workspace's arrays and of one scan segment.  The guards keep their fill, the status word is 0 and the
+    outputs are the wrapper's."""
+    import ctypes as C
+    enc, fx = _encoder(UNIGRAM), er.load_fixture(UNIGRAM)
+    texts = [""] if positions == "empty" else _texts_of_bytes(positions - 3)
+    blob = "".join(texts).encode()
+    b, t, guard = len(texts), 8, 4096
+    assert positions == "empty" or len(blob) + b == positions
+    want = enc(texts, t, fx["map"])
+    off = torch.tensor(np.cumsum([0] + [len(x.encode()) for x in texts]), dtype=torch.int64, device=DEV)
+    text = torch.tensor(list(blob or b"\0"), dtype=torch.uint8, device=DEV)
+    need = enc.workspace_bytes(len(blob), b)
+    frame = torch.full((need + 2 * guard,), 0xA5, dtype=torch.uint8, device=DEV)
+    assert frame.data_ptr() % 16 == 0 and need % 16 == 0
+    ids = torch.full((b, t), -7, dtype=torch.int64, device=DEV)
+    mask = torch.full((b, t), -7, dtype=torch.int64, device=DEV)
+    status = torch.full((1,), -1, dtype=torch.int32, device=DEV)
+    pairs = [(int(k), int(v)) for k, v in (fx["map"] or {}).items()]
+    m_from, m_to = (C.c_int32 * max(len(pairs), 1))(*[p[0] for p in pairs]), (C.c_int32 * max(len(pairs), 1))(*[p[1] for p in pairs])
+    P = lambda x: C.c_void_p(x.data_ptr())          # noqa: E731
+    rc = enc.lib.zett_encode_texts(enc.retok.handle, P(text), P(off), b, len(blob), P(enc._d_table), len(enc.table), enc.spec.flags, enc.spec.prefix_mode, t,
+                                   enc._prefix, len(enc.spec.prefix_ids), enc._suffix, len(enc.spec.suffix_ids), m_from, m_to, len(pairs), enc.spec.pad_id, P(ids), P(mask), 8, t,
+                                   C.c_void_p(frame.data_ptr() + guard), need, P(status), C.c_void_p(torch.cuda.current_stream(DEV).cuda_stream))
+    assert rc == 0, enc.lib.zett_last_error()
+    torch.cuda.synchronize()
+    assert bool((frame[:guard] == 0xA5).all()) and bool((frame[guard + need:] == 0xA5).all())
+    assert int(status.item()) == 0
+    assert torch.equal(ids, want["input_ids"]) and torch.equal(mask, want["attention_mask"])

@@ -359,3 +359,52 @@ def test_end_to_end_sample_then_encode():
     assert np.array_equal(got["attention_mask"].cpu().numpy(), want["attention_mask"])
     enc.close()
     sampler.close()
+
+
+# ---- the word stage's workspace, framed ----------------------------------------------------------------------------------------------------------
+def _texts_of_bytes(n_text):
+    """three distinct ASCII texts of n_text bytes together"""
+    src = "the quick brown fox it's 12 345 times, we'll see. " * (n_text // 50 + 1)
+    a, b = n_text // 3, n_text // 2
+    return [src[:a], src[a:a + b], src[a + b:n_text]]
+
+
+@pytest.mark.parametrize("positions", (15, 16, 17, 1023, 1024, 1025, "empty"))
+def test_c_abi_stays_inside_a_framed_workspace(positions):
+    """Straight through the C ABI with a workspace of exactly zett_sampler_workspace_bytes between two 4096-byte guards: n_text + n_texts
+    at the rounding edges of the workspace's arrays and of one scan segment.  The guards keep their fill, the status word is 0 and the
+    outputs are the wrapper's (both calls pop and do not push, so the queue is the same for both: empty)."""
+    import ctypes as C
+
+    import torch
+    s = _sampler()
+    dev = s.device
+    texts = [""] if positions == "empty" else _texts_of_bytes(positions - 3)
+    assert len(set(texts)) == len(texts)
+    blob = "".join(texts).encode()
+    b, guard, seed_size, max_length, stride = len(texts), 4096, 1000, 16, 1
+    assert positions == "empty" or len(blob) + b == positions
+    want = s.sample_tokenizer(texts, seed_size, max_length, stride, push_current=False)
+    cap = int(want.pieces.shape[0])
+    off = torch.tensor(np.cumsum([0] + [len(x.encode()) for x in texts]), dtype=torch.int64, device=dev)
+    text = torch.tensor(list(blob or b"\0"), dtype=torch.uint8, device=dev)
+    need = C.c_int64(0)
+    assert s.lib.zett_sampler_workspace_bytes(len(blob), b, C.byref(need)) == 0
+    need = need.value
+    frame = torch.full((need + 2 * guard,), 0xA5, dtype=torch.uint8, device=dev)
+    assert frame.data_ptr() % 16 == 0 and need % 16 == 0
+    pieces = torch.zeros((cap, 16), dtype=torch.uint8, device=dev)
+    lengths = torch.zeros(cap, dtype=torch.uint8, device=dev)
+    scores = torch.zeros(cap, dtype=torch.float64, device=dev)
+    n = torch.full((1,), -1, dtype=torch.int32, device=dev)
+    status = torch.full((1,), -1, dtype=torch.int32, device=dev)
+    P = lambda t: C.c_void_p(t.data_ptr())          # noqa: E731
+    rc = s.lib.zett_sampler_sample(s.handle, P(text), P(off), b, len(blob), P(s._d_table), len(s.table), seed_size, max_length, stride, 0.0, 0, 1, 0, P(pieces), P(lengths),
+                                   P(scores), cap, P(n), C.c_void_p(frame.data_ptr() + guard), need, P(status), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    assert rc == 0, s.lib.zett_last_error()
+    torch.cuda.synchronize()
+    assert bool((frame[:guard] == 0xA5).all()) and bool((frame[guard + need:] == 0xA5).all())
+    assert int(status.item()) == 0
+    assert torch.equal(pieces, want.pieces) and torch.equal(lengths, want.lengths) and torch.equal(scores, want.scores) and torch.equal(n, want.n)
+    assert int(n.item()) > 391 or positions == "empty"
+    s.close()

@@ -31,24 +31,19 @@ fixed order.  ``model.train_deterministic`` / ``deterministic=True`` takes them 
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import Dict, List, Optional, Tuple
 
 import torch
 
 from . import _lib
+from ._glue import ptr, stream, zett_dtypes
 from .dims import PROJECTOR_LN_EPS, HypernetDims, weight_shapes
 
-_SRC_DTYPES = {torch.float32: _lib.DTYPE_F32, torch.float16: _lib.DTYPE_F16, torch.bfloat16: _lib.DTYPE_BF16}
 ACT_NONE, GELU_TANH, GELU_ERF = 0, 1, 2
 K_STEP = 32          # contraction widths of the fp32 MFMA GEMM are multiples of this
 
 
 NEVER_READ = frozenset({"model.embeddings.word_embeddings.weight"})     # inputs_embeds bypass the table (modeling_hypernet.py:225-229)
-
-
-def _ptr(t: Optional[torch.Tensor]):
-    return C.c_void_p(0 if t is None else t.data_ptr())
 
 
 class Ops:
@@ -67,9 +62,6 @@ class Ops:
         self.prec = {"f32": None, "bf16": _lib.PREC_BF16, "f16": _lib.PREC_F16}[precision]
         self.lo_dtype = {"f32": None, "bf16": torch.bfloat16, "f16": torch.float16}[precision]
         self.kstep = K_STEP if self.prec is None else 64          # contraction widths are multiples of this
-
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     def new(self, *shape) -> torch.Tensor:
         return torch.empty(shape, dtype=torch.float32, device=self.device)
@@ -93,7 +85,7 @@ class Ops:
         r, c = x.shape
         cp = -(-c // 64) * 64
         out = torch.empty((r, cp), dtype=self.lo_dtype, device=self.device)
-        _lib.check(self.lib.zett_op_convert_lo(self.prec, _ptr(x), x.stride(0), _ptr(out), cp, r, c, cp, self._stream()), "zett_op_convert_lo")
+        _lib.check(self.lib.zett_op_convert_lo(self.prec, ptr(x), x.stride(0), ptr(out), cp, r, c, cp, stream(self.device)), "zett_op_convert_lo")
         return out
 
     def gemm(self, x, w, bias=None, act=ACT_NONE, residual=None, out=None):
@@ -108,8 +100,8 @@ class Ops:
             if out is None:
                 out = self.new(m, n)
             assert out.shape == (m, n) and out.is_contiguous()
-            _lib.check(self.lib.zett_op_gemm_lo(self.prec, _ptr(xa), xa.stride(0), _ptr(wa), wa.stride(0), m, n, k, _ptr(bias), act,
-                                                _ptr(residual), 0 if residual is None else residual.stride(0), _ptr(out), n, self._stream()), "zett_op_gemm_lo")
+            _lib.check(self.lib.zett_op_gemm_lo(self.prec, ptr(xa), xa.stride(0), ptr(wa), wa.stride(0), m, n, k, ptr(bias), act,
+                                                ptr(residual), 0 if residual is None else residual.stride(0), ptr(out), n, stream(self.device)), "zett_op_gemm_lo")
             return out
         assert x.shape[1] == w.shape[1]
         m, k = x.shape
@@ -117,8 +109,8 @@ class Ops:
         if out is None:
             out = self.new(m, n)
         assert out.shape == (m, n) and out.is_contiguous()
-        _lib.check(self.lib.zett_op_gemm_f32(_ptr(x), x.stride(0), _ptr(w), w.stride(0), m, n, k, _ptr(bias), act,
-                                             _ptr(residual), 0 if residual is None else residual.stride(0), _ptr(out), n, self._stream()), "zett_op_gemm_f32")
+        _lib.check(self.lib.zett_op_gemm_f32(ptr(x), x.stride(0), ptr(w), w.stride(0), m, n, k, ptr(bias), act,
+                                             ptr(residual), 0 if residual is None else residual.stride(0), ptr(out), n, stream(self.device)), "zett_op_gemm_f32")
         return out
 
     def wgrad(self, dy_t, x_t):
@@ -158,12 +150,12 @@ class Ops:
             out = torch.empty((c, rp), dtype=self.lo_dtype, device=self.device)
             src = x if x.dtype == self.lo_dtype else self._twin(x)
             if src is not None:
-                _lib.check(self.lib.zett_op_transpose_lo16(self.prec, _ptr(src), src.stride(0), _ptr(out), rp, r, c, rp, self._stream()), "zett_op_transpose_lo16")
+                _lib.check(self.lib.zett_op_transpose_lo16(self.prec, ptr(src), src.stride(0), ptr(out), rp, r, c, rp, stream(self.device)), "zett_op_transpose_lo16")
             else:
-                _lib.check(self.lib.zett_op_transpose_lo(self.prec, _ptr(x), x.stride(0), _ptr(out), rp, r, c, rp, self._stream()), "zett_op_transpose_lo")
+                _lib.check(self.lib.zett_op_transpose_lo(self.prec, ptr(x), x.stride(0), ptr(out), rp, r, c, rp, stream(self.device)), "zett_op_transpose_lo")
             return out
         out = self.new(c, rp)
-        _lib.check(self.lib.zett_op_transpose_f32(_ptr(x), x.stride(0), _ptr(out), rp, r, c, rp, self._stream()), "zett_op_transpose_f32")
+        _lib.check(self.lib.zett_op_transpose_f32(ptr(x), x.stride(0), ptr(out), rp, r, c, rp, stream(self.device)), "zett_op_transpose_f32")
         return out
 
     def _colsum_raw(self, x, out=None, accumulate=False):
@@ -171,7 +163,7 @@ class Ops:
         r, c = x.shape
         if out is None:
             out = self.new(c)
-        _lib.check(self.lib.zett_op_colsum_f32(_ptr(x), x.stride(0), r, c, _ptr(out), int(accumulate), self._stream()), "zett_op_colsum_f32")
+        _lib.check(self.lib.zett_op_colsum_f32(ptr(x), x.stride(0), r, c, ptr(out), int(accumulate), stream(self.device)), "zett_op_colsum_f32")
         return out
 
     def colsum(self, x, out=None, accumulate=False):
@@ -197,7 +189,7 @@ class Ops:
         out = self.new(*(ref.shape if ref is not None else (rows, cols)))
         for t in (a, b):
             assert t is None or t.is_contiguous()
-        _lib.check(self.lib.zett_op_elementwise_f32(op, _ptr(a), _ptr(b), _ptr(vec), _ptr(vec2), _ptr(s), _ptr(out), n, cols, self._stream()),
+        _lib.check(self.lib.zett_op_elementwise_f32(op, ptr(a), ptr(b), ptr(vec), ptr(vec2), ptr(s), ptr(out), n, cols, stream(self.device)),
                    "zett_op_elementwise_f32")
         return out
 
@@ -219,7 +211,7 @@ class Ops:
     def rowdot(self, a, w, b=None):
         assert a.dim() == 2 and a.stride(1) == 1
         out = self.new(a.shape[0])
-        _lib.check(self.lib.zett_op_rowdot_f32(_ptr(a), a.stride(0), _ptr(w), _ptr(b), _ptr(out), a.shape[0], a.shape[1], self._stream()), "zett_op_rowdot_f32")
+        _lib.check(self.lib.zett_op_rowdot_f32(ptr(a), a.stride(0), ptr(w), ptr(b), ptr(out), a.shape[0], a.shape[1], stream(self.device)), "zett_op_rowdot_f32")
         return out
 
     def layernorm(self, x, gamma, beta, eps):
@@ -229,8 +221,8 @@ class Ops:
         r, h = x.shape
         y, stats = self.new(r, h), self.new(r, 2)
         twin = torch.empty((r, h), dtype=self.lo_dtype, device=self.device) if self.prec is not None and h % 64 == 0 else None
-        _lib.check(self.lib.zett_op_layernorm_fwd_f32(_ptr(x), x.stride(0), _ptr(gamma), _ptr(beta), float(eps), _ptr(y), _ptr(stats), r, h, _ptr(twin),
-                                                      self.prec if twin is not None else 0, self._stream()), "zett_op_layernorm_fwd_f32")
+        _lib.check(self.lib.zett_op_layernorm_fwd_f32(ptr(x), x.stride(0), ptr(gamma), ptr(beta), float(eps), ptr(y), ptr(stats), r, h, ptr(twin),
+                                                      self.prec if twin is not None else 0, stream(self.device)), "zett_op_layernorm_fwd_f32")
         if twin is not None:
             y._zett_lo = twin
         return y, stats
@@ -242,8 +234,8 @@ class Ops:
         r, h = x.shape
         n_part = max(1, min(r, 1024))
         dx, part = self.new(r, h), self.new(n_part, 2 * h)
-        _lib.check(self.lib.zett_op_layernorm_bwd_f32(_ptr(dy), _ptr(dy2), _ptr(x), x.stride(0), _ptr(stats), _ptr(gamma), _ptr(dx), _ptr(part), n_part, r, h,
-                                                      self._stream()), "zett_op_layernorm_bwd_f32")
+        _lib.check(self.lib.zett_op_layernorm_bwd_f32(ptr(dy), ptr(dy2), ptr(x), x.stride(0), ptr(stats), ptr(gamma), ptr(dx), ptr(part), n_part, r, h,
+                                                      stream(self.device)), "zett_op_layernorm_bwd_f32")
         g = self._colsum_raw(part)
         return dx, g[:h], g[h:]
 
@@ -252,16 +244,16 @@ class Ops:
         its fp32 form is never stored"""
         if operand and self.prec is not None and z.shape[-1] % 64 == 0 and z.is_contiguous():
             h = torch.empty(z.shape, dtype=self.lo_dtype, device=self.device)
-            _lib.check(self.lib.zett_op_gelu_fwd_lo(self.prec, _ptr(z), _ptr(h), z.numel(), kind, self._stream()), "zett_op_gelu_fwd_lo")
+            _lib.check(self.lib.zett_op_gelu_fwd_lo(self.prec, ptr(z), ptr(h), z.numel(), kind, stream(self.device)), "zett_op_gelu_fwd_lo")
             return h
         h = self.new(*z.shape)
-        _lib.check(self.lib.zett_op_gelu_fwd_f32(_ptr(z), _ptr(h), z.numel(), kind, self._stream()), "zett_op_gelu_fwd_f32")
+        _lib.check(self.lib.zett_op_gelu_fwd_f32(ptr(z), ptr(h), z.numel(), kind, stream(self.device)), "zett_op_gelu_fwd_f32")
         return h
 
     def gelu_bwd(self, z, dh, kind):
         assert dh.is_contiguous() and z.is_contiguous()
         dz = self.new(*z.shape)
-        _lib.check(self.lib.zett_op_gelu_bwd_f32(_ptr(z), _ptr(dh), _ptr(dz), z.numel(), kind, self._stream()), "zett_op_gelu_bwd_f32")
+        _lib.check(self.lib.zett_op_gelu_bwd_f32(ptr(z), ptr(dh), ptr(dz), z.numel(), kind, stream(self.device)), "zett_op_gelu_bwd_f32")
         return dz
 
     def attention(self, q, k, v, mask, row_offset, n_rows, seq, heads, hidden, cls_only=False, operand=False):
@@ -273,39 +265,39 @@ class Ops:
         lo = operand and self.prec is not None and hidden % 64 == 0
         ctx = torch.empty((q.shape[0], hidden), dtype=self.lo_dtype if lo else torch.float32, device=self.device)
         probs = torch.zeros((n_rows, heads, seq, seq), dtype=torch.float32, device=self.device)
-        _lib.check(self.lib.zett_op_attention_fwd_f32(_ptr(q), q.stride(0), _ptr(k), _ptr(v), k.stride(0), _ptr(mask), _ptr(row_offset), n_rows, seq, heads, d,
-                                                      int(cls_only), _ptr(None if lo else ctx), hidden, _ptr(probs), _ptr(ctx if lo else None),
-                                                      self.prec if lo else 0, self._stream()), "zett_op_attention_fwd_f32")
+        _lib.check(self.lib.zett_op_attention_fwd_f32(ptr(q), q.stride(0), ptr(k), ptr(v), k.stride(0), ptr(mask), ptr(row_offset), n_rows, seq, heads, d,
+                                                      int(cls_only), ptr(None if lo else ctx), hidden, ptr(probs), ptr(ctx if lo else None),
+                                                      self.prec if lo else 0, stream(self.device)), "zett_op_attention_fwd_f32")
         return ctx, probs
 
     def attention_bwd(self, dctx, q, k, v, probs, row_offset, n_rows, seq, heads, hidden, dq, dk, dv, cls_only=False):
         """writes dq (rows like q), dk / dv (rows like k; column views of one buffer with equal row stride)"""
         assert dctx.is_contiguous() and dk.stride(0) == dv.stride(0)
         d = hidden // heads
-        _lib.check(self.lib.zett_op_attention_bwd_f32(_ptr(dctx), hidden, _ptr(q), q.stride(0), _ptr(k), _ptr(v), k.stride(0), _ptr(probs), _ptr(row_offset),
-                                                      n_rows, seq, heads, d, int(cls_only), _ptr(dq), dq.stride(0), _ptr(dk), _ptr(dv), dk.stride(0),
-                                                      self._stream()), "zett_op_attention_bwd_f32")
+        _lib.check(self.lib.zett_op_attention_bwd_f32(ptr(dctx), hidden, ptr(q), q.stride(0), ptr(k), ptr(v), k.stride(0), ptr(probs), ptr(row_offset),
+                                                      n_rows, seq, heads, d, int(cls_only), ptr(dq), dq.stride(0), ptr(dk), ptr(dv), dk.stride(0),
+                                                      stream(self.device)), "zett_op_attention_bwd_f32")
 
     def gather_rows(self, src, idx, a=None):
         """out[r] = (a[r] if a is given else 0) + src[idx[r]]"""
         assert src.stride(1) == 1 and idx.dtype == torch.int32 and (a is None or a.is_contiguous())
         out = self.new(idx.numel(), src.shape[1])
-        _lib.check(self.lib.zett_op_gather_rows_f32(_ptr(a), _ptr(src), src.stride(0), _ptr(idx), _ptr(out), idx.numel(), src.shape[1], self._stream()),
+        _lib.check(self.lib.zett_op_gather_rows_f32(ptr(a), ptr(src), src.stride(0), ptr(idx), ptr(out), idx.numel(), src.shape[1], stream(self.device)),
                    "zett_op_gather_rows_f32")
         return out
 
     def scatter_add_rows(self, dst, idx, src):
         """dst[idx[r]] += src[r] (in place; dst must be initialised)"""
         assert dst.stride(1) == 1 and src.is_contiguous() and idx.dtype == torch.int32 and idx.numel() == src.shape[0]
-        _lib.check(self.lib.zett_op_scatter_add_rows_f32(_ptr(dst), dst.stride(0), _ptr(idx), _ptr(src), idx.numel(), src.shape[1], self._stream()),
+        _lib.check(self.lib.zett_op_scatter_add_rows_f32(ptr(dst), dst.stride(0), ptr(idx), ptr(src), idx.numel(), src.shape[1], stream(self.device)),
                    "zett_op_scatter_add_rows_f32")
         return dst
 
     def gather(self, ids, src, v0, fallback, sw, sb):
         t = ids.numel()
         x = self.new(t, src.shape[1])
-        _lib.check(self.lib.zett_op_gather_fwd_f32(_ptr(ids), t, _ptr(src), _SRC_DTYPES[src.dtype], src.shape[1], v0, _ptr(fallback), _ptr(sw), _ptr(sb),
-                                                   _ptr(x), self._stream()), "zett_op_gather_fwd_f32")
+        _lib.check(self.lib.zett_op_gather_fwd_f32(ptr(ids), t, ptr(src), zett_dtypes()[src.dtype], src.shape[1], v0, ptr(fallback), ptr(sw), ptr(sb),
+                                                   ptr(x), stream(self.device)), "zett_op_gather_fwd_f32")
         return x
 
     def index_sum_rows(self, idx, src, n_dst, id_base=0):
@@ -327,13 +319,13 @@ class Ops:
         if deterministic:
             assert dx.is_contiguous()
             prod, keep = self.new(t, e_in), self.new(t, e_in)
-            _lib.check(self.lib.zett_op_gather_bwd_rows_f32(_ptr(ids), t, _ptr(src), _SRC_DTYPES[src.dtype], e_in, v0, _ptr(dx), _ptr(prod), _ptr(keep),
-                                                            self._stream()), "zett_op_gather_bwd_rows_f32")
+            _lib.check(self.lib.zett_op_gather_bwd_rows_f32(ptr(ids), t, ptr(src), zett_dtypes()[src.dtype], e_in, v0, ptr(dx), ptr(prod), ptr(keep),
+                                                            stream(self.device)), "zett_op_gather_bwd_rows_f32")
             return self.index_sum_rows(ids, dx, n_fallback, id_base=v0), self.colsum(prod), self.colsum(keep)
         dfb = torch.zeros((n_fallback, e_in), dtype=torch.float32, device=self.device)
         prod, keep = self.new(t, e_in), self.new(t, e_in)
-        _lib.check(self.lib.zett_op_gather_bwd_f32(_ptr(ids), t, _ptr(src), _SRC_DTYPES[src.dtype], e_in, v0, _ptr(dx), _ptr(dfb), _ptr(prod), _ptr(keep),
-                                                   self._stream()), "zett_op_gather_bwd_f32")
+        _lib.check(self.lib.zett_op_gather_bwd_f32(ptr(ids), t, ptr(src), zett_dtypes()[src.dtype], e_in, v0, ptr(dx), ptr(dfb), ptr(prod), ptr(keep),
+                                                   stream(self.device)), "zett_op_gather_bwd_f32")
         return dfb, self.colsum(prod), self.colsum(keep)
 
     # ---- Linear backward on the same GEMM: dgrad against W^T, wgrad of the transposed activations
@@ -347,8 +339,8 @@ class Ops:
         dy_t = torch.empty((n, mp), dtype=self.lo_dtype, device=self.device)
         part = self.new(bands, n)
         assert act_z is None or (act_z.shape == dy.shape and act_z.stride(1) == 1)
-        _lib.check(self.lib.zett_op_grad_operands_lo(self.prec, _ptr(dy), dy.stride(0), _ptr(act_z), 0 if act_z is None else act_z.stride(0), act_kind, m, n, mp,
-                                                     _ptr(dy_lo), n, _ptr(dy_t), mp, _ptr(part), self._stream()), "zett_op_grad_operands_lo")
+        _lib.check(self.lib.zett_op_grad_operands_lo(self.prec, ptr(dy), dy.stride(0), ptr(act_z), 0 if act_z is None else act_z.stride(0), act_kind, m, n, mp,
+                                                     ptr(dy_lo), n, ptr(dy_t), mp, ptr(part), stream(self.device)), "zett_op_grad_operands_lo")
         return dy_lo, dy_t, self.colsum(part)
 
     def linear_bwd(self, dy, x, w, act_z=None, act_kind=0):
@@ -845,7 +837,7 @@ def differentiable_forward(model, target_surface_forms: torch.Tensor, source_emb
     names = [n for n in weight_shapes(model.dims) if n not in NEVER_READ]
     params = dict(model.named_parameters())
     tensors = [params[n] for n in names]
-    src = source_embeddings if source_embeddings.dtype in _SRC_DTYPES else source_embeddings.float()
+    src = source_embeddings if source_embeddings.dtype in zett_dtypes() else source_embeddings.float()
     pred_in, pred_out, bias = HypernetFunction.apply(model.dims, model._ln_eps_encoder, tuple(names), bool(packed), str(precision), bool(deterministic), target_surface_forms, src.contiguous(),
                                                      int(lang_index), *tensors)
     return pred_in, (pred_out if model.dims.separate_out else None), bias

@@ -22,6 +22,7 @@ from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 import torch
 
 from . import _lib
+from ._glue import default_device, ptr, stream
 
 LABEL_BAD_ID = _lib.LABEL_BAD_ID
 NEGATIVE_INF_FILL_VALUE = -100000.0          # zett/utils.py
@@ -29,14 +30,6 @@ MAX_CHARS_PER_TOKEN = 16                     # zett/utils.py
 _MASK64 = (1 << 64) - 1
 _GOLDEN = 0x9E3779B97F4A7C15
 _LOSSES = {"clm": _lib.LABEL_CLM, "mlm": _lib.LABEL_MLM}
-
-
-def _ptr(t: Optional[torch.Tensor]):
-    return C.c_void_p(0 if t is None else t.data_ptr())
-
-
-def _stream(device):
-    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
 def mlm_thresholds(mlm_probability: float = 0.15, mask_replace_prob: float = 0.8, random_replace_prob: float = 0.1) -> Tuple[int, int, int]:
@@ -149,10 +142,10 @@ def label_batch(input_ids, special_ids: Sequence[int], byte_lengths_per_token, *
         metrics = torch.empty(2, dtype=torch.float64, device=device)
         work = torch.empty(_lib.LABEL_WORKSPACE_BYTES // 8, dtype=torch.int64, device=device)          # (released on return: the allocator reuses it in stream order)
         k = len(special)
-        _lib.check(_lib.load().zett_op_label_batch(_ptr(ids), ids.element_size(), ld_in, b, s, (C.c_int32 * max(k, 1))(*special), k, _ptr(table), table.element_size(), v,
+        _lib.check(_lib.load().zett_op_label_batch(ptr(ids), ids.element_size(), ld_in, b, s, (C.c_int32 * max(k, 1))(*special), k, ptr(table), table.element_size(), v,
                                                    vocab_len, -1 if mask_token_id is None else int(mask_token_id), unk, _LOSSES[loss], t_mask, t_replace, t_random,
-                                                   int(seed) & _MASK64, _ptr(out), ld_out, _ptr(labels), _ptr(byte_lengths), _ptr(record), _ptr(metrics), _ptr(work),
-                                                   work.numel() * 8, _stream(device)), "label_batch")
+                                                   int(seed) & _MASK64, ptr(out), ld_out, ptr(labels), ptr(byte_lengths), ptr(record), ptr(metrics), ptr(work),
+                                                   work.numel() * 8, stream(device)), "label_batch")
     if check and int(record[7].item()) & LABEL_BAD_ID:          # (the one host read of this call)
         raise IndexError(f"label_batch: an id of input_ids is outside [0, {v})")
     return LabelledBatch(input_ids if inplace else out, labels, byte_lengths, metrics, record)
@@ -210,8 +203,8 @@ def pad_vocabulary(surface_forms, priors, n_rows: int) -> PaddedVocabulary:
         out_priors = torch.empty(r, dtype=torch.float32, device=device)
         mask = torch.empty(r, dtype=torch.bool, device=device)
         ids_to_embed = torch.empty(r, dtype=torch.int64, device=device)
-        _lib.check(_lib.load().zett_op_pad_vocabulary(_ptr(sf), sf.element_size(), sf.stride(0) if v > 1 else max(l, sf.stride(0)), l, v, r, _ptr(priors),
-                                                      priors.element_size(), _ptr(out_sf), _ptr(out_priors), _ptr(mask), _ptr(ids_to_embed), _stream(device)),
+        _lib.check(_lib.load().zett_op_pad_vocabulary(ptr(sf), sf.element_size(), sf.stride(0) if v > 1 else max(l, sf.stride(0)), l, v, r, ptr(priors),
+                                                      priors.element_size(), ptr(out_sf), ptr(out_priors), ptr(mask), ptr(ids_to_embed), stream(device)),
                    "pad_vocabulary")
     return PaddedVocabulary(out_sf, out_priors, mask, ids_to_embed)
 
@@ -276,11 +269,7 @@ class DeviceCollator:
             padded_rows(1, a.pad_to_multiple_of, a.tokenizer_sample_max)          # (the reference's assert, once)
         if (tokenizer is None) != bool(a.do_tokenizer_sampling):
             raise ValueError("a tokenizer is given exactly when data_args.do_tokenizer_sampling is false")
-        if device is None:
-            if not torch.cuda.is_available():
-                raise RuntimeError("zett_amd computes on MI355X only: no cuda (ROCm) device is visible; there is no CPU path")
-            device = torch.device("cuda", torch.cuda.current_device())
-        self.device = torch.device(device)
+        self.device = default_device(device)
         self.reference, self.hn_tokenizer, self.data_args, self.loss = reference, hn_tokenizer, a, loss
         self.is_validation, self.lang_code = bool(is_validation), lang_code
         self.thresholds = mlm_thresholds(*mlm_probabilities) if loss == "mlm" else None

@@ -13,7 +13,8 @@
 //              definition: where a match starts depends on where the previous one ended
 //   compact    the flags into the word list woff[] — scan.hip.h's count / scan / place: a wave owns 1024 positions, one workgroup
 //              scans the segment counts
-//              (classify and walk live in text_words.hip.h: tokenizer_sample.hip launches the same kernels)
+//              (these three are the word stage of text_words.hip.h — kernels, workspace layout and launches: tokenizer_sample.hip
+//              begins with the same stage)
 //   words      a lane per word: retok.hip.h's stage 2 (BPE merge / Unigram Viterbi) on the word's raw bytes, state in LDS or — a wave
 //              with more than 4 KiB of text, a lane beyond the arena — in the global scratch.  A word of b bytes gives at most 2b ids
 //              (a byte is at least one symbol, byte fallback makes at most two ids of it), so word w writes at ids[2 * woff[w]]: no
@@ -30,7 +31,6 @@
 #include "../../include/zett_hip.h"
 #define ZETT_RETOK_DEVICE_FUNCTIONS_ONLY
 #include "retok.hip.h"
-#include "scan.hip.h"
 #include "text_words.hip.h"
 
 using namespace zett;
@@ -49,26 +49,19 @@ struct Lists {
 };
 static_assert(sizeof(Lists) < 4096 - 512, "the lists must fit the kernel-argument limit");
 
-// workspace, in bytes (every array starts on a 16-byte boundary)
+// workspace, in bytes: the word stage, then what the words and pack kernels add (every array starts on a 16-byte boundary)
 struct Layout {
-    int64_t codes, flags, raw, woff, counts, segcnt, segoff, totals, ids, scratch, bytes;
-    int64_t np, nseg;
+    WordLayout words;
+    int64_t counts, ids, scratch, bytes;
 };
 Layout layout(int64_t n_text, int64_t b) {
     Layout L{};
-    L.np = n_text + b;
-    L.nseg = compact_segments(L.np);
     Carve w;
-    L.codes = w.take(L.np + 16);
-    L.flags = w.take(L.np + 16);
-    L.raw = w.take(L.np + 32);                      // 16 bytes of slack for the staging loads of the last wave
-    L.woff = w.take((L.np + 1) * 4);
-    L.counts = w.take(L.np * 4);
-    L.segcnt = w.take(L.nseg * 4);
-    L.segoff = w.take(L.nseg * 4);
-    L.totals = w.take(16);
-    L.ids = w.take(L.np * 8);                       // 2 ids per position
-    L.scratch = w.take((L.np * kScrPerByte + 64) * 4);
+    L.words = word_layout(w, n_text, b);
+    const int64_t np = L.words.np;
+    L.counts = w.take(np * 4);
+    L.ids = w.take(np * 8);                         // 2 ids per position
+    L.scratch = w.take((np * kScrPerByte + 64) * 4);
     L.bytes = w.bytes;
     return L;
 }
@@ -218,19 +211,12 @@ __global__ __launch_bounds__(64) void encode_pack_kernel(const int64_t* __restri
     }
 }
 
-
-int shape_args(int64_t n_text, int64_t n_texts) {
-    if (n_text < 0 || n_texts < 0) return fail(ZETT_E_INVALID, "text encoding needs n_text >= 0 bytes and n_texts >= 0 texts (n_text = %lld, n_texts = %lld)", (long long)n_text, (long long)n_texts);
-    if (n_text + n_texts >= kMaxPositions) return fail(ZETT_E_INVALID, "n_text + n_texts = %lld: a call takes fewer than 2^30 positions", (long long)(n_text + n_texts));
-    return 0;
-}
-
 }  // namespace
 
 extern "C" {
 
 int zett_encode_workspace_bytes(int64_t n_text, int64_t n_texts, int64_t* bytes) {
-    if (int rc = shape_args(n_text, n_texts)) return rc;
+    if (int rc = shape_args("text encoding", n_text, n_texts)) return rc;
     if (!bytes) return fail(ZETT_E_INVALID, "null argument");
     *bytes = layout(n_text, n_texts).bytes;
     return 0;
@@ -244,7 +230,7 @@ int zett_encode_texts(zett_retok* r, const uint8_t* text, const int64_t* text_of
     if (!r->tokenizes()) return fail(ZETT_E_STATE, "the handle's tables are built on the device: zett_sampled_vocab_build and zett_sampled_vocab_commit come first");
     if (r->t.kind != ZETT_RETOK_BPE && r->t.kind != ZETT_RETOK_UNIGRAM)
         return fail(ZETT_E_NOT_IMPLEMENTED, "text encoding segments with a BPE or a Unigram model (WordPiece targets need another pre-tokenizer)");
-    if (int rc = shape_args(n_text, n_texts)) return rc;
+    if (int rc = shape_args("text encoding", n_text, n_texts)) return rc;
     if (flags & ~(ZETT_ENCODE_MARKS_ARE_LETTERS | ZETT_ENCODE_RESPLIT)) return fail(ZETT_E_INVALID, "unknown flags 0x%x", (unsigned)flags);
     if (prefix_mode != ZETT_ENCODE_PREFIX_NONE && prefix_mode != ZETT_ENCODE_PREFIX_ALWAYS && prefix_mode != ZETT_ENCODE_PREFIX_UNLESS_SPACE)
         return fail(ZETT_E_INVALID, "unknown prefix mode %d", (int)prefix_mode);
@@ -257,8 +243,7 @@ int zett_encode_texts(zett_retok* r, const uint8_t* text, const int64_t* text_of
     if ((n_prefix && !prefix_ids) || (n_suffix && !suffix_ids) || (n_map && (!map_from || !map_to))) return fail(ZETT_E_INVALID, "null argument");
     if (out_bytes != 4 && out_bytes != 8) return fail(ZETT_E_INVALID, "input_ids and attention_mask must be int32 or int64");
     if (ld_out < block_size) return fail(ZETT_E_INVALID, "ld_out = %lld must be at least block_size = %d", (long long)ld_out, (int)block_size);
-    if (!status || !class_table || n_code_points <= 0 || n_code_points > 0x110000) return fail(ZETT_E_INVALID, "null status or class table, or a table of more than 0x110000 code points");
-    if (n_texts && (!text_offsets || !input_ids || !attention_mask || (n_text && !text))) return fail(ZETT_E_INVALID, "null argument");
+    if (n_texts && (!input_ids || !attention_mask)) return fail(ZETT_E_INVALID, "null argument");
     if (n_texts && (!aligned(input_ids, out_bytes) || !aligned(attention_mask, out_bytes))) return fail(ZETT_E_INVALID, "misaligned output");
     Lists ls{};
     ls.n_prefix = n_prefix; ls.n_suffix = n_suffix; ls.n_map = n_map; ls.pad_id = pad_id;
@@ -266,40 +251,26 @@ int zett_encode_texts(zett_retok* r, const uint8_t* text, const int64_t* text_of
     for (int i = 0; i < n_suffix; ++i) ls.suffix[i] = suffix_ids[i];
     for (int i = 0; i < n_map; ++i) { ls.map_from[i] = map_from[i]; ls.map_to[i] = map_to[i]; }
     const Layout L = layout(n_text, n_texts);
-    if (n_texts) {
-        if (!workspace || !aligned(workspace, 16)) return fail(ZETT_E_INVALID, "null or misaligned workspace (16 bytes)");
-        if (workspace_bytes < L.bytes) return fail(ZETT_E_INVALID, "the workspace holds %lld bytes, %lld are needed", (long long)workspace_bytes, (long long)L.bytes);
-    }
+    if (int rc = word_stage_args(text, text_offsets, n_texts, n_text, class_table, n_code_points, workspace, workspace_bytes, L.bytes, status)) return rc;
     ZETT_ON_DEVICE(r->device);
     hipStream_t st = (hipStream_t)stream;
     HIP_TRY(hipMemsetAsync(status, 0, 4, st));
     if (n_texts == 0) return 0;
 
-    char* w = (char*)workspace;
-    uint8_t* codes = (uint8_t*)(w + L.codes);
-    uint8_t* wflags = (uint8_t*)(w + L.flags);
-    uint8_t* raw = (uint8_t*)(w + L.raw);
-    int* woff = (int*)(w + L.woff);
-    int* counts = (int*)(w + L.counts);
-    int* segcnt = (int*)(w + L.segcnt);
-    int* segoff = (int*)(w + L.segoff);
-    int* totals = (int*)(w + L.totals);
-    int* ids = (int*)(w + L.ids);
-    int* scratch = (int*)(w + L.scratch);
-    const int marks = (flags & ZETT_ENCODE_MARKS_ARE_LETTERS) != 0;
-    hipLaunchKernelGGL(encode_classify_kernel, dim3((unsigned)((L.np + 255) / 256)), dim3(256), 0, st, text, text_offsets, n_texts, n_text, class_table, n_code_points,
-                       (int)prefix_mode, codes, wflags, raw, status);
-    hipLaunchKernelGGL(encode_walk_kernel, dim3((unsigned)((n_texts + 63) / 64)), dim3(64), 0, st, text_offsets, n_texts, n_text, (const uint8_t*)codes, wflags, marks,
-                       (int)((flags & ZETT_ENCODE_RESPLIT) != 0));
-    launch_compact(wflags, L.np, woff, segcnt, segoff, totals, st);
-    hipLaunchKernelGGL(encode_words_kernel, dim3((unsigned)((L.np + 63) / 64)), dim3(64), 0, st, r->t, (const uint8_t*)raw, (const uint8_t*)wflags, (const int32_t*)woff,
-                       (const int32_t*)totals, ids, counts, scratch, status);
+    const WordArrays a(workspace, L.words);
+    int32_t* counts = (int32_t*)((char*)workspace + L.counts);
+    int32_t* ids = (int32_t*)((char*)workspace + L.ids);
+    int32_t* scratch = (int32_t*)((char*)workspace + L.scratch);
+    launch_word_stage(text, text_offsets, n_texts, n_text, class_table, n_code_points, (int)prefix_mode, (flags & ZETT_ENCODE_MARKS_ARE_LETTERS) != 0,
+                      (flags & ZETT_ENCODE_RESPLIT) != 0, false, L.words, a, status, st);
+    hipLaunchKernelGGL(encode_words_kernel, dim3((unsigned)((L.words.np + 63) / 64)), dim3(64), 0, st, r->t, (const uint8_t*)a.raw, (const uint8_t*)a.flags, (const int32_t*)a.woff,
+                       (const int32_t*)a.totals, ids, counts, scratch, status);
     const int per = out_bytes == 8 ? 2 : 4;
     const bool vec = block_size % per == 0 && ld_out % per == 0 && aligned(input_ids, 16) && aligned(attention_mask, 16);
     const size_t lds = (size_t)block_size * 4;
 #define ZETT_PACK(WIDE, VEC)                                                                                                                                       \
-    hipLaunchKernelGGL((encode_pack_kernel<WIDE, VEC>), dim3(grid_for(n_texts, 1 << 16)), dim3(64), lds, st, text_offsets, n_texts, n_text, (const int32_t*)woff, \
-                       (const int32_t*)totals, (const int32_t*)counts, (const int32_t*)ids, (int)block_size, ls, input_ids, attention_mask, ld_out)
+    hipLaunchKernelGGL((encode_pack_kernel<WIDE, VEC>), dim3(grid_for(n_texts, 1 << 16)), dim3(64), lds, st, text_offsets, n_texts, n_text, (const int32_t*)a.woff, \
+                       (const int32_t*)a.totals, (const int32_t*)counts, (const int32_t*)ids, (int)block_size, ls, input_ids, attention_mask, ld_out)
     if (out_bytes == 8) { if (vec) ZETT_PACK(true, true); else ZETT_PACK(true, false); }
     else { if (vec) ZETT_PACK(false, true); else ZETT_PACK(false, false); }
 #undef ZETT_PACK

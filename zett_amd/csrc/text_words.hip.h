@@ -1,7 +1,9 @@
-// text_words.hip.h — the split of a batch of texts into words, shared by text_encode.hip (zett_encode_texts) and tokenizer_sample.hip
-// (zett_sampler_sample): classify / walk, from the text bytes to a flag at every word start (scan.hip.h's compaction makes the word
-// list woff[] of them).  Both entry points launch these kernels; the stages are described at the head of text_encode.hip.  Everything
-// here has internal linkage: a translation unit that includes the header gets its own copy.
+// text_words.hip.h — the word stage: the split of a batch of texts into words, shared by text_encode.hip (zett_encode_texts) and
+// tokenizer_sample.hip (zett_sampler_sample).  The kernels (classify / walk, from the text bytes to a flag at every word start) and
+// their host half: the layout of the stage's seven workspace arrays, the checks both entry points make, and the one launch sequence
+// that ends in scan.hip.h's compaction of the flags into the word list woff[].  The stages are described at the head of
+// text_encode.hip.  Everything here has internal linkage: a translation unit that includes the header gets its own copy (of
+// sample_mark_first_kernel too, whether it launches it or not).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -9,6 +11,7 @@
 #include <cstdint>
 
 #include "../../include/zett_hip.h"
+#include "scan.hip.h"
 
 namespace {
 
@@ -141,6 +144,74 @@ __global__ __launch_bounds__(64) void encode_walk_kernel(const int64_t* __restri
         }
         i = e;
     }
+}
+
+// the sampler's extra step: the slot of every text starts the text's first word
+__global__ __launch_bounds__(256) void sample_mark_first_kernel(const int64_t* __restrict__ off, int64_t b, int64_t n_text, uint8_t* __restrict__ flags) {
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t < b) flags[clamp_off(off[t], n_text) + t] = 5;
+}
+
+// ---- the host half ------------------------------------------------------------------------------------------------------------
+// Bytes behind the np = n_text + n_texts positions of an array, for the kernels that read it 16 bytes at a time:
+constexpr int64_t kCodeSlack = 16;          // codes, flags (the compaction's loads are 16 flags wide)
+constexpr int64_t kRawSlack = 32;           // raw: 16 bytes of slack for the staging loads of the last wave (text_encode.hip's words kernel)
+
+// the seven arrays of the stage as offsets into the caller's workspace (every array starts on a 16-byte boundary); the caller
+// goes on taking its own arrays from the same Carve
+struct WordLayout {
+    int64_t codes, flags, raw, woff, segcnt, segoff, totals;
+    int64_t np, nseg;          // positions, and their scan segments
+};
+inline WordLayout word_layout(zett::Carve& w, int64_t n_text, int64_t n_texts) {
+    WordLayout L{};
+    L.np = n_text + n_texts;
+    L.nseg = zett::compact_segments(L.np);
+    L.codes = w.take(L.np + kCodeSlack);
+    L.flags = w.take(L.np + kCodeSlack);
+    L.raw = w.take(L.np + kRawSlack);
+    L.woff = w.take((L.np + 1) * 4);
+    L.segcnt = w.take(L.nseg * 4);
+    L.segoff = w.take(L.nseg * 4);
+    L.totals = w.take(16);
+    return L;
+}
+
+struct WordArrays {
+    uint8_t *codes, *flags, *raw;
+    int32_t *woff, *segcnt, *segoff, *totals;
+    WordArrays(void* workspace, const WordLayout& L)
+        : codes((uint8_t*)workspace + L.codes), flags((uint8_t*)workspace + L.flags), raw((uint8_t*)workspace + L.raw),
+          woff((int32_t*)((char*)workspace + L.woff)), segcnt((int32_t*)((char*)workspace + L.segcnt)), segoff((int32_t*)((char*)workspace + L.segoff)),
+          totals((int32_t*)((char*)workspace + L.totals)) {}
+};
+
+// `what`: the entry point's name for its call ("text encoding")
+inline int shape_args(const char* what, int64_t n_text, int64_t n_texts) {
+    if (n_text < 0 || n_texts < 0) return zett::fail(ZETT_E_INVALID, "%s needs n_text >= 0 bytes and n_texts >= 0 texts (n_text = %lld, n_texts = %lld)", what, (long long)n_text, (long long)n_texts);
+    if (n_text + n_texts >= kMaxPositions) return zett::fail(ZETT_E_INVALID, "n_text + n_texts = %lld: a call takes fewer than 2^30 positions", (long long)(n_text + n_texts));
+    return 0;
+}
+
+// the arguments both entry points pass on to the word stage; need_bytes: the entry point's whole workspace (shape_args came first)
+inline int word_stage_args(const uint8_t* text, const int64_t* text_offsets, int64_t n_texts, int64_t n_text, const uint8_t* class_table, int64_t n_code_points,
+                           const void* workspace, int64_t workspace_bytes, int64_t need_bytes, const int32_t* status) {
+    if (!status || !class_table || n_code_points <= 0 || n_code_points > 0x110000) return zett::fail(ZETT_E_INVALID, "null status or class table, or a table of more than 0x110000 code points");
+    if (n_texts == 0) return 0;
+    if (!text_offsets || (n_text && !text)) return zett::fail(ZETT_E_INVALID, "null argument");
+    if (!workspace || !zett::aligned(workspace, 16)) return zett::fail(ZETT_E_INVALID, "null or misaligned workspace (16 bytes)");
+    if (workspace_bytes < need_bytes) return zett::fail(ZETT_E_INVALID, "the workspace holds %lld bytes, %lld are needed", (long long)workspace_bytes, (long long)need_bytes);
+    return 0;
+}
+
+// classify, walk, (mark_first: the sampler's flag on the first word of every text,) compact: a.woff[0 .. a.totals[0]] is the word list
+inline void launch_word_stage(const uint8_t* text, const int64_t* text_offsets, int64_t n_texts, int64_t n_text, const uint8_t* class_table, int64_t n_code_points,
+                              int prefix_mode, int marks, int resplit, bool mark_first, const WordLayout& L, const WordArrays& a, int32_t* status, hipStream_t st) {
+    hipLaunchKernelGGL(encode_classify_kernel, dim3((unsigned)((L.np + 255) / 256)), dim3(256), 0, st, text, text_offsets, n_texts, n_text, class_table, n_code_points,
+                       prefix_mode, a.codes, a.flags, a.raw, status);
+    hipLaunchKernelGGL(encode_walk_kernel, dim3((unsigned)((n_texts + 63) / 64)), dim3(64), 0, st, text_offsets, n_texts, n_text, (const uint8_t*)a.codes, a.flags, marks, resplit);
+    if (mark_first) hipLaunchKernelGGL(sample_mark_first_kernel, dim3((unsigned)((n_texts + 255) / 256)), dim3(256), 0, st, text_offsets, n_texts, n_text, a.flags);
+    zett::launch_compact(a.flags, L.np, a.woff, a.segcnt, a.segoff, a.totals, st);
 }
 
 }  // namespace

@@ -1,8 +1,8 @@
 // tokenizer_sample.hip — a step's Unigram seed vocabulary from the batch's texts, on the device (include/zett_hip.h, "tokenizer sampling";
 // what rust_utils.TokenizerSampler.sample_tokenizer computes, restated in tests/sampler_ref.py).
 //
-//   words      text_words.hip.h's classify / walk with the plain split pattern and a U+0020 in front of EVERY text, scan.hip.h's compaction;
-//              the slot of a text is then marked as the start of the text's first word (flag bit 4)
+//   words      text_words.hip.h's word stage (classify / walk / compact) with the plain split pattern and a U+0020 in front of EVERY
+//              text; before the compaction the slot of a text is marked as the start of the text's first word (flag bit 4)
 //   count      a lane per word (lanes of a wave with the same word first sum into one): the word's starts (every stride-th entry of the reference's start list) and from each start the keys
 //              of 1 .. max_length - 1 bytes.  A key is 16 bytes, 15 key bytes and the length; a key of one byte goes into a 256-bin
 //              histogram in LDS (one global add per bin and workgroup), every other key into the open-addressing table
@@ -32,7 +32,6 @@
 
 #include "../../include/zett_hip.h"
 #include "common.hip.h"
-#include "scan.hip.h"
 #include "text_words.hip.h"
 
 using namespace zett;
@@ -79,27 +78,6 @@ struct SelState {
     uint32_t hist[256];
     uint32_t block_n[kSelGrid];          // candidates of each workgroup's share of the slots
 };
-
-// workspace of a call: the word stage alone
-struct Layout {
-    int64_t codes, flags, raw, woff, segcnt, segoff, totals, bytes;
-    int64_t np, nseg;
-};
-Layout layout(int64_t n_text, int64_t b) {
-    Layout L{};
-    L.np = n_text + b;
-    L.nseg = compact_segments(L.np);
-    Carve w;
-    L.codes = w.take(L.np + 16);
-    L.flags = w.take(L.np + 16);
-    L.raw = w.take(L.np + 32);
-    L.woff = w.take((L.np + 1) * 4);
-    L.segcnt = w.take(L.nseg * 4);
-    L.segoff = w.take(L.nseg * 4);
-    L.totals = w.take(16);
-    L.bytes = w.bytes;
-    return L;
-}
 
 __device__ __forceinline__ uint64_t mix64(uint64_t x) {          // the finalizer of splitmix64
     x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull;
@@ -165,12 +143,6 @@ __device__ inline void table_add(unsigned long long* __restrict__ refs, uint32_t
 
 __global__ __launch_bounds__(64) void sample_init_state_kernel(SelState* __restrict__ st, long long k_pieces) {          // (behind a memset to 0)
     if (threadIdx.x == 0) { st->min = 0xFFFFFFFFu; st->krem = k_pieces; }
-}
-
-// the slot of every text starts the text's first word
-__global__ __launch_bounds__(256) void sample_mark_first_kernel(const int64_t* __restrict__ off, int64_t b, int64_t n_text, uint8_t* __restrict__ flags) {
-    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (t < b) flags[clamp_off(off[t], n_text) + t] = 5;
 }
 
 __global__ __launch_bounds__(256) void sample_count_kernel(const uint8_t* __restrict__ raw, const uint8_t* __restrict__ codes, const uint8_t* __restrict__ flags,
@@ -480,12 +452,6 @@ __global__ __launch_bounds__(256) void sample_table_kernel(const unsigned long l
     }
 }
 
-int shape_args(int64_t n_text, int64_t n_texts) {
-    if (n_text < 0 || n_texts < 0) return fail(ZETT_E_INVALID, "tokenizer sampling needs n_text >= 0 bytes and n_texts >= 0 texts (n_text = %lld, n_texts = %lld)", (long long)n_text, (long long)n_texts);
-    if (n_text + n_texts >= kMaxPositions) return fail(ZETT_E_INVALID, "n_text + n_texts = %lld: a call takes fewer than 2^30 positions", (long long)(n_text + n_texts));
-    return 0;
-}
-
 void release(zett_sampler* s) {
     void* all[] = {s->list_keys, s->list_scores, s->list_n, s->refs, s->scores, s->hist1, s->occ, s->idx, s->segcnt, s->segoff, s->totals, s->state, s->cand, s->surv};
     for (void* p : all)
@@ -553,9 +519,11 @@ int zett_sampler_depth(const zett_sampler* s, int32_t* depth) {
 }
 
 int zett_sampler_workspace_bytes(int64_t n_text, int64_t n_texts, int64_t* bytes) {
-    if (int rc = shape_args(n_text, n_texts)) return rc;
+    if (int rc = shape_args("tokenizer sampling", n_text, n_texts)) return rc;
     if (!bytes) return fail(ZETT_E_INVALID, "null argument");
-    *bytes = layout(n_text, n_texts).bytes;
+    Carve w;                                       // the workspace of a call is the word stage alone
+    word_layout(w, n_text, n_texts);
+    *bytes = w.bytes;
     return 0;
 }
 
@@ -564,14 +532,12 @@ int zett_sampler_sample(zett_sampler* s, const uint8_t* text, const int64_t* tex
                         int32_t push_current, uint8_t* pieces, uint8_t* piece_lengths, double* scores, int64_t out_capacity, int32_t* n_out, void* workspace,
                         int64_t workspace_bytes, int32_t* status, void* stream) {
     if (!s) return fail(ZETT_E_INVALID, "null argument");
-    if (int rc = shape_args(n_text, n_texts)) return rc;
+    if (int rc = shape_args("tokenizer sampling", n_text, n_texts)) return rc;
     if (max_length < 1 || max_length > 16) return fail(ZETT_E_INVALID, "max_length = %d must be in [1, 16]: a key is at most 15 bytes", (int)max_length);
     if (stride < 1) return fail(ZETT_E_INVALID, "stride = %d must be at least 1", (int)stride);
     if (seed_size < 0) return fail(ZETT_E_INVALID, "seed_size = %lld must not be negative", (long long)seed_size);
     if (!(noise_std >= 0.0) || !(noise_std < 1e300)) return fail(ZETT_E_INVALID, "noise_std must be a finite number >= 0");
-    if (!status || !n_out || !class_table || n_code_points <= 0 || n_code_points > 0x110000)
-        return fail(ZETT_E_INVALID, "null status, n_out or class table, or a table of more than 0x110000 code points");
-    if (n_texts && (!text_offsets || (n_text && !text))) return fail(ZETT_E_INVALID, "null argument");
+    if (!n_out) return fail(ZETT_E_INVALID, "null argument");
     const int64_t fixed = kFixedBytes + 9 * (int64_t)(max_length - 1);
     const int64_t k_pieces = std::max<int64_t>(1, seed_size - fixed);              // the length is looked at after each push: one piece always goes through
     if (pop_prev) {
@@ -579,11 +545,9 @@ int zett_sampler_sample(zett_sampler* s, const uint8_t* text, const int64_t* tex
         if (k_pieces > s->max_pieces) return fail(ZETT_E_INVALID, "seed_size = %lld asks for %lld table pieces, the sampler was created for %lld", (long long)seed_size, (long long)k_pieces, (long long)s->max_pieces);
     }
     if (!pop_prev && push_current && (int)s->queue.size() >= s->max_depth) return fail(ZETT_E_STATE, "the queue holds %d batches, the sampler was created for %d", (int)s->queue.size(), s->max_depth);
-    const Layout L = layout(n_text, n_texts);
-    if (n_texts) {
-        if (!workspace || ((uintptr_t)workspace & 15)) return fail(ZETT_E_INVALID, "null or misaligned workspace (16 bytes)");
-        if (workspace_bytes < L.bytes) return fail(ZETT_E_INVALID, "the workspace holds %lld bytes, %lld are needed", (long long)workspace_bytes, (long long)L.bytes);
-    }
+    Carve carve;
+    const WordLayout L = word_layout(carve, n_text, n_texts);
+    if (int rc = word_stage_args(text, text_offsets, n_texts, n_text, class_table, n_code_points, workspace, workspace_bytes, carve.bytes, status)) return rc;
     ZETT_ON_DEVICE(s->device);
     hipStream_t st = (hipStream_t)stream;
     HIP_TRY(hipMemsetAsync(status, 0, 4, st));
@@ -597,28 +561,17 @@ int zett_sampler_sample(zett_sampler* s, const uint8_t* text, const int64_t* tex
     if (n_texts == 0) {
         HIP_TRY(hipMemsetAsync(s->list_n + cur, 0, 4, st));
     } else {
-        char* w = (char*)workspace;
-        uint8_t* codes = (uint8_t*)(w + L.codes);
-        uint8_t* wflags = (uint8_t*)(w + L.flags);
-        uint8_t* raw = (uint8_t*)(w + L.raw);
-        int* woff = (int*)(w + L.woff);
-        int* segcnt = (int*)(w + L.segcnt);
-        int* segoff = (int*)(w + L.segoff);
-        int* totals = (int*)(w + L.totals);
-        hipLaunchKernelGGL(encode_classify_kernel, dim3((unsigned)((L.np + 255) / 256)), dim3(256), 0, st, text, text_offsets, n_texts, n_text, class_table, n_code_points,
-                           kPrefixEvenEmpty, codes, wflags, raw, status);
-        hipLaunchKernelGGL(encode_walk_kernel, dim3((unsigned)((n_texts + 63) / 64)), dim3(64), 0, st, text_offsets, n_texts, n_text, (const uint8_t*)codes, wflags, 0, 0);
-        hipLaunchKernelGGL(sample_mark_first_kernel, dim3((unsigned)((n_texts + 255) / 256)), dim3(256), 0, st, text_offsets, n_texts, n_text, wflags);
-        launch_compact(wflags, L.np, woff, segcnt, segoff, totals, st);
+        const WordArrays a(workspace, L);
+        launch_word_stage(text, text_offsets, n_texts, n_text, class_table, n_code_points, kPrefixEvenEmpty, 0, 0, true, L, a, status, st);
         HIP_TRY(hipMemsetAsync(s->refs, 0, (size_t)cap * 8, st));
         HIP_TRY(hipMemsetAsync(s->scores, 0, (size_t)cap * 4, st));
         HIP_TRY(hipMemsetAsync(s->hist1, 0, 256 * 4, st));
-        hipLaunchKernelGGL(sample_count_kernel, dim3(grid256((L.np + 3) / 4, 8192)), dim3(256), 0, st, (const uint8_t*)raw, (const uint8_t*)codes, (const uint8_t*)wflags,
-                           (const int32_t*)woff, (const int32_t*)totals, L.np, (int)max_length, (int)stride, s->refs, s->scores, cap, s->hist1, status);
+        hipLaunchKernelGGL(sample_count_kernel, dim3(grid256((L.np + 3) / 4, 8192)), dim3(256), 0, st, (const uint8_t*)a.raw, (const uint8_t*)a.codes, (const uint8_t*)a.flags,
+                           (const int32_t*)a.woff, (const int32_t*)a.totals, L.np, (int)max_length, (int)stride, s->refs, s->scores, cap, s->hist1, status);
         hipLaunchKernelGGL(sample_occupied_kernel, dim3(grid256(s->np_occ, kGrid)), dim3(256), 0, st, (const unsigned long long*)s->refs, (const uint32_t*)s->hist1, (int64_t)cap, s->occ);
         launch_compact(s->occ, s->np_occ, s->idx, s->segcnt, s->segoff, s->totals, st);
         hipLaunchKernelGGL(sample_gather_kernel, dim3(grid256(s->list_cap, kGrid)), dim3(256), 0, st, (const unsigned long long*)s->refs, (const uint32_t*)s->scores,
-                           (const uint32_t*)s->hist1, (int64_t)cap, (const uint8_t*)raw, (const int32_t*)s->idx, (const int32_t*)s->totals, s->list_cap,
+                           (const uint32_t*)s->hist1, (int64_t)cap, (const uint8_t*)a.raw, (const int32_t*)s->idx, (const int32_t*)s->totals, s->list_cap,
                            s->list_keys + (int64_t)cur * s->list_cap, s->list_scores + (int64_t)cur * s->list_cap, s->list_n + cur, status);
     }
 

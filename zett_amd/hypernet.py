@@ -25,11 +25,11 @@ import torch
 from torch import nn
 from transformers import PreTrainedModel
 
-from . import _lib
+from . import _glue, _lib
+from ._glue import ptr, zett_dtypes
 from .config import ZettHypernetConfig
 from .dims import PROJECTOR_LN_EPS, ROBERTA_LN_EPS, ROBERTA_MAX_POSITIONS, HypernetDims, weight_shapes
 
-_TORCH_TO_ZETT = {torch.float32: _lib.DTYPE_F32, torch.float16: _lib.DTYPE_F16, torch.bfloat16: _lib.DTYPE_BF16}
 DEFAULT_PRECISION = "f16"
 _PRECISIONS = {"bf16": _lib.PREC_BF16, "bfloat16": _lib.PREC_BF16, "f32": _lib.PREC_F32,
                "fp32": _lib.PREC_F32, "float32": _lib.PREC_F32, "f16": _lib.PREC_F16, "fp16": _lib.PREC_F16,
@@ -94,12 +94,11 @@ class HipEngine:
     def load_weights(self, tensors: Dict[str, torch.Tensor]) -> None:
         for name, t in tensors.items():
             t = t.detach()
-            if t.dtype not in _TORCH_TO_ZETT:
+            if t.dtype not in zett_dtypes():
                 t = t.float()
             t = t.contiguous()
             shape = (C.c_int64 * t.dim())(*t.shape)
-            _lib.check(self.lib.zett_load_weight(self.handle, name.encode(), C.c_void_p(t.data_ptr()),
-                                                 _TORCH_TO_ZETT[t.dtype], shape, t.dim()), f"zett_load_weight({name})")
+            _lib.check(self.lib.zett_load_weight(self.handle, name.encode(), ptr(t), zett_dtypes()[t.dtype], shape, t.dim()), f"zett_load_weight({name})")
         _lib.check(self.lib.zett_finalize(self.handle), "zett_finalize")
 
     def set_option(self, key: str, value: int) -> None:
@@ -117,8 +116,7 @@ class HipEngine:
         combination of _lib.RANGE_SOURCE / RANGE_ACTIVATION / RANGE_OUTPUT."""
         flags = C.c_int32(0)
         with torch.cuda.device(self.device):
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-            rc = self.lib.zett_check_range(self.handle, C.c_void_p(stream), C.byref(flags))
+            rc = self.lib.zett_check_range(self.handle, _glue.stream(self.device), C.byref(flags))
         if rc not in (_lib.ZETT_OK, _lib.E_RANGE):
             _lib.check(rc, "zett_check_range")
         return int(flags.value)
@@ -128,7 +126,7 @@ class HipEngine:
         (zett_stream_wait_output): pred_in is final after the first head's last GEMM, while the second head still
         computes — the vocabulary-sharded path starts its all-gather there (zett_amd/sharding.py)."""
         code = {"in": _lib.OUT_IN, "bias": _lib.OUT_BIAS}[which]
-        _lib.check(self.lib.zett_stream_wait_output(self.handle, code, C.c_void_p(stream.cuda_stream)), "zett_stream_wait_output")
+        _lib.check(self.lib.zett_stream_wait_output(self.handle, code, _glue.stream(of=stream)), "zett_stream_wait_output")
 
     def gemm_log(self) -> list:
         """Per-launch records of the GEMMs of the most recent forward (zett_get_gemm_log): dicts with m, n, k, variant,
@@ -153,8 +151,7 @@ class HipEngine:
             raise ValueError("prepare() takes the int32, contiguous [n_tokens, surface_maxlen] tensor on the engine's device that forward() will get")
         n, seq = surface_forms.shape
         with torch.cuda.device(self.device):
-            stream = (input_stream or torch.cuda.current_stream(self.device)).cuda_stream
-            _lib.check(self.lib.zett_forward_prepare(self.handle, C.c_void_p(surface_forms.data_ptr()), n, seq, C.c_void_p(stream)),
+            _lib.check(self.lib.zett_forward_prepare(self.handle, ptr(surface_forms), n, seq, _glue.stream(self.device, of=input_stream)),
                        "zett_forward_prepare")
         self._prepared = surface_forms          # the plan reads it on a stream torch's allocator does not know: keep it alive until the next forward has waited for the plan
 
@@ -166,7 +163,7 @@ class HipEngine:
             raise RuntimeError(f"all tensors must be on {self.device}")
         ids = surface_forms.to(torch.int32).contiguous()
         src = source_embeddings
-        if src.dtype not in _TORCH_TO_ZETT:
+        if src.dtype not in zett_dtypes():
             src = src.float()
         src = src.contiguous()
         if src.dim() != 2 or src.shape[1] != d.n_in_embd:
@@ -176,12 +173,8 @@ class HipEngine:
         out_out = torch.empty((n, d.n_embd), dtype=torch.float32, device=self.device) if d.separate_out else None
         out_bias = torch.empty((n,), dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-            rc = self.lib.zett_forward(
-                self.handle, C.c_void_p(ids.data_ptr()), n, seq, C.c_void_p(src.data_ptr()),
-                _TORCH_TO_ZETT[src.dtype], src.shape[0], int(lang_index),
-                C.c_void_p(out_in.data_ptr()), C.c_void_p(out_out.data_ptr() if out_out is not None else 0),
-                C.c_void_p(out_bias.data_ptr()), C.c_void_p(stream))
+            rc = self.lib.zett_forward(self.handle, ptr(ids), n, seq, ptr(src), zett_dtypes()[src.dtype], src.shape[0], int(lang_index),
+                                       ptr(out_in), ptr(out_out), ptr(out_bias), _glue.stream(self.device))
         self._prepared = None                   # (zett_forward waited on the host for every plan that read a prepared tensor)
         _lib.check(rc, "zett_forward")
         return out_in, out_out, out_bias
@@ -196,7 +189,7 @@ class HipEngine:
                 raise ValueError(f"{what} must be a 2-d tensor")
             if t.device != self.device:
                 raise ValueError(f"{what} must live on {self.device}, got {t.device}")
-            if t.dtype not in _TORCH_TO_ZETT:
+            if t.dtype not in zett_dtypes():
                 raise ValueError(f"{what}: dtype {t.dtype} is not one of float32 / float16 / bfloat16")
             if t.shape[1] != d.n_embd or t.stride(1) != 1:
                 raise ValueError(f"{what} must be [rows, {d.n_embd}] with unit column stride, got shape {tuple(t.shape)} strides {t.stride()}")
@@ -212,7 +205,7 @@ class HipEngine:
         elif out_out is not None:
             raise ValueError("out_out must be None: this hypernetwork has no separate output embeddings")
         if out_bias is not None:
-            if not torch.is_tensor(out_bias) or out_bias.dim() != 1 or out_bias.device != self.device or out_bias.dtype not in _TORCH_TO_ZETT:
+            if not torch.is_tensor(out_bias) or out_bias.dim() != 1 or out_bias.device != self.device or out_bias.dtype not in zett_dtypes():
                 raise ValueError(f"out_bias must be a 1-d float32 / float16 / bfloat16 tensor on {self.device}")
             if out_bias.stride(0) != 1 or out_bias.shape[0] != out_in.shape[0]:
                 raise ValueError("out_bias must be contiguous with one entry per row of out_in")
@@ -223,8 +216,8 @@ class HipEngine:
             rows = rows.contiguous()
             keep.append(rows)
         st = _lib.ZettDest(in_=out_in.data_ptr(), out=out_out.data_ptr() if out_out is not None else None,
-                           bias=out_bias.data_ptr() if out_bias is not None else None, dtype=_TORCH_TO_ZETT[out_in.dtype],
-                           bias_dtype=_TORCH_TO_ZETT[out_bias.dtype] if out_bias is not None else 0, ld_in=out_in.stride(0),
+                           bias=out_bias.data_ptr() if out_bias is not None else None, dtype=zett_dtypes()[out_in.dtype],
+                           bias_dtype=zett_dtypes()[out_bias.dtype] if out_bias is not None else 0, ld_in=out_in.stride(0),
                            ld_out=out_out.stride(0) if out_out is not None else 0, rows=rows.data_ptr() if rows is not None else None,
                            n_dest_rows=out_in.shape[0])
         return st, keep
@@ -242,7 +235,7 @@ class HipEngine:
             raise RuntimeError(f"all tensors must be on {self.device}")
         ids = surface_forms.to(torch.int32).contiguous()
         src = source_embeddings
-        if src.dtype not in _TORCH_TO_ZETT:
+        if src.dtype not in zett_dtypes():
             src = src.float()
         src = src.contiguous()
         if src.dim() != 2 or src.shape[1] != d.n_in_embd:
@@ -250,9 +243,8 @@ class HipEngine:
         n, seq = ids.shape
         dest, keep = self._dest(n, out_in, out_out, out_bias, rows)
         with torch.cuda.device(self.device):
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-            rc = self.lib.zett_forward_into(self.handle, C.c_void_p(ids.data_ptr()), n, seq, C.c_void_p(src.data_ptr()), _TORCH_TO_ZETT[src.dtype],
-                                            src.shape[0], int(lang_index), C.byref(dest), C.c_void_p(stream))
+            rc = self.lib.zett_forward_into(self.handle, ptr(ids), n, seq, ptr(src), zett_dtypes()[src.dtype],
+                                            src.shape[0], int(lang_index), C.byref(dest), _glue.stream(self.device))
         self._prepared = None
         _lib.check(rc, "zett_forward_into")
         del keep
@@ -267,9 +259,8 @@ class HipEngine:
         n, seq = ids.shape
         dest, keep = self._dest(n, out_in, out_out, out_bias, rows)
         with torch.cuda.device(self.device):
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-            rc = self.lib.zett_forward_table_into(self.handle, C.c_void_p(ids.data_ptr()), n, seq, C.c_void_p(table.data_ptr()), C.c_void_p(stats.data_ptr()),
-                                                  C.c_void_p(id_slot.data_ptr()), int(lang_index), C.byref(dest), C.c_void_p(stream))
+            rc = self.lib.zett_forward_table_into(self.handle, ptr(ids), n, seq, ptr(table), ptr(stats),
+                                                  ptr(id_slot), int(lang_index), C.byref(dest), _glue.stream(self.device))
         self._prepared = None
         _lib.check(rc, "zett_forward_table_into")
         del keep
@@ -286,9 +277,8 @@ class HipEngine:
         id_list = torch.empty((v,), dtype=torch.int32, device=self.device)
         n_ids = C.c_int64(0)
         with torch.cuda.device(self.device):
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-            _lib.check(self.lib.zett_table_plan(self.handle, C.c_void_p(ids.data_ptr()), ids.shape[0], ids.shape[1], C.c_void_p(id_slot.data_ptr()),
-                                                C.c_void_p(id_list.data_ptr()), C.byref(n_ids), C.c_void_p(stream)), "zett_table_plan")
+            _lib.check(self.lib.zett_table_plan(self.handle, ptr(ids), ids.shape[0], ids.shape[1], ptr(id_slot),
+                                                ptr(id_list), C.byref(n_ids), _glue.stream(self.device)), "zett_table_plan")
         return id_slot, id_list[:n_ids.value], int(n_ids.value)
 
     def table_buffers(self, n_rows: int):
@@ -301,7 +291,7 @@ class HipEngine:
     def table_rows(self, id_list: torch.Tensor, first: int, count: int, source_embeddings: torch.Tensor, table: torch.Tensor, stats: torch.Tensor) -> None:
         """zett_table_rows: rows [first, first + count) of the table of `id_list` into `table` / `stats` (whole-table buffers). Asynchronous."""
         src = source_embeddings
-        if src.dtype not in _TORCH_TO_ZETT:
+        if src.dtype not in zett_dtypes():
             src = src.float()
         src = src.contiguous()
         if src.dim() != 2 or src.shape[1] != self.dims.n_in_embd or src.device != self.device:
@@ -309,9 +299,8 @@ class HipEngine:
         if not (table.is_contiguous() and stats.is_contiguous() and table.shape[0] >= first + count and stats.shape[0] >= first + count and id_list.numel() >= first + count):
             raise ValueError("table / stats / id_list are smaller than the requested rows")
         with torch.cuda.device(self.device):
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-            _lib.check(self.lib.zett_table_rows(self.handle, C.c_void_p(id_list.data_ptr()), first, count, C.c_void_p(src.data_ptr()), _TORCH_TO_ZETT[src.dtype],
-                                                src.shape[0], C.c_void_p(table.data_ptr()), C.c_void_p(stats.data_ptr()), C.c_void_p(stream)), "zett_table_rows")
+            _lib.check(self.lib.zett_table_rows(self.handle, ptr(id_list), first, count, ptr(src), zett_dtypes()[src.dtype],
+                                                src.shape[0], ptr(table), ptr(stats), _glue.stream(self.device)), "zett_table_rows")
 
     def forward_table(self, surface_forms: torch.Tensor, table: torch.Tensor, stats: torch.Tensor, id_slot: torch.Tensor, lang_index: int):
         """zett_forward_table: forward() on a complete shared table instead of source embeddings; same outputs, bit for bit."""
@@ -324,11 +313,8 @@ class HipEngine:
         out_out = torch.empty((n, d.n_embd), dtype=torch.float32, device=self.device) if d.separate_out else None
         out_bias = torch.empty((n,), dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-            rc = self.lib.zett_forward_table(
-                self.handle, C.c_void_p(ids.data_ptr()), n, seq, C.c_void_p(table.data_ptr()), C.c_void_p(stats.data_ptr()), C.c_void_p(id_slot.data_ptr()),
-                int(lang_index), C.c_void_p(out_in.data_ptr()), C.c_void_p(out_out.data_ptr() if out_out is not None else 0),
-                C.c_void_p(out_bias.data_ptr()), C.c_void_p(stream))
+            rc = self.lib.zett_forward_table(self.handle, ptr(ids), n, seq, ptr(table), ptr(stats), ptr(id_slot), int(lang_index),
+                                             ptr(out_in), ptr(out_out), ptr(out_bias), _glue.stream(self.device))
         self._prepared = None
         _lib.check(rc, "zett_forward_table")
         return out_in, out_out, out_bias

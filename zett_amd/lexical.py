@@ -26,13 +26,13 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._glue import ptr, stream, zett_dtypes
 from .surface_forms import CHARS_TO_BYTES, HnTokenizerSpec, _raw
 
 FVT_MODES = {"no": _lib.LEXICAL_NO, "fvt": _lib.LEXICAL_FVT, "bfvt": _lib.LEXICAL_BFVT}
 FALLBACK_MODES = ("unk", "random")
 DEFAULT_WIDTH = 16          # ids per row of the first plan; rows that need more are planned again at the width they need
 RANDOM_BLOCK_ROWS = 1024    # rows per draw of fallback_mode="random" (bounds host memory; the stream is that of one whole draw)
-_DTYPES = {torch.float32: _lib.DTYPE_F32, torch.float16: _lib.DTYPE_F16, torch.bfloat16: _lib.DTYPE_BF16}
 _NO_CPU = "zett_amd computes on MI355X only: pass a cuda (ROCm) device / cuda tensors; there is no CPU path"
 
 
@@ -110,21 +110,21 @@ class LexicalTransfer:
         vb, vo = HnTokenizerSpec._pack([r for r, _ in entries])
         vi = np.asarray([i for _, i in entries], dtype=np.int32)
 
-        def ptr(a):
+        def host_ptr(a):
             return None if a is None else a.ctypes.data_as(C.c_void_p)
 
         m = _lib.ZettRetokModel(
-            kind=spec.kind, n_pieces=len(spec.piece_ids), piece_bytes=ptr(spec.piece_bytes),
-            piece_offsets=ptr(spec.piece_offsets), piece_ids=ptr(spec.piece_ids), piece_scores=ptr(spec.piece_scores),
-            unigram_min_score=spec.unigram_min_score, n_merges=len(spec.merges), merges=ptr(spec.merges),
+            kind=spec.kind, n_pieces=len(spec.piece_ids), piece_bytes=host_ptr(spec.piece_bytes),
+            piece_offsets=host_ptr(spec.piece_offsets), piece_ids=host_ptr(spec.piece_ids), piece_scores=host_ptr(spec.piece_scores),
+            unigram_min_score=spec.unigram_min_score, n_merges=len(spec.merges), merges=host_ptr(spec.merges),
             unk_id=spec.unk_id, fuse_unk=int(spec.fuse_unk), byte_fallback=int(spec.byte_fallback),
-            byte_fallback_ids=ptr(spec.byte_fallback_ids), ignore_merges=int(spec.ignore_merges),
+            byte_fallback_ids=host_ptr(spec.byte_fallback_ids), ignore_merges=int(spec.ignore_merges),
             n_special=0, special_bytes=None, special_offsets=None, special_ids=None,
-            piece_continuing=ptr(spec.piece_continuing), max_input_chars_per_word=int(spec.max_input_chars_per_word))
+            piece_continuing=host_ptr(spec.piece_continuing), max_input_chars_per_word=int(spec.max_input_chars_per_word))
         handle = C.c_void_p()
         index = device.index if device.index is not None else torch.cuda.current_device()
         self.device = torch.device("cuda", index)
-        _lib.check(self.lib.zett_lexical_create(C.byref(m), len(entries), ptr(vb), ptr(vo), ptr(vi), index, C.byref(handle)), "zett_lexical_create")
+        _lib.check(self.lib.zett_lexical_create(C.byref(m), len(entries), host_ptr(vb), host_ptr(vo), host_ptr(vi), index, C.byref(handle)), "zett_lexical_create")
         self.handle = handle
 
     # ---- stage 2 ---------------------------------------------------------------------------------------------------
@@ -141,10 +141,8 @@ class LexicalTransfer:
         overlap, wide, n_ids, bad = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_int64(-1)
         with torch.cuda.device(self.device):
             text = torch.from_numpy(np.frombuffer(blob or b"\0", dtype=np.uint8).copy()).to(self.device)
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-            rc = self.lib.zett_lexical_plan(self.handle, C.c_void_p(text.data_ptr()), n, len(blob), int(n_source_rows), mode, int(width),
-                                            C.c_void_p(ids.data_ptr()), C.c_void_p(count.data_ptr()), C.byref(overlap), C.byref(wide),
-                                            C.byref(n_ids), C.byref(bad), C.c_void_p(stream))
+            rc = self.lib.zett_lexical_plan(self.handle, ptr(text), n, len(blob), int(n_source_rows), mode, int(width), ptr(ids), ptr(count),
+                                            C.byref(overlap), C.byref(wide), C.byref(n_ids), C.byref(bad), stream(self.device))
         if rc == _lib.E_KEY and 0 <= bad.value < n:
             token = tokens[bad.value]
             chars = [ch for ch in token if ch not in CHARS_TO_BYTES]
@@ -186,9 +184,9 @@ class LexicalTransfer:
     # ---- stage 3 ---------------------------------------------------------------------------------------------------
     def _rows_call(self, plan: LexicalPlan, source_in, source_out, fallback_id: int, dest_in, dest_out, rows) -> None:
         _require_cuda(plan.ids, plan.count, source_in, source_out, dest_in, dest_out, rows)
-        if source_in.dtype not in _DTYPES:
+        if source_in.dtype not in zett_dtypes():
             raise ValueError(f"source dtype {source_in.dtype}: float32, float16 or bfloat16")
-        if dest_in.dtype not in _DTYPES:
+        if dest_in.dtype not in zett_dtypes():
             raise ValueError(f"destination dtype {dest_in.dtype}: float32, float16 or bfloat16")
         if (source_out is None) != (dest_out is None):
             raise ValueError("source_out and dest_out go together (untied embeddings) or are both None (tied)")
@@ -210,13 +208,12 @@ class LexicalTransfer:
                 raise ValueError("rows: an int64 tensor with one destination row per planned token")
             rows = rows.contiguous()
         ids = plan.ids.contiguous()
-        d = _lib.ZettDest(in_=p_di, out=p_do or None, bias=None, dtype=_DTYPES[dest_in.dtype], bias_dtype=_lib.DTYPE_F32, ld_in=ld_di, ld_out=ld_do,
+        d = _lib.ZettDest(in_=p_di, out=p_do or None, bias=None, dtype=zett_dtypes()[dest_in.dtype], bias_dtype=_lib.DTYPE_F32, ld_in=ld_di, ld_out=ld_do,
                           rows=rows.data_ptr() if rows is not None else None, n_dest_rows=int(dest_in.shape[0]))
         with torch.cuda.device(self.device):
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-            rc = self.lib.zett_lexical_rows_into(self.handle, C.c_void_p(ids.data_ptr()), C.c_void_p(plan.count.data_ptr()), plan.n_tokens, plan.width,
-                                                 C.c_void_p(p_si), ld_si, C.c_void_p(p_so or None), ld_so, _DTYPES[source_in.dtype], plan.n_source_rows,
-                                                 n_embd, int(fallback_id), C.byref(d), C.c_void_p(stream))
+            rc = self.lib.zett_lexical_rows_into(self.handle, ptr(ids), ptr(plan.count), plan.n_tokens, plan.width,
+                                                 C.c_void_p(p_si), ld_si, C.c_void_p(p_so or None), ld_so, zett_dtypes()[source_in.dtype], plan.n_source_rows,
+                                                 n_embd, int(fallback_id), C.byref(d), stream(self.device))
         _lib.check(rc, "zett_lexical_rows_into")
 
     def rows_into(self, plan: LexicalPlan, source_in: torch.Tensor, source_out: Optional[torch.Tensor] = None, fallback_mode: str = "unk",

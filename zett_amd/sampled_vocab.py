@@ -24,6 +24,7 @@ from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib
+from ._glue import default_device, ptr, stream
 from .surface_forms import BYTES_TO_CHARS_LIST, CHARS_TO_BYTES, _raw
 from .tokenizer_sampling import MAX_LENGTH, N_ALPHABET, DeviceTokenizerSampler, SampledPieces, build_sampled_tokenizer, n_fixed_pieces, raise_for_status
 
@@ -198,7 +199,7 @@ class DeviceSampledVocabulary:
         import torch
 
         from .surface_forms import DeviceRetokenizer, device_retokenizer
-        from .text_encode import EncodeSpec, class_table, pack_class_table
+        from .text_encode import EncodeSpec, packed_table_on
         if hn_tokenizer is not None and hn_surface_maxlen is None:
             raise ValueError("hn_surface_maxlen is required with an hn_tokenizer")
         tokens, ids = sorted_specials(list(reference.all_special_tokens), [int(i) for i in reference.all_special_ids])
@@ -214,11 +215,7 @@ class DeviceSampledVocabulary:
                 raise NotImplementedError(f"the special token {token!r} has {len(raw)} raw bytes, the device table carries {MAX_SPECIAL_BYTES}")
             raws.append(raw or b"")
             hn_ids.append(int(hn_tokenizer.convert_tokens_to_ids(token)) if is_hn else -1)
-        if device is None:
-            if not torch.cuda.is_available():
-                raise RuntimeError("zett_amd computes on MI355X only: no cuda (ROCm) device is visible; there is no CPU path")
-            device = torch.device("cuda", torch.cuda.current_device())
-        self.device = torch.device(device)
+        self.device = default_device(device)
         if self.device.type != "cuda":
             raise RuntimeError("zett_amd computes on MI355X only: the sampled vocabulary needs a cuda (ROCm) device; there is no CPU path")
         self.special_tokens, self.special_ids, self.special_raw, self.special_hn_ids = tokens, ids, raws, hn_ids
@@ -231,10 +228,9 @@ class DeviceSampledVocabulary:
         self._pad_k = tokens.index(reference.pad_token)
         self.scores_through_json = self._probe_scores(fixed_tokenizer, tokens)
         self.hn = device_retokenizer(hn_tokenizer, self.device) if hn_tokenizer is not None else None
-        self.table = class_table()
         self.lib = _lib.load()
         with torch.cuda.device(self.device):
-            self._d_table = torch.from_numpy(pack_class_table(self.table)).to(self.device)
+            self.table, self._d_table = packed_table_on(self.device, None)
             offsets = np.zeros(len(raws) + 1, dtype=np.int32)
             np.cumsum(np.array([len(r) for r in raws], dtype=np.int32), out=offsets[1:])
             up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.device)          # noqa: E731
@@ -284,18 +280,16 @@ class DeviceSampledVocabulary:
             raise ValueError("sampled: pieces [capacity, 16], lengths [capacity], scores [capacity]")
         v_cap = min(cap, bound) + s
         text_cap = 2 * 16 * min(cap, bound) + 2 * self._raw_bytes + 16
-        P = lambda t: C.c_void_p(t.data_ptr())          # noqa: E731
         with torch.cuda.device(self.device):
             priors = torch.empty(v_cap, dtype=torch.float64, device=self.device)
             byte_lengths = torch.empty(v_cap, dtype=torch.int64, device=self.device)
             text_offsets = torch.empty(v_cap + 1, dtype=torch.int32, device=self.device)
             text = torch.empty(text_cap, dtype=torch.uint8, device=self.device)
             record = torch.empty(4 + (1 if check else 0), dtype=torch.int64, device=self.device)
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-            rc = self.lib.zett_sampled_vocab_build(self.retok.handle, P(sampled.pieces), P(sampled.lengths), P(sampled.scores), P(sampled.n), cap, bound,
-                                                   P(self._d_ids), P(self._d_raw_off), P(self._d_raw), P(self._d_chars), P(self._d_hn), s, self._raw_bytes, self._max_raw,
-                                                   P(priors), P(byte_lengths), P(text_offsets), v_cap, P(text), text_cap, P(record), _lib.VOCAB_SCORES_THROUGH_JSON if self.scores_through_json else 0, P(self._work), self._work.numel(),
-                                                   C.c_void_p(stream))
+            st = stream(self.device)
+            rc = self.lib.zett_sampled_vocab_build(self.retok.handle, ptr(sampled.pieces), ptr(sampled.lengths), ptr(sampled.scores), ptr(sampled.n), cap, bound,
+                                                   ptr(self._d_ids), ptr(self._d_raw_off), ptr(self._d_raw), ptr(self._d_chars), ptr(self._d_hn), s, self._raw_bytes, self._max_raw,
+                                                   ptr(priors), ptr(byte_lengths), ptr(text_offsets), v_cap, ptr(text), text_cap, ptr(record), _lib.VOCAB_SCORES_THROUGH_JSON if self.scores_through_json else 0, ptr(self._work), self._work.numel(), st)
             _lib.check(rc, "zett_sampled_vocab_build")
             if check:          # the sampler's status word rides along: still one read
                 record[4:5] = sampled.status.to(torch.int64)
@@ -315,8 +309,8 @@ class DeviceSampledVocabulary:
                     self.hn.result()
                 text._zett_n_text = int(rec.n_text)
                 surface_forms = self.hn.run_async(text, text_offsets, n_out, self.hn_surface_maxlen)
-                _lib.check(self.lib.zett_sampled_vocab_patch_rows(self.retok.handle, P(record), P(self._d_ids), P(self._d_hn), s, P(surface_forms), n_out,
-                                                                  self.hn_surface_maxlen, self.hn.spec.pad_token_id, C.c_void_p(stream)), "zett_sampled_vocab_patch_rows")
+                _lib.check(self.lib.zett_sampled_vocab_patch_rows(self.retok.handle, ptr(record), ptr(self._d_ids), ptr(self._d_hn), s, ptr(surface_forms), n_out,
+                                                                  self.hn_surface_maxlen, self.hn.spec.pad_token_id, st), "zett_sampled_vocab_patch_rows")
                 if check:
                     self.hn.result()
         from .text_encode import DeviceTextEncoder
@@ -337,9 +331,8 @@ class DeviceSampledVocabulary:
             scores = torch.zeros(cap, dtype=torch.float64, device=self.device)
             single = torch.zeros(256, dtype=torch.int32, device=self.device)
             n = torch.zeros(1, dtype=torch.int32, device=self.device)
-            P = lambda t: C.c_void_p(t.data_ptr())          # noqa: E731
-            _lib.check(self.lib.zett_sampled_vocab_table(self.retok.handle, P(keys), P(lengths), P(ids), P(scores), P(single), cap, P(n),
-                                                         C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)), "zett_sampled_vocab_table")
+            _lib.check(self.lib.zett_sampled_vocab_table(self.retok.handle, ptr(keys), ptr(lengths), ptr(ids), ptr(scores), ptr(single), cap, ptr(n),
+                                                         stream(self.device)), "zett_sampled_vocab_table")
             count = min(int(n.item()), cap)
             k, ln = keys[:count].cpu().numpy(), lengths[:count].cpu().numpy()
         return [bytes(k[i, :ln[i]]) for i in range(count)], ids[:count].cpu().numpy(), scores[:count].cpu().numpy(), single.cpu().numpy()

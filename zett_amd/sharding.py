@@ -90,6 +90,7 @@ def affinity_order(surface_forms: torch.Tensor, world: int, pad_token_id: int, n
     import ctypes as C
 
     from . import _lib
+    from ._glue import ptr, stream
     if not surface_forms.is_cuda:
         raise RuntimeError("zett_amd computes on MI355X only: affinity_order takes the surface-form matrix on a cuda (ROCm) device")
     world = int(world)
@@ -105,9 +106,8 @@ def affinity_order(surface_forms: torch.Tensor, world: int, pad_token_id: int, n
     perm = torch.empty((n,), dtype=torch.int32, device=sfm.device)
     index = sfm.device.index if sfm.device.index is not None else torch.cuda.current_device()
     with torch.cuda.device(sfm.device):
-        stream = torch.cuda.current_stream(sfm.device).cuda_stream
-        _lib.check(lib.zett_partition_rows(C.c_void_p(sfm.data_ptr()), n, seq, int(pad_token_id), int(n_ids), world, (C.c_int32 * world)(*caps),
-                                           C.c_void_p(perm.data_ptr()), C.c_void_p(ws.data_ptr()), ws_bytes.value, index, C.c_void_p(stream)),
+        _lib.check(lib.zett_partition_rows(ptr(sfm), n, seq, int(pad_token_id), int(n_ids), world, (C.c_int32 * world)(*caps),
+                                           ptr(perm), ptr(ws), ws_bytes.value, index, stream(sfm.device)),
                    "zett_partition_rows")
     # where plan_blocks looks for rank r's rows: per block [lo, hi).  src[i] = position in `perm` (grouped by rank) of the row that
     # goes to place i of the sharded order — pure arithmetic on the block plan, cached per (n, world, chunks)
@@ -244,9 +244,8 @@ class RowGather:
         if not full.is_cuda:
             self._pending.append((i, lo, hi))
             return
-        import ctypes as C
-
         from . import _lib
+        from ._glue import ptr, stream
         cur = torch.cuda.current_stream(full.device)
         if early:
             side = self._side                       # (the exchange was issued from it)
@@ -263,9 +262,8 @@ class RowGather:
             if row_bytes != 4 and row_bytes % 16:   # rows zett_scatter_rows does not take (a 16-bit bias, E * element size not a multiple of 16)
                 out.index_copy_(0, self.order[lo:hi], full[lo:hi])
             else:
-                _lib.check(_lib.load().zett_scatter_rows(C.c_void_p(full.data_ptr() + lo * row_bytes), C.c_void_p(out.data_ptr()),
-                                                         C.c_void_p(self.order.data_ptr() + lo * 8), hi - lo, row_bytes, index,
-                                                         C.c_void_p(side.cuda_stream)), "zett_scatter_rows")
+                _lib.check(_lib.load().zett_scatter_rows(ptr(full, lo * row_bytes), ptr(out), ptr(self.order, lo * 8), hi - lo, row_bytes, index, stream(of=side)),
+                           "zett_scatter_rows")
         # finish() must not wait for these again: the compute stream gets them through wait_stream(side), and a SECOND wait() on a
         # gloo send / recv work blocks for ever (its completion has been consumed: the two-ranks-on-one-device bench hung there)
         done = {id(w) for w in works}

@@ -21,6 +21,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._glue import default_device, ptr, stream
 
 
 # ---- the byte <-> character table (reference zett/utils.py:351-609) -----------------------
@@ -201,18 +202,18 @@ class DeviceRetokenizer:
         self.spec = spec
         self.device = device
 
-        def ptr(a):
+        def host_ptr(a):
             return None if a is None else a.ctypes.data_as(C.c_void_p)
 
         m = _lib.ZettRetokModel(
-            kind=spec.kind, n_pieces=len(spec.piece_ids), piece_bytes=ptr(spec.piece_bytes),
-            piece_offsets=ptr(spec.piece_offsets), piece_ids=ptr(spec.piece_ids), piece_scores=ptr(spec.piece_scores),
-            unigram_min_score=spec.unigram_min_score, n_merges=len(spec.merges), merges=ptr(spec.merges),
+            kind=spec.kind, n_pieces=len(spec.piece_ids), piece_bytes=host_ptr(spec.piece_bytes),
+            piece_offsets=host_ptr(spec.piece_offsets), piece_ids=host_ptr(spec.piece_ids), piece_scores=host_ptr(spec.piece_scores),
+            unigram_min_score=spec.unigram_min_score, n_merges=len(spec.merges), merges=host_ptr(spec.merges),
             unk_id=spec.unk_id, fuse_unk=int(spec.fuse_unk), byte_fallback=int(spec.byte_fallback),
-            byte_fallback_ids=ptr(spec.byte_fallback_ids), ignore_merges=int(spec.ignore_merges),
-            n_special=len(spec.special_ids), special_bytes=ptr(spec.special_bytes),
-            special_offsets=ptr(spec.special_offsets), special_ids=ptr(spec.special_ids),
-            piece_continuing=ptr(spec.piece_continuing), max_input_chars_per_word=int(spec.max_input_chars_per_word))
+            byte_fallback_ids=host_ptr(spec.byte_fallback_ids), ignore_merges=int(spec.ignore_merges),
+            n_special=len(spec.special_ids), special_bytes=host_ptr(spec.special_bytes),
+            special_offsets=host_ptr(spec.special_offsets), special_ids=host_ptr(spec.special_ids),
+            piece_continuing=host_ptr(spec.piece_continuing), max_input_chars_per_word=int(spec.max_input_chars_per_word))
         handle = C.c_void_p()
         index = device.index if device.index is not None else torch.cuda.current_device()
         _lib.check(self.lib.zett_retok_create(C.byref(m), index, C.byref(handle)), "zett_retok_create")
@@ -324,10 +325,8 @@ class DeviceRetokenizer:
         n_trunc = C.c_int64(0)
         bad = C.c_int64(-1)
         with torch.cuda.device(self.device):
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-            rc = self.lib.zett_retokenize(self.handle, C.c_void_p(d_text.data_ptr()), C.c_void_p(d_off.data_ptr()), n,
-                                          int(maxlen), self.spec.pad_token_id, C.c_void_p(out.data_ptr()),
-                                          C.byref(n_trunc), C.byref(bad), C.c_void_p(stream))
+            rc = self.lib.zett_retokenize(self.handle, ptr(d_text), ptr(d_off), n, int(maxlen), self.spec.pad_token_id, ptr(out),
+                                          C.byref(n_trunc), C.byref(bad), stream(self.device))
         if rc == _lib.E_KEY and bad.value >= 0 and tokens is not None:
             for ch in tokens[bad.value]:                 # the reference raises KeyError(<character>)
                 if ch not in CHARS_TO_BYTES:
@@ -348,10 +347,7 @@ class DeviceRetokenizer:
                 raise ValueError("NUL-separated text (d_off = None) must come from encode_joined()")
             n_text = int(d_off[-1].item()) if n else 0          # (text not made by encode(): one device round trip)
         with torch.cuda.device(self.device):
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-            rc = self.lib.zett_retokenize_async(self.handle, C.c_void_p(d_text.data_ptr()), C.c_void_p(d_off.data_ptr() if d_off is not None else 0), n,
-                                                n_text, int(maxlen), self.spec.pad_token_id,
-                                                C.c_void_p(out.data_ptr()), C.c_void_p(stream))
+            rc = self.lib.zett_retokenize_async(self.handle, ptr(d_text), ptr(d_off), n, n_text, int(maxlen), self.spec.pad_token_id, ptr(out), stream(self.device))
         _lib.check(rc, "zett_retokenize_async")
         self._outstanding.append((d_text, d_off))       # zett_retok_result reads `offsets` back on a KeyError: alive until result()
         return out
@@ -422,12 +418,7 @@ _CACHE: Dict[Tuple[int, str], DeviceRetokenizer] = {}
 
 
 def device_retokenizer(tokenizer_to_use, device=None) -> DeviceRetokenizer:
-    if device is None:
-        if not torch.cuda.is_available():
-            raise RuntimeError("zett_amd computes on MI355X only: no cuda (ROCm) device is visible; there is no CPU path")
-        device = torch.device("cuda", torch.cuda.current_device())
-    else:
-        device = torch.device(device)
+    device = default_device(device)
     if isinstance(tokenizer_to_use, HnTokenizerSpec):
         spec = tokenizer_to_use
     else:

@@ -28,6 +28,7 @@ from typing import Dict, List, Mapping, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib
+from ._glue import default_device, ptr, stream
 
 # the split pattern of the sampled tokenizers (zett/utils.py:29) and, without \p{M} in the letter class, of pre_tokenizers.ByteLevel(use_regex=True)
 SPLIT_PATTERN_MARKS = r"'s|'t|'re|'ve|'m|'ll|'d| ?[\p{L}\p{M}]+| ?\p{N}+| ?[^\s\p{L}\p{N}]+|\s+(?!\S)|\s+"
@@ -124,6 +125,48 @@ def pack_class_table(table: np.ndarray) -> np.ndarray:
     if len(t) % 2:
         t = np.concatenate([t, np.zeros(1, dtype=np.uint8)])
     return (t[0::2] | (t[1::2] << 4)).astype(np.uint8)
+
+
+_DEVICE_CLASS_TABLES: Dict[object, object] = {}
+
+
+def device_class_table(device):
+    """``pack_class_table(class_table())`` on ``device``, uploaded once per device: the encoder, the sampler and the sampled vocabulary
+    share it (a caller's own ``table`` gets its own upload)."""
+    import torch
+    device = torch.device(device)
+    if device.index is None:
+        device = torch.device(device.type, torch.cuda.current_device())
+    if device not in _DEVICE_CLASS_TABLES:
+        _DEVICE_CLASS_TABLES[device] = torch.from_numpy(pack_class_table(class_table())).to(device)
+    return _DEVICE_CLASS_TABLES[device]
+
+
+def packed_table_on(device, table: Optional[np.ndarray], d_table=None):
+    """(class table, its packed copy on ``device``): the shared default pair for ``table=None``; ``d_table``: the packed copy, where
+    the caller keeps one"""
+    import torch
+    if table is None and d_table is None:
+        return class_table(), device_class_table(device)
+    table = class_table() if table is None else np.asarray(table, dtype=np.uint8)
+    return table, torch.from_numpy(pack_class_table(table)).to(device) if d_table is None else d_table
+
+
+def flatten_texts(texts: Sequence[str], joined: Optional[str] = None) -> Tuple[bytes, np.ndarray]:
+    """``(blob, offsets)``: the UTF-8 bytes of the texts end to end and int64 ``[len(texts) + 1]`` byte offsets, text ``i`` at
+    ``blob[offsets[i]:offsets[i + 1]]`` — what zett_encode_texts and zett_sampler_sample take.  One join and one encode; the byte
+    offsets are the character offsets for ASCII and come from the character starts of the blob otherwise.  ``joined``: ``"".join(texts)``
+    where the caller has it already."""
+    b = len(texts)
+    if joined is None:
+        joined = "".join(texts)
+    blob = joined.encode("utf-8")
+    chars = np.zeros(b + 1, dtype=np.int64)          # character offsets of the texts
+    np.cumsum(np.fromiter(map(len, texts), dtype=np.int64, count=b), out=chars[1:])
+    if len(blob) == len(joined):
+        return blob, chars
+    raw = np.frombuffer(blob, dtype=np.uint8)
+    return blob, np.append(np.flatnonzero((raw & 0xC0) != 0x80), len(raw))[chars]
 
 
 # ---- what the kernels need to know about a tokenizer -------------------------------------------------------------------------------
@@ -244,25 +287,17 @@ class DeviceTextEncoder:
     """``tokenizer(texts, max_length=block_size, truncation=True, padding="max_length", add_special_tokens=True)`` on one GPU."""
 
     def __init__(self, model_spec, encode_spec: EncodeSpec, device=None, table: Optional[np.ndarray] = None):
-        import torch
-
         from .surface_forms import DeviceRetokenizer
-        if device is None:
-            if not torch.cuda.is_available():
-                raise RuntimeError("zett_amd computes on MI355X only: no cuda (ROCm) device is visible; there is no CPU path")
-            device = torch.device("cuda", torch.cuda.current_device())
-        self.device = torch.device(device)
+        self.device = default_device(device)
         if model_spec.kind not in (_lib.RETOK_BPE, _lib.RETOK_UNIGRAM):
             raise NotImplementedError("text encoding with a WordPiece model")
         self._adopt(DeviceRetokenizer(model_spec, self.device), encode_spec, table, None, True)
 
     def _adopt(self, retok, encode_spec: EncodeSpec, table, d_table, owns_handle: bool) -> None:
-        import torch
         self.spec = encode_spec
         self.retok = retok
         self.lib = retok.lib
-        self.table = class_table() if table is None else np.asarray(table, dtype=np.uint8)          # (cached on the encoder)
-        self._d_table = torch.from_numpy(pack_class_table(self.table)).to(self.device) if d_table is None else d_table
+        self.table, self._d_table = packed_table_on(self.device, table, d_table)
         k = _lib.ENCODE_MAX_TEMPLATE
         self._prefix = (C.c_int32 * k)(*encode_spec.prefix_ids)
         self._suffix = (C.c_int32 * k)(*encode_spec.suffix_ids)
@@ -309,15 +344,7 @@ class DeviceTextEncoder:
         texts = list(texts)
         joined, pairs = self.spec.check_call(texts, block_size, special_ids_map)
         b, t = len(texts), int(block_size)
-        blob = joined.encode("utf-8")
-        chars = np.zeros(b + 1, dtype=np.int64)          # character offsets of the texts; byte offsets from the character starts of the blob
-        np.cumsum(np.fromiter(map(len, texts), dtype=np.int64, count=b), out=chars[1:])
-        if len(blob) == len(joined):
-            offsets = chars
-        else:
-            raw = np.frombuffer(blob, dtype=np.uint8)
-            offsets = np.append(np.flatnonzero((raw & 0xC0) != 0x80), len(raw))[chars]
-        assert offsets[-1] == len(blob)
+        blob, offsets = flatten_texts(texts, joined)
         with torch.cuda.device(self.device):
             if out is None:
                 ids = torch.empty((b, t), dtype=dtype, device=self.device)
@@ -335,12 +362,10 @@ class DeviceTextEncoder:
             m_from = (C.c_int32 * max(n_map, 1))(*[p[0] for p in pairs])
             m_to = (C.c_int32 * max(n_map, 1))(*[p[1] for p in pairs])
             ld = ids.stride(0) if b > 1 else t
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-            rc = self.lib.zett_encode_texts(self.retok.handle, C.c_void_p(d_text.data_ptr()), C.c_void_p(d_off.data_ptr()), b, len(blob),
-                                            C.c_void_p(self._d_table.data_ptr()), len(self.table), self.spec.flags, self.spec.prefix_mode, t,
-                                            self._prefix, len(self.spec.prefix_ids), self._suffix, len(self.spec.suffix_ids), m_from, m_to, n_map, self.spec.pad_id,
-                                            C.c_void_p(ids.data_ptr() if b else 0), C.c_void_p(mask.data_ptr() if b else 0), ids.element_size(), ld,
-                                            C.c_void_p(work.data_ptr()), work.numel(), C.c_void_p(status.data_ptr()), C.c_void_p(stream))
+            rc = self.lib.zett_encode_texts(self.retok.handle, ptr(d_text), ptr(d_off), b, len(blob), ptr(self._d_table), len(self.table), self.spec.flags,
+                                            self.spec.prefix_mode, t, self._prefix, len(self.spec.prefix_ids), self._suffix, len(self.spec.suffix_ids), m_from, m_to, n_map,
+                                            self.spec.pad_id, ptr(ids if b else None), ptr(mask if b else None), ids.element_size(), ld, ptr(work), work.numel(),
+                                            ptr(status), stream(self.device))
             _lib.check(rc, "zett_encode_texts")
         if check:
             bits = int(status.item())          # (the one host read of this call)

@@ -23,8 +23,9 @@ from typing import Dict, List, Mapping, NamedTuple, Optional, Sequence, Tuple, U
 import numpy as np
 
 from . import _lib
+from ._glue import default_device, ptr, stream
 from .surface_forms import BYTES_TO_CHARS_LIST, CHARS_TO_BYTES
-from .text_encode import SPLIT_PATTERN_MARKS, class_table, pack_class_table
+from .text_encode import SPLIT_PATTERN_MARKS, flatten_texts, packed_table_on
 
 SAMPLE_BAD_OFFSETS, SAMPLE_TABLE_FULL, SAMPLE_LIST_FULL = _lib.SAMPLE_BAD_OFFSETS, _lib.SAMPLE_TABLE_FULL, _lib.SAMPLE_LIST_FULL
 SAMPLE_SUM_OVERFLOW, SAMPLE_OUT_FULL = _lib.SAMPLE_SUM_OVERFLOW, _lib.SAMPLE_OUT_FULL
@@ -77,18 +78,13 @@ class DeviceTokenizerSampler:
     def __init__(self, device=None, max_depth: int = 16, table_capacity: int = 1 << 22, list_capacity: Optional[int] = None, max_pieces: int = 1 << 16,
                  table: Optional[np.ndarray] = None):
         import torch
-        if device is None:
-            if not torch.cuda.is_available():
-                raise RuntimeError("zett_amd computes on MI355X only: no cuda (ROCm) device is visible; there is no CPU path")
-            device = torch.device("cuda", torch.cuda.current_device())
-        self.device = torch.device(device)
+        self.device = default_device(device)
         if self.device.type != "cuda":
             raise RuntimeError("zett_amd computes on MI355X only: the sampler needs a cuda (ROCm) device; there is no CPU path")
         self.lib = _lib.load()
         self.max_depth, self.table_capacity, self.max_pieces = int(max_depth), int(table_capacity), int(max_pieces)
         self.list_capacity = int(list_capacity) if list_capacity is not None else max(1, self.table_capacity // 2)
-        self.table = class_table() if table is None else np.asarray(table, dtype=np.uint8)
-        self._d_table = torch.from_numpy(pack_class_table(self.table)).to(self.device)
+        self.table, self._d_table = packed_table_on(self.device, table)
         handle = C.c_void_p()
         index = self.device.index if self.device.index is not None else torch.cuda.current_device()
         _lib.check(self.lib.zett_sampler_create(index, self.max_depth, self.list_capacity, self.table_capacity, self.max_pieces, C.byref(handle)), "zett_sampler_create")
@@ -136,15 +132,7 @@ class DeviceTokenizerSampler:
         if not pop_prev and push_current and self.depth >= self.max_depth:
             raise RuntimeError(f"the queue holds {self.depth} batches, the sampler was created with max_depth = {self.max_depth}")
         b = len(texts)
-        joined = "".join(texts)
-        blob = joined.encode("utf-8")
-        chars = np.zeros(b + 1, dtype=np.int64)
-        np.cumsum(np.fromiter(map(len, texts), dtype=np.int64, count=b), out=chars[1:])
-        if len(blob) == len(joined):
-            offsets = chars
-        else:
-            raw = np.frombuffer(blob, dtype=np.uint8)
-            offsets = np.append(np.flatnonzero((raw & 0xC0) != 0x80), len(raw))[chars]
+        blob, offsets = flatten_texts(texts)
         cap = fixed + k if pop_prev else 1
         with torch.cuda.device(self.device):
             pieces = torch.zeros((cap, 16), dtype=torch.uint8, device=self.device)
@@ -157,11 +145,9 @@ class DeviceTokenizerSampler:
             need = C.c_int64(0)
             _lib.check(self.lib.zett_sampler_workspace_bytes(len(blob), b, C.byref(need)), "zett_sampler_workspace_bytes")
             work = torch.empty(max(need.value, 16), dtype=torch.uint8, device=self.device)
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-            rc = self.lib.zett_sampler_sample(self.handle, C.c_void_p(d_text.data_ptr()), C.c_void_p(d_off.data_ptr()), b, len(blob), C.c_void_p(self._d_table.data_ptr()),
-                                              len(self.table), seed_size, max_length, stride, noise_std, int(seed) & (2 ** 64 - 1), int(bool(pop_prev)),
-                                              int(bool(push_current)), C.c_void_p(pieces.data_ptr()), C.c_void_p(lengths.data_ptr()), C.c_void_p(scores.data_ptr()), cap,
-                                              C.c_void_p(n.data_ptr()), C.c_void_p(work.data_ptr()), work.numel(), C.c_void_p(status.data_ptr()), C.c_void_p(stream))
+            rc = self.lib.zett_sampler_sample(self.handle, ptr(d_text), ptr(d_off), b, len(blob), ptr(self._d_table), len(self.table), seed_size, max_length, stride,
+                                              noise_std, int(seed) & (2 ** 64 - 1), int(bool(pop_prev)), int(bool(push_current)), ptr(pieces), ptr(lengths), ptr(scores),
+                                              cap, ptr(n), ptr(work), work.numel(), ptr(status), stream(self.device))
             _lib.check(rc, "zett_sampler_sample")
         self.last_status = status
         if check:
@@ -180,9 +166,7 @@ class DeviceTokenizerSampler:
             counts = torch.zeros(cap, dtype=torch.int32, device=self.device)
             z = torch.zeros(cap, dtype=torch.float64, device=self.device)
             n = torch.zeros(1, dtype=torch.int32, device=self.device)
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-            _lib.check(self.lib.zett_sampler_table(self.handle, C.c_void_p(keys.data_ptr()), C.c_void_p(lengths.data_ptr()), C.c_void_p(counts.data_ptr()),
-                                                   C.c_void_p(z.data_ptr()), cap, C.c_void_p(n.data_ptr()), C.c_void_p(stream)), "zett_sampler_table")
+            _lib.check(self.lib.zett_sampler_table(self.handle, ptr(keys), ptr(lengths), ptr(counts), ptr(z), cap, ptr(n), stream(self.device)), "zett_sampler_table")
         m = min(int(n.item()), cap)
         k, ln = keys[:m].cpu().numpy(), lengths[:m].cpu().numpy()
         return [bytes(k[i, :ln[i]]) for i in range(m)], counts[:m].cpu().numpy().view(np.uint32), z[:m].cpu().numpy()

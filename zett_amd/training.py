@@ -29,17 +29,9 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _lib
+from ._glue import ptr, stream, zett_dtypes
 
 _KINDS = {"mse": _lib.DIST_MSE, "rmse": _lib.DIST_RMSE, "huber": _lib.DIST_HUBER}
-_SRC_DTYPES = {torch.float32: _lib.DTYPE_F32, torch.float16: _lib.DTYPE_F16, torch.bfloat16: _lib.DTYPE_BF16}
-
-
-def _ptr(t: Optional[torch.Tensor]):
-    return C.c_void_p(0 if t is None else t.data_ptr())
-
-
-def _stream(device):
-    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
 # ---- the three kernels of an embedding distance ---------------------------------------------------------------------------
@@ -48,7 +40,7 @@ def _dist_args(pred, src, col0, ids, ids_stride, mask, kind):
         raise ValueError(f"kind must be one of {sorted(_KINDS)}, got {kind!r}")
     if pred.dim() != 2 or pred.dtype != torch.float32 or pred.stride(1) != 1 or not pred.is_cuda:
         raise ValueError("predicted embeddings must be a [n, E] fp32 device tensor with unit column stride")
-    if src.dim() != 2 or src.dtype not in _SRC_DTYPES or src.stride(1) != 1 or src.device != pred.device:
+    if src.dim() != 2 or src.dtype not in zett_dtypes() or src.stride(1) != 1 or src.device != pred.device:
         raise ValueError("source_embeddings must be a 2-D fp32 / f16 / bf16 tensor on the device of the predictions")
     if ids.dtype not in (torch.int32, torch.int64) or ids.device != pred.device:
         raise ValueError("ids must be an int32 / int64 tensor on the device of the predictions")
@@ -59,8 +51,8 @@ def _dist_args(pred, src, col0, ids, ids_stride, mask, kind):
         raise ValueError(f"columns [{col0}, {col0 + e}) are outside source_embeddings {tuple(src.shape)}")
     if mask is not None and (mask.dtype != torch.float32 or mask.shape != (n,) or not mask.is_contiguous()):
         raise ValueError("mask must be a contiguous fp32 [n] tensor")
-    return (_ptr(pred), pred.stride(0), _ptr(src), _SRC_DTYPES[src.dtype], src.stride(0), src.shape[0], int(col0), _ptr(ids), ids.element_size(), int(ids_stride),
-            _ptr(mask)), n, e
+    return (ptr(pred), pred.stride(0), ptr(src), zett_dtypes()[src.dtype], src.stride(0), src.shape[0], int(col0), ptr(ids), ids.element_size(), int(ids_stride),
+            ptr(mask)), n, e
 
 
 def embed_distance_forward(pred, src, col0, ids, ids_stride=1, mask=None, kind="mse", mode=_lib.LOSS_MEAN):
@@ -71,9 +63,9 @@ def embed_distance_forward(pred, src, col0, ids, ids_stride=1, mask=None, kind="
     with torch.cuda.device(pred.device):
         rows = torch.empty((2, n), dtype=torch.float32, device=pred.device)
         record = torch.empty(4, dtype=torch.float32, device=pred.device)
-        st = _stream(pred.device)
-        _lib.check(lib.zett_op_embed_dist_rows(*head, n, e, _KINDS[kind], _ptr(rows[0]), _ptr(rows[1]), st), "embed_dist_rows")
-        _lib.check(lib.zett_op_embed_dist_finalize(_ptr(rows[0]), _ptr(rows[1]), _ptr(mask), n, int(mode), _ptr(record), st), "embed_dist_finalize")
+        st = stream(pred.device)
+        _lib.check(lib.zett_op_embed_dist_rows(*head, n, e, _KINDS[kind], ptr(rows[0]), ptr(rows[1]), st), "embed_dist_rows")
+        _lib.check(lib.zett_op_embed_dist_finalize(ptr(rows[0]), ptr(rows[1]), ptr(mask), n, int(mode), ptr(record), st), "embed_dist_finalize")
     return record, rows[0], rows[1]
 
 
@@ -89,8 +81,8 @@ def embed_distance_backward(pred, src, col0, ids, ids_stride, mask, kind, row_di
         raise ValueError("out must be a [n, E] fp32 tensor with unit column stride on the device of the predictions")
     upstream = upstream.detach().to(device=pred.device, dtype=torch.float32).reshape(1)
     with torch.cuda.device(pred.device):
-        _lib.check(lib.zett_op_embed_dist_grad(*head, _ptr(row_dist), n, e, _KINDS[kind], _ptr(record), _ptr(upstream), _ptr(out), out.stride(0),
-                                               int(bool(accumulate)), _stream(pred.device)), "embed_dist_grad")
+        _lib.check(lib.zett_op_embed_dist_grad(*head, ptr(row_dist), n, e, _KINDS[kind], ptr(record), ptr(upstream), ptr(out), out.stride(0),
+                                               int(bool(accumulate)), stream(pred.device)), "embed_dist_grad")
     return out
 
 
@@ -101,8 +93,8 @@ def single_token_mask(target_surface_forms: torch.Tensor, pad_token_id: int) -> 
         raise ValueError("target_surface_forms must be a [n, L] int32 / int64 device tensor with unit column stride")
     mask = torch.empty(ids.shape[0], dtype=torch.float32, device=ids.device)
     with torch.cuda.device(ids.device):
-        _lib.check(_lib.load().zett_op_single_token_mask(_ptr(ids), ids.element_size(), ids.shape[0], ids.shape[1], ids.stride(0), int(pad_token_id), _ptr(mask),
-                                                         _stream(ids.device)), "single_token_mask")
+        _lib.check(_lib.load().zett_op_single_token_mask(ptr(ids), ids.element_size(), ids.shape[0], ids.shape[1], ids.stride(0), int(pad_token_id), ptr(mask),
+                                                         stream(ids.device)), "single_token_mask")
     return mask
 
 
@@ -135,7 +127,7 @@ def _pair(pred_in, pred_out, source_embeddings, ids, ids_stride, mask, kind, mod
     if pred_in.dim() != 2:
         raise ValueError("predicted embeddings must be [n, E]")
     e = pred_in.shape[1]
-    src = source_embeddings if source_embeddings.dtype in _SRC_DTYPES else source_embeddings.float()
+    src = source_embeddings if source_embeddings.dtype in zett_dtypes() else source_embeddings.float()
     need = e if pred_out is None else 2 * e
     if src.dim() != 2 or src.shape[1] < need:
         raise ValueError(f"source_embeddings must be [V, >= {need}] (input half{'' if pred_out is None else ' + output half'}), got {tuple(src.shape)}")
@@ -235,7 +227,7 @@ def _lm_check(hidden, pred_out, labels, bias, priors, vocab_mask, precision, chu
         raise ValueError(f"precision must be one of {sorted(_LM_PRECISIONS)}, got {precision!r}")
     if path not in _LM_PATHS:
         raise ValueError(f'rows_path must be None, "auto", "once" or "twice", got {path!r}')
-    if hidden.dim() < 2 or hidden.dtype not in _SRC_DTYPES:
+    if hidden.dim() < 2 or hidden.dtype not in zett_dtypes():
         raise ValueError("hidden must be a [..., E] fp32 / f16 / bf16 tensor")
     if pred_out.dim() != 2 or pred_out.dtype != torch.float32 or pred_out.shape[1] != hidden.shape[-1]:
         raise ValueError(f"pred_out must be a [V, E] fp32 tensor with E = {hidden.shape[-1]}, got {tuple(pred_out.shape)} {pred_out.dtype}")
@@ -274,7 +266,7 @@ def _lm_run(hidden, w_out, bias, priors, vocab_mask, lab, wgt, precision, chunk_
     lib = _lib.load()
     dev = w_out.device
     prec, lo_dtype, kstep = _LM_PRECISIONS[precision]
-    lo_code = _SRC_DTYPES[lo_dtype]
+    lo_code = zett_dtypes()[lo_dtype]
     t, e = hidden.shape
     v = w_out.shape[0]
     vp, ep = -(-v // kstep) * kstep, -(-e // kstep) * kstep
@@ -287,41 +279,41 @@ def _lm_run(hidden, w_out, bias, priors, vocab_mask, lab, wgt, precision, chunk_
         return torch.empty(shape, dtype=dtype, device=dev)
 
     with torch.cuda.device(dev):
-        st = _stream(dev)
+        st = stream(dev)
 
         def gemm(a, lda, w, ldw, m, n, k, out, ld_out, addend=None, residual=None, ld_res=0):
             if prec is None:
-                _lib.check(lib.zett_op_gemm_f32(_ptr(a), lda, _ptr(w), ldw, m, n, k, _ptr(addend), 0, _ptr(residual), ld_res, _ptr(out), ld_out, st), "zett_op_gemm_f32")
+                _lib.check(lib.zett_op_gemm_f32(ptr(a), lda, ptr(w), ldw, m, n, k, ptr(addend), 0, ptr(residual), ld_res, ptr(out), ld_out, st), "zett_op_gemm_f32")
             else:
-                _lib.check(lib.zett_op_gemm_lo(prec, _ptr(a), lda, _ptr(w), ldw, m, n, k, _ptr(addend), 0, _ptr(residual), ld_res, _ptr(out), ld_out, st), "zett_op_gemm_lo")
+                _lib.check(lib.zett_op_gemm_lo(prec, ptr(a), lda, ptr(w), ldw, m, n, k, ptr(addend), 0, ptr(residual), ld_res, ptr(out), ld_out, st), "zett_op_gemm_lo")
 
         def transpose(x, ld_in, out, ld_out, rows, cols, rows_padded):          # out[c, r] = x[r, c], rows zero-padded: operands of the training GEMMs
             if prec is None:
-                _lib.check(lib.zett_op_transpose_f32(_ptr(x), ld_in, _ptr(out), ld_out, rows, cols, rows_padded, st), "zett_op_transpose_f32")
+                _lib.check(lib.zett_op_transpose_f32(ptr(x), ld_in, ptr(out), ld_out, rows, cols, rows_padded, st), "zett_op_transpose_f32")
             else:
-                _lib.check(lib.zett_op_transpose_lo16(prec, _ptr(x), ld_in, _ptr(out), ld_out, rows, cols, rows_padded, st), "zett_op_transpose_lo16")
+                _lib.check(lib.zett_op_transpose_lo16(prec, ptr(x), ld_in, ptr(out), ld_out, rows, cols, rows_padded, st), "zett_op_transpose_lo16")
 
         # once per call: the addend vector and the operand forms of pred_out
         addend = None
         if bias is not None or priors is not None or vocab_mask is not None:
             addend = new(vp)
-            _lib.check(lib.zett_op_ce_addend(_ptr(bias), _ptr(priors), _ptr(None if vocab_mask is None else vocab_mask.view(torch.uint8)), v, vp, _ptr(addend), st), "zett_op_ce_addend")
+            _lib.check(lib.zett_op_ce_addend(ptr(bias), ptr(priors), ptr(None if vocab_mask is None else vocab_mask.view(torch.uint8)), v, vp, ptr(addend), st), "zett_op_ce_addend")
         if prec is None:
             if ep == e and w_out.stride(0) % 4 == 0 and w_out.data_ptr() % 16 == 0:
                 w_op = w_out
             else:
                 w_op = new(v, ep)
-                _lib.check(lib.zett_op_ce_cast(_ptr(w_out), _lib.DTYPE_F32, w_out.stride(0), _ptr(w_op), _lib.DTYPE_F32, ep, v, e, ep, st), "zett_op_ce_cast")
+                _lib.check(lib.zett_op_ce_cast(ptr(w_out), _lib.DTYPE_F32, w_out.stride(0), ptr(w_op), _lib.DTYPE_F32, ep, v, e, ep, st), "zett_op_ce_cast")
         else:
             w_op = new(v, ep, dtype=lo_dtype)
-            _lib.check(lib.zett_op_convert_lo(prec, _ptr(w_out), w_out.stride(0), _ptr(w_op), ep, v, e, ep, st), "zett_op_convert_lo")
+            _lib.check(lib.zett_op_convert_lo(prec, ptr(w_out), w_out.stride(0), ptr(w_op), ep, v, e, ep, st), "zett_op_convert_lo")
         w_t = None
         if want_h:                                   # lo(W)^T [E, V'] (V zero-padded to the K step): the operand of d hidden = G . W
             w_t = new(e, vp, dtype=lo_dtype)
             if prec is None:
-                _lib.check(lib.zett_op_transpose_f32(_ptr(w_out), w_out.stride(0), _ptr(w_t), vp, v, e, vp, st), "zett_op_transpose_f32")
+                _lib.check(lib.zett_op_transpose_f32(ptr(w_out), w_out.stride(0), ptr(w_t), vp, v, e, vp, st), "zett_op_transpose_f32")
             else:
-                _lib.check(lib.zett_op_transpose_lo(prec, _ptr(w_out), w_out.stride(0), _ptr(w_t), vp, v, e, vp, st), "zett_op_transpose_lo")
+                _lib.check(lib.zett_op_transpose_lo(prec, ptr(w_out), w_out.stride(0), ptr(w_t), vp, v, e, vp, st), "zett_op_transpose_lo")
 
         direct = hidden.dtype == lo_dtype and ep == e and hidden.stride(0) % 8 == 0 and hidden.data_ptr() % 16 == 0          # the hidden state is an operand as it is
         a_buf = None if direct else new(tc, ep, dtype=lo_dtype)
@@ -343,12 +335,12 @@ def _lm_run(hidden, w_out, bias, priors, vocab_mask, lab, wgt, precision, chunk_
                 a, lda = hidden[r0:r0 + n], hidden.stride(0)
             else:
                 a, lda = a_buf, ep
-                _lib.check(lib.zett_op_ce_cast(_ptr(hidden[r0:r0 + n]), _SRC_DTYPES[hidden.dtype], hidden.stride(0), _ptr(a), lo_code, ep, n, e, ep, st), "zett_op_ce_cast")
+                _lib.check(lib.zett_op_ce_cast(ptr(hidden[r0:r0 + n]), zett_dtypes()[hidden.dtype], hidden.stride(0), ptr(a), lo_code, ep, n, e, ep, st), "zett_op_ce_cast")
             gemm(a, lda, w_op, w_op.stride(0), n, v, ep, logits, vp, addend=addend)
-            _lib.check(lib.zett_op_ce_rows(_ptr(logits), vp, _ptr(lab[r0:]), _ptr(None if wgt is None else wgt[r0:]), n, v, vp, _ptr(g), lo_code, vp,
-                                           _ptr(row_loss[r0:]), _ptr(lse[r0:]), _ptr(argmax[r0:]), _LM_PATHS[path], st), "zett_op_ce_rows")
+            _lib.check(lib.zett_op_ce_rows(ptr(logits), vp, ptr(lab[r0:]), ptr(None if wgt is None else wgt[r0:]), n, v, vp, ptr(g), lo_code, vp,
+                                           ptr(row_loss[r0:]), ptr(lse[r0:]), ptr(argmax[r0:]), _LM_PATHS[path], st), "zett_op_ce_rows")
             if want_b:
-                _lib.check(lib.zett_op_ce_colsum(_ptr(g), lo_code, vp, n, v, _ptr(d_bias), int(i > 0), st), "zett_op_ce_colsum")
+                _lib.check(lib.zett_op_ce_colsum(ptr(g), lo_code, vp, n, v, ptr(d_bias), int(i > 0), st), "zett_op_ce_colsum")
             if want_w:                               # dW += G^T . hidden_chunk
                 transpose(g, vp, g_t, tcp, n, v, np_)
                 transpose(a, lda, h_t, tcp, n, e, np_)
@@ -357,7 +349,7 @@ def _lm_run(hidden, w_out, bias, priors, vocab_mask, lab, wgt, precision, chunk_
                 gemm(g_t, tcp, h_t, tcp, v, e, np_, d_w, e, residual=d_w_prev if i > 0 else None, ld_res=e if i > 0 else 0)
             if want_h:                               # d hidden_chunk = G . W
                 gemm(g, vp, w_t, vp, n, e, vp, d_hidden[r0:], e)
-        _lib.check(lib.zett_op_ce_finalize(_ptr(row_loss), _ptr(wgt), _ptr(lab), _ptr(argmax), t, _ptr(record), st), "zett_op_ce_finalize")
+        _lib.check(lib.zett_op_ce_finalize(ptr(row_loss), ptr(wgt), ptr(lab), ptr(argmax), t, ptr(record), st), "zett_op_ce_finalize")
     return record, row_loss, lse, argmax, d_hidden, d_w if want_w else None, d_bias
 
 
@@ -365,7 +357,7 @@ def _lm_scale(x, record, upstream, dtype):
     """x * upstream / sum(w) as `dtype`; both factors are read on the device."""
     out = torch.empty(x.shape, dtype=dtype, device=x.device)
     with torch.cuda.device(x.device):
-        _lib.check(_lib.load().zett_op_ce_scale(_ptr(x), x.numel(), _ptr(record), _ptr(upstream), _ptr(out), _SRC_DTYPES[dtype], _stream(x.device)), "zett_op_ce_scale")
+        _lib.check(_lib.load().zett_op_ce_scale(ptr(x), x.numel(), ptr(record), ptr(upstream), ptr(out), zett_dtypes()[dtype], stream(x.device)), "zett_op_ce_scale")
     return out
 
 
@@ -508,9 +500,9 @@ def _splice_launch(src_matrix, out, source, col0, rows, refs):
     f = (C.c_int32 * max(n, 1))(*(refs.tolist() if refs is not None else []))
     v, e = out.shape
     with torch.cuda.device(out.device):
-        _lib.check(_lib.load().zett_op_splice_rows(_ptr(src_matrix), 0 if src_matrix is None else src_matrix.stride(0), _ptr(out), out.stride(0), v, e, _ptr(source),
-                                                   _lib.DTYPE_F32 if source is None else _SRC_DTYPES[source.dtype], 0 if source is None else source.stride(0),
-                                                   0 if source is None else source.shape[0], int(col0), r, f, n, _stream(out.device)), "splice_rows")
+        _lib.check(_lib.load().zett_op_splice_rows(ptr(src_matrix), 0 if src_matrix is None else src_matrix.stride(0), ptr(out), out.stride(0), v, e, ptr(source),
+                                                   _lib.DTYPE_F32 if source is None else zett_dtypes()[source.dtype], 0 if source is None else source.stride(0),
+                                                   0 if source is None else source.shape[0], int(col0), r, f, n, stream(out.device)), "splice_rows")
     return out
 
 
@@ -570,7 +562,7 @@ def splice_special_rows(pred_in, pred_out, source_embeddings, special_indices, s
             raise ValueError(f"{name} must be a [V, E] fp32 device tensor{' with unit column stride' if inplace else ''}")
         if p is not None and inplace and torch.is_grad_enabled() and p.requires_grad and p.is_leaf:          # (torch would say so only after the rows are written)
             raise RuntimeError(f"{name} is a leaf that requires grad: it cannot be spliced in place (use inplace=False, or splice the hypernetwork's outputs)")
-    if src.dtype not in _SRC_DTYPES:
+    if src.dtype not in zett_dtypes():
         src = src.float()
     if src.device != pred_in.device or src.stride(1) != 1:
         raise ValueError("source_embeddings must be on the device of the predictions, with unit column stride")
@@ -590,8 +582,8 @@ def _lookup(table, ids, dtype, check_ids):
         return out
     with torch.cuda.device(table.device):
         word = torch.zeros(1, dtype=torch.int32, device=table.device) if check_ids else None
-        _lib.check(_lib.load().zett_op_embed_lookup(_ptr(table), _SRC_DTYPES[table.dtype], table.stride(0), v, e, _ptr(ids), ids.element_size(), t, _ptr(out),
-                                                    _SRC_DTYPES[dtype], _ptr(word), _stream(table.device)), "embed_lookup")
+        _lib.check(_lib.load().zett_op_embed_lookup(ptr(table), zett_dtypes()[table.dtype], table.stride(0), v, e, ptr(ids), ids.element_size(), t, ptr(out),
+                                                    zett_dtypes()[dtype], ptr(word), stream(table.device)), "embed_lookup")
     if check_ids and int(word.item()):          # (the one host read of this call)
         raise IndexError(f"token_embeddings: an id in input_ids is outside [0, {v})")
     return out
@@ -615,11 +607,11 @@ def embed_lookup_plan(ids, v: int, id_base: int = 0):
     scratch = torch.empty(max(scratch_bytes // 4, 1), dtype=torch.int32, device=ids.device)
     with torch.cuda.device(ids.device):
         if id_base:
-            _lib.check(_lib.load().zett_op_embed_lookup_plan_base(_ptr(ids), ids.element_size(), ids.numel(), int(id_base), int(v), _ptr(plan), plan.numel() * 4,
-                                                                  _ptr(scratch), scratch.numel() * 4, _stream(ids.device)), "embed_lookup_plan_base")
+            _lib.check(_lib.load().zett_op_embed_lookup_plan_base(ptr(ids), ids.element_size(), ids.numel(), int(id_base), int(v), ptr(plan), plan.numel() * 4,
+                                                                  ptr(scratch), scratch.numel() * 4, stream(ids.device)), "embed_lookup_plan_base")
         else:
-            _lib.check(_lib.load().zett_op_embed_lookup_plan(_ptr(ids), ids.element_size(), ids.numel(), int(v), _ptr(plan), plan.numel() * 4, _ptr(scratch),
-                                                             scratch.numel() * 4, _stream(ids.device)), "embed_lookup_plan")
+            _lib.check(_lib.load().zett_op_embed_lookup_plan(ptr(ids), ids.element_size(), ids.numel(), int(v), ptr(plan), plan.numel() * 4, ptr(scratch),
+                                                             scratch.numel() * 4, stream(ids.device)), "embed_lookup_plan")
     return plan
 
 
@@ -628,8 +620,8 @@ def embed_lookup_backward(grad, plan, t: int, v: int, e: int):
     d = torch.empty((v, e), dtype=torch.float32, device=grad.device)
     partials = torch.empty(embed_lookup_workspace(t, v, e)[2] // 4, dtype=torch.float32, device=grad.device)
     with torch.cuda.device(grad.device):
-        _lib.check(_lib.load().zett_op_embed_lookup_bwd(_ptr(grad), _SRC_DTYPES[grad.dtype], int(t), int(v), int(e), _ptr(plan), plan.numel() * 4, _ptr(partials),
-                                                        partials.numel() * 4, _ptr(d), e, _stream(grad.device)), "embed_lookup_bwd")
+        _lib.check(_lib.load().zett_op_embed_lookup_bwd(ptr(grad), zett_dtypes()[grad.dtype], int(t), int(v), int(e), ptr(plan), plan.numel() * 4, ptr(partials),
+                                                        partials.numel() * 4, ptr(d), e, stream(grad.device)), "embed_lookup_bwd")
     return d
 
 
@@ -649,7 +641,7 @@ class _TokenEmbeddings(torch.autograd.Function):
         plan, = ctx.saved_tensors
         t, v, e = ctx.shape
         g = grad.detach().reshape(t, e)
-        if g.dtype not in _SRC_DTYPES:
+        if g.dtype not in zett_dtypes():
             g = g.float()
         return embed_lookup_backward(g.contiguous(), plan, t, v, e), None, None, None
 
@@ -675,14 +667,14 @@ def token_embeddings(pred_in, input_ids, *, dtype=None, check_ids=True):
     two runs give the same bits; no float atomics.  Every row of d pred_in is written exactly once, zeros included.  The forward builds the
     inverted index of input_ids on the stream (integers only) and saves nothing else.  Under ``torch.no_grad()`` or when pred_in does not
     require grad — eval_step — only the gather runs: no plan, nothing saved."""
-    if pred_in.dim() != 2 or pred_in.dtype not in _SRC_DTYPES or pred_in.stride(1) != 1 or pred_in.shape[0] == 0 or pred_in.shape[1] == 0:
+    if pred_in.dim() != 2 or pred_in.dtype not in zett_dtypes() or pred_in.stride(1) != 1 or pred_in.shape[0] == 0 or pred_in.shape[1] == 0:
         raise ValueError("pred_in must be a non-empty [V, E] fp32 / f16 / bf16 tensor with unit column stride")
     if not pred_in.is_cuda:
         raise ValueError("zett_amd computes on the GPU only: pred_in must be a cuda (ROCm) tensor; there is no CPU path")
     if input_ids.dtype not in (torch.int32, torch.int64) or input_ids.device != pred_in.device:
         raise ValueError("input_ids must be an int32 / int64 tensor on the device of pred_in")
     dtype = pred_in.dtype if dtype is None else dtype
-    if dtype not in _SRC_DTYPES:
+    if dtype not in zett_dtypes():
         raise ValueError(f"dtype must be torch.float32, torch.float16 or torch.bfloat16, got {dtype!r}")
     ids = input_ids.detach().contiguous()
     if torch.is_grad_enabled() and pred_in.requires_grad:
@@ -835,10 +827,10 @@ def subsample_batch_vocabulary(input_ids, labels, special_ids, n_token_subsample
         mask = torch.empty(n, dtype=torch.bool, device=device)
         words = torch.empty(2, dtype=torch.int32, device=device)          # n_positive, status: both written by the call
         work = torch.empty(batch_vocab_workspace(t, v, n) // 4, dtype=torch.int32, device=device)          # (released on return: the allocator reuses it in stream order)
-        _lib.check(lib.zett_op_batch_vocab(_ptr(ids), ids.element_size(), _ptr(lab), lab.element_size(), t, v, n, _ptr(sf), sf.element_size(), sf.stride(0), l,
-                                           _ptr(priors), _ptr(order), 0 if order is None else order.element_size(), _BATCH_MODES[mode], *arrays, k, _ptr(out_ids),
-                                           _ptr(out_lab), _ptr(ids_to_embed), _ptr(out_sf), _ptr(out_priors), _ptr(mask), _ptr(words[0]), _ptr(words[1]), _ptr(work),
-                                           work.numel() * 4, _stream(device)), "batch_vocab")
+        _lib.check(lib.zett_op_batch_vocab(ptr(ids), ids.element_size(), ptr(lab), lab.element_size(), t, v, n, ptr(sf), sf.element_size(), sf.stride(0), l,
+                                           ptr(priors), ptr(order), 0 if order is None else order.element_size(), _BATCH_MODES[mode], *arrays, k, ptr(out_ids),
+                                           ptr(out_lab), ptr(ids_to_embed), ptr(out_sf), ptr(out_priors), ptr(mask), ptr(words[0]), ptr(words[1]), ptr(work),
+                                           work.numel() * 4, stream(device)), "batch_vocab")
     if check:
         bits = int(words[1].item())          # (the one host read of this call)
         if bits & BATCH_BAD_ID:
@@ -980,13 +972,13 @@ class HypernetAdamW:
         device, n, _, G, _, _, numel, _, record = lists
         with torch.cuda.device(device):
             _lib.check(_lib.load().zett_op_grad_norm(G, numel, n, math.inf if self.max_grad_norm is None else float(self.max_grad_norm), self.betas[0], self.betas[1],
-                                                     _ptr(self._partials), self._partials.numel(), _ptr(record), _stream(device)), "grad_norm")
+                                                     ptr(self._partials), self._partials.numel(), ptr(record), stream(device)), "grad_norm")
 
     def _launch_adamw(self, lists, lr: Optional[float] = None, zero_grad: bool = False) -> None:
         device, n, P, G, M, V, numel, flags, record = lists
         with torch.cuda.device(device):
             _lib.check(_lib.load().zett_op_adamw(P, G, M, V, numel, flags, n, self.lr if lr is None else float(lr), self.betas[0], self.betas[1], self.eps,
-                                                 self.weight_decay, int(bool(zero_grad)), _ptr(record), _stream(device)), "adamw")
+                                                 self.weight_decay, int(bool(zero_grad)), ptr(record), stream(device)), "adamw")
 
     def step(self, lr: Optional[float] = None, zero_grad: bool = False) -> None:
         """One update from the parameters' ``.grad``.  lr: this step's learning rate (the caller's schedule); zero_grad: the
