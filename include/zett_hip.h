@@ -577,6 +577,56 @@ int zett_op_gather_bwd_f32(const int32_t* ids, int64_t n_tokens, const void* src
 int zett_op_gather_bwd_rows_f32(const int32_t* ids, int64_t n_tokens, const void* src, int32_t src_dtype, int32_t e_in, int32_t v0, const float* dx, float* prod,
                                 float* keep, void* stream);
 
+/* ---- the forward's row kernels, one launch at a time (csrc/rowops_entry.hip; additive, the ABI version does not move) -------------
+ * Everything in the inference forward that is not a GEMM, callable on its own so that one launch can be checked element by element
+ * (tests/test_rowops_direct_gpu.py).  Each call goes through the launcher the forward itself calls (csrc/rowops_launch.hip.h): the
+ * kernel, lanes per row, grid and flags are the forward's for the same width and options.  Raw device pointers, asynchronous on
+ * `stream`, nothing is allocated, every argument is validated before any launch (ZETT_E_INVALID with a zett_last_error text).
+ * prec is a zett_precision: the operand type T of out_lo / q / k / v / ctx / tables (float with ZETT_PREC_F32).  Common rules: widths
+ * are multiples of 8, base pointers 16-byte aligned, leading dimensions multiples of 8 and at least the width; a row count of 0
+ * launches nothing. */
+enum zett_ln_kernel {            /* what *kernel_id receives: the kernel a LayerNorm launch went to */
+    ZETT_LN_ROWS8_32 = 0,        /* eight columns per lane, 32 lanes per row (16-bit modes, ln_rows8, h % 256 == 0, h <= 1024) */
+    ZETT_LN_ROWS8_64 = 1,        /* eight columns per lane, 64 lanes per row (16-bit modes, ln_rows8, h % 512 == 0, h <= 2048) */
+    ZETT_LN_WAVE = 2,            /* float4 per lane, one wave per row (h <= 2048) */
+    ZETT_LN_WORKGROUP = 3        /* float4 per lane, one workgroup per row; rows wider than 8192 are read three times */
+};
+/* LayerNorm over h of rows [rows, ld_in]: fp32 `in`, or 16-bit `in_lo` (readout only, not with ZETT_PREC_F32).  Outputs, each nullable:
+ * out_f32 [rows, h], out_lo [rows, h] of T, stats [rows, 2] = (mean, rstd).  out_bias != NULL selects the readout instantiations:
+ * bias[r] = sum_c y[r, c] bias_w[c] + bias_b[0] (bias_w NULL: exactly 0); bias_dtype -1: out_bias is float [rows]; a zett_dtype: out_bias
+ * is the caller's destination of that type and row r goes to element bias_rows[r] (< 0: not written; NULL: r); a finite bias that
+ * becomes inf in an f16 destination ORs ZETT_RANGE_DEST's bit (16) into *range_flag (nullable). */
+int zett_op_fwd_layernorm(int32_t prec, const float* in, const void* in_lo, int32_t ld_in, int32_t rows, int32_t h, const float* gamma, const float* beta,
+                          float eps, int32_t ln_rows8, float* out_f32, void* out_lo, float* stats, const float* bias_w, const float* bias_b, void* out_bias,
+                          const int64_t* bias_rows, int32_t bias_dtype, int32_t* range_flag, int32_t* kernel_id, void* stream);
+/* The embeddings' LayerNorm over packed positions [tok0, tok0 + m): x = table[tok_slot] (fp32 `table`, or — not with ZETT_PREC_F32 — the
+ * 16-bit table_lo normalised on the fly with table_stats (mean, rstd per table row), table_gamma, table_beta), or, tok_slot < 0,
+ * lang - (type0 + pos_emb[lang_pos]); sum = (x + type0) + pos_emb[tok_pos]; out_lo / stats = LayerNorm(sum).  tok_row != NULL: the
+ * position goes to its buffer row of the chunk (row0, rows, row_offset; position 0 of a vocabulary row first); NULL: written in place
+ * (row t - tok0).  out_lo, stats, sum: each nullable. */
+int zett_op_fwd_embed_layernorm(int32_t prec, const float* table, const void* table_lo, const float* table_stats, const float* table_gamma, const float* table_beta,
+                                const int32_t* tok_slot, const int32_t* tok_pos, const float* type0, const float* pos_emb, const float* lang, int32_t lang_pos,
+                                const int32_t* tok_row, const int32_t* row_offset, int64_t row0, int32_t rows, int32_t tok0, int32_t m, int32_t h, const float* gamma,
+                                const float* beta, float eps, int32_t ln_rows8, void* out_lo, float* stats, float* sum, int32_t* kernel_id, void* stream);
+/* attention_rows_kernel over vocabulary rows [row0, row0 + rows) = packed positions from tok0: q / k / v / ctx are BUFFER rows of
+ * the chunk (position 0 first), or — tok_pair != NULL — q / k / v are indexed by pair slot.  flags: bit 0 cls_only (q [rows, ldq],
+ * ctx [rows, h]), bit 1 the fast path for rows of at most 8 positions (16-bit), bit 2 pack a narrow last column group.  head_dim: a
+ * power of two in [8, 512] that divides h. */
+int zett_op_fwd_attention(int32_t prec, const void* q, int64_t ldq, const void* k, const void* v, int64_t ldkv, int32_t h, int32_t head_dim,
+                          const int32_t* row_offset, const uint8_t* row_uniform, const uint8_t* tok_key, int64_t row0, int32_t rows, int32_t tok0, float scaling,
+                          int32_t flags, const int32_t* tok_pair, void* ctx, void* stream);
+/* out[s] (T, [n_slots, e_in]) = id < v0 ? sc_w * src[id] + sc_b : fallback[id - v0], id = id_list[slot0 + s] (sc_w NULL: no rescaler).
+ * A value beyond the f16 range (or NaN) ORs ZETT_RANGE_SOURCE's bit (1) into *range_flag (nullable), with ZETT_PREC_F16 only. */
+int zett_op_fwd_gather_src(int32_t prec, const int32_t* id_list, int32_t slot0, int32_t n_slots, const void* src, int32_t src_dtype, int32_t e_in, int32_t v0,
+                           const float* fallback, const float* sc_w, const float* sc_b, void* out, int32_t* range_flag, void* stream);
+/* stats[r] = (mean, rstd) from the h / 128 partials (sum, sum of squares) of row r: parts is float2 [h / 128, ld_part], added in order;
+ * var = max(q / h - mean^2, 0).  prec is checked and otherwise unused. */
+int zett_op_fwd_ln_stats(int32_t prec, const float* parts, int32_t ld_part, int32_t rows, int32_t h, float eps, float* stats, void* stream);
+/* w_fold[n, k] = T(w[n, k] * gamma[k]), c_out[n] = sum_k w_fold[n, k], b_out[n] = bias[n] + sum_k w[n, k] beta[k] (16-bit T only).  A
+ * product beyond the f16 range ORs ZETT_RANGE_WEIGHT's bit (8) into *range_flag (nullable). */
+int zett_op_fwd_fold_weight(int32_t prec, const float* w, int32_t n, int32_t k, const float* gamma, const float* beta, const float* bias, void* w_fold,
+                            float* c_out, float* b_out, int32_t* range_flag, void* stream);
+
 /* ---- the losses and the parameter update of a training step (zett_amd/training.py) ----------------------------------------------
  * What the reference's trainer puts around the hypernetwork forward: the squared-error loss of the identity warm-up
  * (identity_train_step, train.py:914-975), the lexical loss (train.py:1074-1141) and optax.chain(clip_by_global_norm,

@@ -74,6 +74,8 @@ ABI_SYMBOLS = (
     "zett_sampled_vocab_patch_rows",
     # the order-stable sums of the hypernetwork's backward (zett_amd/autograd.py, deterministic=True)
     "zett_op_embed_lookup_plan_base", "zett_op_gather_bwd_rows_f32",
+    # the forward's row kernels, one launch at a time (tests/test_rowops_direct_gpu.py)
+    "zett_op_fwd_layernorm", "zett_op_fwd_embed_layernorm", "zett_op_fwd_attention", "zett_op_fwd_gather_src", "zett_op_fwd_ln_stats", "zett_op_fwd_fold_weight",
 )
 
 
@@ -248,6 +250,12 @@ def load():
         lib.zett_sampled_vocab_commit.argtypes = [P, P]
         lib.zett_sampled_vocab_table.argtypes = [P, P, P, P, P, P, I64, P, P]
         lib.zett_sampled_vocab_patch_rows.argtypes = [P, P, P, P, I32, P, I64, I32, I32, P]
+        lib.zett_op_fwd_layernorm.argtypes = [I32, P, P, I32, I32, I32, P, P, F, I32, P, P, P, P, P, P, P, I32, P, C.POINTER(I32), P]
+        lib.zett_op_fwd_embed_layernorm.argtypes = [I32, P, P, P, P, P, P, P, P, P, P, I32, P, P, I64, I32, I32, I32, I32, P, P, F, I32, P, P, P, C.POINTER(I32), P]
+        lib.zett_op_fwd_attention.argtypes = [I32, P, I64, P, P, I64, I32, I32, P, P, P, I64, I32, I32, F, I32, P, P, P]
+        lib.zett_op_fwd_gather_src.argtypes = [I32, P, I32, I32, P, I32, I32, I32, P, P, P, P, P, P]
+        lib.zett_op_fwd_ln_stats.argtypes = [I32, P, I32, I32, I32, F, P, P]
+        lib.zett_op_fwd_fold_weight.argtypes = [I32, P, I32, I32, P, P, P, P, P, P, P, P]
         for name in ABI_SYMBOLS:
             fn = getattr(lib, name)
             if name != "zett_last_error":

@@ -20,6 +20,9 @@
 
 namespace zett {
 
+// (the kernels that are not templates are `static`: this header is part of more than one translation unit — zett_hip.hip and
+//  rowops_entry.hip — and each gets its own copy)
+
 // ---------------------------------------------------------------------------
 // Plan.  Reference semantics being preserved (modeling_hypernet.py:190, 220-234 and
 // the eager RobertaSelfAttention mask):
@@ -55,7 +58,7 @@ struct PlanArrays {
     int32_t n_pair_keys;    //       size of pair_flag (0: no pair plan)
 };
 
-__global__ void plan_rows_kernel(const int32_t* __restrict__ sfm, int64_t n_rows, int seq, int pad, int lam,
+static __global__ void plan_rows_kernel(const int32_t* __restrict__ sfm, int64_t n_rows, int seq, int pad, int lam,
                                  int n_ids, PlanArrays p) {
     const int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (n >= n_rows) return;
@@ -86,7 +89,7 @@ __global__ void plan_rows_kernel(const int32_t* __restrict__ sfm, int64_t n_rows
 }
 
 // Single-workgroup exclusive scan (n <= a few million): out[i] = sum(in[0..i)), out[n] = total.
-__global__ __launch_bounds__(1024) void exclusive_scan_kernel(const int32_t* __restrict__ in,
+static __global__ __launch_bounds__(1024) void exclusive_scan_kernel(const int32_t* __restrict__ in,
                                                               int32_t* __restrict__ out, int64_t n) {
     __shared__ int32_t s_waves[16];
     const int t = threadIdx.x;
@@ -107,7 +110,7 @@ __global__ __launch_bounds__(1024) void exclusive_scan_kernel(const int32_t* __r
 //   (3) scan_apply_kernel: out[i] = offs[c] + exclusive scan inside the chunk; out[n] = total.
 constexpr int SCAN_CHUNK = 4096;          // 256 threads x 16 elements
 
-__global__ __launch_bounds__(256) void scan_chunk_sums_kernel(const int32_t* __restrict__ in, int64_t n, int32_t* __restrict__ sums) {
+static __global__ __launch_bounds__(256) void scan_chunk_sums_kernel(const int32_t* __restrict__ in, int64_t n, int32_t* __restrict__ sums) {
     __shared__ int32_t s_waves[4];
     const int64_t base = (int64_t)blockIdx.x * SCAN_CHUNK + threadIdx.x * 16;
     int32_t s = 0;
@@ -118,7 +121,7 @@ __global__ __launch_bounds__(256) void scan_chunk_sums_kernel(const int32_t* __r
     if (threadIdx.x == 0) sums[blockIdx.x] = total;
 }
 
-__global__ __launch_bounds__(256) void scan_apply_kernel(const int32_t* __restrict__ in, int64_t n, const int32_t* __restrict__ offs,
+static __global__ __launch_bounds__(256) void scan_apply_kernel(const int32_t* __restrict__ in, int64_t n, const int32_t* __restrict__ offs,
                                                          int32_t* __restrict__ out) {
     __shared__ int32_t s_waves[4];
     const int64_t base = (int64_t)blockIdx.x * SCAN_CHUNK + threadIdx.x * 16;
@@ -146,7 +149,7 @@ inline void launch_exclusive_scan(const int32_t* in, int32_t* out, int64_t n, in
     hipLaunchKernelGGL(scan_apply_kernel, dim3(chunks), dim3(256), 0, st, in, n, (const int32_t*)offs, out);
 }
 
-__global__ void plan_tokens_kernel(const int32_t* __restrict__ sfm, int64_t n_rows, int seq, int pad, int lam,
+static __global__ void plan_tokens_kernel(const int32_t* __restrict__ sfm, int64_t n_rows, int seq, int pad, int lam,
                                    int n_ids, PlanArrays p) {
     const int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (n >= n_rows) return;
@@ -177,7 +180,7 @@ __global__ void plan_tokens_kernel(const int32_t* __restrict__ sfm, int64_t n_ro
 }
 
 // pair slot of every packed position, and (table slot, position) of every pair (tokens of one pair write the same values)
-__global__ void plan_pairs_kernel(int64_t n_rows, PlanArrays p) {
+static __global__ void plan_pairs_kernel(int64_t n_rows, PlanArrays p) {
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= p.row_offset[n_rows]) return;          // (the grid covers the worst case: the host does not know T yet)
     const int ps = p.pair_slot[p.tok_pkey[t]];
@@ -188,14 +191,14 @@ __global__ void plan_pairs_kernel(int64_t n_rows, PlanArrays p) {
 
 // pair slot per BUFFER row of a chunk (position 0 first, chunk_row below): what the residual epilogue of layer 0 indexes with
 __device__ __forceinline__ int chunk_row(int t_rel, int row_rel, bool first, int rows);
-__global__ void pair_rows_kernel(int m, int tok0, int64_t row0, int rows, PlanArrays p, int32_t* __restrict__ brow_pair) {
+static __global__ void pair_rows_kernel(int m, int tok0, int64_t row0, int rows, PlanArrays p, int32_t* __restrict__ brow_pair) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= m) return;
     const int n = p.tok_row[tok0 + t];
     brow_pair[chunk_row(t, (int)(n - row0), p.row_offset[n] == tok0 + t, rows)] = p.tok_pair[tok0 + t];
 }
 
-__global__ void plan_idlist_kernel(int n_ids, PlanArrays p) {
+static __global__ void plan_idlist_kernel(int n_ids, PlanArrays p) {
     const int id = blockIdx.x * blockDim.x + threadIdx.x;
     if (id < n_ids && p.id_flag[id]) p.id_list[p.id_slot[id]] = id;
     if (id == 0) {          // (the last kernel of a plan: every scan has run)
@@ -890,7 +893,7 @@ __global__ __launch_bounds__(256) void attention_rows_kernel(const T* __restrict
 // (r6, second version: the partials of a row are still ADDED in their sequential order — same bits — but FETCHED eight at a time:
 //  the loop of rounds 3-5 waited for every load before it issued the next, 32 dependent round trips at H = 4096.  64-thread
 //  workgroups, so that a 4 096-row shard's 9.7 k rows reach 150 CUs instead of 38.)
-__global__ __launch_bounds__(64) void ln_stats_kernel(const float2* __restrict__ part, int parts, int ld_part, int rows, int H, float eps,
+static __global__ __launch_bounds__(64) void ln_stats_kernel(const float2* __restrict__ part, int parts, int ld_part, int rows, int H, float eps,
                                                       float* __restrict__ stats) {
     const int r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= rows) return;
@@ -1004,7 +1007,7 @@ __global__ __launch_bounds__(256) void dest_store_rows_kernel(const float* __res
 }
 
 // The row map of a destination against its size: err = 1 + (an index i with rows[i] >= n_dest), 0 when every row fits
-__global__ void dest_rows_check_kernel(const int64_t* __restrict__ rows, int64_t n, int64_t n_dest, int32_t* err) {
+static __global__ void dest_rows_check_kernel(const int64_t* __restrict__ rows, int64_t n, int64_t n_dest, int32_t* err) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n && rows[i] >= n_dest) atomicMax(err, (int)(i < 0x7ffffffe ? i + 1 : 0x7fffffff));
 }

@@ -31,6 +31,7 @@
 #include "gemm.hip.h"
 #include "gemm_launch.hip.h"
 #include "rowops.hip.h"
+#include "rowops_launch.hip.h"
 #include "retok.hip.h"
 #include "lexical.hip.h"
 #include "partition.hip.h"
@@ -544,7 +545,7 @@ int zett_finalize(zett_hypernet* h) {
             with_precision(h->precision, [&](auto a) {
                 using T = typename decltype(a)::type;
                 if constexpr (sizeof(T) == 2)
-                    hipLaunchKernelGGL(fold_weight_kernel<T>, dim3((unsigned)N), dim3(256), 0, 0, w32, (int)K, gamma, beta, bias, (T*)f.w, f.c, f.b, h->range_word);
+                    launch_fold_weight<T>(0, w32, (int)N, (int)K, gamma, beta, bias, (T*)f.w, f.c, f.b, h->range_word);
             });
             return 0;
         };
@@ -1093,27 +1094,14 @@ struct Runner {
         if (e != hipSuccess) rc = fail(ZETT_E_HIP, "%s launch failed: %s", what, hipGetErrorString(e));
     }
 
-    // One LayerNorm launch of the instantiation (EMBED, READOUT, BT): kernel, lanes per row and grid from (H, ln_rows8, sizeof(T)).
-    // (r6) 16-bit modes, narrow rows: layernorm_rows8_kernel, eight columns per lane, 32 lanes per row up to H = 1024 (two rows per
-    // wave), 64 up to 2048.  Otherwise layernorm_rows_kernel: H <= 2048 a wave per row, four rows per workgroup; wider, a workgroup per row.
+    // One LayerNorm launch of the instantiation (EMBED, READOUT, BT): kernel, lanes per row and grid are launch_layernorm's
+    // (rowops_launch.hip.h), from (H, ln_rows8, sizeof(T)).
     template <bool EMBED, bool READOUT, typename BT>
     void ln_launch(const char* what, const float* in, int rows, const float* gamma, const float* beta, float eps, float* of, T* ol, float* stats,
                    float* sum, const LnEmbed& embed, int t0, const LnReadout& readout) {
         const int H = h->cfg.hidden;
-        auto go = [&](auto kernel, dim3 grid) {
-            hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, in, H, rows, H, gamma, beta, eps, of, ol, stats, sum, embed, t0, readout);
-            check(what);
-        };
-        if constexpr (sizeof(T) == 2) {
-            if (const int tpr8 = h->ln_rows8 ? ln_rows8_tpr(H) : 0) {
-                const dim3 grid8((rows + 256 / tpr8 - 1) / (256 / tpr8));
-                if (tpr8 == 32) go(layernorm_rows8_kernel<T, EMBED, 32, READOUT, BT>, grid8);
-                else go(layernorm_rows8_kernel<T, EMBED, 64, READOUT, BT>, grid8);
-                return;
-            }
-        }
-        if (H <= 2048) go(layernorm_rows_kernel<T, EMBED, 64, READOUT, BT>, dim3((rows + 3) / 4));
-        else go(layernorm_rows_kernel<T, EMBED, 256, READOUT, BT>, dim3(rows));
+        launch_layernorm<T, EMBED, READOUT, BT>(st, H, h->ln_rows8, in, H, rows, gamma, beta, eps, of, ol, stats, sum, embed, t0, readout);
+        check(what);
     }
 
     // Every LayerNorm launch of the forward.  Rows `in` (or, embed != null, the embeddings' sum of buffer rows [t0, t0 + rows), also
@@ -1140,8 +1128,7 @@ struct Runner {
     // LayerNorm fold: (mean, rstd) per row from the partials the producer GEMM wrote
     void ln_stats(const float2* parts, int ld_part, int rows, float eps, float* stats) {
         if (rc || rows <= 0) return;
-        hipLaunchKernelGGL(ln_stats_kernel, dim3((rows + 63) / 64), dim3(64), 0, st, parts, h->cfg.hidden / 128, ld_part, rows,
-                           h->cfg.hidden, eps, stats);
+        launch_ln_stats(st, h->cfg.hidden, parts, ld_part, rows, eps, stats);
         check("ln_stats");
     }
 
@@ -1255,8 +1242,7 @@ void table_phase(Runner<T>& R, const Workspace<T>& w, const int32_t* id_list, in
         const int m = (int)std::min<int64_t>(MC, first + count - s0);
         const float* fb = R.Wf("fallback_embeddings.weight");
         with_dtype(src_dtype, [&](auto sd) {
-            hipLaunchKernelGGL((gather_src_kernel<T, decltype(sd)::value>), dim3(m), dim3(256), 0, R.st, id_list, s0, m, src, c.n_in_embd,
-                               c.original_vocab_size, fb, in_w, in_b, w.X0, h->range_word);
+            launch_gather_src<T, decltype(sd)::value>(R.st, id_list, s0, m, src, c.n_in_embd, c.original_vocab_size, fb, in_w, in_b, w.X0, h->range_word);
         });
         R.check("gather_src");
         GemmEpilogue<T> e0 = R.epi();
@@ -1516,8 +1502,6 @@ struct Forward {
         const T* wqkv = k.raw ? (const T*)h->fold_qkv[l].w : (const T*)h->qkv_w[l];
         const float* bqkv = k.raw ? h->fold_qkv[l].b : h->qkv_b[l];
         const float* cqkv = k.raw ? h->fold_qkv[l].c : nullptr;
-        const int64_t waves = attention_waves(k.rows, H, h->attention_pack != 0).total;
-        const int att_flags = (h->attention_fast ? 2 : 0) | (h->attention_pack ? 4 : 0);
         auto qkv = [&](int col0, int cols, int M, T* out) {       // columns [col0, col0 + cols) of [q | k | v] for the first M buffer rows
             GemmEpilogue<T> e = R.epi();
             e.bias = bqkv + col0; e.out_lo = out; e.ld_lo = cols;
@@ -1540,9 +1524,8 @@ struct Forward {
             ld_q = (size_t)H; ld_kv = (size_t)2 * H;
             k.zrows = k.rows;
         }
-        hipLaunchKernelGGL((attention_rows_kernel<T>), dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, k.st, Q, ld_q, KV, KV + H, ld_kv,
-                           H, H / c.heads, p.row_offset, p.row_uniform, p.tok_key, k.r0, k.rows, k.tok0, scaling, (cls_only ? 1 : 0) | att_flags,
-                           by_pair ? (const int32_t*)p.tok_pair : (const int32_t*)nullptr, w.CTX);
+        launch_attention<T>(k.st, H, h->attention_fast, h->attention_pack, Q, ld_q, KV, KV + H, ld_kv, H / c.heads, p.row_offset, p.row_uniform, p.tok_key,
+                            k.r0, k.rows, k.tok0, scaling, cls_only ? 1 : 0, by_pair ? (const int32_t*)p.tok_pair : (const int32_t*)nullptr, w.CTX);
         R.check(cls_only ? "attention(position 0)" : "attention");
     }
 
