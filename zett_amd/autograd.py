@@ -25,13 +25,19 @@ the headline workload.  The dense contractions run in exact fp32 MFMA (default) 
 accumulation, everything else fp32).  bf16 is the 16-bit mode to train in: f16 operands are ~8x more accurate but have the
 half range and there is no loss scaling here — a step whose gradients overflow raises RangeError instead of returning NaNs.
 
+A schedule owns the plumbing AROUND the encoder: which rows exist (``_Rows``), how the embeddings' sum is assembled from the projected
+rows, and how gradients that share an index are added (dense: a column sum over the ``[n, L'*H]`` view; packed: ``scatter_add_rows`` /
+``index_sum_rows``).  The rest stands once: input projection (``_input_*``), embeddings' LayerNorm and encoder layers (``_encoder_*``
+over ``_layer_*``), the embeddings' parameter gradients (``_embeddings_bwd``), heads (``_heads_*``).  So both schedules save the same
+things (``Ops.keep``) and release them, and each consumed gradient, as the backward passes.
+
 The backward adds rows that share an index (per position, per distinct id, per fallback row) with float atomics by default: sums in no
 fixed order.  ``model.train_deterministic`` / ``deterministic=True`` takes them in the fixed order of ``Ops.index_sum_rows`` instead
 (the inverted-index plan and chunked sum of the token lookup's backward): gradients are then the same bits on every run.
 """
 from __future__ import annotations
 
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, NamedTuple, Optional, Tuple
 
 import torch
 
@@ -407,8 +413,26 @@ def _heads_fwd(ops: Ops, dims: HypernetDims, P, S, cls, n, device):
     return pred_in, pred_out, bias
 
 
+def _head_bwd(ops: Ops, P, G, dpred, raw, h, pb, prefix, scalers, fused=False):
+    """One output head backwards: Rescalers -> Linear (prefix.1) -> ProjectorBlock (prefix.0); returns the gradient of the head's
+    input [n, H].  raw: the prediction before the Rescalers, h / pb: what the forward saved of the Linear's input and of the block.
+    scalers: the Rescalers over dpred's columns, in column order (none: no rescaling).  fused: the single head that predicts both
+    embeddings — one scale vector over all columns, each Rescaler's gradient a cloned slice of one pair of column sums."""
+    if scalers:
+        gw, gb = ops.colsum(ops.mul(dpred, raw)), ops.colsum(dpred)
+        e = gw.numel() // len(scalers)
+        for i, s in enumerate(scalers):
+            dw, db = gw[i * e:(i + 1) * e].reshape(1, -1), gb[i * e:(i + 1) * e].reshape(1, -1)
+            G[s + ".w"], G[s + ".b"] = (dw.clone(), db.clone()) if fused else (dw, db)
+        ws = [P[s + ".w"].reshape(-1) for s in scalers]
+        dpred = ops.affine_cols(dpred, torch.cat(ws) if fused else ws[0], None)
+    dh, G[prefix + ".1.weight"], G[prefix + ".1.bias"] = ops.linear_bwd(dpred, h, P[prefix + ".1.weight"])
+    return _projector_bwd(ops, P, G, prefix + ".0.", pb, dh)
+
+
 def _heads_bwd(ops: Ops, dims: HypernetDims, P, S, G, n, d_in, d_out, d_bias):
-    """Backward of _heads_fwd: fills G for the heads' parameters, returns the gradient of hidden[:, 0] [n, H]"""
+    """Backward of _heads_fwd: fills G for the heads' parameters, returns the gradient of hidden[:, 0] [n, H].  What the heads saved
+    is released on the way out (see _layer_bwd)."""
     e = dims.n_embd
     cls = S["cls"]
     dev = cls.device
@@ -416,42 +440,178 @@ def _heads_bwd(ops: Ops, dims: HypernetDims, P, S, G, n, d_in, d_out, d_bias):
     d_in = zeros(n, e) if d_in is None else d_in.contiguous().float()
     if dims.separate_out:
         d_out = zeros(n, e) if d_out is None else d_out.contiguous().float()
-    # ---- heads
+    in_scalers = ("scaler",) if dims.rescale else ()
+    out_scalers = ("out_scaler",) if dims.rescale and dims.separate_out else ()
     if dims.single_head:
         dpred = torch.cat([d_in, d_out], 1).contiguous() if dims.separate_out else d_in
-        if dims.rescale:
-            raw = S["pred_raw"]
-            gw, gb = ops.colsum(ops.mul(dpred, raw)), ops.colsum(dpred)
-            G["scaler.w"], G["scaler.b"] = gw[:e].reshape(1, -1).clone(), gb[:e].reshape(1, -1).clone()
-            if dims.separate_out:
-                G["out_scaler.w"], G["out_scaler.b"] = gw[e:].reshape(1, -1).clone(), gb[e:].reshape(1, -1).clone()
-            scale = torch.cat([P["scaler.w"].reshape(-1)] + ([P["out_scaler.w"].reshape(-1)] if dims.separate_out else []))
-            dpred = ops.affine_cols(dpred, scale, None)
-        dh, G["output_projection.1.weight"], G["output_projection.1.bias"] = ops.linear_bwd(dpred, S["h_in"], P["output_projection.1.weight"])
-        dcls = _projector_bwd(ops, P, G, "output_projection.0.", S["pb_out0"], dh)
+        dcls = _head_bwd(ops, P, G, dpred, S["pred_raw"], S["h_in"], S["pb_out0"], "output_projection", in_scalers + out_scalers, fused=True)
     else:
-        dpred = d_in
-        if dims.rescale:
-            G["scaler.w"] = ops.colsum(ops.mul(dpred, S["pred_raw"])).reshape(1, -1)
-            G["scaler.b"] = ops.colsum(dpred).reshape(1, -1)
-            dpred = ops.affine_cols(dpred, P["scaler.w"].reshape(-1), None)
-        dh, G["output_projection.1.weight"], G["output_projection.1.bias"] = ops.linear_bwd(dpred, S["h_in"], P["output_projection.1.weight"])
-        dcls = _projector_bwd(ops, P, G, "output_projection.0.", S["pb_out0"], dh)
+        dcls = _head_bwd(ops, P, G, d_in, S["pred_raw"], S["h_in"], S["pb_out0"], "output_projection", in_scalers)
         if dims.separate_out:
-            dpo = d_out
-            if dims.rescale:
-                G["out_scaler.w"] = ops.colsum(ops.mul(dpo, S["pred_out_raw"])).reshape(1, -1)
-                G["out_scaler.b"] = ops.colsum(dpo).reshape(1, -1)
-                dpo = ops.affine_cols(dpo, P["out_scaler.w"].reshape(-1), None)
-            dh2, G["output_projection_out.1.weight"], G["output_projection_out.1.bias"] = ops.linear_bwd(dpo, S["h_out"], P["output_projection_out.1.weight"])
-            dcls = ops.add(dcls, _projector_bwd(ops, P, G, "output_projection_out.0.", S["pb_out1"], dh2))
+            dcls = ops.add(dcls, _head_bwd(ops, P, G, d_out, S["pred_out_raw"], S["h_out"], S["pb_out1"], "output_projection_out", out_scalers))
     if dims.predict_bias:
         db = zeros(n) if d_bias is None else d_bias.contiguous().float()
         wb = P["bias_projection.weight"].reshape(-1)
         G["bias_projection.weight"] = ops.colsum(ops.scale_rows(cls, db)).reshape(1, -1)
         G["bias_projection.bias"] = db.view(1, -1).sum(1) if n == 0 else ops.colsum(db.view(-1, 1)).reshape(1)
         dcls = ops.add_outer(dcls, db, wb)
+    for key in ("pb_out0", "pb_out1", "h_in", "h_out", "pred_raw", "pred_out_raw"):
+        S.pop(key, None)
     return dcls
+
+
+class _Rows(NamedTuple):
+    """The row layout an encoder layer runs on: all that the two schedules tell _layer_fwd / _layer_bwd apart by."""
+    key: torch.Tensor                       # uint8 [T]: the position is visible as a key
+    row_offset: Optional[torch.Tensor]      # None: dense, seq positions per row; int32 [n_rows + 1]: packed
+    n_rows: int
+    seq: int                                # positions of the longest row
+    cls: Optional[torch.Tensor]             # int32 [n_rows]: where each row's position 0 lies (cls_only layers)
+    cls_only: Tuple[bool, ...]              # per layer: queries, output projection, FFN and LayerNorms for position 0 only
+
+
+def _check_widths(ops: Ops, dims: HypernetDims):
+    for name, width in (("n_embd", dims.n_embd), ("n_in_embd", dims.n_in_embd), ("hidden", dims.hidden), ("intermediate", dims.intermediate)):
+        if width % ops.kstep:
+            raise NotImplementedError(f"{name} = {width}: the training GEMM contracts over multiples of {ops.kstep}")
+
+
+def _input_fwd(ops: Ops, dims: HypernetDims, P, S, ids32, src):
+    """source rows of ids32 [R] (Rescaler, fallback rows) -> input projection -> [R, H] (modeling_hypernet.py:179-190)"""
+    sw = P["in_scaler.w"].reshape(-1) if dims.rescale else None
+    sb = P["in_scaler.b"].reshape(-1) if dims.rescale else None
+    x0 = ops.gather(ids32, src, dims.original_vocab_size, P["fallback_embeddings.weight"], sw, sb)          # [R, E_in]
+    y0 = ops.gemm(x0, P["input_projection.0.weight"], P["input_projection.0.bias"])
+    t, S["pb_in"] = _projector_fwd(ops, P, "input_projection.1.", y0)
+    S["x0"] = x0
+    return t
+
+
+def _input_bwd(ops: Ops, dims: HypernetDims, P, S, G, src, lang, ids32, dt, dlang_row, deterministic):
+    """Backward of _input_fwd, given the gradient dt [R, H] of its rows, and the language embedding's row (the one input row that
+    does not come through the projection; None without a language token)."""
+    if dlang_row is not None:
+        dlang = torch.zeros_like(P["lang_embeddings.weight"])
+        dlang[lang] = dlang_row
+        G["lang_embeddings.weight"] = dlang
+    dy0 = _projector_bwd(ops, P, G, "input_projection.1.", S["pb_in"], dt)
+    dx0, G["input_projection.0.weight"], G["input_projection.0.bias"] = ops.linear_bwd(dy0, S["x0"], P["input_projection.0.weight"])
+    dfb, dsw, dsb = ops.gather_bwd(ids32, src, dims.original_vocab_size, dx0, P["fallback_embeddings.weight"].shape[0], deterministic=deterministic)
+    G["fallback_embeddings.weight"] = dfb
+    if dims.rescale:
+        # x = w * src + b on source rows: d w = sum dx * src; gather_bwd's `prod` used the raw source row
+        G["in_scaler.w"], G["in_scaler.b"] = dsw.reshape(1, -1), dsb.reshape(1, -1)
+
+
+def _embeddings_bwd(ops: Ops, P, G, per_pos, L):
+    """Parameter gradients of RobertaEmbeddings from per_pos [L', H], the gradient of its sum added up per position (the language
+    token's type / position terms cancel, modeling_hypernet.py:192-199: only the first L positions count)."""
+    dpos = torch.zeros_like(P["model.embeddings.position_embeddings.weight"])
+    dpos[:L] = per_pos[:L]
+    G["model.embeddings.position_embeddings.weight"] = dpos
+    G["model.embeddings.token_type_embeddings.weight"] = ops.colsum(per_pos[:L].contiguous()).reshape(1, -1)
+
+
+def _layer_fwd(ops: Ops, dims: HypernetDims, ln_eps: float, P, l: int, R: _Rows, z):
+    """Encoder layer l on the rows R -> (the next z, what its backward needs).  A cls_only layer (lever 3 below) computes keys /
+    values for every position and the query — and everything behind it — for position 0 only: z [T, H] -> [n_rows, H]."""
+    H = dims.hidden
+    p = f"model.encoder.layer.{l}."
+    a = p + "attention.self."
+    wqkv = torch.cat([P[a + "query.weight"], P[a + "key.weight"], P[a + "value.weight"]], 0)      # fused operand (parameter plumbing)
+    bqkv = torch.cat([P[a + "query.bias"], P[a + "key.bias"], P[a + "value.bias"]], 0)
+    A = dict(z=ops.keep(z), wqkv=wqkv)
+    if not R.cls_only[l]:
+        qkv = ops.gemm(z, wqkv, bqkv)
+        ctx, probs = ops.attention(qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:], R.key, R.row_offset, R.n_rows, R.seq, dims.heads, H, operand=True)
+        res = z
+        A.update(qkv=qkv)
+    else:
+        kv = ops.gemm(z, wqkv[H:], bqkv[H:])
+        zc = ops.gather_rows(z, R.cls)
+        qc = ops.gemm(zc, wqkv[:H], bqkv[:H])
+        ctx, probs = ops.attention(qc, kv[:, :H], kv[:, H:], R.key, R.row_offset, R.n_rows, R.seq, dims.heads, H, cls_only=True, operand=True)
+        res = zc
+        A.update(kv=kv, zc=zc, qc=qc)
+    s1 = ops.gemm(ctx, P[p + "attention.output.dense.weight"], P[p + "attention.output.dense.bias"], residual=res)
+    z1, st1 = ops.layernorm(s1, P[p + "attention.output.LayerNorm.weight"], P[p + "attention.output.LayerNorm.bias"], ln_eps)
+    u = ops.gemm(z1, P[p + "intermediate.dense.weight"], P[p + "intermediate.dense.bias"])
+    g = ops.gelu(u, GELU_ERF, operand=True)
+    s2 = ops.gemm(g, P[p + "output.dense.weight"], P[p + "output.dense.bias"], residual=z1)
+    z2, st2 = ops.layernorm(s2, P[p + "output.LayerNorm.weight"], P[p + "output.LayerNorm.bias"], ln_eps)
+    A.update(probs=probs, ctx=ctx, s1=s1, st1=st1, z1=ops.keep(z1), u=u, g=g, s2=s2, st2=st2)
+    return z2, A
+
+
+def _layer_bwd(ops: Ops, dims: HypernetDims, P, G, l: int, R: _Rows, A, grad):
+    """Backward of _layer_fwd.  grad = [dz, dz_res]: the gradient of the layer's output and the part of it that came over a residual
+    branch (None, or added inside the LayerNorm backward that reads it); taken OUT of the list, so that the caller holds no reference,
+    and returned for the layer's input.  (r5) What the layer saved is released as soon as its backward has run, and a gradient as soon
+    as it has been consumed: the peak of a step is the forward's activations plus ONE stage's temporaries, not plus every stage's."""
+    H = dims.hidden
+    p = f"model.encoder.layer.{l}."
+    a = p + "attention.self."
+    dz, dz_res = grad
+    grad.clear()
+    ds2, G[p + "output.LayerNorm.weight"], G[p + "output.LayerNorm.bias"] = ops.layernorm_bwd(dz, A["s2"], A["st2"], P[p + "output.LayerNorm.weight"], dy2=dz_res)
+    dz = dz_res = None
+    dg, G[p + "output.dense.weight"], G[p + "output.dense.bias"] = ops.linear_bwd(ds2, A["g"], P[p + "output.dense.weight"])
+    del A["s2"], A["g"]
+    dz1, G[p + "intermediate.dense.weight"], G[p + "intermediate.dense.bias"] = ops.linear_bwd(dg, A["z1"], P[p + "intermediate.dense.weight"], A["u"], GELU_ERF)
+    dg = None
+    del A["u"], A["z1"]
+    ds1, G[p + "attention.output.LayerNorm.weight"], G[p + "attention.output.LayerNorm.bias"] = \
+        ops.layernorm_bwd(dz1, A["s1"], A["st1"], P[p + "attention.output.LayerNorm.weight"], dy2=ds2)        # + the residual of the FFN
+    dz1 = ds2 = None
+    del A["s1"]
+    dctx, G[p + "attention.output.dense.weight"], G[p + "attention.output.dense.bias"] = ops.linear_bwd(ds1, A["ctx"], P[p + "attention.output.dense.weight"])
+    del A["ctx"]
+    wqkv = A["wqkv"]
+    if not R.cls_only[l]:
+        qkv = A["qkv"]
+        dqkv = ops.new(qkv.shape[0], 3 * H)
+        ops.attention_bwd(dctx, qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:], A["probs"], R.row_offset, R.n_rows, R.seq, dims.heads, H,
+                          dqkv[:, :H], dqkv[:, H:2 * H], dqkv[:, 2 * H:])
+        dctx = qkv = None
+        del A["qkv"], A["probs"]
+        dz, dwqkv, dbqkv = ops.linear_bwd(dqkv, A["z"], wqkv)
+        dqkv = None
+        dz_res = ds1                                                        # residual of the attention block: added inside the next LayerNorm backward
+    else:
+        kv, qc = A["kv"], A["qc"]
+        dqc, dkv = ops.new(R.n_rows, H), ops.new(kv.shape[0], 2 * H)
+        ops.attention_bwd(dctx, qc, kv[:, :H], kv[:, H:], A["probs"], R.row_offset, R.n_rows, R.seq, dims.heads, H, dqc, dkv[:, :H], dkv[:, H:], cls_only=True)
+        dzc, dwq, dbq = ops.linear_bwd(dqc, A["zc"], wqkv[:H])
+        dzc = ops.add(dzc, ds1)                                             # the residual of the attention block, position 0 only
+        dz, dwkv, dbkv = ops.linear_bwd(dkv, A["z"], wqkv[H:])
+        ops.scatter_add_rows(dz, R.cls, dzc)
+        dz_res = None
+        dwqkv, dbqkv = torch.cat([dwq, dwkv], 0), torch.cat([dbq, dbkv], 0)
+    for i, name in enumerate(("query", "key", "value")):
+        G[a + name + ".weight"] = dwqkv[i * H:(i + 1) * H].clone()
+        G[a + name + ".bias"] = dbqkv[i * H:(i + 1) * H].clone()
+    A.clear()                                                               # this layer's activations are not needed again
+    return [dz, dz_res]
+
+
+def _encoder_bwd(ops: Ops, dims: HypernetDims, P, S, G, grad):
+    """The encoder layers and the embeddings' LayerNorm backwards, from grad = [dz, None] (see _layer_bwd) -> the gradient demb of
+    the embeddings' sum, one row per position of the layout"""
+    for l in reversed(range(dims.layers)):
+        grad = _layer_bwd(ops, dims, P, G, l, S["rows"], S["layers"][l], grad)
+    demb, G["model.embeddings.LayerNorm.weight"], G["model.embeddings.LayerNorm.bias"] = \
+        ops.layernorm_bwd(grad[0], S["emb"], S["emb_st"], P["model.embeddings.LayerNorm.weight"], dy2=grad[1])
+    return demb
+
+
+def _encoder_fwd(ops: Ops, dims: HypernetDims, ln_eps: float, P, S, emb, R: _Rows):
+    """The embeddings' LayerNorm and the encoder layers on the rows R, from the embeddings' sum emb [T, H] -> the last hidden state"""
+    z, st = ops.layernorm(emb, P["model.embeddings.LayerNorm.weight"], P["model.embeddings.LayerNorm.bias"], ln_eps)
+    S["emb"], S["emb_st"], S["rows"], S["layers"] = emb, st, R, []
+    for l in range(dims.layers):
+        z, A = _layer_fwd(ops, dims, ln_eps, P, l, R, z)
+        S["layers"].append(A)
+    return z
 
 
 def forward_train(ops: Ops, dims: HypernetDims, ln_eps: float, P: Dict[str, torch.Tensor], ids: torch.Tensor, src: torch.Tensor, lang: int):
@@ -460,18 +620,11 @@ def forward_train(ops: Ops, dims: HypernetDims, ln_eps: float, P: Dict[str, torc
     n, L = ids.shape
     lam = 1 if dims.embed_lang else 0
     Lp, H = L + lam, dims.hidden
-    for name, width in (("n_embd", dims.n_embd), ("n_in_embd", dims.n_in_embd), ("hidden", H), ("intermediate", dims.intermediate)):
-        if width % ops.kstep:
-            raise NotImplementedError(f"{name} = {width}: the training GEMM contracts over multiples of {ops.kstep}")
+    _check_widths(ops, dims)
     S = {}
     ids32 = ids.to(torch.int32).contiguous()
     S["ids"] = ids32
-    sw = P["in_scaler.w"].reshape(-1) if dims.rescale else None
-    sb = P["in_scaler.b"].reshape(-1) if dims.rescale else None
-    x0 = ops.gather(ids32.view(-1), src, dims.original_vocab_size, P["fallback_embeddings.weight"], sw, sb)          # [N*L, E_in]
-    y0 = ops.gemm(x0, P["input_projection.0.weight"], P["input_projection.0.bias"])
-    t, S["pb_in"] = _projector_fwd(ops, P, "input_projection.1.", y0)
-    S["x0"] = x0
+    t = _input_fwd(ops, dims, P, S, ids32.view(-1), src)                  # [N*L, H]
     # lang token + RobertaEmbeddings (modeling_hypernet.py:192-229): x + type[0] + pos[p], LayerNorm
     type0 = P["model.embeddings.token_type_embeddings.weight"][0]
     pos = P["model.embeddings.position_embeddings.weight"]
@@ -481,28 +634,9 @@ def forward_train(ops: Ops, dims: HypernetDims, ln_eps: float, P: Dict[str, torc
         xin[:, L] = P["lang_embeddings.weight"][lang] - (type0 + pos[L])   # parameter-sized glue ([H])
     posadd = (type0[None, :] + pos[:Lp]).contiguous().view(-1)             # [L'*H], parameter-sized
     emb = ops.affine_cols(xin.view(n, Lp * H), None, posadd).view(n * Lp, H)
-    z, st = ops.layernorm(emb, P["model.embeddings.LayerNorm.weight"], P["model.embeddings.LayerNorm.bias"], ln_eps)
-    S["emb"], S["emb_st"] = emb, st
     mask = torch.ones((n, Lp), dtype=torch.uint8, device=ids.device)
     mask[:, :L] = (ids != dims.pad_token_id).to(torch.uint8)
-    S["mask"] = mask
-    layers = []
-    for l in range(dims.layers):
-        p = f"model.encoder.layer.{l}."
-        a = p + "attention.self."
-        wqkv = torch.cat([P[a + "query.weight"], P[a + "key.weight"], P[a + "value.weight"]], 0)      # fused operand (parameter plumbing)
-        bqkv = torch.cat([P[a + "query.bias"], P[a + "key.bias"], P[a + "value.bias"]], 0)
-        qkv = ops.gemm(z, wqkv, bqkv)
-        ctx, probs = ops.attention(qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:], mask.view(-1), None, n, Lp, dims.heads, H, operand=True)
-        s1 = ops.gemm(ctx, P[p + "attention.output.dense.weight"], P[p + "attention.output.dense.bias"], residual=z)
-        z1, st1 = ops.layernorm(s1, P[p + "attention.output.LayerNorm.weight"], P[p + "attention.output.LayerNorm.bias"], ln_eps)
-        u = ops.gemm(z1, P[p + "intermediate.dense.weight"], P[p + "intermediate.dense.bias"])
-        g = ops.gelu(u, GELU_ERF, operand=True)
-        s2 = ops.gemm(g, P[p + "output.dense.weight"], P[p + "output.dense.bias"], residual=z1)
-        z2, st2 = ops.layernorm(s2, P[p + "output.LayerNorm.weight"], P[p + "output.LayerNorm.bias"], ln_eps)
-        layers.append(dict(z=z, wqkv=wqkv, qkv=qkv, probs=probs, ctx=ctx, s1=s1, st1=st1, z1=z1, u=u, g=g, s2=s2, st2=st2))
-        z = z2
-    S["layers"] = layers
+    z = _encoder_fwd(ops, dims, ln_eps, P, S, emb, _Rows(mask.view(-1), None, n, Lp, None, (False,) * dims.layers))
     cls = z.view(n, Lp, H)[:, 0].contiguous()                                # hidden[:, 0] (modeling_hypernet.py:234)
     S["cls"] = cls
     return _heads_fwd(ops, dims, P, S, cls, n, ids.device), S
@@ -515,54 +649,15 @@ def backward_train(ops: Ops, dims: HypernetDims, P: Dict[str, torch.Tensor], S, 
     G: Dict[str, torch.Tensor] = {}
     n, L = S["ids"].shape
     lam = 1 if dims.embed_lang else 0
-    Lp, H, e = L + lam, dims.hidden, dims.n_embd
-    dev = S["cls"].device
-    zeros = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)
+    Lp, H = L + lam, dims.hidden
     dcls = _heads_bwd(ops, dims, P, S, G, n, d_in, d_out, d_bias)
-    # ---- encoder (only position 0 of the last hidden state carries a gradient)
-    dz = zeros(n, Lp, H)
-    dz[:, 0] = dcls                                                       # layout plumbing
-    dz, dz_res = dz.view(n * Lp, H), None                                 # dz_res: the part of the gradient that came over a residual branch
-    for l in reversed(range(dims.layers)):
-        p = f"model.encoder.layer.{l}."
-        a = p + "attention.self."
-        A = S["layers"][l]
-        ds2, G[p + "output.LayerNorm.weight"], G[p + "output.LayerNorm.bias"] = ops.layernorm_bwd(dz, A["s2"], A["st2"], P[p + "output.LayerNorm.weight"], dy2=dz_res)
-        dg, G[p + "output.dense.weight"], G[p + "output.dense.bias"] = ops.linear_bwd(ds2, A["g"], P[p + "output.dense.weight"])
-        dz1, G[p + "intermediate.dense.weight"], G[p + "intermediate.dense.bias"] = ops.linear_bwd(dg, A["z1"], P[p + "intermediate.dense.weight"], A["u"], GELU_ERF)
-        ds1, G[p + "attention.output.LayerNorm.weight"], G[p + "attention.output.LayerNorm.bias"] = \
-            ops.layernorm_bwd(dz1, A["s1"], A["st1"], P[p + "attention.output.LayerNorm.weight"], dy2=ds2)        # + the residual of the FFN
-        dctx, G[p + "attention.output.dense.weight"], G[p + "attention.output.dense.bias"] = ops.linear_bwd(ds1, A["ctx"], P[p + "attention.output.dense.weight"])
-        dqkv = ops.new(n * Lp, 3 * H)
-        qkv = A["qkv"]
-        ops.attention_bwd(dctx, qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:], A["probs"], None, n, Lp, dims.heads, H,
-                          dqkv[:, :H], dqkv[:, H:2 * H], dqkv[:, 2 * H:])
-        dzin, dwqkv, dbqkv = ops.linear_bwd(dqkv, A["z"], A["wqkv"])
-        for i, name in enumerate(("query", "key", "value")):
-            G[a + name + ".weight"] = dwqkv[i * H:(i + 1) * H].clone()
-            G[a + name + ".bias"] = dbqkv[i * H:(i + 1) * H].clone()
-        dz, dz_res = dzin, ds1                                            # residual of the attention block: added inside the next LayerNorm backward
-    # ---- embeddings
-    demb, G["model.embeddings.LayerNorm.weight"], G["model.embeddings.LayerNorm.bias"] = \
-        ops.layernorm_bwd(dz, S["emb"], S["emb_st"], P["model.embeddings.LayerNorm.weight"], dy2=dz_res)
-    per_pos = ops.colsum(demb.view(n, Lp * H)).view(Lp, H)                # sum over the rows, per position
-    dpos = torch.zeros_like(P["model.embeddings.position_embeddings.weight"])
-    dpos[:L] = per_pos[:L]                                                # (the language token's type / position terms cancel: :192-199)
-    G["model.embeddings.position_embeddings.weight"] = dpos
-    G["model.embeddings.token_type_embeddings.weight"] = ops.colsum(per_pos[:L].contiguous()).reshape(1, -1)
-    if lam:
-        dlang = torch.zeros_like(P["lang_embeddings.weight"])
-        dlang[lang] = per_pos[L]
-        G["lang_embeddings.weight"] = dlang
+    grad = [torch.zeros((n * Lp, H), dtype=torch.float32, device=dcls.device), None]
+    grad[0].view(n, Lp, H)[:, 0] = dcls                                   # layout plumbing: only position 0 of the last hidden state carries a gradient
+    demb = _encoder_bwd(ops, dims, P, S, G, grad)
+    per_pos = ops.colsum(demb.view(n, Lp * H)).view(Lp, H)                # sum over the rows, per position: a fixed order
+    _embeddings_bwd(ops, P, G, per_pos, L)
     dt = demb.view(n, Lp, H)[:, :L].contiguous().view(n * L, H)           # layout plumbing
-    # ---- input projection
-    dy0 = _projector_bwd(ops, P, G, "input_projection.1.", S["pb_in"], dt)
-    dx0, G["input_projection.0.weight"], G["input_projection.0.bias"] = ops.linear_bwd(dy0, S["x0"], P["input_projection.0.weight"])
-    dfb, dsw, dsb = ops.gather_bwd(S["ids"].view(-1), src, dims.original_vocab_size, dx0, P["fallback_embeddings.weight"].shape[0], deterministic=deterministic)
-    G["fallback_embeddings.weight"] = dfb
-    if dims.rescale:
-        # x = w * src + b on source rows: d w = sum dx * src; gather_bwd's `prod` used the raw source row
-        G["in_scaler.w"], G["in_scaler.b"] = dsw.reshape(1, -1), dsb.reshape(1, -1)
+    _input_bwd(ops, dims, P, S, G, src, lang, S["ids"].view(-1), dt, per_pos[L] if lam else None, deterministic)
     return G
 
 
@@ -595,26 +690,19 @@ def plan_packed(ids: torch.Tensor, pad: int, lam: int):
 def forward_packed(ops: Ops, dims: HypernetDims, ln_eps: float, P, ids: torch.Tensor, src: torch.Tensor, lang: int):
     n, L = ids.shape
     lam = 1 if dims.embed_lang else 0
-    Lp, H = L + lam, dims.hidden
-    for name, width in (("n_embd", dims.n_embd), ("n_in_embd", dims.n_in_embd), ("hidden", H), ("intermediate", dims.intermediate)):
-        if width % ops.kstep:
-            raise NotImplementedError(f"{name} = {width}: the training GEMM contracts over multiples of {ops.kstep}")
+    Lp = L + lam
+    _check_widths(ops, dims)
     S = dict(packed=True)
     plan = plan_packed(ids, dims.pad_token_id, lam)
     S["plan"] = plan
-    T, seq = plan["n_tokens"], plan["max_len"]
+    T = plan["n_tokens"]
     # ---- lever 2: the input projection per distinct referenced id
     is_tok = plan["tok_pos"] < L
     tok_ids = ids[plan["tok_row"][is_tok], plan["tok_pos"][is_tok].long()]
     uniq, inv = torch.unique(tok_ids, return_inverse=True)
     uniq32 = uniq.to(torch.int32).contiguous()
     S["uniq"] = uniq32
-    sw = P["in_scaler.w"].reshape(-1) if dims.rescale else None
-    sb = P["in_scaler.b"].reshape(-1) if dims.rescale else None
-    x0 = ops.gather(uniq32, src, dims.original_vocab_size, P["fallback_embeddings.weight"], sw, sb)      # [D, E_in]
-    y0 = ops.gemm(x0, P["input_projection.0.weight"], P["input_projection.0.bias"])
-    table, S["pb_in"] = _projector_fwd(ops, P, "input_projection.1.", y0)
-    S["x0"] = x0
+    table = _input_fwd(ops, dims, P, S, uniq32, src)                           # [D, H]
     d_ids = table.shape[0]
     type0 = P["model.embeddings.token_type_embeddings.weight"][0]
     pos = P["model.embeddings.position_embeddings.weight"]
@@ -625,41 +713,9 @@ def forward_packed(ops: Ops, dims: HypernetDims, ln_eps: float, P, ids: torch.Te
         table = torch.cat([table, (P["lang_embeddings.weight"][lang] - (type0 + pos[L]))[None, :]], 0)      # parameter-sized glue
     posadd = (type0[None, :] + pos[:Lp]).contiguous()
     emb = ops.gather_rows(posadd, plan["tok_pos"], ops.gather_rows(table, slot))        # table[slot] + (type + position)
-    z, st = ops.layernorm(emb, P["model.embeddings.LayerNorm.weight"], P["model.embeddings.LayerNorm.bias"], ln_eps)
-    S["emb"], S["emb_st"] = emb, st
-    off, key = plan["row_offset"], plan["tok_key"]
-    layers = []
-    for l in range(dims.layers):
-        p = f"model.encoder.layer.{l}."
-        a = p + "attention.self."
-        last = l == dims.layers - 1
-        wqkv = torch.cat([P[a + "query.weight"], P[a + "key.weight"], P[a + "value.weight"]], 0)
-        bqkv = torch.cat([P[a + "query.bias"], P[a + "key.bias"], P[a + "value.bias"]], 0)
-        A = dict(z=ops.keep(z), wqkv=wqkv)
-        if not last:
-            qkv = ops.gemm(z, wqkv, bqkv)
-            ctx, probs = ops.attention(qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:], key, off, n, seq, dims.heads, H, operand=True)
-            res = z
-            A.update(qkv=qkv)
-        else:
-            # ---- lever 3: keys / values for every kept position, the query (and everything behind it) for position 0 only
-            kv = ops.gemm(z, wqkv[H:], bqkv[H:])
-            zc = ops.gather_rows(z, plan["cls"])
-            qc = ops.gemm(zc, wqkv[:H], bqkv[:H])
-            ctx, probs = ops.attention(qc, kv[:, :H], kv[:, H:], key, off, n, seq, dims.heads, H, cls_only=True, operand=True)
-            res = zc
-            A.update(kv=kv, zc=zc, qc=qc)
-        s1 = ops.gemm(ctx, P[p + "attention.output.dense.weight"], P[p + "attention.output.dense.bias"], residual=res)
-        z1, st1 = ops.layernorm(s1, P[p + "attention.output.LayerNorm.weight"], P[p + "attention.output.LayerNorm.bias"], ln_eps)
-        u = ops.gemm(z1, P[p + "intermediate.dense.weight"], P[p + "intermediate.dense.bias"])
-        g = ops.gelu(u, GELU_ERF, operand=True)
-        s2 = ops.gemm(g, P[p + "output.dense.weight"], P[p + "output.dense.bias"], residual=z1)
-        z, st2 = ops.layernorm(s2, P[p + "output.LayerNorm.weight"], P[p + "output.LayerNorm.bias"], ln_eps)
-        A.update(probs=probs, ctx=ctx, s1=s1, st1=st1, z1=ops.keep(z1), u=u, g=g, s2=s2, st2=st2)
-        layers.append(A)
-    S["layers"] = layers
-    S["seq"] = seq
-    cls = z                                            # [n, H]: the last layer ran on position 0 only
+    # ---- levers 1 and 3: the kept positions only, and the last layer for position 0 only
+    rows = _Rows(plan["tok_key"], plan["row_offset"], n, plan["max_len"], plan["cls"], tuple(l == dims.layers - 1 for l in range(dims.layers)))
+    cls = _encoder_fwd(ops, dims, ln_eps, P, S, emb, rows)                     # [n, H]
     S["cls"] = cls
     S["ids"] = ids
     return _heads_fwd(ops, dims, P, S, cls, n, ids.device), S
@@ -671,91 +727,20 @@ def backward_packed(ops: Ops, dims: HypernetDims, P, S, src, lang, d_in, d_out, 
     the forward saves nothing more.  The position-0 scatter into dz and gather_bwd over the DISTINCT ids have one addend per
     destination and stay as they are."""
     G: Dict[str, torch.Tensor] = {}
-    ids = S["ids"]
-    n, L = ids.shape
+    n, L = S["ids"].shape
     lam = 1 if dims.embed_lang else 0
     Lp, H = L + lam, dims.hidden
-    plan, seq = S["plan"], S["seq"]
-    T = plan["n_tokens"]
-    off = plan["row_offset"]
-    dev = ids.device
-    dz, dz_res = _heads_bwd(ops, dims, P, S, G, n, d_in, d_out, d_bias), None    # [n, H]: gradient of hidden[:, 0]
-    # (r5) what a stage saved is released as soon as its backward has run, and a gradient as soon as it has been consumed: the
-    # peak of a step is then the forward's activations plus ONE stage's temporaries, not plus every stage's
-    for key in ("pb_out0", "pb_out1", "h_in", "h_out", "pred_raw", "pred_out_raw"):
-        S.pop(key, None)
-    d_in = d_out = d_bias = None
-    for l in reversed(range(dims.layers)):
-        p = f"model.encoder.layer.{l}."
-        a = p + "attention.self."
-        A = S["layers"][l]
-        last = l == dims.layers - 1
-        ds2, G[p + "output.LayerNorm.weight"], G[p + "output.LayerNorm.bias"] = ops.layernorm_bwd(dz, A["s2"], A["st2"], P[p + "output.LayerNorm.weight"], dy2=dz_res)
-        dz = dz_res = None
-        dg, G[p + "output.dense.weight"], G[p + "output.dense.bias"] = ops.linear_bwd(ds2, A["g"], P[p + "output.dense.weight"])
-        del A["s2"], A["g"]
-        dz1, G[p + "intermediate.dense.weight"], G[p + "intermediate.dense.bias"] = ops.linear_bwd(dg, A["z1"], P[p + "intermediate.dense.weight"], A["u"], GELU_ERF)
-        dg = None
-        del A["u"], A["z1"]
-        ds1, G[p + "attention.output.LayerNorm.weight"], G[p + "attention.output.LayerNorm.bias"] = \
-            ops.layernorm_bwd(dz1, A["s1"], A["st1"], P[p + "attention.output.LayerNorm.weight"], dy2=ds2)        # + the residual of the FFN
-        dz1 = ds2 = None
-        del A["s1"]
-        dctx, G[p + "attention.output.dense.weight"], G[p + "attention.output.dense.bias"] = ops.linear_bwd(ds1, A["ctx"], P[p + "attention.output.dense.weight"])
-        del A["ctx"]
-        wqkv = A["wqkv"]
-        if not last:
-            qkv = A["qkv"]
-            dqkv = ops.new(T, 3 * H)
-            ops.attention_bwd(dctx, qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:], A["probs"], off, n, seq, dims.heads, H,
-                              dqkv[:, :H], dqkv[:, H:2 * H], dqkv[:, 2 * H:])
-            dctx = qkv = None
-            del A["qkv"], A["probs"]
-            dzin, dwqkv, dbqkv = ops.linear_bwd(dqkv, A["z"], wqkv)
-            dqkv = None
-            dz, dz_res = dzin, ds1                                              # (added inside the next LayerNorm backward)
-        else:
-            kv, qc = A["kv"], A["qc"]
-            dqc, dkv = ops.new(n, H), ops.new(T, 2 * H)
-            ops.attention_bwd(dctx, qc, kv[:, :H], kv[:, H:], A["probs"], off, n, seq, dims.heads, H, dqc, dkv[:, :H], dkv[:, H:], cls_only=True)
-            dzc, dwq, dbq = ops.linear_bwd(dqc, A["zc"], wqkv[:H])
-            dzc = ops.add(dzc, ds1)                                             # the residual of the attention block, position 0 only
-            dz, dwkv, dbkv = ops.linear_bwd(dkv, A["z"], wqkv[H:])
-            ops.scatter_add_rows(dz, plan["cls"], dzc)
-            dz_res = None
-            dwqkv, dbqkv = torch.cat([dwq, dwkv], 0), torch.cat([dbq, dbkv], 0)
-        for i, name in enumerate(("query", "key", "value")):
-            G[a + name + ".weight"] = dwqkv[i * H:(i + 1) * H].clone()
-            G[a + name + ".bias"] = dbqkv[i * H:(i + 1) * H].clone()
-        dwqkv = dbqkv = wqkv = None
-        A.clear()                                                               # this layer's activations are not needed again
-    demb, G["model.embeddings.LayerNorm.weight"], G["model.embeddings.LayerNorm.bias"] = \
-        ops.layernorm_bwd(dz, S["emb"], S["emb_st"], P["model.embeddings.LayerNorm.weight"], dy2=dz_res)
-    if deterministic:
-        per_pos = ops.index_sum_rows(plan["tok_pos"], demb, Lp)
-    else:
-        per_pos = torch.zeros((Lp, H), dtype=torch.float32, device=dev)
-        ops.scatter_add_rows(per_pos, plan["tok_pos"], demb)
-    dpos = torch.zeros_like(P["model.embeddings.position_embeddings.weight"])
-    dpos[:L] = per_pos[:L]                                                     # (the language token's type / position terms cancel)
-    G["model.embeddings.position_embeddings.weight"] = dpos
-    G["model.embeddings.token_type_embeddings.weight"] = ops.colsum(per_pos[:L].contiguous()).reshape(1, -1)
-    d_ids = S["uniq"].numel()
-    if deterministic:
-        dtable = ops.index_sum_rows(S["slot"], demb, d_ids + lam)
-    else:
-        dtable = torch.zeros((d_ids + lam, H), dtype=torch.float32, device=dev)
-        ops.scatter_add_rows(dtable, S["slot"], demb)                           # lever 2 backwards: the uses of an id add up
-    if lam:
-        dlang = torch.zeros_like(P["lang_embeddings.weight"])
-        dlang[lang] = dtable[d_ids]
-        G["lang_embeddings.weight"] = dlang
-    dy0 = _projector_bwd(ops, P, G, "input_projection.1.", S["pb_in"], dtable[:d_ids].contiguous())
-    dx0, G["input_projection.0.weight"], G["input_projection.0.bias"] = ops.linear_bwd(dy0, S["x0"], P["input_projection.0.weight"])
-    dfb, dsw, dsb = ops.gather_bwd(S["uniq"], src, dims.original_vocab_size, dx0, P["fallback_embeddings.weight"].shape[0])
-    G["fallback_embeddings.weight"] = dfb
-    if dims.rescale:
-        G["in_scaler.w"], G["in_scaler.b"] = dsw.reshape(1, -1), dsb.reshape(1, -1)
+    tok_pos, slot, d_ids = S["plan"]["tok_pos"], S["slot"], S["uniq"].numel()
+    demb = _encoder_bwd(ops, dims, P, S, G, [_heads_bwd(ops, dims, P, S, G, n, d_in, d_out, d_bias), None])
+
+    def index_sum(idx, n_dst):          # lever 2 backwards (and lever 1's positions): the uses of an index add up
+        if deterministic:
+            return ops.index_sum_rows(idx, demb, n_dst)
+        return ops.scatter_add_rows(torch.zeros((n_dst, H), dtype=torch.float32, device=demb.device), idx, demb)
+
+    _embeddings_bwd(ops, P, G, index_sum(tok_pos, Lp), L)
+    dtable = index_sum(slot, d_ids + lam)
+    _input_bwd(ops, dims, P, S, G, src, lang, S["uniq"], dtable[:d_ids].contiguous(), dtable[d_ids] if lam else None, False)
     return G
 
 
