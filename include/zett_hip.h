@@ -200,6 +200,10 @@ int zett_forward_prepare(zett_hypernet* h, const int32_t* surface_forms, int64_t
 
 int zett_get_stats(const zett_hypernet* h, zett_stats* out);
 
+/* Rows of the most recent forward that had a single kept position and whose query / key GEMM rows were skipped (the
+ * "single_rows" option below); 0 when the forward did not take the lever.  (A getter of its own: zett_stats keeps its layout.) */
+int zett_single_rows(const zett_hypernet* h, int64_t* out);
+
 /* Per-launch record of the GEMMs of the most recent zett_forward ("time_gemm" on: durations from HIP events recorded on
  * the launch stream around every launch).  What bench.py prices its roofline on, launch class by launch class. */
 typedef struct zett_gemm_record {
@@ -288,7 +292,12 @@ int zett_workspace_bytes(const zett_hypernet* h, int64_t n_rows, int32_t seq, in
  * modes at hidden sizes of 256 k <= 1024 / 512 k <= 2048 give a lane eight columns and a row 32 / 64 lanes; 0 = the float4
  * kernel; the row sums are added in another order, results differ by rounding), "attention_pack" (0/1, default 1, round 6: a
  * last group of 256 / 128 / 64 hidden columns of the attention kernel — hidden size 768 — takes 2 / 4 / 8 rows per wave instead
- * of leaving lanes idle; same bits). */
+ * of leaving lanes idle; same bits), "single_rows" (0/1/2, default 1: a vocabulary row with ONE kept position attends to exactly
+ * one key — softmax weight exactly 1, context = its value row — so its query and key are never needed: such rows are put first
+ * in the position-0 block of the hidden-state buffers and the Q|K launches of the layers behind the per-pair one skip them
+ * with a pointer offset; the outputs are stored through the inverse row map; same bits.  1 = for a call that is one chunk on
+ * one lane with seq + language token > 1, when floor(singles / 256) * (2 * hidden / 256) tiles fill at least one round of
+ * the 256 CUs; 2 = for every such call with a single row; 0 = never.  Not taken: nothing differs, launch for launch). */
 int zett_set_option(zett_hypernet* h, const char* key, int64_t value);
 
 /* ---- id-affinity row partition (ABI 6) ----------------------------------------------

@@ -76,6 +76,8 @@ ABI_SYMBOLS = (
     "zett_op_embed_lookup_plan_base", "zett_op_gather_bwd_rows_f32",
     # the forward's row kernels, one launch at a time (tests/test_rowops_direct_gpu.py)
     "zett_op_fwd_layernorm", "zett_op_fwd_embed_layernorm", "zett_op_fwd_attention", "zett_op_fwd_gather_src", "zett_op_fwd_ln_stats", "zett_op_fwd_fold_weight",
+    # single rows whose query / key work the last forward skipped (HipEngine.single_rows)
+    "zett_single_rows",
 )
 
 
@@ -157,6 +159,7 @@ def load():
         lib.zett_forward.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int, C.c_int64,
                                      C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.zett_get_stats.argtypes = [C.c_void_p, C.POINTER(ZettStats)]
+        lib.zett_single_rows.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
         lib.zett_workspace_bytes.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.POINTER(C.c_int64)]
         lib.zett_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_int64]
         lib.zett_check_range.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]

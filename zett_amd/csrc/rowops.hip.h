@@ -190,12 +190,13 @@ static __global__ void plan_pairs_kernel(int64_t n_rows, PlanArrays p) {
 }
 
 // pair slot per BUFFER row of a chunk (position 0 first, chunk_row below): what the residual epilogue of layer 0 indexes with
-__device__ __forceinline__ int chunk_row(int t_rel, int row_rel, bool first, int rows);
-static __global__ void pair_rows_kernel(int m, int tok0, int64_t row0, int rows, PlanArrays p, int32_t* __restrict__ brow_pair) {
+__device__ __forceinline__ int chunk_row(int t_rel, int row_rel, bool first, int rows, const int32_t* cls_slot);
+static __global__ void pair_rows_kernel(int m, int tok0, int64_t row0, int rows, PlanArrays p, int32_t* __restrict__ brow_pair,
+                                        const int32_t* __restrict__ cls_slot) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= m) return;
     const int n = p.tok_row[tok0 + t];
-    brow_pair[chunk_row(t, (int)(n - row0), p.row_offset[n] == tok0 + t, rows)] = p.tok_pair[tok0 + t];
+    brow_pair[chunk_row(t, (int)(n - row0), p.row_offset[n] == tok0 + t, rows, cls_slot)] = p.tok_pair[tok0 + t];
 }
 
 static __global__ void plan_idlist_kernel(int n_ids, PlanArrays p) {
@@ -318,6 +319,7 @@ struct LnEmbed {
     const float* table_stats;  // [D] (mean, rstd)
     const float* table_gamma;  // [H] input_projection.1.ln.weight
     const float* table_beta;   // [H]
+    const int32_t* cls_slot;   // [rows] buffer row of position 0 of each vocabulary row of the chunk (chunk_row() below), or null: the row itself
 };
 
 // Row order of a chunk's hidden-state buffers: POSITION 0 FIRST.  A chunk covers vocabulary rows [row0, row0 + rows) =
@@ -326,8 +328,11 @@ struct LnEmbed {
 // last layer and the output heads consume is then simply the first `rows` rows of every buffer — no gather in front of
 // the last layer's query GEMM, none in front of the heads; GEMMs and LayerNorms do not care about the order of rows.
 //   t_rel = packed position - tok0, row_rel = its vocabulary row - row0, first = it is the row's position 0
-__device__ __forceinline__ int chunk_row(int t_rel, int row_rel, bool first, int rows) {
-    return first ? row_rel : rows + t_rel - row_rel - 1;
+// cls_slot != null (lever 5, zett_hip.hip Forward::plan_single_rows): the position-0 block is a permutation of the chunk's rows —
+// position 0 of vocabulary row row0 + r sits in buffer row cls_slot[r], rows with a single kept position first — and whoever reads
+// the block out maps buffer rows back to vocabulary rows.  The other positions keep their place.
+__device__ __forceinline__ int chunk_row(int t_rel, int row_rel, bool first, int rows, const int32_t* cls_slot) {
+    return first ? (cls_slot ? cls_slot[row_rel] : row_rel) : rows + t_rel - row_rel - 1;
 }
 
 // Position-0 readout fused into the LAST LayerNorm launch (which runs on the first `rows` buffer rows only): the bias
@@ -398,7 +403,7 @@ __global__ __launch_bounds__(256) void layernorm_rows_kernel(const float* __rest
         posr = emb.pos_emb + (size_t)emb.tok_pos[tok0 + r] * H;
         if (emb.tok_row) {                 // (null: rows are pairs, written in place)
             const int n = emb.tok_row[tok0 + r];
-            ro = chunk_row(r, (int)(n - emb.row0), emb.row_offset[n] == tok0 + r, emb.rows);
+            ro = chunk_row(r, (int)(n - emb.row0), emb.row_offset[n] == tok0 + r, emb.rows, emb.cls_slot);
         }
     } else {
         x = in + (size_t)r * ld_in;
@@ -578,7 +583,7 @@ __global__ __launch_bounds__(256) void layernorm_rows8_kernel(const float* __res
         posr = emb.pos_emb + (size_t)emb.tok_pos[tok0 + r] * H;
         if (emb.tok_row) {
             const int n = emb.tok_row[tok0 + r];
-            ro = chunk_row(r, (int)(n - emb.row0), emb.row_offset[n] == tok0 + r, emb.rows);
+            ro = chunk_row(r, (int)(n - emb.row0), emb.row_offset[n] == tok0 + r, emb.rows, emb.cls_slot);
         }
     } else {
         x = in + (size_t)r * ld_in;
@@ -732,6 +737,8 @@ __host__ __device__ inline AttentionWaves attention_waves(int rows, int H, bool 
 // q: [T, ldq] per packed position, or (cls_only) [rows, ldq] holding the query of position 0
 // of each row; k, v: [T, ldkv]; ctx: [T or rows, H].  cls_only: compute query 0 only and
 // write it at ctx[row_local] (compact [rows, H] output for the last layer).
+// cls_slot != null (lever 5): position 0 of row_local lives in buffer row cls_slot[row_local] instead — q of a cls_only launch and
+// its ctx included.  flags bit 3: a row with ONE kept position takes ctx = v without loading q or k (their cells were never written).
 template <typename T>
 __global__ __launch_bounds__(256) void attention_rows_kernel(const T* __restrict__ qbase, size_t ldq,
                                                              const T* __restrict__ kbase, const T* __restrict__ vbase,
@@ -739,8 +746,9 @@ __global__ __launch_bounds__(256) void attention_rows_kernel(const T* __restrict
                                                              const int32_t* __restrict__ row_offset,
                                                              const uint8_t* __restrict__ row_uniform,
                                                              const uint8_t* __restrict__ tok_key, int64_t row0,
-                                                             int rows, int tok0, float scaling, int flags /* bit 0: cls_only, bit 1: fast path on, bit 2: pack a narrow last group */,
-                                                             const int32_t* __restrict__ tok_pair, T* __restrict__ ctx) {
+                                                             int rows, int tok0, float scaling,
+                                                             int flags /* bit 0: cls_only, bit 1: fast path on, bit 2: pack a narrow last group, bit 3: single rows copy v */,
+                                                             const int32_t* __restrict__ tok_pair, T* __restrict__ ctx, const int32_t* __restrict__ cls_slot) {
     const int cls_only = flags & 1;
     const int lane = threadIdx.x & 63;
     const int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -773,7 +781,9 @@ __global__ __launch_bounds__(256) void attention_rows_kernel(const T* __restrict
     const int nq = cls_only ? 1 : (t1 - t0);
     const int ccol = active ? col : 0;
     // buffer row of packed position t of this row (position 0 first: chunk_row above)
-    auto brow = [&](int t) -> size_t { return (size_t)chunk_row(t, rl, t == t0, rows); };
+    // (position 0's row — the one indexed load of the row map — and the offset of the others, up front: rl itself is not kept)
+    const int slot0 = chunk_row(t0, rl, true, rows, cls_slot), rest = chunk_row(0, rl, false, rows, nullptr);
+    auto brow = [&](int t) -> size_t { return (size_t)(t == t0 ? slot0 : rest + t); };
     // row of q / k / v of packed position t: its buffer row, or — layer 0 with the pair lever — the row of its
     // (source id, position) pair, whose Q/K/V were computed once
     // (the row's first 64 pair slots are fetched once, one per lane, and handed out by shuffle: an index load in front of
@@ -787,6 +797,20 @@ __global__ __launch_bounds__(256) void attention_rows_kernel(const T* __restrict
         return t - t0 < lpr ? (size_t)__shfl(pslot, base + (t - t0), 64) : (size_t)tok_pair[tok0 + t];
     };
     const int nk = t1 - t0;
+    if ((flags & 8) && nk == 1) {
+        // One kept position (never a uniform row: the caller takes this path only when seq + lang > 1): its one key is visible, the
+        // softmax weight is exactly 1 and the context is the value row — fma(1, v, 0) * (1 / 1) in the fast path, fma(0, 0, 1 * v) in the
+        // generic one: v + 0 either way (a negative zero leaves as a positive one).  q and k are not loaded.
+        const size_t vr = qrow(t0);
+        if (active) {
+            float v[8];
+            load8<T>(vbase + vr * ldkv + ccol, v);
+#pragma unroll
+            for (int c = 0; c < 8; ++c) v[c] += 0.f;
+            store8<T>(ctx + brow(t0) * H + col, v);
+        }
+        return;
+    }
     if constexpr (sizeof(T) == 2) {
         if (nk <= ATT_FAST_KEYS && (flags & 2)) {
             // which keys count: lane j asks for key j, the answer is a wave-uniform bit mask
@@ -802,7 +826,7 @@ __global__ __launch_bounds__(256) void attention_rows_kernel(const T* __restrict
                     if (!cls_only) qq[j] = *(const uint4*)(qbase + kr * ldq + ccol);
                 }
             }
-            if (cls_only) qq[0] = *(const uint4*)(qbase + (size_t)rl * ldq + ccol);
+            if (cls_only) qq[0] = *(const uint4*)(qbase + brow(t0) * ldq + ccol);
             const float sc2 = scaling * 1.4426950408889634f;       // softmax in base 2: exp(x) = 2^(x log2 e)
 #pragma unroll
             for (int qi = 0; qi < ATT_FAST_KEYS; ++qi) {
@@ -837,7 +861,7 @@ __global__ __launch_bounds__(256) void attention_rows_kernel(const T* __restrict
 #pragma unroll
                     for (int c = 0; c < 8; ++c) acc[c] *= inv;
                     if (active) {
-                        const size_t orow = cls_only ? (size_t)rl : brow(t0 + qi);
+                        const size_t orow = brow(t0 + qi);      // (cls_only: qi = 0, the row's position-0 slot)
                         store8<T>(ctx + orow * H + col, acc);
                     }
                 }
@@ -847,7 +871,7 @@ __global__ __launch_bounds__(256) void attention_rows_kernel(const T* __restrict
     }
     for (int qi = 0; qi < nq; ++qi) {
         float q[8];
-        load8<T>(qbase + (cls_only ? (size_t)rl : qrow(t0 + qi)) * ldq + ccol, q);
+        load8<T>(qbase + (cls_only ? brow(t0) : qrow(t0 + qi)) * ldq + ccol, q);
         // one pass over the keys with a running maximum (online softmax): K and V are read once
         float mx = -INFINITY, l = 0.f, acc[8];
 #pragma unroll
@@ -875,7 +899,7 @@ __global__ __launch_bounds__(256) void attention_rows_kernel(const T* __restrict
 #pragma unroll
         for (int c = 0; c < 8; ++c) acc[c] *= inv;
         if (active) {
-            const size_t orow = cls_only ? (size_t)rl : brow(t0 + qi);
+            const size_t orow = brow(t0 + qi);      // (cls_only: qi = 0, the row's position-0 slot)
             store8<T>(ctx + orow * H + col, acc);
         }
     }
@@ -1004,6 +1028,12 @@ __global__ __launch_bounds__(256) void dest_store_rows_kernel(const float* __res
         }
     }
     range_report(range_flag, bad, ZETT_RANGE_BIT_DEST);
+}
+
+// (lever 5 with a caller's row map) out[i] = outer[inner[i]]: the destination row of buffer row i of the position-0 block
+static __global__ void compose_rows_kernel(const int64_t* __restrict__ outer, const int64_t* __restrict__ inner, int64_t n, int64_t* __restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = outer[inner[i]];
 }
 
 // The row map of a destination against its size: err = 1 + (an index i with rows[i] >= n_dest), 0 when every row fits

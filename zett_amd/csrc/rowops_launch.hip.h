@@ -32,15 +32,16 @@ inline int launch_layernorm(hipStream_t st, int H, int ln_rows8, const float* in
     return ZETT_LN_WORKGROUP;
 }
 
-// attention_rows_kernel over `rows` vocabulary rows -> the flags word it ran with (bit 0 cls_only, bit 1 fast path, bit 2 pack)
+// attention_rows_kernel over `rows` vocabulary rows -> the flags word it ran with (bit 0 cls_only, bit 1 fast path, bit 2 pack,
+// bit 3 single rows copy their value row: with cls_slot, the forward's lever 5)
 template <typename T>
 inline int launch_attention(hipStream_t st, int H, int attention_fast, int attention_pack, const T* q, size_t ldq, const T* k, const T* v, size_t ldkv,
                             int head_dim, const int32_t* row_offset, const uint8_t* row_uniform, const uint8_t* tok_key, int64_t row0, int rows, int tok0,
-                            float scaling, int cls_only, const int32_t* tok_pair, T* ctx) {
+                            float scaling, int cls_only, const int32_t* tok_pair, T* ctx, const int32_t* cls_slot = nullptr, int skip_single = 0) {
     const int64_t waves = attention_waves(rows, H, attention_pack != 0).total;
-    const int flags = (cls_only ? 1 : 0) | (attention_fast ? 2 : 0) | (attention_pack ? 4 : 0);
+    const int flags = (cls_only ? 1 : 0) | (attention_fast ? 2 : 0) | (attention_pack ? 4 : 0) | (skip_single ? 8 : 0);
     hipLaunchKernelGGL((attention_rows_kernel<T>), dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, q, ldq, k, v, ldkv, H, head_dim, row_offset,
-                       row_uniform, tok_key, row0, rows, tok0, scaling, flags, tok_pair, ctx);
+                       row_uniform, tok_key, row0, rows, tok0, scaling, flags, tok_pair, ctx, cls_slot);
     return flags;
 }
 

@@ -130,6 +130,16 @@ struct zett_hypernet {
     DevBuf dest_word, dest_stage[2], dest_sink;
     int32_t* dest_host = nullptr;
     hipEvent_t dest_checked = nullptr;
+    // Lever 5 (Forward::plan_single_rows): rows with a single kept position first in the position-0 block, their query /
+    // key GEMM rows skipped.  single_map — reserved only when a forward takes the lever, outside zett_workspace_bytes like dest_sink —
+    // holds cls_row int64 [N] (buffer row -> vocabulary row), cls_slot int32 [N] (the inverse) and, behind them, the composition with a
+    // caller's row map; single_host is the pinned staging of the first two, single_copied the event behind their copy.
+    int single_rows = 1;              // 0 off, 1 auto (one chunk on one lane, at least one full round of 256x256 tiles saved per launch), 2 whenever possible
+    int64_t single_rows_last = 0;     // single rows the last forward skipped (zett_single_rows)
+    DevBuf single_map;
+    void* single_host = nullptr;
+    size_t single_host_bytes = 0;
+    hipEvent_t single_copied = nullptr;
     std::vector<hipEvent_t> ev;
     size_t ev_used = 0;
     std::vector<zett_gemm_record> gemm_log;     // every GEMM launch of the last forward (zett_get_gemm_log); "time_gemm": launch k has the event pair ev[2k], ev[2k + 1]
@@ -425,8 +435,10 @@ int zett_destroy(zett_hypernet* h) {
         if (kv.second.lo && kv.second.lo != (void*)kv.second.f32) (void)hipFree(kv.second.lo);
     }
     for (void* p : h->owned) (void)hipFree(p);
-    for (DevBuf* b : {&h->table, &h->x0, &h->yf, &h->yt, &h->big, &h->pre, &h->ctx, &h->cf, &h->ct, &h->lnstats, &h->lnparts, &h->dest_word, &h->dest_stage[0], &h->dest_stage[1], &h->dest_sink})
+    for (DevBuf* b : {&h->table, &h->x0, &h->yf, &h->yt, &h->big, &h->pre, &h->ctx, &h->cf, &h->ct, &h->lnstats, &h->lnparts, &h->dest_word, &h->dest_stage[0], &h->dest_stage[1], &h->dest_sink, &h->single_map})
         b->release();
+    if (h->single_host) (void)hipHostFree(h->single_host);
+    if (h->single_copied) (void)hipEventDestroy(h->single_copied);
     for (zett_hypernet::PlanSlot* psp : {&h->plan[0], &h->plan[1], &h->table_plan}) {
         zett_hypernet::PlanSlot& ps = *psp;
         ps.i32.release(); ps.u8.release();
@@ -656,6 +668,9 @@ int zett_set_option(zett_hypernet* h, const char* key, int64_t value) {
         h->gemm4d_min_k = (int)value;
     } else if (k == "range_accumulate") {
         h->range_accumulate = value != 0;
+    } else if (k == "single_rows") {
+        if (value < 0 || value > 2) return fail(ZETT_E_INVALID, "single_rows must be 0 (off), 1 (auto) or 2 (whenever a call is one chunk on one lane)");
+        h->single_rows = (int)value;
     } else if (k == "gemm_variant") {
         if (value != 0 && value != 1 && value != 2 && value != 3 && value != 7 && value != 8)
             return fail(ZETT_E_INVALID, "gemm_variant must be 0 (auto), 1 (128x128), 2 (256x256 register-staged), 3 (384x256), 7 (256x256 four-wave direct-to-LDS) or 8 (7 with the generic epilogue drain)");
@@ -681,6 +696,12 @@ int zett_workspace_bytes(const zett_hypernet* h, int64_t n_rows, int32_t seq, in
 int zett_get_stats(const zett_hypernet* h, zett_stats* out) {
     if (!h || !out) return fail(ZETT_E_INVALID, "null argument");
     *out = h->stats;
+    return 0;
+}
+
+int zett_single_rows(const zett_hypernet* h, int64_t* out) {
+    if (!h || !out) return fail(ZETT_E_INVALID, "null argument");
+    *out = h->single_rows_last;
     return 0;
 }
 
@@ -1325,6 +1346,11 @@ struct Forward {
     float* TBL = nullptr; T* TBL16 = nullptr; float* TBLST = nullptr;      // the hoisted table: fp32, or folded (16-bit sums + statistics)
     const float* lang_vec = nullptr;
     const float scaling = 1.0f / std::sqrt((float)(H / c.heads));
+    // lever 5 (plan_single_rows): single rows of the call (0: not taken), and the maps of the position-0 block on the device
+    int n_s = 0;
+    const int32_t* cls_slot = nullptr;    // [N] vocabulary row -> buffer row of its position 0
+    const int64_t* cls_row = nullptr;     // [N] buffer row -> vocabulary row
+    const int64_t* out_rows = nullptr;    // [N] buffer row -> row of the outputs: cls_row, or a destination's own map behind it
 
     int run() {
         h->stats = zett_stats{};
@@ -1339,6 +1365,7 @@ struct Forward {
         if (!h->ext.table)
             table_phase<T>(R, lane_workspace<T>(h, 0, MCS), p.id_list, 0, D, src, src_dtype, MC, mode.table_lo, TBL16, TBLST, TBL);
         if (R.rc) return R.rc;
+        if (int rc = plan_single_rows()) return rc;      // (host work, under the table phase enqueued above)
         if (int rc = run_chunks(guard)) return rc;
         h->out_recorded = true;          // (ps.released — the plan slot may be rewritten behind it, zett_forward_prepare — is recorded by the guard)
         return h->time_gemm ? read_gemm_timing(h, st) : 0;
@@ -1421,10 +1448,60 @@ struct Forward {
         return 0;
     }
 
+    // ---- lever 5: rows with a single kept position --------------------------------------
+    // Such a row (row_offset[n + 1] - row_offset[n] == 1 in a call with seq + lang > 1: never a uniform row, and its one position is
+    // a visible key) attends to exactly one key: the softmax weight is exactly 1 and its context is its own value row, bit for bit
+    // (attention_rows_kernel), so its query and key are never needed.  The host orders the position-0 block singles first — stable
+    // within both groups — from the row offsets it already holds; the GEMMs then skip those rows with a pointer offset: Q|K of a
+    // middle layer over buffer rows [n_s, m), the last layer's K over [n_s, m) and its query over [n_s, rows); V over every row.  The
+    // Q/K cells of single rows stay unwritten and are never read.  The block is read out through cls_row (readout, heads).
+    // Taken for a call that is ONE chunk on one lane; auto: when floor(n_s / 256) * (2H / 256) tiles — what a middle layer's Q|K
+    // launch loses — fill at least one round of the 256 CUs (less only empties part of a last round that is partly empty anyway).
+    int plan_single_rows() {
+        h->single_rows_last = 0;
+        if (!h->single_rows || seq + (c.embed_lang ? 1 : 0) <= 1 || Ttot > MC || two_lanes()) return 0;
+        int64_t ns = 0;
+        for (int64_t n = 0; n < N; ++n) ns += hoff[n + 1] - hoff[n] == 1;
+        if (ns == 0 || (h->single_rows == 1 && (ns / 256) * (int64_t)(2 * H / 256) < 256)) return 0;
+        const size_t map_bytes = (size_t)N * 12, comp_at = round_up(map_bytes, 16);
+        if (h->single_copied) HIP_TRY(hipEventSynchronize(h->single_copied));      // the staging's last copy has left it
+        else HIP_TRY(hipEventCreateWithFlags(&h->single_copied, hipEventDisableTiming));
+        if (h->single_host_bytes < map_bytes) {
+            if (h->single_host) (void)hipHostFree(h->single_host);
+            h->single_host = nullptr; h->single_host_bytes = 0;
+            HIP_TRY(hipHostMalloc(&h->single_host, map_bytes, hipHostMallocDefault));
+            h->single_host_bytes = map_bytes;
+        }
+        if (int rc = h->single_map.reserve(comp_at + (size_t)N * 8)) return rc;
+        int64_t* hrow = (int64_t*)h->single_host;
+        int32_t* hslot = (int32_t*)(hrow + N);
+        int64_t at_single = 0, at_other = ns;
+        for (int64_t n = 0; n < N; ++n) {
+            const int64_t slot = hoff[n + 1] - hoff[n] == 1 ? at_single++ : at_other++;
+            hslot[n] = (int32_t)slot;
+            hrow[slot] = n;
+        }
+        HIP_TRY(hipMemcpyAsync(h->single_map.p, h->single_host, map_bytes, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipEventRecord(h->single_copied, st));
+        n_s = (int)ns;
+        cls_row = h->single_map.as<int64_t>();
+        cls_slot = (const int32_t*)(cls_row + N);
+        out_rows = cls_row;
+        if (dest && dest->rows) {
+            int64_t* comp = (int64_t*)((char*)h->single_map.p + comp_at);
+            hipLaunchKernelGGL(compose_rows_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, dest->rows, cls_row, N, comp);
+            HIP_TRY(hipGetLastError());
+            out_rows = comp;
+        }
+        h->single_rows_last = ns;
+        return 0;
+    }
+
     // ---- encoder + heads over row chunks -----------------------------------------------
     // Buffer rows of a chunk are ordered POSITION 0 FIRST (rowops.hip.h chunk_row): rows [0, rows) are position 0 of the
     // chunk's vocabulary rows, the other packed positions follow.  What the last layer and the heads consume — position 0
     // only (modeling_hypernet.py:234) — is then the first `rows` rows of every buffer, with no gather in between.
+    // (Lever 5 taken: that block is permuted, single rows first — cls_slot / cls_row above.)
     // One chunk = vocabulary rows [r0, r1) on one LANE: a stream and a slice of every workspace buffer starting `off` rows in.
     // Normally there is one lane (the caller's stream, offset 0) and the chunks follow each other.  A call that is ONE chunk
     // can instead run as two half-vocabulary chunks on two lanes at once (r4, "concurrent_lanes"): rows are independent, so the
@@ -1472,7 +1549,7 @@ struct Forward {
     void embeddings(Chunk& k) {
         LnEmbed emb{TBL, p.tok_slot, p.tok_pos, R.Wf("model.embeddings.token_type_embeddings.weight"),
                     R.Wf("model.embeddings.position_embeddings.weight"), lang_vec, seq, p.tok_row, p.row_offset, k.r0, k.rows,
-                    mode.table_lo ? (const void*)TBL16 : nullptr, TBLST, R.Wf("input_projection.1.ln.weight"), R.Wf("input_projection.1.ln.bias")};
+                    mode.table_lo ? (const void*)TBL16 : nullptr, TBLST, R.Wf("input_projection.1.ln.weight"), R.Wf("input_projection.1.ln.bias"), cls_slot};
         k.hs_sum = k.w.Zf;
         k.hs_stats = k.w.STb;
         k.hs_gamma = R.Wf("model.embeddings.LayerNorm.weight");
@@ -1485,7 +1562,7 @@ struct Forward {
             emb.tok_slot = p.pair_tslot; emb.tok_pos = p.pair_pos; emb.tok_row = nullptr;
             R.layernorm(nullptr, k.P, k.hs_gamma, k.hs_beta, c.ln_eps_encoder, nullptr, k.w.Zt, k.hs_stats, LnReadout{}, -1, &emb, 0, sum);
             // p.tok_pkey becomes the pair slot of every buffer row (the keys are dead once plan_pairs_kernel has run)
-            hipLaunchKernelGGL(pair_rows_kernel, dim3((k.m + 255) / 256), dim3(256), 0, k.st, k.m, k.tok0, k.r0, k.rows, p, p.tok_pkey);
+            hipLaunchKernelGGL(pair_rows_kernel, dim3((k.m + 255) / 256), dim3(256), 0, k.st, k.m, k.tok0, k.r0, k.rows, p, p.tok_pkey, cls_slot);
             R.check("pair_rows");
             h->stats.distinct_positions = k.P;
         } else {
@@ -1502,30 +1579,43 @@ struct Forward {
         const T* wqkv = k.raw ? (const T*)h->fold_qkv[l].w : (const T*)h->qkv_w[l];
         const float* bqkv = k.raw ? h->fold_qkv[l].b : h->qkv_b[l];
         const float* cqkv = k.raw ? h->fold_qkv[l].c : nullptr;
-        auto qkv = [&](int col0, int cols, int M, T* out) {       // columns [col0, col0 + cols) of [q | k | v] for the first M buffer rows
+        // columns [col0, col0 + cols) of [q | k | v] for buffer rows [row0, M), into the same rows of `out` (leading dimension ld)
+        auto qkv = [&](int col0, int cols, int row0, int M, T* out, size_t ld) {
             GemmEpilogue<T> e = R.epi();
-            e.bias = bqkv + col0; e.out_lo = out; e.ld_lo = cols;
-            if (k.raw) { e.fold_stats = k.hs_stats; e.fold_c = cqkv + col0; }
-            R.gemm(w.Zt, H, wqkv + (size_t)col0 * H, H, M, cols, H, e);
+            e.bias = bqkv + col0; e.out_lo = out + (size_t)row0 * ld; e.ld_lo = (int)ld;
+            if (k.raw) { e.fold_stats = k.hs_stats + 2 * (size_t)row0; e.fold_c = cqkv + col0; }
+            R.a_rows_readable = k.w.a_rows - row0;
+            R.gemm(w.Zt + (size_t)row0 * H, H, wqkv + (size_t)col0 * H, H, M - row0, cols, H, e);
+            R.a_rows_readable = k.w.a_rows;
         };
         const bool by_pair = !cls_only && k.pairs && l == 0;       // Zt holds the P pair rows; BIG gets their Q/K/V
         const T* Q = w.BIG;                               // [m | P, 3H]: q | k | v
         const T* KV = w.BIG + H;
         size_t ld_q = (size_t)3 * H, ld_kv = (size_t)3 * H;
         if (!cls_only) {
-            qkv(0, 3 * H, by_pair ? k.P : k.m, w.BIG);
+            if (n_s && !by_pair) {          // lever 5: no query / key for the single rows, which are buffer rows [0, n_s)
+                qkv(0, 2 * H, n_s, k.m, w.BIG, ld_q);
+                qkv(2 * H, H, 0, k.m, w.BIG + 2 * H, ld_q);
+            } else {
+                qkv(0, 3 * H, 0, by_pair ? k.P : k.m, w.BIG, ld_q);
+            }
         } else {
             // Only hidden[:,0] is consumed after this layer (modeling_hypernet.py:234): keys and values for every
             // position, the query (and everything downstream) for position 0 = the first `rows` rows of the
             // hidden state (sum, statistics and 16-bit operand alike).
-            qkv(H, 2 * H, k.m, w.BIG);                                   // KV [m, 2H]
-            qkv(0, H, k.rows, w.BIG + (size_t)k.m * 2 * H);              // Q [rows, H]  (rows <= m, BIG holds >= m x 3H)
             KV = w.BIG; Q = w.BIG + (size_t)k.m * 2 * H;
             ld_q = (size_t)H; ld_kv = (size_t)2 * H;
+            if (n_s) {                                                   // lever 5: K and the query without the single rows
+                qkv(H, H, n_s, k.m, w.BIG, ld_kv);
+                qkv(2 * H, H, 0, k.m, w.BIG + H, ld_kv);
+            } else {
+                qkv(H, 2 * H, 0, k.m, w.BIG, ld_kv);                     // KV [m, 2H]
+            }
+            qkv(0, H, n_s, k.rows, w.BIG + (size_t)k.m * 2 * H, ld_q);   // Q [rows, H]  (rows <= m, BIG holds >= m x 3H)
             k.zrows = k.rows;
         }
         launch_attention<T>(k.st, H, h->attention_fast, h->attention_pack, Q, ld_q, KV, KV + H, ld_kv, H / c.heads, p.row_offset, p.row_uniform, p.tok_key,
-                            k.r0, k.rows, k.tok0, scaling, cls_only ? 1 : 0, by_pair ? (const int32_t*)p.tok_pair : (const int32_t*)nullptr, w.CTX);
+                            k.r0, k.rows, k.tok0, scaling, cls_only ? 1 : 0, by_pair ? (const int32_t*)p.tok_pair : (const int32_t*)nullptr, w.CTX, cls_slot, n_s ? 1 : 0);
         R.check(cls_only ? "attention(position 0)" : "attention");
     }
 
@@ -1620,6 +1710,13 @@ struct Forward {
             if (int rc = h->dest_sink.reserve((size_t)N * sizeof(float))) return rc;      // (the whole call: both lanes of a pair share it)
             ro.out_bias = h->dest_sink.as<float>() + k.r0;
         }
+        // lever 5: buffer row r is vocabulary row cls_row[r] — every bias goes through the row map (one chunk: r0 = 0), zett_forward's
+        // fp32 vector through the fp32 destination store (the same bytes)
+        if (n_s && (!dest || dest->bias)) {
+            ro.bias_rows = out_rows;
+            if (!dest) bias_dtype = ZETT_F32;
+            else ro.out_bias = (float*)dest->bias;
+        }
         ro.range_flag = h->range_word;
         ro.in_lo = mode.lo_stream ? (const T*)k.w.Zt : (const T*)nullptr;       // (16-bit residual stream: the rows are read from the 16-bit copy of the sum)
         R.layernorm(k.hs_sum, k.rows, k.hs_gamma, k.hs_beta, c.ln_eps_encoder, k.w.Cf, k.w.Ct, nullptr, ro, bias_dtype);
@@ -1629,6 +1726,7 @@ struct Forward {
     // (zett_forward_into) a destination matrix as the heads of the chunk starting at vocabulary row r0 see it
     DestOut dest_out(void* base, int64_t ld, int64_t r0) const {
         const size_t es = dest->dtype == ZETT_F32 ? 4 : 2;
+        if (n_s) return DestOut{base, out_rows, ld, dest->dtype};      // lever 5 (one chunk): the position-0 block's own order behind the caller's map
         return DestOut{dest->rows ? base : (void*)((char*)base + (size_t)r0 * (size_t)ld * es), dest->rows ? dest->rows + r0 : nullptr, ld, dest->dtype};
     }
 
@@ -1652,6 +1750,9 @@ struct Forward {
         const T* wl = fold ? (const T*)f.w : R.Wlo(name + ".1.weight");
         if (dest) {
             const DestOut d = dest_out(dst, ld_dst, k.r0), d_b = split ? dest_out(dst_b, ld_dst_b, k.r0) : DestOut{};
+            R.head_gemm(w.CTX, wl, k.rows, width, H, e, &d, split ? &d_b : nullptr, E);
+        } else if (n_s) {      // lever 5: zett_forward's fp32 matrices through the fp32 destination store and cls_row (the same bytes)
+            const DestOut d{out, out_rows, E, ZETT_F32}, d_b{out_b, out_rows, E, ZETT_F32};
             R.head_gemm(w.CTX, wl, k.rows, width, H, e, &d, split ? &d_b : nullptr, E);
         } else {
             e.out_f32 = out + (size_t)k.r0 * E;

@@ -142,6 +142,13 @@ class HipEngine:
         _lib.check(self.lib.zett_get_stats(self.handle, C.byref(s)))
         return {n: getattr(s, n) for n, _ in s._fields_}
 
+    def single_rows(self) -> int:
+        """Rows of the most recent forward whose query / key GEMM rows were skipped because they keep a single position
+        (zett_single_rows; the "single_rows" option); 0 when the forward did not take the lever."""
+        out = C.c_int64(0)
+        _lib.check(self.lib.zett_single_rows(self.handle, C.byref(out)), "zett_single_rows")
+        return out.value
+
     def prepare(self, surface_forms: torch.Tensor, input_stream: Optional["torch.cuda.Stream"] = None) -> None:
         """zett_forward_prepare: enqueue the plan of the NEXT forward(surface_forms, ...) on the handle's own stream, behind the
         work `input_stream` (default: the current stream) holds now.  The forward that follows with the SAME tensor then waits
