@@ -3,7 +3,7 @@ from the commit BEFORE a change of the forward's host orchestration, and tests/t
 under test.  Per case: the GEMM launch sequence (m, n, k, variant, epilogue), stats() without its timing fields, workspace_bytes()
 and the sha256 of every output's bytes.  The shapes are the smallest that reach each branch of the orchestration (csrc/zett_hip.hip):
 the LayerNorm launcher's four kernels, every ForwardMode, one and two chunks, two lanes, the pair lever, both head layouts, every
-destination store, the shared table and a prepared plan."""
+destination store, the shared table, a prepared plan and the single-rows lever."""
 import hashlib
 
 import numpy as np
@@ -27,6 +27,7 @@ CONFIGS = {
     "h512_nobias": (_cfg(512, 8, 1024, 2, hn_predict_bias=False), 600),
     "h512_oneout": (_cfg(512, 8, 1024, 2, separate_out_embeddings=False), 600),
     "h512_split": (_cfg(512, 8, 1024, 2, hn_single_head=True), 600),                  # single_head + separate_out: the split head, unfolded
+    "h512_nolang": (_cfg(512, 8, 1024, 2, hn_embed_lang_id=False), 600),              # no language position: rows that keep ONE position exist
     "h1536": (_cfg(1536, 24, 512, 2), 300),                    # rows8 TPR 64
     "h2560": (_cfg(2560, 20, 512, 1), 300),                    # TPR 256; the only layer is the position-0-only one; no pair plan
 }
@@ -52,6 +53,11 @@ CASES["into_no_bias"] = ("h512", "f16", {}, "into_no_bias")                  # t
 CASES["shared_table"] = ("h512", "f16", {}, "shared_table")                  # table_plan -> table_rows -> forward_table
 CASES["prepared"] = ("h512", "f16", {}, "prepared")                          # prepare(x) then forward(x)
 CASES["prepared_other"] = ("h512", "f16", {}, "prepared_other")              # prepare(x) then forward(y): the plan is made again
+# "single_rows": 2 (skip the query / key GEMM rows of single-position rows whenever possible).  On h512 every row also keeps the language
+# position, so the forward asks and declines; h512_nolang takes it: Q|K launches from a row offset, outputs through cls_row
+for _cfg_name, _tag in (("h512", "single_rows"), ("h512_nolang", "single_rows_taken")):
+    CASES[_tag] = (_cfg_name, "f16", {"single_rows": 2}, "forward")
+    CASES[_tag + "_into"] = (_cfg_name, "f16", {"single_rows": 2}, "into_bf16_permuted")
 
 TIMING_FIELDS = ("gemm_ms", "gemm_flops_timed")
 

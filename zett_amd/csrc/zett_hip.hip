@@ -49,6 +49,38 @@ struct Tensor {
 
 inline size_t round_up(size_t v, size_t m) { return (v + m - 1) / m * m; }
 
+// The model as the forward reads it: device pointers that own nothing (the handle's tensors and `owned` do), bound once by
+// zett_finalize.  A GEMM operand (Linear::w, Folded::w) is in the handle's arithmetic type, everything else fp32.  What the
+// config switches off stays null.
+struct Linear { const void* w = nullptr; const float* b = nullptr; };
+struct Affine { const float* w = nullptr; const float* b = nullptr; };      // LayerNorm (gamma, beta), Rescaler, bias projection
+struct Projector { Linear dense1, dense2; Affine ln; };
+// LayerNorm fold (16-bit modes): the gamma-folded operand of a GEMM that follows a LayerNorm, its row sums and beta-folded bias
+struct Folded { void* w = nullptr; float* c = nullptr; float* b = nullptr; };
+struct Layer {
+    Linear q, k, v;                    // as the checkpoint has them: read by zett_finalize only, which fuses them into
+    Linear qkv;                        // rows [q | k | v]: [3H, H], [3H]
+    Linear attn_out, up, down; Affine attn_ln, out_ln;
+    Folded fold_qkv, fold_up;          // qkv of layers >= 1 folded with the previous layer's out_ln, up with attn_ln
+};
+struct Head {
+    Projector block; Linear out;
+    const float* scale = nullptr; const float* shift = nullptr;      // Rescaler over the head's columns (first head: scaler | out_scaler for single_head)
+    Folded fold;                       // `out` folded with the block's LayerNorm (not for the split single head: its two-destination epilogue is the generic one)
+};
+struct Model {
+    const float* lang = nullptr; const float* token_type = nullptr; const float* position = nullptr; Affine emb_ln;
+    std::vector<Layer> layers;
+    const float* fallback = nullptr; Affine in_scaler, scaler, out_scaler, bias;
+    Linear in_proj; Projector in_block;      // input_projection.0 / .1
+    Head head_in, head_out;
+    float* head_one = nullptr;         // [head_out_width] ones / zeros: the Rescaler of a config without hn_rescale_embeddings, for the
+    float* head_zero = nullptr;        // folded head epilogue, which is compiled with it
+};
+// One weight of the declaration (declare_weights): its checkpoint name and shape, and the field of Model its device pointer goes
+// to — `operand` for a GEMM operand (converted to the arithmetic type, fp32 original freed in the 16-bit modes), else `vec`.
+struct WeightDecl { std::string name; std::vector<int64_t> shape; const void** operand; const float** vec; };
+
 }  // namespace
 
 struct zett_hypernet {
@@ -56,22 +88,11 @@ struct zett_hypernet {
     int device = 0;
     int precision = ZETT_PREC_BF16;
     bool finalized = false;
-    std::map<std::string, Tensor> w;
-    // fused / derived operands built by zett_finalize
-    std::vector<void*> qkv_w;         // per layer [3H, H]
-    std::vector<float*> qkv_b;        // per layer [3H]
-    // LayerNorm fold (16-bit modes): gamma-folded operands of the GEMMs that follow an encoder LayerNorm — the fused QKV of
-    // layers >= 1 (folded with the previous layer's output LayerNorm) and every intermediate.dense (with the layer's
-    // attention-output LayerNorm) — with their row sums and beta-folded biases
-    struct Folded { void* w = nullptr; float* c = nullptr; float* b = nullptr; };
-    std::vector<Folded> fold_qkv, fold_up;
-    Folded fold_head_in, fold_head_out;    // the final Linear of each output head, folded with its ProjectorBlock's LayerNorm
-    float* head_one = nullptr;        // [head_out_width] ones / zeros: the Rescaler of a config without hn_rescale_embeddings, for the
-    float* head_zero = nullptr;       // folded head epilogue, which is compiled with it
+    std::map<std::string, Tensor> w;  // the uploaded tensors, by name: their owner (zett_load_weight, zett_finalize, zett_destroy)
+    std::vector<WeightDecl> decl;     // every weight the library reads, sorted by name (zett_create); its slots point into `m`
+    Model m;                          // what the forward reads
     int ln_fold = 1;
-    float* head_scale = nullptr;      // [head_out_width] scaler.w (| out_scaler.w for single_head)
-    float* head_shift = nullptr;
-    std::vector<void*> owned;         // everything to hipFree at destroy
+    std::vector<void*> owned;         // the fused / derived operands zett_finalize built: everything else to hipFree at destroy
     // options
     int64_t max_chunk_tokens = 0;          // 0 = auto: chunk_token_cap() below (131 072 at H = 4096, more for narrower hypernets)
     int time_gemm = 0;
@@ -150,58 +171,40 @@ namespace {
 
 size_t elt_size(int precision) { return precision == ZETT_PREC_F32 ? 4 : 2; }
 
-bool is_gemm_weight(const std::string& n) {
-    static const char* suffixes[] = {"input_projection.0.weight", "dense1.weight", "dense2.weight",
-                                     "query.weight", "key.weight", "value.weight", "dense.weight",
-                                     "output_projection.1.weight", "output_projection_out.1.weight"};
-    for (const char* s : suffixes) {
-        const size_t ls = strlen(s);
-        if (n.size() >= ls && n.compare(n.size() - ls, ls, s) == 0) return true;
-    }
-    return false;
-}
-
-// expected shapes (mirrors zett_amd/dims.py:weight_shapes)
-void expected_shapes(const zett_config& c, std::map<std::string, std::vector<int64_t>>& s) {
-    const int64_t H = c.hidden, I = c.intermediate;
-    auto proj = [&](const std::string& p) {
-        s[p + "dense1.weight"] = {I, H}; s[p + "dense1.bias"] = {I};
-        s[p + "dense2.weight"] = {H, I}; s[p + "dense2.bias"] = {H};
-        s[p + "ln.weight"] = {H}; s[p + "ln.bias"] = {H};
-    };
-    if (c.embed_lang) s["lang_embeddings.weight"] = {c.n_langs, H};
-    s["model.embeddings.token_type_embeddings.weight"] = {1, H};
-    s["model.embeddings.LayerNorm.weight"] = {H};
-    s["model.embeddings.LayerNorm.bias"] = {H};
-    s["model.embeddings.position_embeddings.weight"] = {c.max_positions, H};
+// The ONE declaration of the model's weights (names and shapes: zett_amd/dims.py weight_shapes, minus the word-embedding table,
+// which nothing reads): what zett_load_weight accepts, what zett_finalize requires, converts and binds.  m.layers is sized here.
+std::vector<WeightDecl> declare_weights(const zett_config& c, Model& m) {
+    const int64_t H = c.hidden, I = c.intermediate, E = c.n_embd, EIN = c.n_in_embd;
+    std::vector<WeightDecl> d;
+    auto vec = [&](const std::string& n, std::vector<int64_t> shape, const float*& slot) { d.push_back({n, std::move(shape), nullptr, &slot}); };
+    auto linear = [&](const std::string& p, int64_t n, int64_t k, Linear& l) { d.push_back({p + "weight", {n, k}, &l.w, nullptr}); vec(p + "bias", {n}, l.b); };
+    auto norm = [&](const std::string& p, Affine& a) { vec(p + "weight", {H}, a.w); vec(p + "bias", {H}, a.b); };
+    auto scaler = [&](const std::string& p, int64_t n, Affine& a) { vec(p + "w", {1, n}, a.w); vec(p + "b", {1, n}, a.b); };
+    auto block = [&](const std::string& p, Projector& b) { linear(p + "dense1.", I, H, b.dense1); linear(p + "dense2.", H, I, b.dense2); norm(p + "ln.", b.ln); };
+    if (c.embed_lang) vec("lang_embeddings.weight", {c.n_langs, H}, m.lang);
+    vec("model.embeddings.token_type_embeddings.weight", {1, H}, m.token_type);
+    norm("model.embeddings.LayerNorm.", m.emb_ln);
+    vec("model.embeddings.position_embeddings.weight", {c.max_positions, H}, m.position);
+    m.layers.resize(c.layers);
     for (int l = 0; l < c.layers; ++l) {
         const std::string p = "model.encoder.layer." + std::to_string(l) + ".";
-        for (const char* q : {"query", "key", "value"}) {
-            s[p + "attention.self." + q + ".weight"] = {H, H};
-            s[p + "attention.self." + q + ".bias"] = {H};
-        }
-        s[p + "attention.output.dense.weight"] = {H, H}; s[p + "attention.output.dense.bias"] = {H};
-        s[p + "attention.output.LayerNorm.weight"] = {H}; s[p + "attention.output.LayerNorm.bias"] = {H};
-        s[p + "intermediate.dense.weight"] = {I, H}; s[p + "intermediate.dense.bias"] = {I};
-        s[p + "output.dense.weight"] = {H, I}; s[p + "output.dense.bias"] = {H};
-        s[p + "output.LayerNorm.weight"] = {H}; s[p + "output.LayerNorm.bias"] = {H};
+        Layer& L = m.layers[l];
+        linear(p + "attention.self.query.", H, H, L.q); linear(p + "attention.self.key.", H, H, L.k); linear(p + "attention.self.value.", H, H, L.v);
+        linear(p + "attention.output.dense.", H, H, L.attn_out); norm(p + "attention.output.LayerNorm.", L.attn_ln);
+        linear(p + "intermediate.dense.", I, H, L.up);
+        linear(p + "output.dense.", H, I, L.down); norm(p + "output.LayerNorm.", L.out_ln);
     }
-    s["fallback_embeddings.weight"] = {c.n_extra, c.n_in_embd};
-    s["input_projection.0.weight"] = {H, c.n_in_embd}; s["input_projection.0.bias"] = {H};
-    proj("input_projection.1.");
-    proj("output_projection.0.");
-    const int64_t w0 = c.single_head ? c.n_in_embd : c.n_embd;
-    s["output_projection.1.weight"] = {w0, H}; s["output_projection.1.bias"] = {w0};
-    if (c.separate_out && !c.single_head) {
-        proj("output_projection_out.0.");
-        s["output_projection_out.1.weight"] = {c.n_embd, H}; s["output_projection_out.1.bias"] = {c.n_embd};
-    }
+    vec("fallback_embeddings.weight", {c.n_extra, EIN}, m.fallback);
+    linear("input_projection.0.", H, EIN, m.in_proj); block("input_projection.1.", m.in_block);
+    block("output_projection.0.", m.head_in.block); linear("output_projection.1.", c.single_head ? EIN : E, H, m.head_in.out);
+    if (c.separate_out && !c.single_head) { block("output_projection_out.0.", m.head_out.block); linear("output_projection_out.1.", E, H, m.head_out.out); }
     if (c.rescale) {
-        s["in_scaler.w"] = {1, c.n_in_embd}; s["in_scaler.b"] = {1, c.n_in_embd};
-        s["scaler.w"] = {1, c.n_embd}; s["scaler.b"] = {1, c.n_embd};
-        if (c.separate_out) { s["out_scaler.w"] = {1, c.n_embd}; s["out_scaler.b"] = {1, c.n_embd}; }
+        scaler("in_scaler.", EIN, m.in_scaler); scaler("scaler.", E, m.scaler);
+        if (c.separate_out) scaler("out_scaler.", E, m.out_scaler);
     }
-    if (c.predict_bias) { s["bias_projection.weight"] = {1, H}; s["bias_projection.bias"] = {1}; }
+    if (c.predict_bias) { vec("bias_projection.weight", {1, H}, m.bias.w); vec("bias_projection.bias", {1}, m.bias.b); }
+    std::sort(d.begin(), d.end(), [](const WeightDecl& a, const WeightDecl& b) { return a.name < b.name; });
+    return d;
 }
 
 int validate_config(const zett_config& c, int precision) {
@@ -416,6 +419,7 @@ int zett_create(const zett_config* cfg, int device, int precision, zett_hypernet
     h->cfg = *cfg;
     h->device = device;
     h->precision = precision;
+    h->decl = declare_weights(h->cfg, h->m);
     if (hipMalloc((void**)&h->range_word, 64) != hipSuccess || hipHostMalloc((void**)&h->range_host, 64, hipHostMallocDefault) != hipSuccess ||
         hipMemset(h->range_word, 0, 64) != hipSuccess) {
         if (h->range_word) (void)hipFree(h->range_word);
@@ -463,16 +467,14 @@ int zett_destroy(zett_hypernet* h) {
 int zett_load_weight(zett_hypernet* h, const char* name, const void* data, int dtype, const int64_t* shape, int ndim) {
     if (!h || !name || !data || !shape || ndim < 1) return fail(ZETT_E_INVALID, "null argument");
     if (h->finalized) return fail(ZETT_E_STATE, "weights are frozen after zett_finalize");
-    std::map<std::string, std::vector<int64_t>> exp;
-    expected_shapes(h->cfg, exp);
     const std::string n(name);
-    auto it = exp.find(n);
-    if (it == exp.end()) return 0;   // e.g. model.embeddings.word_embeddings.weight: never read
+    auto it = std::lower_bound(h->decl.begin(), h->decl.end(), n, [](const WeightDecl& d, const std::string& key) { return d.name < key; });
+    if (it == h->decl.end() || it->name != n) return 0;   // e.g. model.embeddings.word_embeddings.weight: never read
     std::vector<int64_t> got(shape, shape + ndim);
-    if (got != it->second) {
+    if (got != it->shape) {
         std::string a, b;
         for (auto v : got) a += std::to_string(v) + ",";
-        for (auto v : it->second) b += std::to_string(v) + ",";
+        for (auto v : it->shape) b += std::to_string(v) + ",";
         return fail(ZETT_E_INVALID, "%s: shape [%s] does not match the config's [%s]", name, a.c_str(), b.c_str());
     }
     ZETT_ON_DEVICE(h->device);
@@ -507,16 +509,19 @@ int zett_finalize(zett_hypernet* h) {
     if (!h) return fail(ZETT_E_INVALID, "null handle");
     if (h->finalized) return 0;
     ZETT_ON_DEVICE(h->device);
-    std::map<std::string, std::vector<int64_t>> exp;
-    expected_shapes(h->cfg, exp);
-    for (auto& kv : exp)
-        if (!h->w.count(kv.first)) return fail(ZETT_E_STATE, "missing weight: %s", kv.first.c_str());
+    std::vector<Tensor*> ts;          // the uploaded tensor of every declared weight, in the declaration's order
+    for (const WeightDecl& d : h->decl) {
+        auto it = h->w.find(d.name);
+        if (it == h->w.end()) return fail(ZETT_E_STATE, "missing weight: %s", d.name.c_str());
+        ts.push_back(&it->second);
+    }
     const zett_config& c = h->cfg;
+    Model& m = h->m;
     const size_t es = elt_size(h->precision);
     // GEMM operands in the arithmetic type
-    for (auto& kv : h->w) {
-        Tensor& t = kv.second;
-        if (!is_gemm_weight(kv.first)) continue;
+    for (size_t i = 0; i < ts.size(); ++i) {
+        Tensor& t = *ts[i];
+        if (!h->decl[i].operand) continue;
         if (h->precision == ZETT_PREC_F32) { t.lo = t.f32; continue; }
         HIP_TRY(hipMalloc(&t.lo, t.numel * 2));
         const int blocks = (int)std::min<size_t>((t.numel / 4 + 255) / 256 + 1, 65535);
@@ -527,29 +532,34 @@ int zett_finalize(zett_hypernet* h) {
         });
     }
     HIP_TRY(hipDeviceSynchronize());
+    // bind the model: a GEMM operand's copy in the arithmetic type, the fp32 tensor of everything else — the tensors as they are
+    // NOW, whatever order they were uploaded in and however often
+    for (size_t i = 0; i < ts.size(); ++i)
+        if (h->decl[i].operand) *h->decl[i].operand = ts[i]->lo;
+        else *h->decl[i].vec = ts[i]->f32;
+    auto original = [&](const Linear& l) -> const float* {      // the fp32 original of an operand (until it is freed below)
+        for (size_t i = 0; i < ts.size(); ++i)
+            if (h->decl[i].operand == &l.w) return ts[i]->f32;
+        return nullptr;
+    };
     // fused QKV operand per layer: rows [q | k | v]
     const size_t H = c.hidden;
-    for (int l = 0; l < c.layers; ++l) {
-        const std::string p = "model.encoder.layer." + std::to_string(l) + ".attention.self.";
+    for (Layer& L : m.layers) {
         void* wq = nullptr; float* bq = nullptr;
         HIP_TRY(hipMalloc(&wq, 3 * H * H * es));
         HIP_TRY(hipMalloc((void**)&bq, 3 * H * 4));
         h->owned.push_back(wq); h->owned.push_back(bq);
         int k = 0;
-        for (const char* q : {"query", "key", "value"}) {
-            Tensor& tw = h->w[p + q + ".weight"];
-            Tensor& tb = h->w[p + q + ".bias"];
-            HIP_TRY(hipMemcpy((char*)wq + (size_t)k * H * H * es, tw.lo, H * H * es, hipMemcpyDeviceToDevice));
-            HIP_TRY(hipMemcpy(bq + (size_t)k * H, tb.f32, H * 4, hipMemcpyDeviceToDevice));
+        for (const Linear* part : {&L.q, &L.k, &L.v}) {
+            HIP_TRY(hipMemcpy((char*)wq + (size_t)k * H * H * es, part->w, H * H * es, hipMemcpyDeviceToDevice));
+            HIP_TRY(hipMemcpy(bq + (size_t)k * H, part->b, H * 4, hipMemcpyDeviceToDevice));
             ++k;
         }
-        h->qkv_w.push_back(wq);
-        h->qkv_b.push_back(bq);
+        L.qkv = Linear{wq, bq};
     }
     // LayerNorm fold operands (rowops.hip.h fold_weight_kernel); needs the fp32 originals, which are freed below
     if (h->precision != ZETT_PREC_F32 && c.hidden % 128 == 0) {
-        auto fold = [&](const float* w32, size_t N, size_t K, const float* gamma, const float* beta, const float* bias,
-                        zett_hypernet::Folded& f) -> int {
+        auto fold = [&](const float* w32, size_t N, size_t K, const Affine& ln, const float* bias, Folded& f) -> int {
             HIP_TRY(hipMalloc(&f.w, N * K * es));
             HIP_TRY(hipMalloc((void**)&f.c, N * 4));
             HIP_TRY(hipMalloc((void**)&f.b, N * 4));
@@ -557,41 +567,36 @@ int zett_finalize(zett_hypernet* h) {
             with_precision(h->precision, [&](auto a) {
                 using T = typename decltype(a)::type;
                 if constexpr (sizeof(T) == 2)
-                    launch_fold_weight<T>(0, w32, (int)N, (int)K, gamma, beta, bias, (T*)f.w, f.c, f.b, h->range_word);
+                    launch_fold_weight<T>(0, w32, (int)N, (int)K, ln.w, ln.b, bias, (T*)f.w, f.c, f.b, h->range_word);
             });
             return 0;
         };
-        h->fold_qkv.resize(c.layers); h->fold_up.resize(c.layers);
         float* tmp = nullptr;                       // fp32 [3H, H] fused QKV of one layer
         HIP_TRY(hipMalloc((void**)&tmp, 3 * H * H * 4));
         for (int l = 0; l < c.layers; ++l) {
-            const std::string lp = "model.encoder.layer." + std::to_string(l) + ".";
-            if (int rc = fold(h->w[lp + "intermediate.dense.weight"].f32, c.intermediate, H, h->w[lp + "attention.output.LayerNorm.weight"].f32,
-                              h->w[lp + "attention.output.LayerNorm.bias"].f32, h->w[lp + "intermediate.dense.bias"].f32, h->fold_up[l])) return rc;
+            Layer& L = m.layers[l];
+            if (int rc = fold(original(L.up), c.intermediate, H, L.attn_ln, L.up.b, L.fold_up)) return rc;
             if (l == 0) continue;
-            const std::string pp = "model.encoder.layer." + std::to_string(l - 1) + ".output.LayerNorm.";
             int k = 0;
-            for (const char* q : {"query", "key", "value"}) {
-                HIP_TRY(hipMemcpy(tmp + (size_t)k * H * H, h->w[lp + "attention.self." + q + ".weight"].f32, H * H * 4, hipMemcpyDeviceToDevice));
+            for (const Linear* part : {&L.q, &L.k, &L.v}) {
+                HIP_TRY(hipMemcpy(tmp + (size_t)k * H * H, original(*part), H * H * 4, hipMemcpyDeviceToDevice));
                 ++k;
             }
-            if (int rc = fold(tmp, 3 * H, H, h->w[pp + "weight"].f32, h->w[pp + "bias"].f32, h->qkv_b[l], h->fold_qkv[l])) return rc;
+            if (int rc = fold(tmp, 3 * H, H, m.layers[l - 1].out_ln, L.qkv.b, L.fold_qkv)) return rc;
         }
         // the output heads: Linear(LN_1e-6(.)) with the ProjectorBlock's LayerNorm folded in (not for the split single head,
         // whose two-destination epilogue is the generic one)
         if (!(c.single_head && c.separate_out)) {
-            const size_t w0 = c.single_head ? c.n_in_embd : c.n_embd;
-            if (int rc = fold(h->w["output_projection.1.weight"].f32, w0, H, h->w["output_projection.0.ln.weight"].f32,
-                              h->w["output_projection.0.ln.bias"].f32, h->w["output_projection.1.bias"].f32, h->fold_head_in)) return rc;
-            if (c.separate_out && !c.single_head)
-                if (int rc = fold(h->w["output_projection_out.1.weight"].f32, c.n_embd, H, h->w["output_projection_out.0.ln.weight"].f32,
-                                  h->w["output_projection_out.0.ln.bias"].f32, h->w["output_projection_out.1.bias"].f32, h->fold_head_out)) return rc;
+            const size_t w0 = c.single_head ? c.n_in_embd : c.n_embd;      // (= n_embd: a single head is not split here)
+            for (Head* hd : {&m.head_in, &m.head_out})
+                if (hd->out.w)
+                    if (int rc = fold(original(hd->out), w0, H, hd->block.ln, hd->out.b, hd->fold)) return rc;
             std::vector<float> ones(w0, 1.0f), zeros(w0, 0.0f);
-            HIP_TRY(hipMalloc((void**)&h->head_one, w0 * 4));
-            HIP_TRY(hipMalloc((void**)&h->head_zero, w0 * 4));
-            h->owned.push_back(h->head_one); h->owned.push_back(h->head_zero);
-            HIP_TRY(hipMemcpy(h->head_one, ones.data(), w0 * 4, hipMemcpyHostToDevice));
-            HIP_TRY(hipMemcpy(h->head_zero, zeros.data(), w0 * 4, hipMemcpyHostToDevice));
+            HIP_TRY(hipMalloc((void**)&m.head_one, w0 * 4));
+            HIP_TRY(hipMalloc((void**)&m.head_zero, w0 * 4));
+            h->owned.push_back(m.head_one); h->owned.push_back(m.head_zero);
+            HIP_TRY(hipMemcpy(m.head_one, ones.data(), w0 * 4, hipMemcpyHostToDevice));
+            HIP_TRY(hipMemcpy(m.head_zero, zeros.data(), w0 * 4, hipMemcpyHostToDevice));
         }
         HIP_TRY(hipDeviceSynchronize());
         (void)hipFree(tmp);
@@ -604,23 +609,23 @@ int zett_finalize(zett_hypernet* h) {
     // output Rescaler vectors laid out over the first head's columns
     if (c.rescale) {
         const size_t w0 = c.single_head ? c.n_in_embd : c.n_embd;
-        HIP_TRY(hipMalloc((void**)&h->head_scale, w0 * 4));
-        HIP_TRY(hipMalloc((void**)&h->head_shift, w0 * 4));
-        h->owned.push_back(h->head_scale); h->owned.push_back(h->head_shift);
-        HIP_TRY(hipMemcpy(h->head_scale, h->w["scaler.w"].f32, c.n_embd * 4, hipMemcpyDeviceToDevice));
-        HIP_TRY(hipMemcpy(h->head_shift, h->w["scaler.b"].f32, c.n_embd * 4, hipMemcpyDeviceToDevice));
+        float* scale = nullptr; float* shift = nullptr;
+        HIP_TRY(hipMalloc((void**)&scale, w0 * 4));
+        HIP_TRY(hipMalloc((void**)&shift, w0 * 4));
+        h->owned.push_back(scale); h->owned.push_back(shift);
+        HIP_TRY(hipMemcpy(scale, m.scaler.w, c.n_embd * 4, hipMemcpyDeviceToDevice));
+        HIP_TRY(hipMemcpy(shift, m.scaler.b, c.n_embd * 4, hipMemcpyDeviceToDevice));
         if (c.single_head && c.separate_out) {
-            HIP_TRY(hipMemcpy(h->head_scale + c.n_embd, h->w["out_scaler.w"].f32, c.n_embd * 4, hipMemcpyDeviceToDevice));
-            HIP_TRY(hipMemcpy(h->head_shift + c.n_embd, h->w["out_scaler.b"].f32, c.n_embd * 4, hipMemcpyDeviceToDevice));
+            HIP_TRY(hipMemcpy(scale + c.n_embd, m.out_scaler.w, c.n_embd * 4, hipMemcpyDeviceToDevice));
+            HIP_TRY(hipMemcpy(shift + c.n_embd, m.out_scaler.b, c.n_embd * 4, hipMemcpyDeviceToDevice));
         }
+        m.head_in.scale = scale; m.head_in.shift = shift;
+        m.head_out.scale = m.out_scaler.w; m.head_out.shift = m.out_scaler.b;
     }
-    // the fp32 originals of bf16 GEMM operands are no longer needed
-    if (h->precision != ZETT_PREC_F32) {
-        for (auto& kv : h->w) {
-            Tensor& t = kv.second;
-            if (is_gemm_weight(kv.first) && t.f32) { (void)hipFree(t.f32); t.f32 = nullptr; }
-        }
-    }
+    // the fp32 originals of 16-bit GEMM operands are no longer needed
+    if (h->precision != ZETT_PREC_F32)
+        for (size_t i = 0; i < ts.size(); ++i)
+            if (h->decl[i].operand && ts[i]->f32) { (void)hipFree(ts[i]->f32); ts[i]->f32 = nullptr; }
     h->finalized = true;
     return 0;
 }
@@ -980,8 +985,7 @@ struct Runner {
     hipStream_t st;
     int rc = 0;
 
-    const T* Wlo(const std::string& n) { return (const T*)h->w.at(n).lo; }
-    const float* Wf(const std::string& n) { return h->w.at(n).f32; }
+    static const T* W(const Linear& l) { return (const T*)l.w; }      // a bound GEMM operand (Model) in this forward's arithmetic type
 
     GemmEpilogue<T> epi() {
         GemmEpilogue<T> e{};
@@ -1158,20 +1162,20 @@ struct Runner {
     // fold_parts != null (output heads, LayerNorm fold): the block's LayerNorm is not launched — dense2 writes the 16-bit copy of
     // the pre-LayerNorm sum to `ol` and partial row statistics, fold_stats receives (mean, rstd), and the caller's next GEMM
     // runs on the gamma-folded weight (no fp32 sum is written: nothing else reads it)
-    void projector(const std::string& p, const T* x_lo, const float* x_f32, int rows, T* big, float* pre, float* of, T* ol,
+    void projector(const Projector& b, const T* x_lo, const float* x_f32, int rows, T* big, float* pre, float* of, T* ol,
                    float2* fold_parts = nullptr, int ld_part = 0, float* fold_stats = nullptr) {
         const zett_config& c = h->cfg;
         GemmEpilogue<T> e1 = epi();
-        e1.bias = Wf(p + "dense1.bias"); e1.act = ACT_GELU_TANH; e1.out_lo = big; e1.ld_lo = c.intermediate;
-        gemm(x_lo, c.hidden, Wlo(p + "dense1.weight"), c.hidden, rows, c.intermediate, c.hidden, e1);
+        e1.bias = b.dense1.b; e1.act = ACT_GELU_TANH; e1.out_lo = big; e1.ld_lo = c.intermediate;
+        gemm(x_lo, c.hidden, W(b.dense1), c.hidden, rows, c.intermediate, c.hidden, e1);
         GemmEpilogue<T> e2 = epi();
-        e2.bias = Wf(p + "dense2.bias"); e2.act = ACT_GELU_TANH; e2.residual = x_f32; e2.ld_res = c.hidden;
+        e2.bias = b.dense2.b; e2.act = ACT_GELU_TANH; e2.residual = x_f32; e2.ld_res = c.hidden;
         e2.ld_f32 = c.hidden;
         if (fold_parts) { e2.out_lo = ol; e2.ld_lo = c.hidden; e2.stats_part = fold_parts; e2.ld_part = ld_part; }
         else e2.out_f32 = pre;
-        gemm(big, c.intermediate, Wlo(p + "dense2.weight"), c.intermediate, rows, c.hidden, c.intermediate, e2);
+        gemm(big, c.intermediate, W(b.dense2), c.intermediate, rows, c.hidden, c.intermediate, e2);
         if (fold_parts) ln_stats(fold_parts, ld_part, rows, c.ln_eps_projector, fold_stats);
-        else layernorm(pre, rows, Wf(p + "ln.weight"), Wf(p + "ln.bias"), c.ln_eps_projector, of, ol);
+        else layernorm(pre, rows, b.ln.w, b.ln.b, c.ln_eps_projector, of, ol);
     }
 };
 
@@ -1199,10 +1203,10 @@ template <typename T>
 ForwardMode forward_mode(const zett_hypernet* h) {
     const zett_config& c = h->cfg;
     ForwardMode m{};
-    m.fold = h->ln_fold && !std::is_same<T, float>::value && h->gemm_variant == 0 && c.hidden % 128 == 0 && c.hidden >= 512 && (int)h->fold_up.size() == c.layers;
+    m.fold = h->ln_fold && !std::is_same<T, float>::value && h->gemm_variant == 0 && c.hidden % 128 == 0 && c.hidden >= 512 && h->m.layers.back().fold_up.w != nullptr;
     m.lo_stream = m.fold && c.layers >= 1 && sizeof(T) == 2 && (h->residual_lo == 2 || (h->residual_lo == 1 && std::is_same<T, f16_t>::value));
     m.table_lo = m.lo_stream && h->table_lo != 0;
-    m.fold_heads = m.fold && h->ln_fold == 1 && h->fold_head_in.w != nullptr;
+    m.fold_heads = m.fold && h->ln_fold == 1 && h->m.head_in.fold.w != nullptr;
     return m;
 }
 int needs_folded_table(const char* entry) {
@@ -1256,21 +1260,19 @@ void table_phase(Runner<T>& R, const Workspace<T>& w, const int32_t* id_list, in
                  bool table_lo, T* tbl16, float* tblst, float* tbl32) {
     zett_hypernet* h = R.h;
     const zett_config& c = h->cfg;
+    const Model& md = h->m;
     const int H = c.hidden, EIN = c.n_in_embd;
-    const float* in_w = c.rescale ? R.Wf("in_scaler.w") : nullptr;
-    const float* in_b = c.rescale ? R.Wf("in_scaler.b") : nullptr;
     for (int s0 = first; s0 < first + count && !R.rc; s0 += (int)MC) {
         const int m = (int)std::min<int64_t>(MC, first + count - s0);
-        const float* fb = R.Wf("fallback_embeddings.weight");
-        with_dtype(src_dtype, [&](auto sd) {
-            launch_gather_src<T, decltype(sd)::value>(R.st, id_list, s0, m, src, c.n_in_embd, c.original_vocab_size, fb, in_w, in_b, w.X0, h->range_word);
+        with_dtype(src_dtype, [&](auto sd) {          // (in_scaler: null without hn_rescale_embeddings)
+            launch_gather_src<T, decltype(sd)::value>(R.st, id_list, s0, m, src, c.n_in_embd, c.original_vocab_size, md.fallback, md.in_scaler.w, md.in_scaler.b, w.X0, h->range_word);
         });
         R.check("gather_src");
         GemmEpilogue<T> e0 = R.epi();
-        e0.bias = R.Wf("input_projection.0.bias"); e0.out_f32 = w.Zf; e0.ld_f32 = H; e0.out_lo = w.Zt; e0.ld_lo = H;
-        R.gemm(w.X0, EIN, R.Wlo("input_projection.0.weight"), EIN, m, H, EIN, e0);
-        if (table_lo) R.projector("input_projection.1.", w.Zt, w.Zf, m, w.BIG, w.PRE, nullptr, tbl16 + (size_t)s0 * H, w.PARTS, w.ld_parts, tblst + 2 * (size_t)s0);
-        else R.projector("input_projection.1.", w.Zt, w.Zf, m, w.BIG, w.PRE, tbl32 + (size_t)s0 * H, nullptr);
+        e0.bias = md.in_proj.b; e0.out_f32 = w.Zf; e0.ld_f32 = H; e0.out_lo = w.Zt; e0.ld_lo = H;
+        R.gemm(w.X0, EIN, R.W(md.in_proj), EIN, m, H, EIN, e0);
+        if (table_lo) R.projector(md.in_block, w.Zt, w.Zf, m, w.BIG, w.PRE, nullptr, tbl16 + (size_t)s0 * H, w.PARTS, w.ld_parts, tblst + 2 * (size_t)s0);
+        else R.projector(md.in_block, w.Zt, w.Zf, m, w.BIG, w.PRE, tbl32 + (size_t)s0 * H, nullptr);
     }
 }
 
@@ -1334,6 +1336,7 @@ struct Forward {
     // what the stages find
     Runner<T> R{h, st};
     const zett_config& c = h->cfg;
+    const Model& md = h->m;
     const int H = c.hidden, I = c.intermediate, E = c.n_embd;
     const ForwardMode mode = forward_mode<T>(h);
     zett_hypernet::PlanSlot* ps = nullptr;
@@ -1444,7 +1447,7 @@ struct Forward {
         TBL = h->table.as<float>();
         TBL16 = ext_table ? (T*)const_cast<void*>(h->ext.table) : (T*)h->table.as<float>();
         TBLST = ext_table ? const_cast<float*>(h->ext.stats) : (float*)((char*)h->table.as<float>() + (((size_t)D * H * sizeof(T) + 15) / 16) * 16);
-        lang_vec = c.embed_lang ? R.Wf("lang_embeddings.weight") + (size_t)lang_index * H : nullptr;
+        lang_vec = c.embed_lang ? md.lang + (size_t)lang_index * H : nullptr;
         return 0;
     }
 
@@ -1530,9 +1533,8 @@ struct Forward {
         R.a_rows_readable = k.w.a_rows;
         embeddings(k);
         for (int l = 0; l < c.layers && !R.rc; ++l) {
-            const std::string lp = "model.encoder.layer." + std::to_string(l) + ".";
-            attention(k, l);
-            feed_forward(k, l, lp);
+            attention(k, l, md.layers[l]);
+            feed_forward(k, l, md.layers[l]);
         }
         if (R.rc) return R.rc;
         if (int rc = readout(k)) return rc;
@@ -1547,13 +1549,12 @@ struct Forward {
     // statistics) exists per pair only.  Same values, same bits.  Taken when the call is one chunk and at least 15 % of
     // the positions repeat a pair.
     void embeddings(Chunk& k) {
-        LnEmbed emb{TBL, p.tok_slot, p.tok_pos, R.Wf("model.embeddings.token_type_embeddings.weight"),
-                    R.Wf("model.embeddings.position_embeddings.weight"), lang_vec, seq, p.tok_row, p.row_offset, k.r0, k.rows,
-                    mode.table_lo ? (const void*)TBL16 : nullptr, TBLST, R.Wf("input_projection.1.ln.weight"), R.Wf("input_projection.1.ln.bias"), cls_slot};
+        LnEmbed emb{TBL, p.tok_slot, p.tok_pos, md.token_type, md.position, lang_vec, seq, p.tok_row, p.row_offset, k.r0, k.rows,
+                    mode.table_lo ? (const void*)TBL16 : nullptr, TBLST, md.in_block.ln.w, md.in_block.ln.b, cls_slot};
         k.hs_sum = k.w.Zf;
         k.hs_stats = k.w.STb;
-        k.hs_gamma = R.Wf("model.embeddings.LayerNorm.weight");
-        k.hs_beta = R.Wf("model.embeddings.LayerNorm.bias");
+        k.hs_gamma = md.emb_ln.w;
+        k.hs_beta = md.emb_ln.b;
         k.zrows = k.m;
         k.P = pair_plan ? hoff[N + 3] : 0;
         k.pairs = pair_plan && k.rows == N && k.P > 0 && (int64_t)k.P * 100 <= (int64_t)k.m * 85;
@@ -1571,14 +1572,14 @@ struct Forward {
     }
 
     // Self-attention of layer l: fused QKV (per distinct pair in layer 0 under lever 4), attention_rows_kernel into CTX.
-    void attention(Chunk& k, int l) {
+    void attention(Chunk& k, int l, const Layer& L) {
         const Workspace<T>& w = k.w;
         const bool cls_only = h->cls_only_last && l == c.layers - 1;
         // raw: Zt holds the 16-bit copy of the pre-LayerNorm sum (LayerNorm fold: the previous layer's FFN-down wrote it
         // with the statistics in hs_stats) instead of the normalised operand — then this layer's QKV runs on the folded weight
-        const T* wqkv = k.raw ? (const T*)h->fold_qkv[l].w : (const T*)h->qkv_w[l];
-        const float* bqkv = k.raw ? h->fold_qkv[l].b : h->qkv_b[l];
-        const float* cqkv = k.raw ? h->fold_qkv[l].c : nullptr;
+        const T* wqkv = k.raw ? (const T*)L.fold_qkv.w : R.W(L.qkv);
+        const float* bqkv = k.raw ? L.fold_qkv.b : L.qkv.b;
+        const float* cqkv = k.raw ? L.fold_qkv.c : nullptr;
         // columns [col0, col0 + cols) of [q | k | v] for buffer rows [row0, M), into the same rows of `out` (leading dimension ld)
         auto qkv = [&](int col0, int cols, int row0, int M, T* out, size_t ld) {
             GemmEpilogue<T> e = R.epi();
@@ -1621,7 +1622,7 @@ struct Forward {
 
     // The rest of layer l on CTX: attention output + residual, intermediate, FFN output + residual; the LayerNorms in between are
     // launches (fp32 modes), or folded into the GEMMs around them.
-    void feed_forward(Chunk& k, int l, const std::string& lp) {
+    void feed_forward(Chunk& k, int l, const Layer& L) {
         const Workspace<T>& w = k.w;
         const bool last = l == c.layers - 1, fold = mode.fold, lo_stream = mode.lo_stream;
         const int zrows = k.zrows;
@@ -1629,7 +1630,7 @@ struct Forward {
         float* s1 = k.other(k.hs_sum);
         float* st1 = k.other_stats(k.hs_stats);
         GemmEpilogue<T> eo = R.epi();
-        eo.bias = R.Wf(lp + "attention.output.dense.bias");
+        eo.bias = L.attn_out.b;
         if (k.pairs && l == 0) eo.res_index = p.tok_pkey;       // hs_sum / hs_stats are still per pair here
         if (lo_stream) {
             // the hidden state is Zt: the embeddings' LayerNorm output itself (layer 0: used as stored), or the raw 16-bit
@@ -1643,26 +1644,26 @@ struct Forward {
             eo.out_f32 = s1; eo.ld_f32 = H;
             if (fold) { eo.out_lo = w.Zt; eo.ld_lo = H; eo.stats_part = w.PARTS; eo.ld_part = w.ld_parts; }
         }
-        R.gemm(w.CTX, H, R.Wlo(lp + "attention.output.dense.weight"), H, zrows, H, H, eo);
-        const float* g1 = R.Wf(lp + "attention.output.LayerNorm.weight");
-        const float* b1 = R.Wf(lp + "attention.output.LayerNorm.bias");
+        R.gemm(w.CTX, H, R.W(L.attn_out), H, zrows, H, H, eo);
+        const float* g1 = L.attn_ln.w;
+        const float* b1 = L.attn_ln.b;
         const T* mid = lo_stream ? w.Ct : w.Zt;                  // 16-bit operand of intermediate.dense
         GemmEpilogue<T> ei = R.epi();
         ei.act = ACT_GELU_ERF; ei.out_lo = w.BIG; ei.ld_lo = I;
         if (fold) {          // the attention-output LayerNorm is folded into intermediate.dense
             R.ln_stats(w.PARTS, w.ld_parts, zrows, c.ln_eps_encoder, st1);
-            ei.bias = h->fold_up[l].b; ei.fold_stats = st1; ei.fold_c = h->fold_up[l].c;
-            R.gemm(mid, H, (const T*)h->fold_up[l].w, H, zrows, I, H, ei);
+            ei.bias = L.fold_up.b; ei.fold_stats = st1; ei.fold_c = L.fold_up.c;
+            R.gemm(mid, H, (const T*)L.fold_up.w, H, zrows, I, H, ei);
         } else {
             R.layernorm(s1, zrows, g1, b1, c.ln_eps_encoder, nullptr, w.Zt, st1);
-            ei.bias = R.Wf(lp + "intermediate.dense.bias");
-            R.gemm(w.Zt, H, R.Wlo(lp + "intermediate.dense.weight"), H, zrows, I, H, ei);
+            ei.bias = L.up.b;
+            R.gemm(w.Zt, H, R.W(L.up), H, zrows, I, H, ei);
         }
         // FFN output: sum = dense(gelu) + LN(s1)
         float* s2 = k.other(s1);
         float* st2 = k.other_stats(st1);
         GemmEpilogue<T> ef = R.epi();
-        ef.bias = R.Wf(lp + "output.dense.bias");
+        ef.bias = L.down.b;
         if (lo_stream) {      // (also in the last layer: the readout takes the 16-bit sum)
             ef.residual_lo = w.Ct; ef.ld_res_lo = H; ef.res_stats = st1; ef.res_gamma = g1; ef.res_beta = b1;
             ef.out_lo = w.Zt; ef.ld_lo = H; ef.stats_part = w.PARTS; ef.ld_part = w.ld_parts;
@@ -1672,9 +1673,9 @@ struct Forward {
             ef.out_f32 = s2; ef.ld_f32 = H;
             if (fold && !last) { ef.out_lo = w.Zt; ef.ld_lo = H; ef.stats_part = w.PARTS; ef.ld_part = w.ld_parts; }
         }
-        R.gemm(w.BIG, I, R.Wlo(lp + "output.dense.weight"), I, zrows, H, I, ef);
-        k.hs_gamma = R.Wf(lp + "output.LayerNorm.weight");
-        k.hs_beta = R.Wf(lp + "output.LayerNorm.bias");
+        R.gemm(w.BIG, I, R.W(L.down), I, zrows, H, I, ef);
+        k.hs_gamma = L.out_ln.w;
+        k.hs_beta = L.out_ln.b;
         k.hs_sum = s2; k.hs_stats = st2;
         // (the last layer's output LayerNorm is the readout: position 0 only, whatever the layer computed)
         if (!last) {
@@ -1698,8 +1699,7 @@ struct Forward {
     //  A destination without one still takes the READOUT instantiation — only it reads the 16-bit residual stream — into a
     //  workspace vector that nothing reads)
     int readout(Chunk& k) {
-        LnReadout ro{c.predict_bias ? R.Wf("bias_projection.weight") : (const float*)nullptr,
-                     c.predict_bias ? R.Wf("bias_projection.bias") : (const float*)nullptr, out_bias ? out_bias + k.r0 : nullptr};
+        LnReadout ro{md.bias.w, md.bias.b, out_bias ? out_bias + k.r0 : nullptr};      // (bias projection: null without hn_predict_bias)
         int bias_dtype = -1;
         if (dest && dest->bias) {
             const size_t bes = dest->bias_dtype == ZETT_F32 ? 4 : 2;
@@ -1730,24 +1730,24 @@ struct Forward {
         return DestOut{dest->rows ? base : (void*)((char*)base + (size_t)r0 * (size_t)ld * es), dest->rows ? dest->rows + r0 : nullptr, ld, dest->dtype};
     }
 
-    // One output head (modeling_hypernet.py:236-258): ProjectorBlock `name`.0 on hidden[:,0], Linear `name`.1, Rescaler (scale, shift),
-    // into rows [r0, r0 + rows) of zett_forward's fp32 matrix `out` or of the destination's `dst`.  out_b / dst_b: the split single
-    // head, whose columns from n_embd on are a second matrix.  mode.fold_heads: the block's LayerNorm is folded into the Linear (f).
-    void head(const Chunk& k, const std::string& name, const zett_hypernet::Folded& f, const float* scale, const float* shift, bool split,
-              float* out, float* out_b, void* dst, int64_t ld_dst, void* dst_b, int64_t ld_dst_b) {
+    // One output head (modeling_hypernet.py:236-258): its ProjectorBlock on hidden[:,0], its Linear, its Rescaler, into rows
+    // [r0, r0 + rows) of zett_forward's fp32 matrix `out` or of the destination's `dst`.  out_b / dst_b: the split single head, whose
+    // columns from n_embd on are a second matrix.  mode.fold_heads: the block's LayerNorm is folded into the Linear (hd.fold).
+    void head(const Chunk& k, const Head& hd, bool split, float* out, float* out_b, void* dst, int64_t ld_dst, void* dst_b, int64_t ld_dst_b) {
         const Workspace<T>& w = k.w;
         const bool fold = mode.fold_heads;
-        if (fold) R.projector(name + ".0.", w.Ct, w.Cf, k.rows, w.BIG, w.PRE, nullptr, w.CTX, w.PARTS, w.ld_parts, w.STa);
-        else R.projector(name + ".0.", w.Ct, w.Cf, k.rows, w.BIG, w.PRE, nullptr, w.CTX);
+        const Folded& f = hd.fold;
+        if (fold) R.projector(hd.block, w.Ct, w.Cf, k.rows, w.BIG, w.PRE, nullptr, w.CTX, w.PARTS, w.ld_parts, w.STa);
+        else R.projector(hd.block, w.Ct, w.Cf, k.rows, w.BIG, w.PRE, nullptr, w.CTX);
         GemmEpilogue<T> e = R.epi();
-        e.bias = fold ? f.b : R.Wf(name + ".1.bias");
-        e.scale = c.rescale ? scale : (fold ? h->head_one : nullptr);
-        e.shift = c.rescale ? shift : (fold ? h->head_zero : nullptr);
+        e.bias = fold ? f.b : hd.out.b;
+        e.scale = c.rescale ? hd.scale : (fold ? md.head_one : nullptr);
+        e.shift = c.rescale ? hd.shift : (fold ? md.head_zero : nullptr);
         if (fold) { e.fold_stats = w.STa; e.fold_c = f.c; }
         e.ld_f32 = E; e.range_final = 1;
         if (split) e.split_col = E;
         const int width = split ? 2 * E : E;
-        const T* wl = fold ? (const T*)f.w : R.Wlo(name + ".1.weight");
+        const T* wl = fold ? (const T*)f.w : R.W(hd.out);
         if (dest) {
             const DestOut d = dest_out(dst, ld_dst, k.r0), d_b = split ? dest_out(dst_b, ld_dst_b, k.r0) : DestOut{};
             R.head_gemm(w.CTX, wl, k.rows, width, H, e, &d, split ? &d_b : nullptr, E);
@@ -1763,13 +1763,11 @@ struct Forward {
 
     int heads(const Chunk& k) {
         const bool split = c.single_head && c.separate_out;      // one head of 2 * n_embd columns: [in | out]
-        head(k, "output_projection", h->fold_head_in, h->head_scale, h->head_shift, split, out_in, out_out,
-             dest ? dest->in : nullptr, dest ? dest->ld_in : 0, dest ? dest->out : nullptr, dest ? dest->ld_out : 0);
+        head(k, md.head_in, split, out_in, out_out, dest ? dest->in : nullptr, dest ? dest->ld_in : 0, dest ? dest->out : nullptr, dest ? dest->ld_out : 0);
         if (!R.rc)           // out_in complete: the second head runs behind it
             if (int rc = output_ready(k, ZETT_OUT_IN, h->lane_ev[2])) return rc;
         if (c.separate_out && !c.single_head)
-            head(k, "output_projection_out", h->fold_head_out, c.rescale ? R.Wf("out_scaler.w") : nullptr, c.rescale ? R.Wf("out_scaler.b") : nullptr, false,
-                 out_out, nullptr, dest ? dest->out : nullptr, dest ? dest->ld_out : 0, nullptr, 0);
+            head(k, md.head_out, false, out_out, nullptr, dest ? dest->out : nullptr, dest ? dest->ld_out : 0, nullptr, 0);
         return R.rc;
     }
 
