@@ -1,5 +1,5 @@
 """Checker (test infrastructure only: imported by tests/ and tools/, never by zett_amd/) for zett_partition_rows
-(zett_amd/csrc/partition.hip.h): a numpy restatement of the SAME batch-synchronous assignment, round by round, so that the
+(zett_amd/csrc/partition.hip): a numpy restatement of the SAME batch-synchronous assignment, round by round, so that the
 kernel's permutation can be demanded bit for bit.  There is no reference counterpart — the reference hands its devices the
 rows of a random permutation in order (scripts/transfer.py:54-67, 90-91; zett/utils.py:26); what is pinned against the
 reference is that the row ORDER is free (rows are independent: tests/test_invariants_gpu.py) — parity of this file is

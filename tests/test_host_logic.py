@@ -524,6 +524,32 @@ def test_no_forward_source_reaches_a_training_only_header():
         assert "train_common.hip.h" in reached(name), name
 
 
+def test_retokenizer_lexical_and_partition_are_units_of_their_own():
+    """The forward's translation unit holds the forward only: an edit to the retokenizer, the lexical transfer or the row partition
+    does not recompile it, nor the other way round.  retok.hip.h is an ordinary header (no macro cuts parts of it out), and the units
+    that share its tables do not pull in the forward's row kernels."""
+    from zett_amd import build
+
+    def reached(name):
+        return {os.path.basename(p) for p in build._includes(os.path.join(build.CSRC, name))}
+
+    forward = reached("zett_hip.hip")
+    assert "rowops.hip.h" in forward and "scan.hip.h" in forward, forward          # (the walk does follow the unit's includes)
+    moved = {f for f in forward if f == "retok.hip.h" or f.startswith("lexical.") or f.startswith("partition.")}
+    assert not moved, moved
+    for name in ("text_encode.hip", "sampled_vocab.hip", "retok.hip"):
+        assert "retok.hip.h" in reached(name), name
+        assert "rowops.hip.h" not in reached(name), name
+    for name in sorted(os.listdir(build.CSRC)):
+        path = os.path.join(build.CSRC, name)
+        if os.path.isfile(path):
+            with open(path, "rb") as f:
+                assert b"ZETT_RETOK_DEVICE_FUNCTIONS_ONLY" not in f.read(), name
+    assert not os.path.exists(os.path.join(build.CSRC, "lexical.hip.h"))
+    assert not os.path.exists(os.path.join(build.CSRC, "partition.hip.h"))
+    assert {"retok.hip", "lexical.hip", "partition.hip"} <= set(build.SOURCES), build.SOURCES
+
+
 def test_training_primitives_refuse_bad_arguments_before_touching_the_device():
     """Error behaviour of the zett_op_* entry points at the boundary: arguments are validated before any launch, the return code is
     ZETT_E_INVALID and zett_last_error says why (no GPU needed: nothing is launched)."""

@@ -1,4 +1,4 @@
-// lexical.hip.h — lexical (FVT / BFVT) embedding transfer on the device (reference scripts/transfer_lexical.py:50-91).
+// lexical.hip — lexical (FVT / BFVT) embedding transfer on the device (reference scripts/transfer_lexical.py:50-91).
 //
 // Three stages:
 //
@@ -13,10 +13,13 @@
 //     divides once, converts and stores.
 //
 // THE MEAN: add the rows in `ids` order in fp32, then one IEEE (correctly rounded) division by float(n).  n = 1 is a plain copy.
-#pragma once
-
+//
+// A translation unit of its own: the kernels and the zett_lexical_* entry points (include/zett_hip.h).  The retokenizer's tables,
+// handle and retok_enqueue_call come from retok.hip.h, the typed row loads and destination stores from rowops.hip.h.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <algorithm>
 
 #include "common.hip.h"
 #include "retok.hip.h"

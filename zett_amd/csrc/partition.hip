@@ -1,4 +1,6 @@
-// partition.hip.h — id-affinity row partition for the vocabulary-sharded path (zett_partition_rows, include/zett_hip.h).
+// partition.hip — id-affinity row partition for the vocabulary-sharded path, and the scatter that puts exchanged rows back in
+// vocabulary order: the kernels and their entry points (zett_partition_workspace_bytes, zett_partition_rows, zett_scatter_rows;
+// include/zett_hip.h), a translation unit of their own.
 //
 // Rows of a surface-form matrix are independent, and the reference hands them to its devices in whatever order its random
 // permutation left them (scripts/transfer.py:54-67, 90-91; zett/utils.py:26).  Which rows a rank gets is therefore free — and it
@@ -24,10 +26,12 @@
 // distinct ids per rank and 0.953 -> 0.81 pairs per position (the pair lever's 0.85 threshold is met again), positions within
 // 1.4 % of the mean; Mistral -> NeoX 11 904 -> 7 720.  A sequential greedy on the host reaches 5 644 but costs 3 ms of host time
 // on the critical path.
-#pragma once
-
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <algorithm>
+
+#include "common.hip.h"
 
 namespace zett {
 
@@ -255,3 +259,68 @@ inline size_t partition_workspace_bytes(int64_t n_rows, int n_ids) {
 }
 
 }  // namespace zett
+
+using namespace zett;
+
+extern "C" {
+
+int zett_partition_workspace_bytes(int64_t n_rows, int32_t n_ids, int64_t* out_bytes) {
+    if (!out_bytes || n_rows < 0 || n_ids < 1) return fail(ZETT_E_INVALID, "bad argument");
+    *out_bytes = (int64_t)partition_workspace_bytes(n_rows, n_ids);
+    return 0;
+}
+
+int zett_partition_rows(const int32_t* surface_forms, int64_t n_rows, int32_t seq, int32_t pad_id, int32_t n_ids, int32_t world,
+                        const int32_t* caps, int32_t* perm_out, void* workspace, int64_t workspace_bytes, int32_t device, void* stream) {
+    if (n_rows < 0 || seq < 1 || n_ids < 1) return fail(ZETT_E_INVALID, "bad surface-form shape [%lld, %d] / id range %d", (long long)n_rows, seq, n_ids);
+    if (world < 1 || world > PART_MAX_RANKS) return fail(ZETT_E_INVALID, "zett_partition_rows handles 1..%d ranks (one node), got %d", PART_MAX_RANKS, world);
+    if (n_rows == 0) return 0;
+    if (!surface_forms || !caps || !perm_out || !workspace) return fail(ZETT_E_INVALID, "null argument");
+    if (n_rows >= (int64_t)0x7fffffff) return fail(ZETT_E_INVALID, "too many rows for one call");
+    int64_t total = 0;
+    for (int r = 0; r < world; ++r) { if (caps[r] < 0) return fail(ZETT_E_INVALID, "negative capacity"); total += caps[r]; }
+    if (total != n_rows) return fail(ZETT_E_INVALID, "the ranks' capacities sum to %lld, the matrix has %lld rows", (long long)total, (long long)n_rows);
+    if ((size_t)workspace_bytes < partition_workspace_bytes(n_rows, n_ids)) return fail(ZETT_E_INVALID, "workspace too small (zett_partition_workspace_bytes)");
+    ZETT_ON_DEVICE(device);
+    hipStream_t st = (hipStream_t)stream;
+    const size_t have_bytes = ((size_t)(n_ids + 3) / 4) * 4 + 64;
+    uint32_t* have = (uint32_t*)workspace;
+    PartCaps caps_arg = {};
+    for (int r = 0; r < world; ++r) caps_arg.v[r] = caps[r];
+    HIP_TRY(hipMemsetAsync(have, 0, have_bytes, st));
+    // the rank bytes live in LDS when the id range fits (a byte per id beside ~1 KiB of counters), else in the workspace
+    const size_t lds_have = ((size_t)(n_ids + 3) / 4) * 4;
+    if (lds_have <= 150 * 1024) {
+        static bool attr_set[64] = {};          // (per device: the attribute belongs to the device's copy of the kernel)
+        if (device >= 64 || !attr_set[device]) {
+            HIP_TRY(hipFuncSetAttribute((const void*)partition_rows_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+            if (device < 64) attr_set[device] = true;
+        }
+        hipLaunchKernelGGL(partition_rows_kernel<true>, dim3(1), dim3(PART_THREADS), lds_have, st, surface_forms, n_rows, (int)seq, (int)pad_id, (int)n_ids,
+                           (int)world, caps_arg, have, perm_out);
+    } else {
+        hipLaunchKernelGGL(partition_rows_kernel<false>, dim3(1), dim3(PART_THREADS), 0, st, surface_forms, n_rows, (int)seq, (int)pad_id, (int)n_ids,
+                           (int)world, caps_arg, have, perm_out);
+    }
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int zett_scatter_rows(const void* src, void* dst, const int64_t* order, int64_t n_rows, int64_t row_bytes, int32_t device, void* stream) {
+    if (n_rows < 0 || row_bytes < 1) return fail(ZETT_E_INVALID, "bad shape");
+    if (n_rows == 0) return 0;
+    if (!src || !dst || !order) return fail(ZETT_E_INVALID, "null argument");
+    if (row_bytes != 4 && row_bytes % 16 != 0) return fail(ZETT_E_INVALID, "row_bytes must be 4 or a multiple of 16, got %lld", (long long)row_bytes);
+    if (((uintptr_t)src | (uintptr_t)dst) % (row_bytes == 4 ? 4 : 16)) return fail(ZETT_E_INVALID, "misaligned buffer");
+    ZETT_ON_DEVICE(device);
+    hipStream_t st = (hipStream_t)stream;
+    if (row_bytes == 4)
+        hipLaunchKernelGGL(scatter_words_kernel, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, st, (const uint32_t*)src, (uint32_t*)dst, order, n_rows);
+    else
+        hipLaunchKernelGGL(scatter_rows_kernel, dim3((unsigned)std::min<int64_t>(n_rows, 65535 * 16)), dim3(256), 0, st, (const unsigned char*)src, (unsigned char*)dst,
+                           order, n_rows, row_bytes);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+}  // extern "C"

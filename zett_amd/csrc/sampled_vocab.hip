@@ -28,7 +28,6 @@
 #include <cstring>
 
 #include "../../include/zett_hip.h"
-#define ZETT_RETOK_DEVICE_FUNCTIONS_ONLY
 #include "retok.hip.h"
 #include "scan.hip.h"
 #include "score_json.hip.h"

@@ -1,4 +1,5 @@
-// scan.hip.h — the integer prefix sums of the device code, once: a wave's inclusive scan, a workgroup's exclusive scan, and the
+// scan.hip.h — the integer prefix sums of the device code, once: a wave's inclusive scan, a workgroup's exclusive scan, the
+// exclusive scan of an array (one workgroup, or chunked over many: the forward's plan, the retokenizer's block totals), and the
 // compaction of byte flags into an ascending index list built from them.  Integers only (addition is associative: however a sum
 // is bracketed, the bits are the same); the float reductions, whose order is part of their callers' results, live in
 // train_common.hip.h.  The kernels and their launcher have internal linkage: a translation unit that includes the header gets its
@@ -48,6 +49,68 @@ template <int N, typename T> __device__ __forceinline__ T block_exclusive_scan(T
     }
     if (total) *total = all;
     return below + inc - v;
+}
+
+// ---- the exclusive scan of an int32 array in global memory ------------------------------------------------------------------
+// Single-workgroup exclusive scan (n <= a few million): out[i] = sum(in[0..i)), out[n] = total.
+static __global__ __launch_bounds__(1024) void exclusive_scan_kernel(const int32_t* __restrict__ in,
+                                                              int32_t* __restrict__ out, int64_t n) {
+    __shared__ int32_t s_waves[16];
+    const int t = threadIdx.x;
+    const int64_t per = (n + 1023) / 1024;
+    const int64_t b = (int64_t)t * per, e = (b + per < n) ? b + per : n;
+    int32_t s = 0;
+    for (int64_t i = b; i < e; ++i) s += in[i];
+    int32_t total;
+    int32_t run = block_exclusive_scan<1024>(s, s_waves, &total);
+    for (int64_t i = b; i < e; ++i) { const int32_t v = in[i]; out[i] = run; run += v; }
+    if (t == 1023) out[n] = total;
+}
+
+// Multi-block exclusive scan for the plan arrays (V can be 250 k source ids, N 262 k rows: the single
+// workgroup above takes 75-400 us on those).  Chunks of SCAN_CHUNK elements:
+//   (1) scan_chunk_sums_kernel: sums[c] = sum of chunk c;
+//   (2) exclusive_scan_kernel on sums (a few hundred entries) -> offs[c], offs[chunks] = total;
+//   (3) scan_apply_kernel: out[i] = offs[c] + exclusive scan inside the chunk; out[n] = total.
+constexpr int SCAN_CHUNK = 4096;          // 256 threads x 16 elements
+
+static __global__ __launch_bounds__(256) void scan_chunk_sums_kernel(const int32_t* __restrict__ in, int64_t n, int32_t* __restrict__ sums) {
+    __shared__ int32_t s_waves[4];
+    const int64_t base = (int64_t)blockIdx.x * SCAN_CHUNK + threadIdx.x * 16;
+    int32_t s = 0;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) { const int64_t i = base + k; if (i < n) s += in[i]; }
+    int32_t total;
+    block_exclusive_scan<256>(s, s_waves, &total);
+    if (threadIdx.x == 0) sums[blockIdx.x] = total;
+}
+
+static __global__ __launch_bounds__(256) void scan_apply_kernel(const int32_t* __restrict__ in, int64_t n, const int32_t* __restrict__ offs,
+                                                         int32_t* __restrict__ out) {
+    __shared__ int32_t s_waves[4];
+    const int64_t base = (int64_t)blockIdx.x * SCAN_CHUNK + threadIdx.x * 16;
+    int32_t v[16];
+    int32_t s = 0;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) { const int64_t i = base + k; v[k] = i < n ? in[i] : 0; s += v[k]; }
+    int32_t run = offs[blockIdx.x] + block_exclusive_scan<256>(s, s_waves);
+#pragma unroll
+    for (int k = 0; k < 16; ++k) { const int64_t i = base + k; if (i < n) out[i] = run; run += v[k]; }
+    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) out[n] = offs[gridDim.x];
+}
+
+// out[0..n] = exclusive scan of in[0..n) (out[n] = total); scratch: 2*chunks + 1 ints
+inline void launch_exclusive_scan(const int32_t* in, int32_t* out, int64_t n, int32_t* scratch, hipStream_t st) {
+    if (n <= SCAN_CHUNK * 4) {        // small: one workgroup does it in one launch
+        hipLaunchKernelGGL(exclusive_scan_kernel, dim3(1), dim3(1024), 0, st, in, out, n);
+        return;
+    }
+    const int chunks = (int)((n + SCAN_CHUNK - 1) / SCAN_CHUNK);
+    int32_t* sums = scratch;
+    int32_t* offs = scratch + chunks;
+    hipLaunchKernelGGL(scan_chunk_sums_kernel, dim3(chunks), dim3(256), 0, st, in, n, sums);
+    hipLaunchKernelGGL(exclusive_scan_kernel, dim3(1), dim3(1024), 0, st, (const int32_t*)sums, offs, (int64_t)chunks);
+    hipLaunchKernelGGL(scan_apply_kernel, dim3(chunks), dim3(256), 0, st, in, n, (const int32_t*)offs, out);
 }
 
 namespace {

@@ -29,7 +29,6 @@
 #include <cstdint>
 
 #include "../../include/zett_hip.h"
-#define ZETT_RETOK_DEVICE_FUNCTIONS_ONLY
 #include "retok.hip.h"
 #include "text_words.hip.h"
 

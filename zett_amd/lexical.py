@@ -6,7 +6,7 @@
 Every target token gets the source model's embedding row of the same string where the source vocabulary has one, else the
 mean of the rows of its decomposition under the source tokenizer (``fvt`` / ``bfvt``), else a fallback row
 (scripts/transfer_lexical.py:50-91).  The reference's per-token Python loop — one ``model.tokenize`` and one ``torch.mean`` per
-token — is three stages behind the C ABI (include/zett_hip.h, zett_amd/csrc/lexical.hip.h):
+token — is three stages behind the C ABI (include/zett_hip.h, zett_amd/csrc/lexical.hip):
 
     LexicalTransfer(source_tokenizer, device)      the lexicon: bare model + the whole get_vocab() as a device hash table
     .plan(tokens, n_source_rows, fvt_mode)         one retokenization + lookup + mode filter  -> ids, count, overlap

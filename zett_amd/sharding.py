@@ -80,7 +80,7 @@ def affinity_order(surface_forms: torch.Tensor, world: int, pad_token_id: int, n
                    min_rows_per_shard: int = 4096) -> torch.Tensor:
     """Row order for the vocabulary-sharded path in which rows that share source ids land on the same rank (int64 [n_rows] on the
     device: `surface_forms.index_select(0, order)` is the matrix predict_sharded should then shard CONTIGUOUSLY, and
-    `out.index_copy_(0, order, gathered)` undoes it).  zett_partition_rows (csrc/partition.hip.h) groups the rows by rank —
+    `out.index_copy_(0, order, gathered)` undoes it).  zett_partition_rows (csrc/partition.hip) groups the rows by rank —
     capacities = the row counts plan_blocks gives each rank — and the groups are laid out block by block, rank by rank, exactly
     where plan_blocks(…, rank) will look for them.  Deterministic and communication-free: every rank computes the same order
     from the same matrix.  Why: a rank's forward runs the hoisted input projection once per DISTINCT source id of its shard and

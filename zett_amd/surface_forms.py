@@ -6,7 +6,7 @@ expresses every (byte-level) target token as at most ``maxlen`` ids of the sourc
 model's ("hn") tokenizer, pad-filled, exactly as the reference does — but the per-token
 Python loop around ``tokenizer_to_use._tokenizer.model.tokenize`` is replaced by two
 HIP kernels behind ``zett_retokenize`` (byte-table gather + scan, then BPE merge /
-Unigram Viterbi / WordPiece longest match per token; zett_amd/csrc/retok.hip.h).  This module only flattens the
+Unigram Viterbi / WordPiece longest match per token; zett_amd/csrc/retok.hip.h, retok.hip).  This module only flattens the
 hn tokenizer's bare model (vocabulary, merges / scores, flags, special tokens) into
 the arrays the C ABI takes.  There is no CPU path.
 """
