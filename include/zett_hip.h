@@ -985,6 +985,42 @@ int zett_sampled_vocab_table(zett_retok* r, uint8_t* keys, int32_t* key_lengths,
 int zett_sampled_vocab_patch_rows(zett_retok* r, const void* record, const int32_t* special_ids, const int32_t* special_hn_ids, int32_t n_special,
                                   int32_t* surface_forms, int64_t n_rows, int32_t maxlen, int32_t pad_id, void* stream);
 
+/* ---- fitting a fresh hypernetwork's Rescalers (zett_amd/training.py column_moments, rescaler_fit) -----------------------------------
+ * Hypernet.init_rescaler of the reference (zett/model/__init__.py:348-385) through Rescaler.scale_to (zett/utils.py:165-175): per
+ * column, w = t_std / (std(x) + 1e-8) and b = t_mean - mean(x * w), with the population std (ddof = 0).  The calls below are
+ * csrc/train_init.hip.  No float atomics and a partition that depends on (rows, cols) alone: the same call gives the same bits on
+ * every run and every device.
+ *
+ * The STATE of `cols` columns is cols triples of doubles, column c at state[3 c .. 3 c + 2]:
+ *     count (an integer value), mean, M2 = sum (x - mean)^2
+ * 24 bytes per column, 8-byte aligned, on the device.  Interleaved, so that the state of a column range [c0, c1) of a matrix is the
+ * contiguous slice state + 3 c0 of the matrix's state: no second pass for a range.  fp64, because a state is merged into (below)
+ * and read back by a fit whose quotient t_std / (std + 1e-8) amplifies what the state lost; it is 24 bytes per column either way. */
+#define ZETT_COL_MOMENTS_CHUNK 256     /* rows of one partial: part of the definition of the result */
+/* bytes of the workspace of a call over `rows` rows and `cols` columns: two doubles per (chunk, column), at least 16 */
+int zett_op_col_moments_workspace_bytes(int64_t rows, int32_t cols, int64_t* bytes);
+/* The moments of columns [col0, col0 + cols) of the row-major matrix x (zett_dtype dtype, leading dimension ld elements, `rows` rows),
+ * every element read exactly once and converted exactly.  With R = ZETT_COL_MOMENTS_CHUNK the rows are cut into the chunks
+ * [j R, min(rows, (j + 1) R)).  Within a chunk a column is one Welford recurrence in fp64 over ascending rows,
+ *     d = x - mean;  mean = fma(d, 1 / k, mean);  M2 = fma(d, x - mean, M2)          k = 1, 2, ... the rows so far
+ * whose (mean, M2) goes to the workspace; a second kernel then merges the chunks in ascending order with Chan's update
+ *     n = na + nb;  d = mean_b - mean_a;  r = nb / n;  mean = mean_a + d r;  M2 = M2_a + M2_b + d d (na r)
+ * starting from the empty state (accumulate = 0) or from what `state` holds (accumulate = 1: rows fed call by call).  The result
+ * does not depend on col0, ld or the alignment of x: 16-byte reads per lane where the address of a row's column and ld allow them,
+ * element reads for the columns in front of the first aligned one, behind the last whole vector, or for all of them — the recurrence
+ * of a column is the same on both paths.  It DOES depend on how a caller cuts the rows into calls.
+ * rows = 0: accumulate = 1 leaves the state untouched, accumulate = 0 writes the empty state (0, 0, 0), which the fit refuses.
+ * ZETT_E_INVALID, before any launch: a null or misaligned x / state / workspace (8 bytes), rows < 0, cols < 1, col0 < 0, col0 + cols > ld,
+ * an unknown dtype, a workspace below the queried size. */
+int zett_op_col_moments(const void* x, int32_t dtype, int64_t ld, int64_t rows, int32_t col0, int32_t cols, void* state, int32_t accumulate, void* workspace,
+                        int64_t workspace_bytes, void* stream);
+/* w[c] = t_std / (std_x + 1e-8), b[c] = t_mean - w[c] mean_x for c < cols, fp32 (computed in fp64, rounded once each), with
+ * std = sqrt(M2 / count) of a state.  The target's std and mean come from target_state (a state of the same number of columns), or,
+ * with target_state NULL, from the two scalars target_std / target_mean for every column.  (The reference takes the mean of x * w;
+ * w mean(x) is the same quantity.)  The call reads the count of both states back — it waits for `stream` once — and a state of
+ * count 0 is ZETT_E_INVALID, as are null x_state / w / b, a misaligned state and cols < 1; nothing is launched then. */
+int zett_op_rescaler_fit(const void* x_state, int32_t cols, const void* target_state, double target_std, double target_mean, float* w, float* b, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -40,6 +40,7 @@ SAMPLE_BAD_OFFSETS, SAMPLE_TABLE_FULL, SAMPLE_LIST_FULL, SAMPLE_SUM_OVERFLOW, SA
 VOCAB_NOT_A_SAMPLE, VOCAB_DUPLICATE, VOCAB_TABLE_FULL, VOCAB_OUT_FULL = 1, 2, 4, 8      # zett_vocab_status
 VOCAB_SCORES_THROUGH_JSON = 1                        # zett_vocab_flags
 SAMPLED_VOCAB_KEY_BYTES = 64                         # ZETT_SAMPLED_VOCAB_KEY_BYTES
+COL_MOMENTS_CHUNK = 256                              # ZETT_COL_MOMENTS_CHUNK
 
 ABI_SYMBOLS = (
     "zett_last_error", "zett_abi_version", "zett_create", "zett_destroy", "zett_load_weight",
@@ -78,6 +79,8 @@ ABI_SYMBOLS = (
     "zett_op_fwd_layernorm", "zett_op_fwd_embed_layernorm", "zett_op_fwd_attention", "zett_op_fwd_gather_src", "zett_op_fwd_ln_stats", "zett_op_fwd_fold_weight",
     # single rows whose query / key work the last forward skipped (HipEngine.single_rows)
     "zett_single_rows",
+    # fitting a fresh hypernetwork's Rescalers (zett_amd/training.py column_moments, rescaler_fit)
+    "zett_op_col_moments_workspace_bytes", "zett_op_col_moments", "zett_op_rescaler_fit",
 )
 
 
@@ -259,6 +262,9 @@ def load():
         lib.zett_op_fwd_gather_src.argtypes = [I32, P, I32, I32, P, I32, I32, I32, P, P, P, P, P, P]
         lib.zett_op_fwd_ln_stats.argtypes = [I32, P, I32, I32, I32, F, P, P]
         lib.zett_op_fwd_fold_weight.argtypes = [I32, P, I32, I32, P, P, P, P, P, P, P, P]
+        lib.zett_op_col_moments_workspace_bytes.argtypes = [I64, I32, C.POINTER(I64)]
+        lib.zett_op_col_moments.argtypes = [P, I32, I64, I64, I32, I32, P, I32, P, I64, P]
+        lib.zett_op_rescaler_fit.argtypes = [P, I32, P, D, D, P, P, P]
         for name in ABI_SYMBOLS:
             fn = getattr(lib, name)
             if name != "zett_last_error":

@@ -31,6 +31,9 @@ from .config import ZettHypernetConfig
 from .dims import PROJECTOR_LN_EPS, ROBERTA_LN_EPS, ROBERTA_MAX_POSITIONS, HypernetDims, weight_shapes
 
 DEFAULT_PRECISION = "f16"
+# initializer_range of the hn backbone's config (RobertaConfig's default, which every backbone this class accepts keeps): the std
+# fresh weights are drawn with, and the reference's embed_init_range, the std init_rescaler brings the source embeddings to
+EMBED_INIT_RANGE = 0.02
 _PRECISIONS = {"bf16": _lib.PREC_BF16, "bfloat16": _lib.PREC_BF16, "f32": _lib.PREC_F32,
                "fp32": _lib.PREC_F32, "float32": _lib.PREC_F32, "f16": _lib.PREC_F16, "fp16": _lib.PREC_F16,
                "float16": _lib.PREC_F16}
@@ -416,10 +419,56 @@ class ZettHypernet(PreTrainedModel):
                 elif name.endswith("LayerNorm.bias") or name.endswith("ln.bias") or leaf == "bias":
                     p.zero_()
                 else:
-                    p.normal_(mean=0.0, std=0.02)
+                    p.normal_(mean=0.0, std=EMBED_INIT_RANGE)
 
     def _init_weights(self, module) -> None:     # parameters are initialised in __init__
         return
+
+    @torch.no_grad()
+    def init_rescaler(self, target_surface_forms, source_embeddings, target_embeddings_in=None, target_embeddings_out=None, *, lang_index=0) -> None:
+        """``Hypernet.init_rescaler`` (zett/model/__init__.py:348-385, called once before the first step, train.py:689-702): fit
+        in_scaler so that the source embeddings reach the encoder with mean 0 and std EMBED_INIT_RANGE per column, then scaler /
+        out_scaler so that the predictions over the anchor tokens ``target_surface_forms`` have the per-column mean and std of the
+        target matrices.  The targets default to the halves of ``source_embeddings`` (train.py:667-672), whose moments are then
+        column ranges of the one pass in_scaler needs: the matrix is read once.  The statistics and the fit are HIP kernels
+        (zett_amd/training.py column_moments, rescaler_fit); the anchors are predicted as an eval-mode call predicts, under the same
+        precision policy and range guard.  Does nothing without hn_rescale_embeddings, as the reference."""
+        if not self.dims.rescale:
+            return
+        from . import training
+        d = self.dims
+        if not torch.is_tensor(source_embeddings) or source_embeddings.dim() != 2 or source_embeddings.shape[1] != d.n_in_embd:
+            raise ValueError(f"source_embeddings must be a [V, {d.n_in_embd}] tensor")
+        if not source_embeddings.is_cuda:
+            raise RuntimeError("zett_amd computes on MI355X only: source_embeddings must live on a cuda (ROCm) device")
+        params = dict(self.named_parameters())
+
+        def put(name, w, b):          # through the parameters themselves, so that the engines notice (refresh_weights)
+            params[name + ".w"].copy_(w)
+            params[name + ".b"].copy_(b)
+
+        source = training.column_moments(source_embeddings)
+        put("in_scaler", *training.rescaler_fit(source, target_std=EMBED_INIT_RANGE, target_mean=0.0))
+        for name in ("scaler", "out_scaler"):          # the identity of the Flax module's initialiser (zett/utils.py:149-160), not the torch port's b = 1
+            if name + ".w" in params:
+                params[name + ".w"].fill_(1.0)
+                params[name + ".b"].zero_()
+        was_training = self.training
+        self.eval()
+        try:
+            pred_in, pred_out, _ = self(target_surface_forms, source_embeddings=source_embeddings, lang_index=lang_index)
+        finally:
+            self.train(was_training)
+        target_in = source.columns(0, d.n_embd) if target_embeddings_in is None else training.column_moments(target_embeddings_in)
+        put("scaler", *training.rescaler_fit(training.column_moments(pred_in), target_in))
+        if target_embeddings_out is None and d.separate_out:
+            target_out = source.columns(d.n_embd, 2 * d.n_embd)
+        else:
+            target_out = None if target_embeddings_out is None else training.column_moments(target_embeddings_out)
+        if target_out is not None:
+            if pred_out is None:
+                raise ValueError("target_embeddings_out was given, but this hypernetwork predicts no separate output embeddings")
+            put("out_scaler", *training.rescaler_fit(training.column_moments(pred_out), target_out))
 
     # ---- engine management ---------------------------------------------------------------
     def _drop_engines(self) -> None:

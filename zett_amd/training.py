@@ -15,7 +15,9 @@ warm-up loss (train.py:914-975), the lexical loss (train.py:1074-1141) and the p
 
     bv = subsample_batch_vocabulary(input_ids, labels, special_ids, n_token_subsample, surface_forms, priors, negative_order=perm)      # collator.py:207-282: what feeds all of the above
 
-Losses, update, splice, lookup and the batch's sub-vocabulary are HIP kernels (csrc/train_step.hip, csrc/train_loss.hip, csrc/train_embed.hip, csrc/train_batch.hip); torch holds the tensors and the tape.  Nothing in this module waits for
+    init_hypernet_state(model, source_embeddings, example_surface_forms, pretrained_state=sd)      # once, before the first step: the Rescaler fit (column_moments, rescaler_fit) and the overlay of pretrained parameters (train.py:689-725)
+
+Losses, update, splice, lookup, the batch's sub-vocabulary and the column moments behind the Rescaler fit are HIP kernels (csrc/train_step.hip, csrc/train_loss.hip, csrc/train_embed.hip, csrc/train_batch.hip, csrc/train_init.hip); torch holds the tensors and the tape.  Nothing in this module waits for
 the host except ``last_step_stats()``, ``state_dict()``, ``token_embeddings(check_ids=True)`` and ``subsample_batch_vocabulary(check=True)`` (the model's forward in front of it still reads its id range back once per
 step).  Results are bit-reproducible from run to run.
 """
@@ -1037,3 +1039,132 @@ class HypernetAdamW:
         record.view(torch.int32)[3] = step
         record[1] = 1.0
         self._record = record.to(device) if device.type == "cuda" else record
+
+
+# ---- fitting a fresh hypernetwork's Rescalers (csrc/train_init.hip) ------------------------------------------------------------------
+COL_MOMENTS_CHUNK = _lib.COL_MOMENTS_CHUNK          # rows of one partial of column_moments: part of the definition of its result
+
+
+class ColumnMoments(NamedTuple):
+    """Per-column count, mean and M2 = sum (x - mean)^2 of the rows fed so far: ``state`` is the device record of
+    include/zett_hip.h, a contiguous float64 ``[C, 3]`` tensor (count, mean, M2 per column)."""
+    state: torch.Tensor
+
+    @property
+    def cols(self) -> int:
+        return self.state.shape[0]
+
+    @property
+    def count(self) -> torch.Tensor:
+        return self.state[:, 0].to(torch.float32)
+
+    def mean(self) -> torch.Tensor:
+        return self.state[:, 1].to(torch.float32)
+
+    def std(self) -> torch.Tensor:
+        """the population std (ddof = 0), as ``jnp.std``"""
+        return (self.state[:, 2].clamp_min(0.0) / self.state[:, 0]).sqrt().to(torch.float32)
+
+    def columns(self, c0: int, c1: int) -> "ColumnMoments":
+        """The moments of columns [c0, c1): a view, no pass over the matrix.  Accumulating into the view accumulates into this state."""
+        if not 0 <= c0 < c1 <= self.cols:
+            raise ValueError(f"columns [{c0}, {c1}) are outside the {self.cols} columns of the state")
+        return ColumnMoments(self.state[c0:c1])
+
+
+def _check_state(m, what):
+    s = m.state if isinstance(m, ColumnMoments) else None
+    if s is None or s.dim() != 2 or s.shape[1] != 3 or s.shape[0] < 1 or s.dtype != torch.float64 or not s.is_contiguous():
+        raise ValueError(f"{what} must be a ColumnMoments over a contiguous float64 [C, 3] state")
+    return s
+
+
+def column_moments(x, *, col0: int = 0, cols: Optional[int] = None, state: Optional[ColumnMoments] = None) -> ColumnMoments:
+    """Count, mean and M2 of columns [col0, col0 + cols) of the [R, C] fp32 / f16 / bf16 device matrix ``x`` in one read of it
+    (zett_op_col_moments: chunks of COL_MOMENTS_CHUNK rows, merged in order; the same call gives the same bits on every run).
+    ``state=``: the rows are merged into that state (Chan's update), which is returned: predicted rows can be fed chunk by chunk.
+    R = 0 is allowed; a state that holds no row is refused by rescaler_fit."""
+    if not torch.is_tensor(x) or x.dim() != 2 or x.dtype not in zett_dtypes() or not x.is_cuda or (x.shape[1] > 1 and x.stride(1) != 1):
+        raise ValueError("x must be a [R, C] fp32 / f16 / bf16 device tensor with unit column stride")
+    rows, width = x.shape
+    cols = width - col0 if cols is None else int(cols)
+    if col0 < 0 or cols < 1 or col0 + cols > width:
+        raise ValueError(f"columns [{col0}, {col0 + cols}) are outside x {tuple(x.shape)}")
+    ld = x.stride(0) if rows > 1 else max(x.stride(0), width)
+    if ld < width:
+        raise ValueError("x must be row-major: its row stride is below its width")
+    if state is not None:
+        s = _check_state(state, "state")
+        if s.shape[0] != cols or s.device != x.device:
+            raise ValueError(f"state holds {s.shape[0]} columns on {s.device}, the call is over {cols} columns on {x.device}")
+    else:
+        s = torch.empty((cols, 3), dtype=torch.float64, device=x.device)
+    lib = _lib.load()
+    need = C.c_int64(0)
+    _lib.check(lib.zett_op_col_moments_workspace_bytes(rows, cols, C.byref(need)), "col_moments_workspace_bytes")
+    with torch.cuda.device(x.device):
+        workspace = torch.empty(need.value // 8, dtype=torch.float64, device=x.device)
+        _lib.check(lib.zett_op_col_moments(ptr(x), zett_dtypes()[x.dtype], ld, rows, int(col0), cols, ptr(s), int(state is not None), ptr(workspace), need.value,
+                                           stream(x.device)), "col_moments")
+    return state if state is not None else ColumnMoments(s)
+
+
+def rescaler_fit(x_moments: ColumnMoments, target: Optional[ColumnMoments] = None, *, target_std: Optional[float] = None,
+                 target_mean: Optional[float] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``Rescaler.scale_to`` (zett/utils.py:165-175) from moments: w = t_std / (std(x) + 1e-8), b = t_mean - w * mean(x), both fp32
+    ``[1, C]``, ready to copy into a Rescaler.  The target is the moments of a matrix of the same width, or two scalars for every column
+    (``target_std=embed_init_range, target_mean=0``: in_scaler).  Waits for the stream once: a state without rows raises ValueError."""
+    xs = _check_state(x_moments, "x_moments")
+    if (target is None) == (target_std is None and target_mean is None) or (target is None and (target_std is None or target_mean is None)):
+        raise ValueError("give either target (ColumnMoments) or both target_std and target_mean")
+    ts = None
+    if target is not None:
+        ts = _check_state(target, "target")
+        if ts.shape[0] != xs.shape[0] or ts.device != xs.device:
+            raise ValueError(f"target holds {ts.shape[0]} columns on {ts.device}, x_moments {xs.shape[0]} on {xs.device}")
+    if not xs.is_cuda:
+        raise ValueError("zett_amd computes on MI355X only: the states must live on a cuda (ROCm) device")
+    out = torch.empty((2, 1, xs.shape[0]), dtype=torch.float32, device=xs.device)
+    with torch.cuda.device(xs.device):
+        _lib.check(_lib.load().zett_op_rescaler_fit(ptr(xs), xs.shape[0], ptr(ts), float(target_std or 0.0), float(target_mean or 0.0), ptr(out[0]), ptr(out[1]),
+                                                    stream(xs.device)), "rescaler_fit")
+    return out[0], out[1]
+
+
+# The modules train.py:705-718 re-initialises with reinit_projectors: the first component of a parameter's name.  The reference's list
+# has no out_scaler (and, matching on the whole component, no output_projection_out): a pretrained out_scaler survives.  Kept as it is.
+REINIT_PROJECTOR_MODULES = ("fallback_embeddings", "input_projection", "output_projection", "bias_projection", "scaler", "in_scaler")
+
+
+def split_pretrained_state(pretrained_state: Mapping[str, torch.Tensor], reinit_projectors: bool):
+    """-> (the entries to overlay, the names dropped): with reinit_projectors the keys under REINIT_PROJECTOR_MODULES are dropped."""
+    kept, dropped = {}, []
+    for name, value in pretrained_state.items():
+        if reinit_projectors and name.split(".", 1)[0] in REINIT_PROJECTOR_MODULES:
+            dropped.append(name)
+        else:
+            kept[name] = value
+    return kept, dropped
+
+
+def init_hypernet_state(model, source_embeddings, example_surface_forms, *, pretrained_state: Optional[Mapping[str, torch.Tensor]] = None,
+                        reinit_projectors: bool = False) -> List[str]:
+    """The hypernetwork's half of the reference's ``init_state`` (train.py:689-725) on a freshly constructed ``model``: fit the Rescalers
+    on ``example_surface_forms`` (ZettHypernet.init_rescaler, language 0 as the reference), then overlay ``pretrained_state`` — a state
+    dict of hypernetwork parameters, which need not be complete — without the projector modules when ``reinit_projectors`` is set.
+    Returns the names that were dropped.  A name the model does not have raises KeyError before anything is overlaid."""
+    model.init_rescaler(example_surface_forms, source_embeddings)
+    if not pretrained_state:
+        return []
+    kept, dropped = split_pretrained_state(pretrained_state, reinit_projectors)
+    params = dict(model.named_parameters())
+    unknown = [n for n in kept if n not in params]
+    if unknown:
+        raise KeyError(f"pretrained parameters the model does not have: {unknown}")
+    for name, value in kept.items():
+        if tuple(value.shape) != tuple(params[name].shape):
+            raise ValueError(f"pretrained {name} has shape {tuple(value.shape)}, the model's is {tuple(params[name].shape)}")
+    with torch.no_grad():
+        for name, value in kept.items():
+            params[name].copy_(value)          # (through the parameter: the engines notice, ZettHypernet.refresh_weights)
+    return dropped
