@@ -682,6 +682,33 @@ int zett_op_grad_norm(const void* const* grads, const int64_t* numel, int32_t n_
  * stay behind for the next backward to accumulate into.  The pointer and count arrays are HOST arrays, as above.  Any element count and any 4-byte-aligned pointer. */
 int zett_op_adamw(void* const* params, void* const* grads, void* const* exp_avg, void* const* exp_avg_sq, const int64_t* numel, const uint8_t* flags, int32_t n_tensors,
                   double lr, double b1, double b2, double eps, double weight_decay, int32_t zero_grad, const float* record, void* stream);
+/* The other branch of the reference's optimizer (train.py:631-656, use_adafactor): optax.chain(clip_by_global_norm(max_norm),
+ * multi_transform({train: optax.adafactor(lr, weight_decay_rate, weight_decay_mask), freeze: set_to_zero})) with every other argument of
+ * optax.adafactor (optax/_src/alias.py, adafactor) at its default: scale_by_factored_rms(factored, decay_rate 0.8, step offset 0,
+ * min_dim_size_to_factor 128, eps 1e-30), clip_by_block_rms(1.0), scale_by_learning_rate, scale_by_param_block_rms (eps 1e-3),
+ * add_decayed_weights, no momentum (optax/_src/factorized.py scale_by_factored_rms; clipping.py clip_by_block_rms; transform.py
+ * scale_by_param_block_rms, add_decayed_weights).  Tensor i is [rows[i], cols[i]] fp32, contiguous (1-D: rows 1); flags[i] as for
+ * zett_op_adamw.  With t = record[3], the updates applied so far:
+ *   norm, coef, skip: as zett_op_grad_norm, over every tensor of the list, frozen ones included;  g' = coef g;  q = g'^2 + 1e-30
+ *   beta = 1 - (t + 1)^-0.8 (float64 power, rounded to fp32 once)
+ *   FACTORED, not frozen and min(rows, cols) >= 128: with d0 the larger and d1 the smaller dimension by numpy.argsort(shape) (a square
+ *     matrix: d1 = 0, d0 = 1), v_row[shape[d1]] = beta v_row + (1 - beta) mean(q, axis d0), v_col[shape[d0]] = beta v_col + (1 - beta)
+ *     mean(q, axis d1), u = g' (v_row / mean(v_row))^-1/2 (along d0) v_col^-1/2 (along d1);  v[i] is not read
+ *   every other tensor that is not frozen: v[rows, cols] = beta v + (1 - beta) q, u = g' v^-1/2;  v_row[i], v_col[i] are not read
+ *   s = max(sqrt(mean p^2), 1e-3) of the parameter before the update;  p -= lr s u / max(1, sqrt(mean u^2)) + (decay ? weight_decay p : 0)
+ *     — the decay is NOT multiplied by lr: optax adds the decayed weights after the learning-rate scaling.
+ * record: 8 words as zett_op_grad_norm's, [4] beta, [5] 1 - beta.  A norm that is not finite sets skip: no parameter, no statistic and
+ * not the count is written.  zero_grad: as zett_op_adamw.  A frozen tensor needs its gradient only.  The arrays are HOST arrays; the
+ * workspace is device memory, 16-byte aligned, of at least zett_op_adafactor_workspace_floats floats, free again when the stream has
+ * run the call.  A factored tensor is worked on in tiles of ZETT_ADAFACTOR_TILE_ROWS x ZETT_ADAFACTOR_TILE_COLS, the others in chunks of
+ * ZETT_MT_CHUNK, ZETT_ADAFACTOR_GROUP tensors per launch; every sum is taken in a fixed order (csrc/train_adafactor.hip states it). */
+#define ZETT_ADAFACTOR_TILE_ROWS 64
+#define ZETT_ADAFACTOR_TILE_COLS 256
+#define ZETT_ADAFACTOR_GROUP 40
+int zett_op_adafactor_workspace_floats(const int64_t* rows, const int64_t* cols, const uint8_t* flags, int32_t n_tensors, int64_t* floats);
+int zett_op_adafactor_step(void* const* params, void* const* grads, void* const* v_row, void* const* v_col, void* const* v, const int64_t* rows, const int64_t* cols,
+                           const uint8_t* flags, int32_t n_tensors, double lr, double weight_decay, double max_norm, int32_t zero_grad, float* workspace,
+                           int64_t workspace_floats, float* record, void* stream);
 
 /* ---- the language-model loss over predicted output embeddings (zett_amd/training.py lm_head_loss) --------------------------------
  * train_step / eval_step of the reference (train.py:1039-1056, 874-912, 1226-1255):

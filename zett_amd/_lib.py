@@ -41,6 +41,7 @@ VOCAB_NOT_A_SAMPLE, VOCAB_DUPLICATE, VOCAB_TABLE_FULL, VOCAB_OUT_FULL = 1, 2, 4,
 VOCAB_SCORES_THROUGH_JSON = 1                        # zett_vocab_flags
 SAMPLED_VOCAB_KEY_BYTES = 64                         # ZETT_SAMPLED_VOCAB_KEY_BYTES
 COL_MOMENTS_CHUNK = 256                              # ZETT_COL_MOMENTS_CHUNK
+ADAFACTOR_TILE_ROWS, ADAFACTOR_TILE_COLS, ADAFACTOR_GROUP = 64, 256, 40      # ZETT_ADAFACTOR_TILE_ROWS, ZETT_ADAFACTOR_TILE_COLS, ZETT_ADAFACTOR_GROUP
 
 ABI_SYMBOLS = (
     "zett_last_error", "zett_abi_version", "zett_create", "zett_destroy", "zett_load_weight",
@@ -81,6 +82,8 @@ ABI_SYMBOLS = (
     "zett_single_rows",
     # fitting a fresh hypernetwork's Rescalers (zett_amd/training.py column_moments, rescaler_fit)
     "zett_op_col_moments_workspace_bytes", "zett_op_col_moments", "zett_op_rescaler_fit",
+    # the Adafactor branch of the optimizer (zett_amd/training.py HypernetAdafactor)
+    "zett_op_adafactor_workspace_floats", "zett_op_adafactor_step",
 )
 
 
@@ -265,6 +268,8 @@ def load():
         lib.zett_op_col_moments_workspace_bytes.argtypes = [I64, I32, C.POINTER(I64)]
         lib.zett_op_col_moments.argtypes = [P, I32, I64, I64, I32, I32, P, I32, P, I64, P]
         lib.zett_op_rescaler_fit.argtypes = [P, I32, P, D, D, P, P, P]
+        lib.zett_op_adafactor_workspace_floats.argtypes = [P, P, P, I32, C.POINTER(I64)]
+        lib.zett_op_adafactor_step.argtypes = [P, P, P, P, P, P, P, P, I32, D, D, D, I32, P, I64, P, P]
         for name in ABI_SYMBOLS:
             fn = getattr(lib, name)
             if name != "zett_last_error":
