@@ -204,6 +204,10 @@ int zett_get_stats(const zett_hypernet* h, zett_stats* out);
  * "single_rows" option below); 0 when the forward did not take the lever.  (A getter of its own: zett_stats keeps its layout.) */
 int zett_single_rows(const zett_hypernet* h, int64_t* out);
 
+/* Table rows layer 0's Q/K/V GEMM of the most recent forward ran on — one per distinct source id instead of one per (id, position)
+ * pair or packed position (the "id_qkv" option below); 0 when the forward did not take the lever.  (A getter of its own, as above.) */
+int zett_id_qkv(const zett_hypernet* h, int64_t* out);
+
 /* Per-launch record of the GEMMs of the most recent zett_forward ("time_gemm" on: durations from HIP events recorded on
  * the launch stream around every launch).  What bench.py prices its roofline on, launch class by launch class. */
 typedef struct zett_gemm_record {
@@ -297,7 +301,13 @@ int zett_workspace_bytes(const zett_hypernet* h, int64_t n_rows, int32_t seq, in
  * in the position-0 block of the hidden-state buffers and the Q|K launches of the layers behind the per-pair one skip them
  * with a pointer offset; the outputs are stored through the inverse row map; same bits.  1 = for a call that is one chunk on
  * one lane with seq + language token > 1, when floor(singles / 256) * (2 * hidden / 256) tiles fill at least one round of
- * the 256 CUs; 2 = for every such call with a single row; 0 = never.  Not taken: nothing differs, launch for launch). */
+ * the 256 CUs; 2 = for every such call with a single row; 0 = never.  Not taken: nothing differs, launch for launch),
+ * "id_qkv" (0/1/2, default 1: layer 0's fused Q/K/V as ONE LayerNorm-fold GEMM over the distinct source ids' table rows, followed
+ * by a row kernel that applies each position's additive term and the row's LayerNorm statistics — the position enters the
+ * embeddings additively and the LayerNorm's centring is linear.  Possible with the folded 16-bit table, at least two encoder layers
+ * and no language position; decided from the configuration and options alone, never from a call's counts, so every call shape of a
+ * handle computes layer 0 the same way: 1 = when possible and hidden >= 4096, 2 = whenever possible, 0 = never.  Taken, the outputs
+ * differ from "id_qkv" 0 by one 16-bit rounding placed elsewhere; zett_id_qkv reports it). */
 int zett_set_option(zett_hypernet* h, const char* key, int64_t value);
 
 /* ---- id-affinity row partition (ABI 6) ----------------------------------------------
@@ -635,6 +645,16 @@ int zett_op_fwd_ln_stats(int32_t prec, const float* parts, int32_t ld_part, int3
  * product beyond the f16 range ORs ZETT_RANGE_WEIGHT's bit (8) into *range_flag (nullable). */
 int zett_op_fwd_fold_weight(int32_t prec, const float* w, int32_t n, int32_t k, const float* gamma, const float* beta, const float* bias, void* w_fold,
                             float* c_out, float* b_out, int32_t* range_flag, void* stream);
+/* Layer 0's [q | k | v] rows from the id-level product U (lever 6, "id_qkv"; 16-bit T only):
+ *   out[row, col] = T( fma(r_x, (U[slot, col] + c_pos[pos, col]) - mu_x * c_w[col], b_q[col]) ),  (mu_x, r_x) = stats[row],
+ * in exactly this order of fp32 operations.  u is [*, n_cols] of T, c_pos float [n_pos, n_cols] (every pos < n_pos), c_w / b_q float
+ * [n_cols].  Output row j of n: tok_row NULL: slot[t0 + j], pos[t0 + j], stats and out row j (pair rows); tok_row != NULL: packed
+ * position t0 + j goes to its buffer row of the chunk (row0, rows, row_offset, cls_slot; position 0 of a vocabulary row first), where
+ * its statistics lie too.  |value| beyond the f16 range (or NaN) ORs ZETT_RANGE_ACTIVATION's bit (2) into *range_flag (nullable),
+ * with ZETT_PREC_F16 only. */
+int zett_op_fwd_pair_qkv(int32_t prec, const void* u, const int32_t* slot, const int32_t* pos, int32_t t0, int32_t n, const int32_t* tok_row,
+                         const int32_t* row_offset, int64_t row0, int32_t rows, const int32_t* cls_slot, const float* stats, const float* c_pos, int32_t n_pos,
+                         const float* c_w, const float* b_q, int32_t n_cols, void* out, int64_t ld_out, int32_t* range_flag, void* stream);
 
 /* ---- the losses and the parameter update of a training step (zett_amd/training.py) ----------------------------------------------
  * What the reference's trainer puts around the hypernetwork forward: the squared-error loss of the identity warm-up

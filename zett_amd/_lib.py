@@ -80,6 +80,8 @@ ABI_SYMBOLS = (
     "zett_op_fwd_layernorm", "zett_op_fwd_embed_layernorm", "zett_op_fwd_attention", "zett_op_fwd_gather_src", "zett_op_fwd_ln_stats", "zett_op_fwd_fold_weight",
     # single rows whose query / key work the last forward skipped (HipEngine.single_rows)
     "zett_single_rows",
+    # layer 0's Q/K/V once per source id: the row kernel on its own, and whether the last forward took the lever (HipEngine.id_qkv)
+    "zett_op_fwd_pair_qkv", "zett_id_qkv",
     # fitting a fresh hypernetwork's Rescalers (zett_amd/training.py column_moments, rescaler_fit)
     "zett_op_col_moments_workspace_bytes", "zett_op_col_moments", "zett_op_rescaler_fit",
     # the Adafactor branch of the optimizer (zett_amd/training.py HypernetAdafactor)
@@ -166,6 +168,7 @@ def load():
                                      C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.zett_get_stats.argtypes = [C.c_void_p, C.POINTER(ZettStats)]
         lib.zett_single_rows.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+        lib.zett_id_qkv.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
         lib.zett_workspace_bytes.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.POINTER(C.c_int64)]
         lib.zett_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_int64]
         lib.zett_check_range.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]
@@ -265,6 +268,7 @@ def load():
         lib.zett_op_fwd_gather_src.argtypes = [I32, P, I32, I32, P, I32, I32, I32, P, P, P, P, P, P]
         lib.zett_op_fwd_ln_stats.argtypes = [I32, P, I32, I32, I32, F, P, P]
         lib.zett_op_fwd_fold_weight.argtypes = [I32, P, I32, I32, P, P, P, P, P, P, P, P]
+        lib.zett_op_fwd_pair_qkv.argtypes = [I32, P, P, P, I32, I32, P, P, I64, I32, P, P, P, I32, P, P, I32, P, I64, P, P]
         lib.zett_op_col_moments_workspace_bytes.argtypes = [I64, I32, C.POINTER(I64)]
         lib.zett_op_col_moments.argtypes = [P, I32, I64, I64, I32, I32, P, I32, P, I64, P]
         lib.zett_op_rescaler_fit.argtypes = [P, I32, P, D, D, P, P, P]

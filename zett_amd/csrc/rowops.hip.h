@@ -905,6 +905,144 @@ __global__ __launch_bounds__(256) void fold_weight_kernel(const float* __restric
     if (threadIdx.x == 0) { c_out[n] = ct; b_out[n] = bias[n] + bt; }
 }
 
+// ---------------------------------------------------------------------------
+// Lever 6: layer 0's Q/K/V once per distinct source id.  The embeddings' sum is x = t + c_p (t the hoisted table row,
+// c_p = type0 + pos[p]) and the LayerNorm's centring is linear, so with W' = gamma (.) W of layer 0's fused qkv
+//     qkv(row)[col] = r_x * ( U[slot][col] + C[p][col] - mu_x * cW[col] ) + bq[col]
+// where U = t W'^T is ONE LayerNorm-fold consumer GEMM over the distinct table rows, and C = c_p W'^T, cW = colsum(W'),
+// bq = beta W^T + b depend on the weights only.
+//   pos_qkv_kernel   one-off, at zett_finalize: C [n_pos, N], cW [N], bq [N] in fp32 from the fp32 weight (one workgroup per
+//                    output column n, its row gamma (.) W[n] in LDS, a wave per position, lanes stride k, butterfly sum)
+//   pair_qkv_kernel  per forward: the rows of [q | k | v] from U, (mu_x, r_x) of the embeddings' LayerNorm, C, cW, bq
+// ---------------------------------------------------------------------------
+static __global__ __launch_bounds__(256) void pos_qkv_kernel(const float* __restrict__ w, int K, const float* __restrict__ gamma,
+                                                             const float* __restrict__ beta, const float* __restrict__ bias,
+                                                             const float* __restrict__ type0, const float* __restrict__ pos_emb, int n_pos, int N,
+                                                             float* __restrict__ c_pos, float* __restrict__ c_w, float* __restrict__ b_q) {
+#pragma clang fp contract(off)
+    extern __shared__ float pq_row[];          // [K] gamma[k] * W[n, k]
+    const int n = blockIdx.x;
+    const float* row = w + (size_t)n * K;
+    for (int k = threadIdx.x; k < K; k += 256) pq_row[k] = row[k] * gamma[k];
+    __syncthreads();
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if (wave == 0) {
+        float cs = 0.f, bs = 0.f;
+        for (int k = lane; k < K; k += 64) { cs += pq_row[k]; bs = fmaf(row[k], beta[k], bs); }
+        cs = wave_sum(cs); bs = wave_sum(bs);
+        if (lane == 0) { c_w[n] = cs; b_q[n] = bias[n] + bs; }
+    }
+    for (int p = wave; p < n_pos; p += 4) {
+        const float* pr = pos_emb + (size_t)p * K;
+        float s = 0.f;
+        for (int k = lane; k < K; k += 64) s = fmaf(type0[k] + pr[k], pq_row[k], s);
+        s = wave_sum(s);
+        if (lane == 0) c_pos[(size_t)p * N + n] = s;
+    }
+}
+
+// A workgroup owns a block of PQ_COLS = 2048 columns of [q | k | v] (eight per lane, 16-byte accesses on the 16-bit side) and walks
+// rows blockIdx.y, blockIdx.y + gridDim.y, ..., four at a time.  What depends on the column only is read ONCE per workgroup: cW and bq
+// of the lane's columns stay in registers, C's rows of the first PQ_LDS_POS positions in LDS (a lane reads back only what it wrote
+// itself: no barrier); a position beyond them reads its C row from memory.
+// Output row j in [0, n):
+//   tok_row == null (pair rows): slot[j], pos[j], statistics and output row j
+//   tok_row != null (buffer rows of a chunk): packed position t0 + j, written to its buffer row chunk_row(...) — position 0 first,
+//     the order the embeddings' LayerNorm wrote the statistics in
+// The arithmetic of one element, in this order, contraction off (the compiler may not fuse the first three):
+//     a = f32(U[slot][col]) + C[p][col];  b = mu_x * cW[col];  d = a - b;  v = fma(r_x, d, bq[col]);  out = to_lo(v)
+// |v| beyond the f16 range (or NaN) sets ZETT_RANGE_ACTIVATION's bit, as every 16-bit writer of an activation does.
+constexpr int PQ_COLS = 2048;
+constexpr int PQ_LDS_POS = 8;
+constexpr int PQ_UNROLL = 4;
+struct PairQkvRows {
+    const int32_t* slot;        // [t0 + n] table slot (row of U)
+    const int32_t* pos;         // [t0 + n] position (row of C)
+    int t0;
+    const int32_t* tok_row;     // [t0 + n] or null
+    const int32_t* row_offset;  // with tok_row
+    int64_t row0; int rows;     // the chunk's first vocabulary row and its number of rows
+    const int32_t* cls_slot;    // chunk_row()
+};
+template <typename T>
+__global__ __launch_bounds__(256) void pair_qkv_kernel(const T* __restrict__ U, PairQkvRows rw, int n, const float* __restrict__ stats,
+                                                       const float* __restrict__ c_pos, int n_pos_lds, const float* __restrict__ c_w,
+                                                       const float* __restrict__ b_q, int N, T* __restrict__ out, size_t ld_out,
+                                                       int32_t* __restrict__ range_flag) {
+#pragma clang fp contract(off)
+    extern __shared__ float4 pq_c[];           // [n_pos_lds][2][256]: the two float4 of lane l's columns at [p][0][l], [p][1][l]
+    const int col = blockIdx.x * PQ_COLS + (int)threadIdx.x * 8;
+    if (col >= N) return;                      // (N % 8 == 0; no barrier follows)
+    float cw[8], bq[8];
+    load8<float>(c_w + col, cw);
+    load8<float>(b_q + col, bq);
+    for (int p = 0; p < n_pos_lds; ++p) {
+        pq_c[(p * 2) * 256 + threadIdx.x] = *(const float4*)(c_pos + (size_t)p * N + col);
+        pq_c[(p * 2 + 1) * 256 + threadIdx.x] = *(const float4*)(c_pos + (size_t)p * N + col + 4);
+    }
+    bool bad = false;
+    for (int j0 = blockIdx.y; j0 < n; j0 += PQ_UNROLL * gridDim.y) {
+        int slot[PQ_UNROLL], pos[PQ_UNROLL], ro[PQ_UNROLL];
+        float2 st[PQ_UNROLL];
+        float u[PQ_UNROLL][8];
+#pragma unroll
+        for (int i = 0; i < PQ_UNROLL; ++i) {
+            const int j = j0 + i * gridDim.y;
+            if (j >= n) { ro[i] = -1; continue; }
+            const int t = rw.t0 + j;
+            slot[i] = rw.slot[t];
+            pos[i] = rw.pos[t];
+            ro[i] = j;
+            if (rw.tok_row) {
+                const int r = rw.tok_row[t];
+                ro[i] = chunk_row(j, (int)(r - rw.row0), rw.row_offset[r] == t, rw.rows, rw.cls_slot);
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < PQ_UNROLL; ++i) {
+            if (ro[i] < 0) continue;
+            st[i] = *(const float2*)(stats + 2 * (size_t)ro[i]);
+            load8<T>(U + (size_t)slot[i] * N + col, u[i]);
+        }
+#pragma unroll
+        for (int i = 0; i < PQ_UNROLL; ++i) {
+            if (ro[i] < 0) continue;
+            float c[8];
+            if (pos[i] < n_pos_lds) {
+                const float4 a = pq_c[(pos[i] * 2) * 256 + threadIdx.x], b = pq_c[(pos[i] * 2 + 1) * 256 + threadIdx.x];
+                c[0] = a.x; c[1] = a.y; c[2] = a.z; c[3] = a.w; c[4] = b.x; c[5] = b.y; c[6] = b.z; c[7] = b.w;
+            } else {
+                load8<float>(c_pos + (size_t)pos[i] * N + col, c);
+            }
+            float v[8];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const float a = u[i][e] + c[e];
+                const float b = st[i].x * cw[e];
+                const float d = a - b;
+                v[e] = __builtin_fmaf(st[i].y, d, bq[e]);
+                if (LoRange<T>::checked) bad |= out_of_range(v[e], LoRange<T>::limit);
+            }
+            store8<T>(out + (size_t)ro[i] * ld_out + col, v);
+        }
+    }
+    range_report(range_flag, bad, ZETT_RANGE_BIT_ACTIVATION);
+}
+
+// Lever 6 on a caller's table: rows id_slot[id_list[s]] of the folded table (16-bit sums, (mean, rstd)) -> rows s = 0 .. n - 1 of the
+// handle's own table; one workgroup per row, 16-byte copies (H % 8 == 0, 16-byte aligned bases)
+template <typename T>
+__global__ __launch_bounds__(256) void table_gather_kernel(const T* __restrict__ table, const float* __restrict__ stats, const int32_t* __restrict__ id_slot,
+                                                           const int32_t* __restrict__ id_list, int n, int H, T* __restrict__ out, float* __restrict__ out_stats) {
+    const int s = blockIdx.x;
+    if (s >= n) return;
+    const int g = id_slot[id_list[s]];
+    const uint4* src = (const uint4*)(table + (size_t)g * H);
+    uint4* dst = (uint4*)(out + (size_t)s * H);
+    for (int c = threadIdx.x; c < H / 8; c += 256) dst[c] = src[c];
+    if (threadIdx.x == 0) *(float2*)(out_stats + 2 * (size_t)s) = *(const float2*)(stats + 2 * (size_t)g);
+}
+
 // dtype conversion used when weights are uploaded
 template <typename T>
 __global__ void convert_f32_to_lo_kernel(const float* __restrict__ in, T* __restrict__ out, size_t n, int32_t* __restrict__ range_flag) {

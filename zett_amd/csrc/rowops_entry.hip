@@ -175,4 +175,30 @@ int zett_op_fwd_fold_weight(int32_t prec, const float* w, int32_t n, int32_t k, 
     return 0;
 }
 
+int zett_op_fwd_pair_qkv(int32_t prec, const void* u, const int32_t* slot, const int32_t* pos, int32_t t0, int32_t n, const int32_t* tok_row,
+                         const int32_t* row_offset, int64_t row0, int32_t rows, const int32_t* cls_slot, const float* stats, const float* c_pos, int32_t n_pos,
+                         const float* c_w, const float* b_q, int32_t n_cols, void* out, int64_t ld_out, int32_t* range_flag, void* stream) {
+    if (!is_prec(prec)) return fail(ZETT_E_INVALID, "zett_op_fwd_pair_qkv: unknown precision %d", prec);
+    if (prec == ZETT_PREC_F32) return fail(ZETT_E_INVALID, "zett_op_fwd_pair_qkv: the id-level Q/K/V is a 16-bit feature, not available with ZETT_PREC_F32");
+    if (!u || !slot || !pos || !stats || !c_pos || !c_w || !b_q || !out) return fail(ZETT_E_INVALID, "zett_op_fwd_pair_qkv: null argument");
+    if (tok_row && !row_offset) return fail(ZETT_E_INVALID, "zett_op_fwd_pair_qkv: tok_row without row_offset (null argument)");
+    if (cls_slot && !tok_row) return fail(ZETT_E_INVALID, "zett_op_fwd_pair_qkv: cls_slot orders buffer rows: it needs tok_row (null argument)");
+    if (n_cols < 8 || n_cols % 8) return fail(ZETT_E_INVALID, "zett_op_fwd_pair_qkv: the width must be a positive multiple of 8, got %d", n_cols);
+    if (ld_out < n_cols || ld_out % 8) return fail(ZETT_E_INVALID, "zett_op_fwd_pair_qkv: ld_out must be a multiple of 8 and at least the width, got %lld for %d", (long long)ld_out, n_cols);
+    if (!aligned(u, 16) || !aligned(out, 16) || !aligned(c_pos, 16) || !aligned(c_w, 16) || !aligned(b_q, 16) || !aligned(stats, 8))
+        return fail(ZETT_E_INVALID, "zett_op_fwd_pair_qkv needs 16-byte aligned base pointers, 8-byte aligned statistics");
+    if (n < 0 || t0 < 0 || row0 < 0 || rows < 0 || n_pos < 1 || (tok_row && rows > n))
+        return fail(ZETT_E_INVALID, "zett_op_fwd_pair_qkv: negative count or offset, no position, or more vocabulary rows than positions");
+    if (n == 0) return 0;
+    const PairQkvRows rw{slot, pos, t0, tok_row, row_offset, row0, rows, cls_slot};
+    with_precision(prec, [&](auto a) -> int {
+        using T = typename decltype(a)::type;
+        if constexpr (sizeof(T) == 2)
+            launch_pair_qkv<T>((hipStream_t)stream, (const T*)u, rw, n, stats, c_pos, n_pos, c_w, b_q, n_cols, (T*)out, (size_t)ld_out, range_flag);
+        return 0;
+    });
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 }  // extern "C"

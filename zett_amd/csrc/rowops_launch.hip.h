@@ -6,6 +6,7 @@
 #pragma once
 
 #include "../../include/zett_hip.h"
+#include "common.hip.h"
 #include "rowops.hip.h"
 
 namespace zett {
@@ -66,6 +67,35 @@ inline int launch_fold_weight(hipStream_t st, const float* w, int N, int K, cons
                               float* b_out, int32_t* range_flag) {
     hipLaunchKernelGGL(fold_weight_kernel<T>, dim3((unsigned)N), dim3(256), 0, st, w, K, gamma, beta, bias, w_fold, c_out, b_out, range_flag);
     return N;
+}
+
+// Lever 6, one-off: C [n_pos, N], cW [N], bq [N] of a weight [N, K] (pos_qkv_kernel; K floats of LDS) -> the grid
+inline int launch_pos_qkv(hipStream_t st, const float* w, int N, int K, const float* gamma, const float* beta, const float* bias, const float* type0,
+                          const float* pos_emb, int n_pos, float* c_pos, float* c_w, float* b_q) {
+    hipLaunchKernelGGL(pos_qkv_kernel, dim3((unsigned)N), dim3(256), (size_t)K * sizeof(float), st, w, K, gamma, beta, bias, type0, pos_emb, n_pos, N, c_pos, c_w,
+                       b_q);
+    return N;
+}
+
+// Lever 6 on a caller's table: its rows of the call's n distinct ids into the handle's own table (table_gather_kernel) -> n
+template <typename T>
+inline int launch_table_gather(hipStream_t st, const T* table, const float* stats, const int32_t* id_slot, const int32_t* id_list, int n, int H, T* out,
+                               float* out_stats) {
+    hipLaunchKernelGGL(table_gather_kernel<T>, dim3((unsigned)n), dim3(256), 0, st, table, stats, id_slot, id_list, n, H, out, out_stats);
+    return n;
+}
+
+// Lever 6: n rows of [q | k | v] (N = 3H columns) from U (pair_qkv_kernel).  Column blocks of PQ_COLS in x; in y as many row walkers as
+// give the chip about 2 048 workgroups (each reads its C rows once: the first min(n_pos, PQ_LDS_POS) positions in LDS) -> the y extent
+template <typename T>
+inline int launch_pair_qkv(hipStream_t st, const T* U, const PairQkvRows& rw, int n, const float* stats, const float* c_pos, int n_pos, const float* c_w,
+                           const float* b_q, int N, T* out, size_t ld_out, int32_t* range_flag) {
+    const int bx = (N + PQ_COLS - 1) / PQ_COLS;
+    const int by = grid_for((n + PQ_UNROLL - 1) / PQ_UNROLL, std::max(1, 2048 / bx));
+    const int n_lds = std::min(n_pos, PQ_LDS_POS);
+    hipLaunchKernelGGL(pair_qkv_kernel<T>, dim3(bx, by), dim3(256), (size_t)n_lds * 2 * 256 * sizeof(float4), st, U, rw, n, stats, c_pos, n_lds, c_w, b_q, N, out,
+                       ld_out, range_flag);
+    return by;
 }
 
 }  // namespace zett

@@ -73,12 +73,18 @@ struct Model {
     Head head_in, head_out;
     float* head_one = nullptr;         // [head_out_width] ones / zeros: the Rescaler of a config without hn_rescale_embeddings, for the
     float* head_zero = nullptr;        // folded head epilogue, which is compiled with it
+    // Lever 6 (id_qkv; null where it is not possible): layer 0's fused qkv folded with BOTH LayerNorms in front of it, for the GEMM on
+    // raw table rows — w = lo(gamma_t (.) gamma (.) W), c its row sums, b = (beta_t (.) gamma) W^T — and what the row kernel adds per
+    // position and column: id_cpos [max_positions, 3H] = (type0 + pos[p]) (gamma (.) W)^T, id_cw = colsum(gamma (.) W), id_bq = beta W^T + b
+    Folded id_u; float* id_cpos = nullptr; float* id_cw = nullptr; float* id_bq = nullptr;
 };
 // One weight of the declaration (declare_weights): its checkpoint name and shape, and the field of Model its device pointer goes
 // to — `operand` for a GEMM operand (converted to the arithmetic type, fp32 original freed in the 16-bit modes), else `vec`.
 struct WeightDecl { std::string name; std::vector<int64_t> shape; const void** operand; const float** vec; };
 
 }  // namespace
+
+constexpr int ID_QKV_MIN_HIDDEN = 4096;      // lever 6's default rule
 
 struct zett_hypernet {
     zett_config cfg{};
@@ -126,6 +132,7 @@ struct zett_hypernet {
         int seq = 0;
         bool pair_plan = false;           // the layout it was made with (an option changed in between: the forward plans again)
         const int32_t* ext_id_slot = nullptr;   // the id -> table-slot map its tok_slot was written with (null: the plan's own)
+        bool local_slots = false;         // lever 6 was configured: tok_slot holds the plan's own slots even with a caller's table
         bool pending = false;
     } plan[2];
     PlanSlot table_plan;              // (ABI 8) scratch plan of zett_table_plan: the distinct ids of a WHOLE vocabulary, never taken by a forward
@@ -154,6 +161,9 @@ struct zett_hypernet {
     // caller's row map; single_host is the pinned staging of the first two, single_copied the event behind their copy.
     int single_rows = 1;              // 0 off, 1 auto (one chunk on one lane, at least one full round of 256x256 tiles saved per launch), 2 whenever possible
     int64_t single_rows_last = 0;     // single rows the last forward skipped (zett_single_rows)
+    // Lever 6 (Forward::id_qkv_rows): layer 0's Q/K/V once per distinct source id
+    int id_qkv = 1;                   // 0 off, 1 when possible and hidden >= ID_QKV_MIN_HIDDEN, 2 whenever possible
+    int64_t id_qkv_last = 0;          // table rows layer 0's Q/K/V GEMM of the last forward ran on (zett_id_qkv)
     DevBuf single_map;
     void* single_host = nullptr;
     size_t single_host_bytes = 0;
@@ -310,6 +320,12 @@ static PlanLayout plan_layout(const zett_hypernet* h, const zett_hypernet::PlanS
 // worst case of a slot's int32 arena for [N, seq] surface forms: what enqueue_plan reserves and zett_workspace_bytes counts
 static size_t plan_i32_bytes(const zett_hypernet* h, int64_t N, int seq) { return plan_layout(h, nullptr, N, seq, true).words * 4; }
 
+// Lever 6 as far as the configuration and the options decide it (what is left to the forward: ForwardMode::table_lo, which a
+// caller's table needs anyway): zett_finalize built the operands (16-bit mode, >= 2 layers, no language position) and the rule holds.
+static bool id_qkv_configured(const zett_hypernet* h) {
+    return h->id_qkv && h->m.id_u.w && (h->id_qkv == 2 || h->cfg.hidden >= ID_QKV_MIN_HIDDEN);
+}
+
 // The plan of one forward into slot s, on stream st: six small kernels, three scans, and the copy of the row offsets and the
 // three counters to pinned memory; s.done is recorded behind them.
 static int enqueue_plan(zett_hypernet* h, zett_hypernet::PlanSlot& s, const int32_t* sfm, int64_t N, int seq, hipStream_t st) {
@@ -338,7 +354,8 @@ static int enqueue_plan(zett_hypernet* h, zett_hypernet::PlanSlot& s, const int3
     {
         // (ABI 8) a forward on a caller-provided table: a token's table slot is its id's slot in the GLOBAL distinct-id list
         PlanArrays pt = p;
-        if (h->ext.id_slot) pt.id_slot = const_cast<int32_t*>(h->ext.id_slot);
+        // (lever 6 gathers the call's rows of that table into the handle's own table first and keeps the plan's own slots)
+        if (h->ext.id_slot && !id_qkv_configured(h)) pt.id_slot = const_cast<int32_t*>(h->ext.id_slot);
         hipLaunchKernelGGL(plan_tokens_kernel, dim3(rb), dim3(256), 0, st, sfm, N, seq, c.pad_token_id, lam, V, pt);
     }
     if (L.pair_plan) {
@@ -350,7 +367,7 @@ static int enqueue_plan(zett_hypernet* h, zett_hypernet::PlanSlot& s, const int3
     // the row offsets and, right behind them, the three counters (distinct ids, error word, distinct pairs) to the host: one copy
     HIP_TRY(hipMemcpyAsync(s.host, p.row_offset, ((size_t)N + 1 + 3) * 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipEventRecord(s.done, st));
-    s.sfm = sfm; s.n_rows = N; s.seq = seq; s.pair_plan = L.pair_plan; s.ext_id_slot = h->ext.id_slot;
+    s.sfm = sfm; s.n_rows = N; s.seq = seq; s.pair_plan = L.pair_plan; s.ext_id_slot = h->ext.id_slot; s.local_slots = id_qkv_configured(h);
     return 0;
 }
 
@@ -573,13 +590,39 @@ int zett_finalize(zett_hypernet* h) {
         for (int l = 0; l < c.layers; ++l) {
             Layer& L = m.layers[l];
             if (int rc = fold(original(L.up), c.intermediate, H, L.attn_ln, L.up.b, L.fold_up)) return rc;
-            if (l == 0) continue;
+            // lever 6 is possible for this configuration (what the options add: forward_mode's table_lo)
+            const bool id_qkv = l == 0 && c.layers >= 2 && !c.embed_lang && H * sizeof(float) <= 64 * 1024;
+            if (l == 0 && !id_qkv) continue;
             int k = 0;
             for (const Linear* part : {&L.q, &L.k, &L.v}) {
                 HIP_TRY(hipMemcpy(tmp + (size_t)k * H * H, original(*part), H * H * 4, hipMemcpyDeviceToDevice));
                 ++k;
             }
-            if (int rc = fold(tmp, 3 * H, H, m.layers[l - 1].out_ln, L.qkv.b, L.fold_qkv)) return rc;
+            if (l > 0) {
+                if (int rc = fold(tmp, 3 * H, H, m.layers[l - 1].out_ln, L.qkv.b, L.fold_qkv)) return rc;
+                continue;
+            }
+            // gamma_t (.) gamma and beta_t (.) gamma (fp32 products, made on the host), no bias: the fold of layer 0's qkv onto raw table rows
+            std::vector<float> gt(H), bt(H), ge(H), g2(H), b2(H);
+            HIP_TRY(hipMemcpy(gt.data(), m.in_block.ln.w, H * 4, hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(bt.data(), m.in_block.ln.b, H * 4, hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(ge.data(), m.emb_ln.w, H * 4, hipMemcpyDeviceToHost));
+            for (size_t i = 0; i < H; ++i) { g2[i] = gt[i] * ge[i]; b2[i] = bt[i] * ge[i]; }
+            float* aux = nullptr;                   // [H] gamma'', [H] beta'', [3H] zero bias
+            HIP_TRY(hipMalloc((void**)&aux, 5 * H * 4));
+            HIP_TRY(hipMemset(aux, 0, 5 * H * 4));
+            HIP_TRY(hipMemcpy(aux, g2.data(), H * 4, hipMemcpyHostToDevice));
+            HIP_TRY(hipMemcpy(aux + H, b2.data(), H * 4, hipMemcpyHostToDevice));
+            const Affine ln2{aux, aux + H};
+            if (int rc = fold(tmp, 3 * H, H, ln2, aux + 2 * H, m.id_u)) return rc;
+            HIP_TRY(hipMalloc((void**)&m.id_cpos, (size_t)c.max_positions * 3 * H * 4));
+            HIP_TRY(hipMalloc((void**)&m.id_cw, 3 * H * 4));
+            HIP_TRY(hipMalloc((void**)&m.id_bq, 3 * H * 4));
+            h->owned.push_back(m.id_cpos); h->owned.push_back(m.id_cw); h->owned.push_back(m.id_bq);
+            launch_pos_qkv(0, tmp, (int)(3 * H), (int)H, m.emb_ln.w, m.emb_ln.b, L.qkv.b, m.token_type, m.position, c.max_positions, m.id_cpos, m.id_cw, m.id_bq);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipDeviceSynchronize());
+            (void)hipFree(aux);
         }
         // the output heads: Linear(LN_1e-6(.)) with the ProjectorBlock's LayerNorm folded in (not for the split single head,
         // whose two-destination epilogue is the generic one)
@@ -673,6 +716,9 @@ int zett_set_option(zett_hypernet* h, const char* key, int64_t value) {
     } else if (k == "single_rows") {
         if (value < 0 || value > 2) return fail(ZETT_E_INVALID, "single_rows must be 0 (off), 1 (auto) or 2 (whenever a call is one chunk on one lane)");
         h->single_rows = (int)value;
+    } else if (k == "id_qkv") {
+        if (value < 0 || value > 2) return fail(ZETT_E_INVALID, "id_qkv must be 0 (off), 1 (when possible and hidden >= 4096) or 2 (whenever possible)");
+        h->id_qkv = (int)value;
     } else if (k == "gemm_variant") {
         if (value != 0 && value != 1 && value != 2 && value != 3 && value != 7 && value != 8)
             return fail(ZETT_E_INVALID, "gemm_variant must be 0 (auto), 1 (128x128), 2 (256x256 register-staged), 3 (384x256), 7 (256x256 four-wave direct-to-LDS) or 8 (7 with the generic epilogue drain)");
@@ -704,6 +750,12 @@ int zett_get_stats(const zett_hypernet* h, zett_stats* out) {
 int zett_single_rows(const zett_hypernet* h, int64_t* out) {
     if (!h || !out) return fail(ZETT_E_INVALID, "null argument");
     *out = h->single_rows_last;
+    return 0;
+}
+
+int zett_id_qkv(const zett_hypernet* h, int64_t* out) {
+    if (!h || !out) return fail(ZETT_E_INVALID, "null argument");
+    *out = h->id_qkv_last;
     return 0;
 }
 
@@ -1292,6 +1344,9 @@ struct Forward {
     const int32_t* cls_slot = nullptr;    // [N] vocabulary row -> buffer row of its position 0
     const int64_t* cls_row = nullptr;     // [N] buffer row -> vocabulary row
     const int64_t* out_rows = nullptr;    // [N] buffer row -> row of the outputs: cls_row, or a destination's own map behind it
+    // lever 6 (id_qkv_rows): rows of the table in use (0: not taken) and U [Du, 3H] = their product with layer 0's folded qkv
+    int Du = 0;
+    T* U = nullptr;
 
     int run() {
         h->stats = zett_stats{};
@@ -1305,6 +1360,7 @@ struct Forward {
         // ---- table: input_projection once per distinct source id (A2-A4) -----------------
         if (!h->ext.table)
             table_phase<T>(R, lane_workspace<T>(h, 0, MCS), p.id_list, 0, D, src, src_dtype, MC, mode.table_lo, TBL16, TBLST, TBL);
+        id_qkv_rows();
         if (R.rc) return R.rc;
         if (int rc = plan_single_rows()) return rc;      // (host work, under the table phase enqueued above)
         if (int rc = run_chunks(guard)) return rc;
@@ -1319,7 +1375,7 @@ struct Forward {
     int take_plan() {
         zett_hypernet::PlanSlot& s = h->plan[h->plan_cur ^ 1];
         if (s.pending && s.sfm == sfm && s.n_rows == N && s.seq == seq && s.pair_plan == plan_layout(h, &s, N, seq).pair_plan &&
-            s.ext_id_slot == h->ext.id_slot) {
+            s.ext_id_slot == h->ext.id_slot && s.local_slots == id_qkv_configured(h)) {
             HIP_TRY(hipStreamWaitEvent(st, s.done, 0));
         } else {
             if (s.pending) HIP_TRY(hipEventSynchronize(s.done));       // a prepared plan nobody took: let it finish before the slot is reused
@@ -1383,10 +1439,56 @@ struct Forward {
         const bool ext_table = h->ext.table != nullptr;
         if (ext_table && !mode.table_lo) return needs_folded_table("zett_forward_table");
         TBL = h->table.as<float>();
-        TBL16 = ext_table ? (T*)const_cast<void*>(h->ext.table) : (T*)h->table.as<float>();
-        TBLST = ext_table ? const_cast<float*>(h->ext.stats) : (float*)((char*)h->table.as<float>() + (((size_t)D * H * sizeof(T) + 15) / 16) * 16);
+        // (lever 6: the call's rows of a caller's table are gathered into the handle's own table — gather_ext_table — and read from there)
+        const bool ext_direct = ext_table && !id_qkv_configured(h);
+        TBL16 = ext_direct ? (T*)const_cast<void*>(h->ext.table) : (T*)h->table.as<float>();
+        TBLST = ext_direct ? const_cast<float*>(h->ext.stats) : (float*)((char*)h->table.as<float>() + (((size_t)D * H * sizeof(T) + 15) / 16) * 16);
         lang_vec = c.embed_lang ? md.lang + (size_t)lang_index * H : nullptr;
+        return reserve_id_qkv(ws);
+    }
+
+    // ---- lever 6: layer 0's Q/K/V once per distinct source id ----------------------------
+    // Taken from the configuration and the options alone (so that every call shape of a handle — shards, chunks, pairs or not, a
+    // caller's table — computes layer 0 the same way, bit for bit): the folded 16-bit table, layer 0 not the position-0-only layer,
+    // no language position (zett_finalize built the operands), and hidden >= ID_QKV_MIN_HIDDEN unless the option says "whenever possible".
+    // U [Du, 3H] lives for the whole call (every chunk reads it).  X0 is written and read by the table phase only, which is over
+    // before U's GEMM is enqueued: U goes there when it fits (MCS x n_in_embd against Du x 3H elements: the whole vocabulary of the
+    // headline does, 131 840 x 8192 against 29 187 x 12 288).  No workspace buffer is large enough for EVERY call shape (a call whose
+    // positions are all distinct ids), so otherwise the table allocation
+    // grows by Du x 3H elements behind the table's own rows and statistics — outside zett_workspace_bytes, like single_map.
+    int reserve_id_qkv(const WorkspaceSizes& ws) {
+        h->id_qkv_last = 0;
+        if (!id_qkv_configured(h) || !mode.table_lo || D <= 0) return 0;      // (a caller's table without table_lo was refused above)
+        Du = D;
+        const size_t u_bytes = (size_t)Du * 3 * H * sizeof(T);
+        if (ws.x0 >= u_bytes) {
+            U = h->x0.as<T>();
+        } else {
+            const size_t own = round_up(round_up((size_t)D * H * sizeof(T), 16) + (size_t)D * 8, 256);
+            if (int rc = h->table.reserve(own + u_bytes)) return rc;
+            TBL = h->table.as<float>();
+            TBL16 = (T*)h->table.p;
+            TBLST = (float*)((char*)h->table.p + round_up((size_t)D * H * sizeof(T), 16));
+            U = (T*)((char*)h->table.p + own);
+        }
+        h->id_qkv_last = Du;
         return 0;
+    }
+
+    // U = ln_affine(table rows) (gamma (.) W_qkv)^T as a LayerNorm-fold consumer launch on the raw 16-bit table and its statistics.
+    // With a caller's table (zett_forward_table) the rows of THIS call's distinct ids are first copied out of it, in the order of the
+    // plan's own slots (id_list), into the handle's table: U then costs the call's ids, not the whole vocabulary's, and everything
+    // behind reads the copy — the same bits.
+    void id_qkv_rows() {
+        if (!Du || R.rc) return;
+        if (h->ext.table) {
+            if constexpr (sizeof(T) == 2) launch_table_gather<T>(st, (const T*)h->ext.table, h->ext.stats, h->ext.id_slot, p.id_list, D, H, TBL16, TBLST);
+            R.check("table_gather");
+        }
+        GemmEpilogue<T> e = R.epi();
+        e.bias = md.id_u.b; e.out_lo = U; e.ld_lo = 3 * H;
+        e.fold_stats = TBLST; e.fold_c = md.id_u.c;
+        R.gemm(TBL16, H, (const T*)md.id_u.w, H, Du, 3 * H, H, e);
     }
 
     // ---- lever 5: rows with a single kept position --------------------------------------
@@ -1531,7 +1633,16 @@ struct Forward {
         const T* Q = w.BIG;                               // [m | P, 3H]: q | k | v
         const T* KV = w.BIG + H;
         size_t ld_q = (size_t)3 * H, ld_kv = (size_t)3 * H;
-        if (!cls_only) {
+        if (Du && l == 0 && !cls_only) {
+            // lever 6: the rows from U (per pair, or per buffer row in the order the embeddings' LayerNorm wrote its statistics in);
+            // independent of lever 5 — every row gets its q | k | v
+            if constexpr (sizeof(T) == 2) {
+                const PairQkvRows rw = by_pair ? PairQkvRows{p.pair_tslot, p.pair_pos, 0, nullptr, nullptr, 0, 0, nullptr}
+                                               : PairQkvRows{p.tok_slot, p.tok_pos, k.tok0, p.tok_row, p.row_offset, k.r0, k.rows, cls_slot};
+                launch_pair_qkv<T>(k.st, U, rw, by_pair ? k.P : k.m, k.hs_stats, md.id_cpos, seq, md.id_cw, md.id_bq, 3 * H, w.BIG, ld_q, h->range_word);
+                R.check("pair_qkv");
+            }
+        } else if (!cls_only) {
             if (n_s && !by_pair) {          // lever 5: no query / key for the single rows, which are buffer rows [0, n_s)
                 qkv(0, 2 * H, n_s, k.m, w.BIG, ld_q);
                 qkv(2 * H, H, 0, k.m, w.BIG + 2 * H, ld_q);

@@ -152,6 +152,13 @@ class HipEngine:
         _lib.check(self.lib.zett_single_rows(self.handle, C.byref(out)), "zett_single_rows")
         return out.value
 
+    def id_qkv(self) -> int:
+        """Distinct source ids layer 0's Q/K/V GEMM of the most recent forward ran on (zett_id_qkv; the "id_qkv" option);
+        0 when the forward did not take the lever."""
+        out = C.c_int64(0)
+        _lib.check(self.lib.zett_id_qkv(self.handle, C.byref(out)), "zett_id_qkv")
+        return out.value
+
     def prepare(self, surface_forms: torch.Tensor, input_stream: Optional["torch.cuda.Stream"] = None) -> None:
         """zett_forward_prepare: enqueue the plan of the NEXT forward(surface_forms, ...) on the handle's own stream, behind the
         work `input_stream` (default: the current stream) holds now.  The forward that follows with the SAME tensor then waits
