@@ -89,7 +89,7 @@ def test_five_steps_against_the_definition():
         finally:
             torch.cuda.set_sync_debug_mode("default")
         stats = opt.last_step_stats()
-        words = opt._record.cpu()
+        words = opt.record.cpu()
         want = ac.record_ref(list(grads.values()), MAX_NORM, t)
         assert stats["step"] == t + 1 and stats["skipped"] == 0
         tc.check(torch.stack([words[0], words[1], words[4], words[5]]), torch.stack([want[k][0] for k in ("norm", "coef", "beta", "omb")]),

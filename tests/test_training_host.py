@@ -95,6 +95,86 @@ def test_load_state_dict_validates_what_the_constructor_validates():
     assert opt.lr == 0.5 and opt.last_step_stats()["step"] == 3         # a refused state dict changes nothing
 
 
+def test_adafactor_load_state_dict_validates_what_the_constructor_validates():
+    """the cases of the test above that apply to HypernetAdafactor (it has no betas or eps), and its own: the statistics a shape keeps"""
+    import torch
+    from zett_amd.training import HypernetAdafactor, adafactor_state_shapes
+    model = _tiny_model()
+    opt = HypernetAdafactor(model, lr=1e-3)
+    assert not hasattr(opt, "betas") and not hasattr(opt, "eps")
+    good = opt.state_dict()
+    assert good["step"] == 0 and good["state"] == {} and good["hyper"] == {"lr": 1e-3, "weight_decay": 0.01, "max_grad_norm": 0.1}
+    big = next(n for n, p in model.named_parameters() if p.dim() == 2 and min(p.shape) >= 128)
+    shapes = adafactor_state_shapes(dict(model.named_parameters())[big].shape)
+    assert set(shapes) == {"v_row", "v_col"}
+    state = {big: {k: torch.full(s, 0.25) for k, s in shapes.items()}, "bias_projection.bias": {"v": torch.ones(model.bias_projection.bias.shape)}}
+    opt.load_state_dict(dict(good, step=7, state=state, hyper=dict(good["hyper"], lr=0.5, max_grad_norm=None)))
+    assert opt.lr == 0.5 and opt.max_grad_norm is None and opt.last_step_stats()["step"] == 7 and set(opt.state) == set(state)
+    assert float(opt.state[big]["v_row"][0]) == 0.25 and opt.state[big]["v_row"] is not state[big]["v_row"]
+    opt.load_state_dict({"step": 3, "state": state})                    # "hyper" and "labels" are optional
+    assert opt.lr == 0.5 and opt.last_step_stats()["step"] == 3
+    with pytest.raises(KeyError, match="step"):
+        opt.load_state_dict({"state": {}})
+    with pytest.raises(ValueError, match="negative"):
+        opt.load_state_dict(dict(good, step=-1))
+    for bad in (dict(max_grad_norm=0.0), dict(max_grad_norm=-1.0)):
+        with pytest.raises(ValueError):
+            opt.load_state_dict(dict(good, hyper=dict(good["hyper"], **bad)))
+    with pytest.raises(KeyError, match="nonexistent"):
+        opt.load_state_dict(dict(good, state={"nonexistent.weight": {}}))
+    wrong_shape = {big: dict(state[big], v_row=torch.zeros(shapes["v_row"][0] + 1))}
+    full_v = {big: {"v": torch.zeros(dict(model.named_parameters())[big].shape)}}          # a factored shape keeps no full-size v
+    extra_key = {big: dict(state[big], v=torch.zeros(1))}
+    for bad in (wrong_shape, full_v, extra_key, {big: {"v_row": state[big]["v_row"]}}):
+        with pytest.raises(ValueError, match=big):
+            opt.load_state_dict(dict(good, state=bad))
+    with pytest.raises(ValueError):
+        opt.load_state_dict(dict(good, labels=dict(good["labels"], **{"scaler.w": "train"})))
+    assert opt.lr == 0.5 and opt.last_step_stats()["step"] == 3 and set(opt.state) == set(state)          # a refused state dict changes nothing
+    assert float(opt.state[big]["v_row"][0]) == 0.25 and opt.labels == good["labels"]
+
+
+def test_adamw_load_state_dict_takes_exactly_the_two_moments():
+    """what the shared load_state_dict changed for HypernetAdamW: an entry's keys must be exactly exp_avg and exp_avg_sq of the
+    parameter's shape.  A missing moment is a ValueError naming the parameter (it was a bare KeyError), an extra key is refused (it
+    was dropped without a word); betas / eps and max_grad_norm are validated one after the other, each with its own message."""
+    import torch
+    from zett_amd.training import HypernetAdamW
+    model = _tiny_model()
+    opt = HypernetAdamW(model, lr=1e-3)
+    good = opt.state_dict()
+    name, p = next(iter(model.named_parameters()))
+    moments = {"exp_avg": torch.full(p.shape, 0.5), "exp_avg_sq": torch.full(p.shape, 0.25)}
+    opt.load_state_dict(dict(good, step=2, state={name: moments}))
+    assert set(opt.state[name]) == {"exp_avg", "exp_avg_sq"} and float(opt.state[name]["exp_avg"].flatten()[0]) == 0.5
+    assert opt.state[name]["exp_avg"] is not moments["exp_avg"]
+    for bad in ({"exp_avg": moments["exp_avg"]}, dict(moments, step=torch.zeros(())), dict(moments, exp_avg_sq=torch.zeros(p.numel() + 1))):
+        with pytest.raises(ValueError, match=name):
+            opt.load_state_dict(dict(good, step=9, state={name: bad}))
+    with pytest.raises(ValueError, match="betas"):
+        opt.load_state_dict(dict(good, step=9, hyper=dict(good["hyper"], betas=(1.0, 0.5))))
+    with pytest.raises(ValueError, match="max_grad_norm"):
+        opt.load_state_dict(dict(good, step=9, hyper=dict(good["hyper"], max_grad_norm=0.0)))
+    assert opt.last_step_stats()["step"] == 2 and float(opt.state[name]["exp_avg_sq"].flatten()[0]) == 0.25          # refused: nothing changed
+
+
+@pytest.mark.parametrize("which", ["HypernetAdamW", "HypernetAdafactor"])
+def test_a_parameter_without_a_label_is_refused(which):
+    """a parameter added to the model after the optimizer was built has no label: ValueError before anything is launched or allocated,
+    from both classes (AdamW used to decay it silently)"""
+    import torch
+    from zett_amd import training
+    model = _tiny_model()
+    opt = getattr(training, which)(model, lr=1e-3)
+    model.late = torch.nn.Parameter(torch.zeros(4))
+    assert "late" not in opt.labels and "late" in dict(model.named_parameters())
+    for p in model.parameters():
+        p.grad = torch.zeros_like(p)
+    with pytest.raises(ValueError, match="late has no label"):
+        opt.step()
+    assert opt.state == {} and opt.record is None and opt.last_step_stats()["step"] == 0
+
+
 def test_header_and_binding_agree_on_the_training_step_symbols():
     from zett_amd import _lib
     header = open(os.path.join(REPO, "include", "zett_hip.h")).read()
@@ -113,3 +193,5 @@ def test_the_training_step_kernels_stay_outside_the_measured_forward():
     """csrc/train_step.hip is training-only: profiles/pmc_traffic.json stays tied to the forward's sources."""
     from zett_amd import build
     assert "train_step.hip" in build.SOURCES and "train_step.hip" in build.TRAINING_ONLY
+    assert "train_dist.hip" in build.SOURCES and "train_dist.hip" in build.TRAINING_ONLY
+    assert "train_optim.hip.h" in build.HEADERS and "train_optim.hip.h" in build.TRAINING_ONLY

@@ -5,6 +5,10 @@ as it was (profiles/autograd_refactor.md).
 
     python tools/train_digest.py [--trace] > table.tsv        # case <tab> item <tab> sha256 of the item's bits
     python tools/train_digest.py --peak packed bf16           # torch.cuda.max_memory_allocated() of one forward + backward
+    python tools/train_digest.py --optimizer > table.tsv      # the optimizer step instead (zett_amd/optim.py): see optimizer_digest
+
+The script imports the tree it lies in: to digest another tree (a parent commit with its own build), copy this file into that tree's
+tools/ and run it there.  --optimizer needs only names that zett_amd.training has exported since Adafactor was added.
 
 Cases: the seven flag sets of tests/test_autograd_gpu.py x {packed, dense} x {f32, bf16, f16} x {deterministic, default} on two
 batches of synth.workload("tiny") — 300 rows of L = 7 with fallback ids of 100 and 65 uses and one special row (the case of
@@ -81,11 +85,81 @@ def step(cfg, w, src, ids, packed, precision, deterministic):
     return items
 
 
+class Bag(torch.nn.Module):
+    """parameters t000, t001, ... and the refresh_weights() an optimizer asks of its model"""
+
+    def __init__(self, tensors):
+        super().__init__()
+        for i, t in enumerate(tensors):
+            self.register_parameter(f"t{i:03d}", torch.nn.Parameter(t))
+
+    def refresh_weights(self):
+        pass
+
+
+def optimizer_digest():
+    """Both optimizers over three steps on the tensor lists of the direct GPU tests (tests/loss_step_check.mt_list, tests/adafactor_check
+    mixed_list + single_cases: chunk and tile edges, pointers 4 bytes off a 16-byte boundary, frozen and empty tensors, more tensors than
+    either unit's launch group), with zero_grad on and off.  Step 0 is clipped, step 1 has an infinite gradient and is skipped, step 2 is
+    below max_grad_norm.  One line per parameter, state tensor and gradient after every step, and one for the record's eight words."""
+    from tests import adafactor_check as ac
+    from tests import loss_step_check as lc
+    from zett_amd.training import HypernetAdafactor, HypernetAdamW, adafactor_state_shapes
+    label = {lc.DECAY: "decay", 0: "no_decay", lc.FROZEN: "frozen"}
+    entries = [((e["n"],), e["flags"], e["off"][:2], e["off"][2:]) for e in lc.mt_list()]
+    entries += [(e["shape"], e["flags"], e["off"][:2], e["off"][2:] * 2) for e in ac.mixed_list() + ac.single_cases()]
+    sha = lambda t: hashlib.sha256(t.contiguous().cpu().numpy().tobytes()).hexdigest()          # noqa: E731
+
+    def at(shape, off, gen=None, scale=1.0):
+        """a contiguous device tensor of `shape` that starts `off` elements into its allocation"""
+        n = 1
+        for s in shape:
+            n *= s
+        buf = torch.zeros(n + off, device=DEV)
+        if gen is not None:
+            buf[off:] = (torch.randn(n, generator=gen) * scale).to(DEV)
+        return buf[off:].view(shape)
+
+    gen = torch.Generator().manual_seed(77)
+    grads = [[torch.randn(shape, generator=gen) * scale for shape, *_ in entries] for scale in (0.1, 0.1, 1e-5)]
+    poisoned = next(i for i, (shape, flags, *_) in enumerate(entries) if flags != lc.FROZEN and min(shape) >= 128)
+    grads[1][poisoned].view(-1)[5] = float("inf")
+    max_norm = 0.01 * float(torch.sqrt(sum((g.double() ** 2).sum() for g in grads[0])))
+    for name, cls in (("adamw", HypernetAdamW), ("adafactor", HypernetAdafactor)):
+        for zero_grad in (True, False):
+            gen = torch.Generator().manual_seed(78)
+            model = Bag([at(shape, off[0], gen, 0.5) for shape, _, off, _ in entries])
+            names = [n for n, _ in model.named_parameters()]
+            opt = cls(model, lr=1e-2, weight_decay=0.01, max_grad_norm=max_norm, labels={n: label[e[1]] for n, e in zip(names, entries)})
+            for (n, p), (shape, flags, off, state_off) in zip(model.named_parameters(), entries):
+                p.grad = at(shape, off[1])
+                if flags != lc.FROZEN:          # the states start where the tests' do: the optimizer takes what is there
+                    shapes = adafactor_state_shapes(shape) if cls is HypernetAdafactor else {"exp_avg": shape, "exp_avg_sq": shape}
+                    opt.state[n] = {k: at(s, o) for (k, s), o in zip(shapes.items(), state_off)}
+            for step in range(3):
+                for p, g in zip(model.parameters(), grads[step]):
+                    p.grad.copy_(g)
+                opt.step(zero_grad=zero_grad)
+                torch.cuda.synchronize()
+                case = f"{name}/{'zero_grad' if zero_grad else 'keep_grad'}/step{step}"
+                words = (opt.record if hasattr(opt, "record") else opt._record).cpu()          # (a tree from before the accessor: to compare it with this one)
+                stats = opt.last_step_stats()
+                assert (stats["skipped"], stats["clip_coef"] < 1.0, stats["step"]) == ((0, True, 1), (1, True, 1), (0, False, 2))[step], (case, stats)
+                print(f"{case}\trecord\t{sha(words)}\t{words.view(torch.int32).tolist()}")
+                for n, p in model.named_parameters():
+                    print(f"{case}\t{n}\t{sha(p.detach())}\n{case}\t{n}.grad\t{sha(p.grad)}")
+                    for k, t in sorted(opt.state.get(n, {}).items()):
+                        print(f"{case}\t{n}.{k}\t{sha(t)}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--trace", action="store_true")
+    ap.add_argument("--optimizer", action="store_true")
     ap.add_argument("--peak", nargs=2, metavar=("SCHEDULE", "PRECISION"))
     args = ap.parse_args()
+    if args.optimizer:
+        return optimizer_digest()
     if args.peak:
         cfg, w, src, batches = case({})
         torch.cuda.reset_peak_memory_stats()

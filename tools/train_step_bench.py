@@ -5,7 +5,7 @@ parameter), each timed two ways in one process, with HIP events, on the same ten
 
   torch : the glue a user writes without this module — index_select of the target rows, torch element-wise loss, autograd,
           the optax-style clip in torch (_foreach_norm, a device-side coefficient, _foreach_mul_) and torch.optim.AdamW(fused=True)
-  hip   : zett_amd.training.identity_loss / HypernetAdamW.step (csrc/train_step.hip)
+  hip   : zett_amd.training.identity_loss (csrc/train_dist.hip) / zett_amd.optim.HypernetAdamW.step (csrc/train_step.hip)
 
     python tools/train_step_bench.py [--workload mistral_gpt2_32k] [--rows N] [--steps K] [--warmup W]
 
@@ -112,17 +112,17 @@ def main():
         ref.step()
 
     opt = HypernetAdamW(model, lr=lr, betas=betas, eps=eps, weight_decay=wd, max_grad_norm=max_norm)
-    # the two launches of step() are timed one by one as well: its private halves, on tensor lists collected once (the pointers do
-    # not change here).  The bias corrections move with the device step count, the work per element does not.
-    lists = opt._collect()
+    # the two launches of step() are timed one by one as well (HypernetAdamW.launch_norm, launch_adamw), on tensor lists collected
+    # once (the pointers do not change here).  The bias corrections move with the device step count, the work per element does not.
+    lists = opt.collect()
     opt_ms = {"torch clip": timed(torch_clip, args.steps, args.warmup), "torch adamw(fused)": timed(ref.step, args.steps, args.warmup),
               "torch clip + adamw": timed(torch_step, args.steps, args.warmup),
-              "hip norm": timed(lambda: opt._launch_norm(lists), args.steps, args.warmup),
-              "hip adamw": timed(lambda: opt._launch_adamw(lists), args.steps, args.warmup),
+              "hip norm": timed(lambda: opt.launch_norm(lists), args.steps, args.warmup),
+              "hip adamw": timed(lambda: opt.launch_adamw(lists), args.steps, args.warmup),
               "hip step": timed(opt.step, args.steps, args.warmup)}
     stats = opt.last_step_stats()
     stats.pop("step")          # (every timed call of the norm entry point advanced the device step count: not a count of real steps)
-    opt_ms["hip adamw + zero_grad"] = timed(lambda: opt._launch_adamw(lists, zero_grad=True), args.steps, args.warmup)      # (last: it clears the gradients)
+    opt_ms["hip adamw + zero_grad"] = timed(lambda: opt.launch_adamw(lists, zero_grad=True), args.steps, args.warmup)      # (last: it clears the gradients)
     tbs = {"hip adamw": 28.0 * n_updated / (opt_ms["hip adamw"] * 1e-3) / 1e12, "hip adamw + zero_grad": 32.0 * n_updated / (opt_ms["hip adamw + zero_grad"] * 1e-3) / 1e12,
            "hip norm": 4.0 * n_params / (opt_ms["hip norm"] * 1e-3) / 1e12, "torch adamw(fused)": 28.0 * n_updated / (opt_ms["torch adamw(fused)"] * 1e-3) / 1e12}
 

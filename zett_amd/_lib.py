@@ -57,7 +57,7 @@ ABI_SYMBOLS = (
     "zett_op_layernorm_fwd_f32", "zett_op_layernorm_bwd_f32", "zett_op_gelu_fwd_f32", "zett_op_gelu_bwd_f32",
     "zett_op_attention_fwd_f32", "zett_op_attention_bwd_f32", "zett_op_gather_fwd_f32", "zett_op_gather_bwd_f32",
     "zett_op_gather_rows_f32", "zett_op_scatter_add_rows_f32", "zett_op_gemm_lo", "zett_op_convert_lo", "zett_op_transpose_lo", "zett_op_grad_operands_lo", "zett_op_transpose_lo16", "zett_op_gelu_fwd_lo",
-    # losses and the parameter update of a training step (zett_amd/training.py)
+    # losses (zett_amd/training.py) and the parameter update (zett_amd/optim.py) of a training step
     "zett_op_single_token_mask", "zett_op_embed_dist_rows", "zett_op_embed_dist_finalize", "zett_op_embed_dist_grad", "zett_op_grad_norm", "zett_op_adamw",
     # the language-model loss over predicted output embeddings (zett_amd/training.py lm_head_loss)
     "zett_op_ce_addend", "zett_op_ce_rows", "zett_op_ce_finalize", "zett_op_ce_colsum", "zett_op_ce_scale", "zett_op_ce_cast",
@@ -84,7 +84,7 @@ ABI_SYMBOLS = (
     "zett_op_fwd_pair_qkv", "zett_id_qkv",
     # fitting a fresh hypernetwork's Rescalers (zett_amd/training.py column_moments, rescaler_fit)
     "zett_op_col_moments_workspace_bytes", "zett_op_col_moments", "zett_op_rescaler_fit",
-    # the Adafactor branch of the optimizer (zett_amd/training.py HypernetAdafactor)
+    # the Adafactor branch of the optimizer (zett_amd/optim.py HypernetAdafactor)
     "zett_op_adafactor_workspace_floats", "zett_op_adafactor_step",
 )
 

@@ -8,35 +8,31 @@
 //     (tr, tc) is item tr * nTC + tc of the tensor.  Wave w of the workgroup owns rows 16 w .. 16 w + 15 of the tile, lane l owns columns
 //     4 l .. 4 l + 3: one 16-byte access per lane and row where the pointer and C allow it, four 4-byte accesses of the same elements
 //     otherwise — both forms add in the same order, so alignment never changes a bit of the result;
-//   * every other tensor (1-D, a matrix with a dimension below 128, a frozen one) is flat: chunks of ZETT_MT_CHUNK elements, read exactly
-//     as train_step.hip's sumsq_kernel / adamw_kernel read theirs.
+//   * every other tensor (1-D, a matrix with a dimension below 128, a frozen one) is flat: chunks of ZETT_MT_CHUNK elements, summed
+//     and cleared by the helpers train_step.hip's sumsq_kernel / adamw_kernel use (train_optim.hip.h).
 //
 // Sums (fp32 unless said otherwise, no atomics; depth = the longest chain of additions behind one result):
 //   tile row sum of g^2      (x0 + x1) + (x2 + x3) per lane, wave_sum                                          depth 8, 256 terms
 //   tile column sum of g^2   per lane its wave's 16 rows top to bottom, the four waves (w0 + w1) + (w2 + w3)    depth 18, 64 terms
 //   tile sum of g^2          block_sum_pairwise of the 256 column sums                                         depth 26
 //   tile sum of p^2, of u^2  per lane four column sums over 16 rows, (a0 + a1) + (a2 + a3), block_sum_pairwise  depth 26
-//   chunk sums               sumsq_kernel's order                                                              depth 74 (16-byte aligned) / 266
+//   chunk sums               chunk_sum's order                                                                 depth 74 (16-byte aligned) / 266
 //   segment sum of v_row     block_sum_pairwise of 256 consecutive new v_row values                            depth 8
 //   every second stage       (tile partials of a row or column, items of a tensor, segments of v_row, all items of the list) in
 //                            float64 in index order (a thread's strided terms, then block_sum_f64's tree), rounded to fp32 once.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cmath>
 #include <cstdint>
 #include <vector>
 
 #include "../../include/zett_hip.h"
-#include "common.hip.h"
-#include "train_common.hip.h"
+#include "train_optim.hip.h"      // (and through it train_common.hip.h, common.hip.h)
 
 using namespace zett;
 
 namespace {
 
-constexpr int kMaxGrid = 2048;                  // 256 CUs x 8 workgroups
-constexpr int64_t kChunk = ZETT_MT_CHUNK;
 constexpr int kGroup = ZETT_ADAFACTOR_GROUP;    // tensors per launch: the lists travel as kernel arguments (< 4 KB)
 constexpr int kTileRows = ZETT_ADAFACTOR_TILE_ROWS, kTileCols = ZETT_ADAFACTOR_TILE_COLS, kSeg = 256;
 constexpr int kMinFactor = 128;                 // optax.adafactor min_dim_size_to_factor
@@ -74,12 +70,6 @@ struct AfHyper {
 };
 static_assert(sizeof(AfList) + sizeof(AfWs) + sizeof(AfHyper) + 16 < 4096, "tensor lists must fit the kernel-argument limit");
 
-__device__ __forceinline__ int tensor_of_item(const AfList& a, int item) {
-    int t = 0;
-    while (t + 1 < a.n_tensors && a.item_start[t + 1] <= item) ++t;
-    return t;
-}
-
 __device__ __forceinline__ int tiles_across(int cols) { return (cols + kTileCols - 1) / kTileCols; }
 
 // elements c .. c + 3 of a row of `cols` elements, zeros past its end
@@ -106,21 +96,6 @@ __device__ __forceinline__ bool tile_vec(const float* a, const float* b, int col
     return ((((uintptr_t)a | (uintptr_t)b) & 15) == 0) && (cols & 3) == 0;
 }
 
-// the sum of a chunk's f(i) over the workgroup in sumsq_kernel's order: four sums per thread over 16-byte accesses where `vec`, one otherwise
-template <typename F4, typename F1> __device__ __forceinline__ float chunk_sum(int len, bool vec, float* red, F4 four, F1 one) {
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-    int tail = 0;
-    if (vec) {
-        tail = len & ~3;
-        for (int i = threadIdx.x * 4; i < tail; i += 1024) {
-            const float4 x = four(i);
-            s0 += x.x; s1 += x.y; s2 += x.z; s3 += x.w;
-        }
-    }
-    for (int i = tail + threadIdx.x; i < len; i += 256) s0 += one(i);
-    return block_sum_pairwise((s0 + s1) + (s2 + s3), red);
-}
-
 // ---- pass 1: one read of g and p ---------------------------------------------------------------------------------------------------
 // gpart[item] = sum g^2, ppart[item] = sum p^2 (0 for a frozen tensor: its p is not read); a tile also leaves its 64 row sums and 256
 // column sums of g^2 in rowpart [tc, r] and colpart [tr, c].
@@ -130,7 +105,7 @@ __global__ __launch_bounds__(256) void af_pass1_kernel(const AfList a, const AfW
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int total = a.item_start[a.n_tensors];
     for (int item = blockIdx.x; item < total; item += gridDim.x) {
-        const int t = tensor_of_item(a, item);
+        const int t = tensor_of(a.item_start, a.n_tensors, item);
         const int local = item - a.item_start[t];
         const int flags = a.flags[t];
         float sg, sp = 0.f;
@@ -165,16 +140,8 @@ __global__ __launch_bounds__(256) void af_pass1_kernel(const AfList a, const AfW
         } else {
             const int64_t off = (int64_t)local * kChunk;
             const int len = (int)std::min<int64_t>(kChunk, a.n[t] - off);
-            const float* g = a.g[t] + off;
-            sg = chunk_sum(len, ((uintptr_t)g & 15) == 0, red,
-                           [&](int i) { const float4 x = *(const float4*)(g + i); return make_float4(x.x * x.x, x.y * x.y, x.z * x.z, x.w * x.w); },
-                           [&](int i) { return g[i] * g[i]; });
-            if (!(flags & ZETT_ADAMW_FROZEN)) {
-                const float* p = a.p[t] + off;
-                sp = chunk_sum(len, ((uintptr_t)p & 15) == 0, red,
-                               [&](int i) { const float4 x = *(const float4*)(p + i); return make_float4(x.x * x.x, x.y * x.y, x.z * x.z, x.w * x.w); },
-                               [&](int i) { return p[i] * p[i]; });
-            }
+            sg = chunk_sumsq(a.g[t] + off, len, red);
+            if (!(flags & ZETT_ADAMW_FROZEN)) sp = chunk_sumsq(a.p[t] + off, len, red);
         }
         if (threadIdx.x == 0) {
             ws[w.gpart + a.item_base + item] = sg;
@@ -183,29 +150,17 @@ __global__ __launch_bounds__(256) void af_pass1_kernel(const AfList a, const AfW
     }
 }
 
-// record = { norm, coef, skip (int32), count (int32), beta, 1 - beta, 0, 0 }: zett_op_grad_norm's rules for norm, coef and skip; the count
-// t is the number of updates applied so far and beta = 1 - (t + 1)^-0.8 (optax.scale_by_factored_rms: decay_rate 0.8, step t + 1), the
-// power taken in float64 and rounded to fp32 once (word 5), beta = (float)(1 - power).
+// record = { norm, coef, skip (int32), count (int32), beta, 1 - beta, 0, 0 }: norm_words; the count t before this step is the number
+// of updates applied so far and beta = 1 - (t + 1)^-0.8 (optax.scale_by_factored_rms: decay_rate 0.8, step t + 1), the power taken in
+// float64 and rounded to fp32 once (word 5), beta = (float)(1 - power).
 __global__ __launch_bounds__(256) void af_norm_kernel(const float* __restrict__ gpart, int64_t total, double max_norm, float* __restrict__ record) {
     __shared__ double red[256];
-    double s = 0.0;
-#pragma unroll 8                                                     // (the loads of eight terms in flight; the additions stay in index order)
-    for (int64_t i = threadIdx.x; i < total; i += 256) s += (double)gpart[i];
-    s = block_sum_f64(s, red);
+    const double s = strided_sum_f64(gpart, total, red);
     if (threadIdx.x == 0) {
-        const double norm = sqrt(s);
-        const bool finite = isfinite(norm);
-        int32_t* ri = (int32_t*)record;
-        const int32_t step = ri[3] + (finite ? 1 : 0);
-        const double pw = pow((double)ri[3] + 1.0, -0.8);
-        record[0] = (float)norm;
-        record[1] = !finite ? 0.f : (norm < max_norm ? 1.f : (float)(max_norm / norm));
-        ri[2] = finite ? 0 : 1;
-        ri[3] = step;
+        const double pw = pow((double)norm_words(s, max_norm, record).before + 1.0, -0.8);
         record[4] = (float)(1.0 - pw);
         record[5] = (float)pw;
-        record[6] = 0.f;
-        record[7] = 0.f;
+        record[6] = record[7] = 0.f;
     }
 }
 
@@ -218,8 +173,7 @@ __global__ __launch_bounds__(256) void af_stats_kernel(const AfList a, float* __
     const float beta = record[4], omb = record[5];
     const int total = a.seg_start[a.n_tensors];
     for (int item = blockIdx.x; item < total; item += gridDim.x) {
-        int t = 0;
-        while (t + 1 < a.n_tensors && a.seg_start[t + 1] <= item) ++t;
+        const int t = tensor_of(a.seg_start, a.n_tensors, item);
         const int R = a.rows[t], C = a.cols[t], ntc = tiles_across(C), ntr = (R + kTileRows - 1) / kTileRows;
         const int segs_a = (R + kSeg - 1) / kSeg;
         int seg = item - a.seg_start[t];
@@ -235,7 +189,7 @@ __global__ __launch_bounds__(256) void af_stats_kernel(const AfList a, float* __
         float vn = 0.f;
         if (i < len) {
             double s = 0.0;
-#pragma unroll 8                                                     // (as in af_norm_kernel)
+#pragma unroll 8                                                     // (as in strided_sum_f64: loads in flight, the same order)
             for (int k = 0; k < parts; ++k) s += (double)part[(int64_t)k * len + i];
             const float mq = (float)(c2 * s / (double)count + kEps);
             vn = beta * v[i] + omb * mq;
@@ -261,9 +215,7 @@ __global__ __launch_bounds__(256) void af_tensor_kernel(const AfList a, const Af
     float* ts = ws + w.ts + 4 * (int64_t)(a.tensor_base + t);
     const int64_t first = a.item_base + a.item_start[t], items = a.item_start[t + 1] - a.item_start[t];
     const float* part = ws + (stage == 0 ? w.ppart : w.upart) + first;
-    double s = 0.0;
-    for (int64_t i = threadIdx.x; i < items; i += 256) s += (double)part[i];
-    s = block_sum_f64(s, red);
+    const double s = strided_sum_f64(part, items, red);
     if (stage == 0) {
         double m = 0.0;
         int len = 1;
@@ -336,7 +288,7 @@ __global__ __launch_bounds__(256) void af_pass2_kernel(const AfList a, const AfW
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int total = a.item_start[a.n_tensors];
     for (int item = blockIdx.x; item < total; item += gridDim.x) {
-        const int t = tensor_of_item(a, item);
+        const int t = tensor_of(a.item_start, a.n_tensors, item);
         const int local = item - a.item_start[t];
         const int flags = a.flags[t];
         if (flags & ZETT_ADAMW_FROZEN) continue;
@@ -385,16 +337,6 @@ __global__ __launch_bounds__(256) void af_pass2_kernel(const AfList a, const AfW
 
 __device__ __forceinline__ float p_new(float p, float u, float scale, float wd) { return p - (scale * u + wd * p); }
 
-// g[0 .. len) = 0 by the whole workgroup: 16-byte stores where the pointer allows it
-__device__ __forceinline__ void zero_chunk(float* __restrict__ g, int len) {
-    int tail = 0;
-    if (((uintptr_t)g & 15) == 0) {
-        tail = len & ~3;
-        for (int i = threadIdx.x * 4; i < tail; i += 1024) *(float4*)(g + i) = make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-    for (int i = tail + threadIdx.x; i < len; i += 256) g[i] = 0.f;
-}
-
 // ---- pass 3: p -= scale u + (decay ? wd p : 0); gradients cleared where asked — those of frozen tensors and of a skipped step too ------
 __global__ __launch_bounds__(256) void af_pass3_kernel(const AfList a, const AfWs w, const AfHyper h, float* __restrict__ ws, const float* __restrict__ record) {
     __shared__ float rf[kTileRows];
@@ -405,7 +347,7 @@ __global__ __launch_bounds__(256) void af_pass3_kernel(const AfList a, const AfW
     const int total = a.item_start[a.n_tensors];
     const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
     for (int item = blockIdx.x; item < total; item += gridDim.x) {
-        const int t = tensor_of_item(a, item);
+        const int t = tensor_of(a.item_start, a.n_tensors, item);
         const int local = item - a.item_start[t];
         const int flags = a.flags[t];
         const float wd = (flags & ZETT_ADAMW_DECAY) ? h.wd : 0.f;
@@ -492,7 +434,7 @@ int make_plan(const int64_t* rows, const int64_t* cols, const uint8_t* flags, in
             items += ntr * ntc;
             region[i] = carve.take(ntc * rows[i] + ntr * cols[i] + (std::min(rows[i], cols[i]) + kSeg - 1) / kSeg);
         } else {
-            items += (n + kChunk - 1) / kChunk;
+            items += chunk_items(n);
         }
         if (items >= 0x7fffffff) return fail(ZETT_E_INVALID, "too many elements");
     }
@@ -503,43 +445,35 @@ int make_plan(const int64_t* rows, const int64_t* cols, const uint8_t* flags, in
     plan->floats = carve.bytes;
     plan->items = items;
     plan->tensors = (int32_t)tensors;
-    int64_t item_base = 0;
-    int32_t tensor_base = 0;
-    for (int first = 0; first < n_tensors;) {
-        AfList a{};
-        std::vector<int> entry;
-        int k = 0, it = 0, seg = 0;
-        for (; first < n_tensors && k < kGroup; ++first) {
-            const int64_t n = rows[first] * cols[first];
-            if (!n) continue;
-            a.n[k] = n;
-            a.rows[k] = (int32_t)rows[first];
-            a.cols[k] = (int32_t)cols[first];
-            a.flags[k] = flags[first];
-            a.item_start[k] = it;
-            a.seg_start[k] = seg;
-            a.ws[k] = region[first];
-            entry.push_back(first);
-            if (is_factored(rows[first], cols[first], flags[first])) {
-                a.flags[k] |= kFactored | (rows[first] <= cols[first] ? kNormRows : 0);
-                it += (int)(((rows[first] + kTileRows - 1) / kTileRows) * ((cols[first] + kTileCols - 1) / kTileCols));
-                seg += (int)((rows[first] + kSeg - 1) / kSeg + (cols[first] + kSeg - 1) / kSeg);
-            } else {
-                it += (int)((n + kChunk - 1) / kChunk);
-            }
-            ++k;
-        }
-        if (!k) break;
-        a.item_start[k] = it;
-        a.seg_start[k] = seg;
-        a.n_tensors = k;
-        a.tensor_base = tensor_base;
-        a.item_base = item_base;
-        tensor_base += k;
-        item_base += it;
-        plan->lists.push_back(a);
-        plan->entry.push_back(entry);
-    }
+    AfList a{};
+    std::vector<int> entry;
+    int seg = 0;
+    for_each_group(n_tensors, kGroup, a.item_start,
+                   [&](int k, int i) {
+                       const int64_t n = rows[i] * cols[i];
+                       if (!n) return 0;
+                       a.n[k] = n;
+                       a.rows[k] = (int32_t)rows[i];
+                       a.cols[k] = (int32_t)cols[i];
+                       a.flags[k] = flags[i];
+                       a.seg_start[k] = seg;
+                       a.ws[k] = region[i];
+                       entry.push_back(i);
+                       if (!is_factored(rows[i], cols[i], flags[i])) return (int)chunk_items(n);
+                       a.flags[k] |= kFactored | (rows[i] <= cols[i] ? kNormRows : 0);
+                       seg += (int)((rows[i] + kSeg - 1) / kSeg + (cols[i] + kSeg - 1) / kSeg);
+                       return (int)(((rows[i] + kTileRows - 1) / kTileRows) * ((cols[i] + kTileCols - 1) / kTileCols));
+                   },
+                   [&](int k, int group_items) {
+                       a.seg_start[k] = seg;
+                       a.n_tensors = k;
+                       plan->lists.push_back(a);
+                       plan->entry.push_back(entry);
+                       a.tensor_base += k;          // (for the next group: tensors and work items of the launches before it)
+                       a.item_base += group_items;
+                       entry.clear();
+                       seg = 0;
+                   });
     return 0;
 }
 

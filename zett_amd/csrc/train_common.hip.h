@@ -1,5 +1,5 @@
-// train_common.hip.h — the small device / host layer the four training units (train_ops.hip, train_step.hip, train_loss.hip,
-// train_embed.hip) share: element accessors over gemm.hip.h's conversions (to_lo, lo_to_f32, pack2_lo, unpack2_lo: widen on load —
+// train_common.hip.h — the small device / host layer the training units (train_ops.hip, train_dist.hip, train_step.hip,
+// train_adafactor.hip, train_loss.hip, train_embed.hip, train_batch.hip, train_init.hip) share: element accessors over gemm.hip.h's conversions (to_lo, lo_to_f32, pack2_lo, unpack2_lo: widen on load —
 // bf16 by the 16-bit left shift —, round to nearest even on store), the reductions, the id read and the splitmix64 finalizer.  (The zett_dtype ->
 // storage-type map and the dtype dispatch of the launches — elem_t, is_dtype, with_dtype — are common.hip.h's: the forward uses
 // them too.)  The device helpers here hold only conversions and additions, so a caller's `#pragma clang fp contract(off)` keeps
@@ -72,7 +72,7 @@ __device__ __forceinline__ float block_sum_ltr(float v, float* red /* [4] */) {
     __syncthreads();
     return red[0] + red[1] + red[2] + red[3];
 }
-// pairwise, (r0 + r1) + (r2 + r3): train_step.hip (the sums of squares behind the gradient norm)
+// pairwise, (r0 + r1) + (r2 + r3): train_optim.hip.h (the sums of squares behind the gradient norm), train_adafactor.hip
 __device__ __forceinline__ float block_sum_pairwise(float v, float* red /* [4] */) {
     v = wave_sum(v);
     __syncthreads();

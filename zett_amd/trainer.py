@@ -22,8 +22,9 @@ import numpy as np
 import torch
 
 from .collate import _mix64
+from .optim import make_optimizer
 from .train_config import TrainingArguments
-from .training import identity_loss, lexical_loss, lm_head_loss, make_optimizer, splice_special_rows, token_embeddings
+from .training import identity_loss, lexical_loss, lm_head_loss, splice_special_rows, token_embeddings
 
 # the reference's TrainingArguments defaults (train.py:82-121); output_dir has none
 TRAINING_DEFAULTS = {f.name: (None if f.default is dataclasses.MISSING else f.default) for f in dataclasses.fields(TrainingArguments)}
@@ -284,7 +285,7 @@ class HypernetTrainer:
         (loss / self.k).backward()
         if (self.micro_step + 1) % self.k == 0:
             self.optimizer.step(lr=lr, zero_grad=True)
-            record = self.optimizer._record
+            record = self.optimizer.record
             if record is not None:
                 metrics["grad_norm"] = record[0].clone()
                 metrics["skipped"] = record.view(torch.int32)[2].clone()

@@ -17,15 +17,14 @@ warm-up loss (train.py:914-975), the lexical loss (train.py:1074-1141) and the p
 
     init_hypernet_state(model, source_embeddings, example_surface_forms, pretrained_state=sd)      # once, before the first step: the Rescaler fit (column_moments, rescaler_fit) and the overlay of pretrained parameters (train.py:689-725)
 
-Losses, update, splice, lookup, the batch's sub-vocabulary and the column moments behind the Rescaler fit are HIP kernels (csrc/train_step.hip, csrc/train_adafactor.hip, csrc/train_loss.hip, csrc/train_embed.hip, csrc/train_batch.hip, csrc/train_init.hip); torch holds the tensors and the tape.  Nothing in this module waits for
+Losses, update, splice, lookup, the batch's sub-vocabulary and the column moments behind the Rescaler fit are HIP kernels (csrc/train_dist.hip, csrc/train_step.hip, csrc/train_adafactor.hip, csrc/train_loss.hip, csrc/train_embed.hip, csrc/train_batch.hip, csrc/train_init.hip); torch holds the tensors and the tape.  Nothing in this module waits for
 the host except ``last_step_stats()``, ``state_dict()``, ``token_embeddings(check_ids=True)`` and ``subsample_batch_vocabulary(check=True)`` (the model's forward in front of it still reads its id range back once per
 step).  Results are bit-reproducible from run to run.
 """
 from __future__ import annotations
 
 import ctypes as C
-import math
-from typing import Callable, Dict, List, Mapping, NamedTuple, Optional, Sequence, Tuple, Union
+from typing import List, Mapping, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 from torch.autograd.function import once_differentiable
@@ -856,345 +855,8 @@ from .sampled_vocab import DeviceSampledVocabulary, SampledVocabulary, sample_to
 from .collate import DeviceCollator, LabelledBatch, PaddedVocabulary, label_batch, mlm_thresholds, pad_vocabulary, padded_rows  # noqa: E402,F401
 
 
-# ---- which parameters train, and which decay -------------------------------------------------------------------------------
-LABELS = ("decay", "no_decay", "frozen")
-
-
-def param_labels(model, overrides: Union[None, Mapping[str, str], Callable[[str], Optional[str]]] = None) -> Dict[str, str]:
-    """name -> "decay" | "no_decay" | "frozen" for every parameter of `model`: the reference's rule (train.py:591-622) on the
-    checkpoint's PyTorch names.
-
-    - frozen: ``scaler.*`` and ``in_scaler.*`` (get_labels: a path whose parent is "scaler" or "in_scaler").  ``out_scaler.*`` is
-      NOT in the reference's freeze set, so it trains — and decays: its leaves are called "w" and "b", not "bias".  Kept as is.
-    - no_decay: every ``.bias`` and every parameter of a LayerNorm (``LayerNorm.*``, ``ln.*``) (decay_mask_fn).
-    - decay: everything else.
-
-    overrides: a mapping (exact name, or a prefix ending in "." for a whole module) or a callable name -> label | None."""
-    out = {}
-    for name, _ in model.named_parameters():
-        parts = name.split(".")
-        if len(parts) >= 2 and parts[-2] in ("scaler", "in_scaler"):
-            label = "frozen"
-        elif parts[-1] == "bias" or (len(parts) >= 2 and parts[-2] in ("LayerNorm", "ln", "layer_norm", "layernorm")):
-            label = "no_decay"
-        else:
-            label = "decay"
-        if callable(overrides):
-            label = overrides(name) or label
-        elif overrides:
-            for key, value in overrides.items():
-                if name == key or (key.endswith(".") and name.startswith(key)):
-                    label = value
-        if label not in LABELS:
-            raise ValueError(f"label of {name} must be one of {LABELS}, got {label!r}")
-        out[name] = label
-    return out
-
-
-class HypernetAdamW:
-    """optax.chain(clip_by_global_norm(max_grad_norm), multi_transform({train: adamw(lr, b1, b2, eps, weight_decay, mask),
-    freeze: set_to_zero})) (train.py:638-656) for the parameters of `model`, as two multi-tensor HIP kernels per step:
-
-    - the global gradient norm over EVERY parameter that has a gradient, frozen ones included (the reference clips before the
-      freeze), then ``coef = 1 if norm < max_grad_norm else max_grad_norm / norm`` (optax's rule; max_grad_norm None: no clip);
-    - one pass: ``g' = coef g; m = b1 m + (1-b1) g'; v = b2 v + (1-b2) g'^2; p -= lr ((m/c1) / (sqrt(v/c2) + eps) + wd p)``,
-      weight decay on "decay" parameters only (param_labels), "frozen" parameters untouched.
-
-    A step whose gradient norm is not finite changes no parameter, no moment and not the step count, and is reported by
-    ``last_step_stats()["skipped"]``.  With ``zero_grad=True`` it still clears every gradient, so that the non-finite values are not
-    what the next backward accumulates into (every later step would be skipped too); without it the caller clears them.
-
-    `model` is a ZettHypernet or a wrapper that holds one as ``.module`` (DistributedDataParallel): the wrapper is unwrapped.  step() does not wait for the host: norm, coefficient, skip flag and step count live in a
-    device record.  It ends with ``model.refresh_weights()`` — the kernels write through raw pointers, which torch's version
-    counters do not see — so a no_grad / eval forward after it runs on the new weights."""
-
-    def __init__(self, model, lr: float, betas=(0.9, 0.95), eps: float = 1e-8, weight_decay: float = 0.01, max_grad_norm: Optional[float] = 0.1,
-                 labels: Union[None, Mapping[str, str], Callable[[str], Optional[str]]] = None):
-        if not hasattr(model, "refresh_weights") and hasattr(getattr(model, "module", None), "refresh_weights"):
-            model = model.module                              # DistributedDataParallel and the like: the same Parameter objects
-        if not hasattr(model, "refresh_weights"):
-            raise TypeError(f"{type(self).__name__} needs a model with refresh_weights() (a ZettHypernet, or a wrapper holding one as .module)")
-        self.model = model
-        self._set_hyper(lr, betas, eps, weight_decay, max_grad_norm)
-        self.labels = param_labels(model, labels)
-        self.state: Dict[str, Dict[str, torch.Tensor]] = {}
-        self._record: Optional[torch.Tensor] = None          # [norm, coef, skip (i32), step (i32), 1 - b1^step, 1 - b2^step, 0, 0]
-        self._partials: Optional[torch.Tensor] = None
-
-    def _set_hyper(self, lr, betas, eps, weight_decay, max_grad_norm) -> None:
-        betas = (float(betas[0]), float(betas[1]))
-        max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
-        if not (0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0) or float(eps) < 0 or (max_grad_norm is not None and not max_grad_norm > 0):
-            raise ValueError("betas must be in [0, 1), eps >= 0, max_grad_norm > 0 or None")
-        self.lr, self.betas, self.eps, self.weight_decay, self.max_grad_norm = float(lr), betas, float(eps), float(weight_decay), max_grad_norm
-
-    def _params(self):
-        return [(n, p) for n, p in self.model.named_parameters() if p.grad is not None]
-
-    def _device_record(self, device) -> torch.Tensor:
-        if self._record is None or self._record.device != device:
-            old = self._record
-            self._record = torch.zeros(8, dtype=torch.float32, device=device)
-            if old is not None:
-                self._record.copy_(old)
-        return self._record
-
-    def _collect(self):
-        """The tensor lists of this step as host arrays (they travel to the kernels as launch arguments), moments allocated."""
-        todo = self._params()
-        if not todo:
-            return None
-        device = todo[0][1].device
-        n = len(todo)
-        P, G, M, V = ((C.c_void_p * n)() for _ in range(4))
-        numel, flags = (C.c_int64 * n)(), (C.c_uint8 * n)()
-        items = 0
-        for i, (name, p) in enumerate(todo):
-            g = p.grad
-            if p.dtype != torch.float32 or g.dtype != torch.float32 or not p.is_contiguous() or not g.is_contiguous() or p.device != device or g.device != device:
-                raise ValueError(f"{name}: parameters and gradients must be contiguous fp32 tensors on one device")
-            label = self.labels.get(name, "decay")
-            P[i], G[i], numel[i] = p.data_ptr(), g.data_ptr(), p.numel()
-            items += -(-p.numel() // _lib.MT_CHUNK)
-            if label == "frozen":
-                flags[i] = _lib.ADAMW_FROZEN
-                continue
-            st = self.state.get(name)
-            if st is None:
-                st = self.state[name] = {k: torch.zeros_like(p, memory_format=torch.contiguous_format) for k in ("exp_avg", "exp_avg_sq")}
-            elif st["exp_avg"].device != device:
-                st = self.state[name] = {k: t.to(device) for k, t in st.items()}
-            M[i], V[i] = st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr()
-            flags[i] = _lib.ADAMW_DECAY if label == "decay" else 0
-        if self._partials is None or self._partials.numel() < items or self._partials.device != device:
-            self._partials = torch.empty(max(items, 1), dtype=torch.float32, device=device)
-        return device, n, P, G, M, V, numel, flags, self._device_record(device)
-
-    def _launch_norm(self, lists) -> None:
-        device, n, _, G, _, _, numel, _, record = lists
-        with torch.cuda.device(device):
-            _lib.check(_lib.load().zett_op_grad_norm(G, numel, n, math.inf if self.max_grad_norm is None else float(self.max_grad_norm), self.betas[0], self.betas[1],
-                                                     ptr(self._partials), self._partials.numel(), ptr(record), stream(device)), "grad_norm")
-
-    def _launch_adamw(self, lists, lr: Optional[float] = None, zero_grad: bool = False) -> None:
-        device, n, P, G, M, V, numel, flags, record = lists
-        with torch.cuda.device(device):
-            _lib.check(_lib.load().zett_op_adamw(P, G, M, V, numel, flags, n, self.lr if lr is None else float(lr), self.betas[0], self.betas[1], self.eps,
-                                                 self.weight_decay, int(bool(zero_grad)), ptr(record), stream(device)), "adamw")
-
-    def step(self, lr: Optional[float] = None, zero_grad: bool = False) -> None:
-        """One update from the parameters' ``.grad``.  lr: this step's learning rate (the caller's schedule); zero_grad: the
-        gradients are zeroed in the same pass (they stay allocated: the next backward accumulates into zeros) — on a skipped
-        step too."""
-        lists = self._collect()
-        if lists is None:
-            return
-        self._launch_norm(lists)
-        self._launch_adamw(lists, lr, zero_grad)
-        self.model.refresh_weights()
-
-    def zero_grad(self, set_to_none: bool = True) -> None:
-        self.model.zero_grad(set_to_none=set_to_none)
-
-    def last_step_stats(self) -> Dict[str, float]:
-        """Synchronises.  grad_norm: the global norm before clipping; clip_coef: what the gradients were multiplied by; skipped: 1 if
-        the norm was not finite and the step changed nothing; step: updates applied so far."""
-        if self._record is None:
-            return {"grad_norm": 0.0, "clip_coef": 1.0, "skipped": 0, "step": 0}
-        f = self._record.cpu()
-        i = f.view(torch.int32)
-        return {"grad_norm": float(f[0]), "clip_coef": float(f[1]), "skipped": int(i[2]), "step": int(i[3])}
-
-    def state_dict(self) -> dict:
-        return {"step": self.last_step_stats()["step"],
-                "state": {n: {k: t.clone() for k, t in st.items()} for n, st in self.state.items()},
-                "hyper": {"lr": self.lr, "betas": self.betas, "eps": self.eps, "weight_decay": self.weight_decay, "max_grad_norm": self.max_grad_norm},
-                "labels": dict(self.labels)}
-
-    def load_state_dict(self, sd: dict) -> None:
-        """What state_dict() returned: "step" and "state" are required; "hyper" and "labels" (optional) replace the constructor's."""
-        missing = [k for k in ("step", "state") if k not in sd]
-        if missing:
-            raise KeyError(f"optimizer state dict lacks {missing}")
-        step = int(sd["step"])
-        if step < 0:
-            raise ValueError(f"step count {step} is negative")
-        params = dict(self.model.named_parameters())
-        unknown = [n for n in sd["state"] if n not in params]
-        if unknown:
-            raise KeyError(f"optimizer state for parameters the model does not have: {unknown}")
-        state = {}
-        for n, st in sd["state"].items():
-            p = params[n]
-            if tuple(st["exp_avg"].shape) != tuple(p.shape) or tuple(st["exp_avg_sq"].shape) != tuple(p.shape):
-                raise ValueError(f"optimizer state of {n} does not match the parameter's shape {tuple(p.shape)}")
-            state[n] = {k: st[k].detach().to(device=p.device, dtype=torch.float32).contiguous().clone() for k in ("exp_avg", "exp_avg_sq")}
-        labels = param_labels(self.model, {n: l for n, l in sd["labels"].items() if n in self.labels}) if "labels" in sd else self.labels
-        h = sd.get("hyper", {})
-        self._set_hyper(h.get("lr", self.lr), h.get("betas", self.betas), h.get("eps", self.eps), h.get("weight_decay", self.weight_decay),
-                        h.get("max_grad_norm", self.max_grad_norm))          # (validated like the constructor's; nothing was assigned before this)
-        self.state, self.labels = state, labels
-        device = next(iter(params.values())).device
-        record = torch.zeros(8, dtype=torch.float32)
-        record.view(torch.int32)[3] = step
-        record[1] = 1.0
-        self._record = record.to(device) if device.type == "cuda" else record
-
-
-ADAFACTOR_MIN_DIM_TO_FACTOR = 128      # optax.adafactor's min_dim_size_to_factor
-
-
-def adafactor_state_shapes(shape) -> Dict[str, Tuple[int, ...]]:
-    """The statistics optax.scale_by_factored_rms keeps for a parameter of `shape` (1-D or 2-D): {"v_row", "v_col"} for a factored
-    one (2-D, smaller dimension >= 128), {"v"} otherwise.  d0 is the larger and d1 the smaller dimension by ``numpy.argsort(shape)``
-    (a square matrix: d1 = 0, d0 = 1); v_row is the mean over d0 and has shape[d1] entries, v_col the mean over d1 with shape[d0]."""
-    shape = tuple(int(s) for s in shape)
-    if len(shape) > 2:
-        raise ValueError(f"Adafactor on the device takes 1-D and 2-D parameters, got shape {shape}")
-    if len(shape) == 2 and min(shape) >= ADAFACTOR_MIN_DIM_TO_FACTOR:
-        d1 = 0 if shape[0] <= shape[1] else 1
-        return {"v_row": (shape[d1],), "v_col": (shape[1 - d1],)}
-    return {"v": shape}
-
-
-class HypernetAdafactor(HypernetAdamW):
-    """optax.chain(clip_by_global_norm(max_grad_norm), multi_transform({train: adafactor(lr, weight_decay_rate=weight_decay,
-    weight_decay_mask), freeze: set_to_zero})) (train.py:631-636, 651-656) for the parameters of `model`, every other argument of
-    optax.adafactor at its default (min_dim_size_to_factor 128, decay_rate 0.8, multiply_by_parameter_scale, clipping_threshold 1.0,
-    no momentum, eps 1e-30), as one call of the library (zett_op_adafactor_step, csrc/train_adafactor.hip).  Per step, t updates applied so far:
-
-    - norm and ``coef`` as HypernetAdamW; ``g' = coef g``, ``q = g'^2 + 1e-30``, ``beta = 1 - (t + 1)^-0.8``;
-    - a 2-D parameter whose smaller dimension is >= 128 keeps two vectors (adafactor_state_shapes): ``v_row = beta v_row + (1 - beta)
-      mean(q, d0)``, ``v_col`` likewise over d1, ``u = g' (v_row / mean(v_row))^-1/2 v_col^-1/2``; every other parameter keeps a full
-      ``v = beta v + (1 - beta) q`` and ``u = g' v^-1/2``;
-    - ``u_hat = u / max(1, RMS(u))``, ``s = max(RMS(p), 1e-3)``, ``p -= lr s u_hat + (weight_decay p if "decay" else 0)``.
-
-    The weight decay is NOT multiplied by lr: optax.adafactor chains add_decayed_weights after the learning-rate scaling (with
-    optax.adamw it is the other way round, and HypernetAdamW's decay is lr wd p).  Labels, the skipped step, ``zero_grad``, the device
-    record, the unwrapping of ``.module`` and the closing ``refresh_weights()`` are HypernetAdamW's; the interface is the same, so the
-    two can be swapped (make_optimizer).  Parameters of more than two dimensions, and tensors that are not contiguous fp32 on one
-    device, are refused with ValueError before anything is launched."""
-
-    def __init__(self, model, lr: float, weight_decay: float = 0.01, max_grad_norm: Optional[float] = 0.1,
-                 labels: Union[None, Mapping[str, str], Callable[[str], Optional[str]]] = None):
-        super().__init__(model, lr, weight_decay=weight_decay, max_grad_norm=max_grad_norm, labels=labels)
-        self.betas = self.eps = None                          # (Adafactor has neither)
-        self._workspace: Optional[torch.Tensor] = None
-
-    def _set_hyper(self, lr, betas, eps, weight_decay, max_grad_norm) -> None:
-        super()._set_hyper(lr, (0.0, 0.0), 0.0, weight_decay, max_grad_norm)
-        self.betas = self.eps = None
-
-    def _collect(self):
-        """The tensor lists of this step as host arrays, statistics and workspace allocated."""
-        todo = self._params()
-        if not todo:
-            return None
-        device = todo[0][1].device
-        n = len(todo)
-        P, G, VR, VC, V = ((C.c_void_p * n)() for _ in range(5))
-        rows, cols, flags = (C.c_int64 * n)(), (C.c_int64 * n)(), (C.c_uint8 * n)()
-        for i, (name, p) in enumerate(todo):
-            g = p.grad
-            if p.dim() > 2:
-                raise ValueError(f"{name}: Adafactor on the device takes 1-D and 2-D parameters, got shape {tuple(p.shape)}")
-            if p.dtype != torch.float32 or g.dtype != torch.float32 or not p.is_contiguous() or not g.is_contiguous() or p.device != device or g.device != device:
-                raise ValueError(f"{name}: parameters and gradients must be contiguous fp32 tensors on one device")
-            if name not in self.labels:
-                raise ValueError(f"{name} has no label")
-        for i, (name, p) in enumerate(todo):
-            label = self.labels[name]
-            P[i], G[i] = p.data_ptr(), p.grad.data_ptr()
-            rows[i], cols[i] = (p.shape[0], p.shape[1]) if p.dim() == 2 else (1, p.numel())
-            if label == "frozen":
-                flags[i] = _lib.ADAMW_FROZEN
-                continue
-            st = self.state.get(name)
-            if st is None:
-                st = self.state[name] = {k: torch.zeros(shape, dtype=torch.float32, device=device) for k, shape in adafactor_state_shapes(p.shape).items()}
-            elif next(iter(st.values())).device != device:
-                st = self.state[name] = {k: t.to(device) for k, t in st.items()}
-            if "v" in st:
-                V[i] = st["v"].data_ptr()
-            else:
-                VR[i], VC[i] = st["v_row"].data_ptr(), st["v_col"].data_ptr()
-            flags[i] = _lib.ADAMW_DECAY if label == "decay" else 0
-        need = C.c_int64(0)
-        _lib.check(_lib.load().zett_op_adafactor_workspace_floats(rows, cols, flags, n, C.byref(need)), "adafactor workspace")
-        if self._workspace is None or self._workspace.numel() < need.value or self._workspace.device != device:
-            self._workspace = torch.empty(need.value, dtype=torch.float32, device=device)
-        return device, n, P, G, VR, VC, V, rows, cols, flags, self._device_record(device)
-
-    def step(self, lr: Optional[float] = None, zero_grad: bool = False) -> None:
-        """One update from the parameters' ``.grad``; lr and zero_grad as HypernetAdamW.step."""
-        lists = self._collect()
-        if lists is None:
-            return
-        device, n, P, G, VR, VC, V, rows, cols, flags, record = lists
-        with torch.cuda.device(device):
-            _lib.check(_lib.load().zett_op_adafactor_step(P, G, VR, VC, V, rows, cols, flags, n, self.lr if lr is None else float(lr), self.weight_decay,
-                                                          math.inf if self.max_grad_norm is None else float(self.max_grad_norm), int(bool(zero_grad)),
-                                                          ptr(self._workspace), self._workspace.numel(), ptr(record), stream(device)), "adafactor")
-        self.model.refresh_weights()
-
-    def state_dict(self) -> dict:
-        return {"step": self.last_step_stats()["step"],
-                "state": {n: {k: t.clone() for k, t in st.items()} for n, st in self.state.items()},
-                "hyper": {"lr": self.lr, "weight_decay": self.weight_decay, "max_grad_norm": self.max_grad_norm},
-                "labels": dict(self.labels)}
-
-    def load_state_dict(self, sd: dict) -> None:
-        """What state_dict() returned: "step" and "state" are required; "hyper" and "labels" (optional) replace the constructor's.
-        Every parameter's statistics must be the ones the factoring rule gives its shape (adafactor_state_shapes)."""
-        missing = [k for k in ("step", "state") if k not in sd]
-        if missing:
-            raise KeyError(f"optimizer state dict lacks {missing}")
-        step = int(sd["step"])
-        if step < 0:
-            raise ValueError(f"step count {step} is negative")
-        params = dict(self.model.named_parameters())
-        unknown = [n for n in sd["state"] if n not in params]
-        if unknown:
-            raise KeyError(f"optimizer state for parameters the model does not have: {unknown}")
-        state = {}
-        for n, st in sd["state"].items():
-            p = params[n]
-            want = adafactor_state_shapes(p.shape)
-            if set(st) != set(want) or any(tuple(st[k].shape) != want[k] for k in want):
-                raise ValueError(f"optimizer state of {n} is {({k: tuple(t.shape) for k, t in st.items()})}, a parameter of shape {tuple(p.shape)} keeps {want}")
-            state[n] = {k: st[k].detach().to(device=p.device, dtype=torch.float32).contiguous().clone() for k in want}
-        labels = param_labels(self.model, {n: l for n, l in sd["labels"].items() if n in self.labels}) if "labels" in sd else self.labels
-        h = sd.get("hyper", {})
-        self._set_hyper(h.get("lr", self.lr), None, None, h.get("weight_decay", self.weight_decay), h.get("max_grad_norm", self.max_grad_norm))
-        self.state, self.labels = state, labels
-        device = next(iter(params.values())).device
-        record = torch.zeros(8, dtype=torch.float32)
-        record.view(torch.int32)[3] = step
-        record[1] = 1.0
-        self._record = record.to(device) if device.type == "cuda" else record
-
-
-def make_optimizer(model, training_args, labels: Union[None, Mapping[str, str], Callable[[str], Optional[str]]] = None):
-    """The optimizer the reference builds from its TrainingArguments (train.py:631-656): HypernetAdafactor when ``use_adafactor`` is
-    set, HypernetAdamW(adam_beta1, adam_beta2, adam_epsilon) otherwise, with ``learning_rate`` (a float, or the first entry of a list),
-    ``weight_decay`` and ``max_grad_norm`` (None: no clip).  training_args: an object with these attributes or a mapping; a field it
-    lacks takes the reference's default (train.py:91-101).  The learning-rate schedule stays the caller's: ``step(lr=...)``."""
-    defaults = {"use_adafactor": False, "learning_rate": 3e-4, "max_grad_norm": None, "weight_decay": 0.0, "adam_beta1": 0.9, "adam_beta2": 0.999, "adam_epsilon": 1e-8}
-
-    def field(name):
-        if isinstance(training_args, Mapping):
-            return training_args.get(name, defaults[name])
-        return getattr(training_args, name, defaults[name])
-
-    lr = field("learning_rate")
-    if isinstance(lr, (list, tuple)):
-        if not lr:
-            raise ValueError("learning_rate is an empty list")
-        lr = lr[0]
-    if field("use_adafactor"):
-        return HypernetAdafactor(model, float(lr), weight_decay=float(field("weight_decay")), max_grad_norm=field("max_grad_norm"), labels=labels)
-    return HypernetAdamW(model, float(lr), betas=(float(field("adam_beta1")), float(field("adam_beta2"))), eps=float(field("adam_epsilon")),
-                         weight_decay=float(field("weight_decay")), max_grad_norm=field("max_grad_norm"), labels=labels)
+# ---- the parameter update (train.py:591-656): labels, the step skeleton, AdamW, Adafactor, make_optimizer: zett_amd/optim.py ----------------------
+from .optim import ADAFACTOR_MIN_DIM_TO_FACTOR, LABELS, HypernetAdafactor, HypernetAdamW, HypernetOptimizer, adafactor_state_shapes, make_optimizer, param_labels  # noqa: E402,F401
 
 
 # ---- fitting a fresh hypernetwork's Rescalers (csrc/train_init.hip) ------------------------------------------------------------------
