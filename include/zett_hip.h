@@ -656,6 +656,57 @@ int zett_op_fwd_pair_qkv(int32_t prec, const void* u, const int32_t* slot, const
                          const int32_t* row_offset, int64_t row0, int32_t rows, const int32_t* cls_slot, const float* stats, const float* c_pos, int32_t n_pos,
                          const float* c_w, const float* b_q, int32_t n_cols, void* out, int64_t ld_out, int32_t* range_flag, void* stream);
 
+/* ---- one GEMM launch of the forward (csrc/gemm_entry.hip; additive, the ABI version does not move) ------------------------------
+ * C[m, n] = epilogue(a[m, k] . w[n, k]^T) exactly as the forward launches it: the tile variant and gemm4d's tail cut come from the rule
+ * the forward's own launches use (csrc/gemm_launch.hip.h gemm_variant_for / gemm_row0_for), the kernel from launch_gemm_variant, so
+ * that ONE launch with any epilogue can be checked element by element (tests/test_gemm_fwd_direct_gpu.py).  The descriptor mirrors
+ * GemmArgs / GemmEpilogue of csrc/gemm.hip.h field for field (T = the operand type of prec; every pointer a raw device pointer,
+ * nullable unless noted; leading dimensions in elements):
+ *   v = acc + bias[col]  (fold_stats: acc <- rstd_row * (acc - mean_row * fold_c[col]) first);  v = act(v);  v += r[row, col];
+ *   v = scale[col] * v + shift[col];   r = residual (fp32) or residual_lo (T) at row res_index[row] (NULL: row), with res_stats
+ *   LayerNorm'd on the fly: ((r - mean) * rstd) * res_gamma[col] + res_beta[col], (mean, rstd) = res_stats[2 * that row ..];
+ *   columns < split_col -> out_f32 / out_lo, columns >= split_col -> out_f32_b (split_col <= 0 or >= n: no split);
+ *   dst: row m goes to row dst_rows[m] (NULL: m; < 0: not written) of the caller's matrix of zett_dtype dst_dtype, instead of out_f32;
+ *   stats_part [n / 128][ld_part] float2: (sum, sum of squares) of v over each 128-column slice of a row (LayerNorm-fold producer);
+ *   range_flag: where the range guard ORs its zett_range_bits; range_final: the fp32 outputs are checked for inf / NaN.
+ * The entry validates everything before any launch, allocates nothing and is asynchronous on `stream`; a refusal is ZETT_E_INVALID with
+ * a zett_last_error text: an unknown precision / act / dst_dtype / option value, k not a positive multiple of 128 bytes, lda / ldw
+ * below k or rows that are not multiples of 16 bytes, base pointers that are not 16-byte aligned (statistics and partials 8, index
+ * arrays and range_flag their element size, dst what its type's four-value store needs), a leading dimension below its width, no output,
+ * 16-bit features (stats_part, fold_stats, residual_lo, dst) with ZETT_PREC_F32, res_stats without gamma / beta or a residual,
+ * residual with residual_lo, scale without shift, fold_stats without fold_c, a LayerNorm-fold or destination launch no gemm4d
+ * instantiation carries, dst together with another output.  res_index and dst_rows are trusted, as in the forward.  The 384-row tile
+ * (variant 3) does not clamp rows: it runs only when a_rows_readable >= ceil(m / 384) * 384, otherwise the launch takes variant 2.
+ * m == 0 or n == 0 launches nothing.  *variant_out (nullable): the tile variant that ran (1, 2, 3, 7, 8; -1: nothing launched);
+ * *mode_out (nullable): for variants 7 / 8 the epilogue instantiation (0 generic, 1 LO, 2 F32, 3 F32_SCALE, 4 BOTH, 5 F32_LN,
+ * 6 LO_FOLD, 7 LO_LN, 8 F32_SCALE_FOLD, 9 LN16: G4D_EPI_* of csrc/gemm4d.hip.h), -1 otherwise. */
+typedef struct zett_fwd_gemm_desc {
+    int64_t size;                     /* sizeof(zett_fwd_gemm_desc): any other value is refused */
+    const void* a; const void* w;     /* T [m, lda], T [n, ldw]; required */
+    const float* bias;                /* [n] */
+    const float* residual;            /* [*, ld_res] */
+    const void* residual_lo;          /* T [*, ld_res_lo]: the 16-bit residual stream (with stats_part only) */
+    const float* res_stats;           /* [*, 2] */
+    const float* res_gamma; const float* res_beta;      /* [n] */
+    const int32_t* res_index;         /* [m] */
+    float* stats_part;                /* float2 [n / 128][ld_part] */
+    const float* fold_stats;          /* [m, 2] (mean, rstd) of the A rows */
+    const float* fold_c;              /* [n] */
+    const float* scale; const float* shift;             /* [n] */
+    float* out_f32; void* out_lo; float* out_f32_b;
+    int32_t* range_flag;
+    void* dst; const int64_t* dst_rows;
+    int64_t ld_dst;
+    int64_t a_rows_readable;          /* rows of `a` that may be read (>= m) */
+    int32_t lda, ldw, m, n, k, act;   /* act: 0 none, 1 tanh-GELU, 2 erf-GELU */
+    int32_t ld_res, ld_res_lo, ld_part, ld_f32, ld_lo, split_col;
+    int32_t range_final, dst_dtype;
+    /* the options Runner::gemm reads from the handle (zett_set_option names and ranges) */
+    int32_t gemm_variant, gemm4d_min_k, gemm_tail_split, gemm_tile_order, gemm_group;
+    int32_t reserved;                 /* 0 */
+} zett_fwd_gemm_desc;
+int zett_op_fwd_gemm(int32_t prec, const zett_fwd_gemm_desc* desc, int32_t* variant_out, int32_t* mode_out, void* stream);
+
 /* ---- the losses and the parameter update of a training step (zett_amd/training.py) ----------------------------------------------
  * What the reference's trainer puts around the hypernetwork forward: the squared-error loss of the identity warm-up
  * (identity_train_step, train.py:914-975), the lexical loss (train.py:1074-1141) and optax.chain(clip_by_global_norm,

@@ -82,6 +82,8 @@ ABI_SYMBOLS = (
     "zett_single_rows",
     # layer 0's Q/K/V once per source id: the row kernel on its own, and whether the last forward took the lever (HipEngine.id_qkv)
     "zett_op_fwd_pair_qkv", "zett_id_qkv",
+    # one GEMM launch of the forward with any epilogue (tests/test_gemm_fwd_direct_gpu.py)
+    "zett_op_fwd_gemm",
     # fitting a fresh hypernetwork's Rescalers (zett_amd/training.py column_moments, rescaler_fit)
     "zett_op_col_moments_workspace_bytes", "zett_op_col_moments", "zett_op_rescaler_fit",
     # the Adafactor branch of the optimizer (zett_amd/optim.py HypernetAdafactor)
@@ -115,6 +117,15 @@ class ZettDest(C.Structure):
     """struct zett_dest (zett_forward_into / zett_forward_table_into): where the predicted rows go."""
     _fields_ = [("in_", C.c_void_p), ("out", C.c_void_p), ("bias", C.c_void_p), ("dtype", C.c_int32), ("bias_dtype", C.c_int32),
                 ("ld_in", C.c_int64), ("ld_out", C.c_int64), ("rows", C.c_void_p), ("n_dest_rows", C.c_int64)]
+
+
+class ZettFwdGemmDesc(C.Structure):
+    """struct zett_fwd_gemm_desc (zett_op_fwd_gemm): one GEMM launch of the forward, GemmArgs / GemmEpilogue field for field."""
+    _fields_ = [("size", C.c_int64)] + [(n, C.c_void_p) for n in (
+        "a", "w", "bias", "residual", "residual_lo", "res_stats", "res_gamma", "res_beta", "res_index", "stats_part", "fold_stats", "fold_c", "scale", "shift",
+        "out_f32", "out_lo", "out_f32_b", "range_flag", "dst", "dst_rows")] + [("ld_dst", C.c_int64), ("a_rows_readable", C.c_int64)] + [(n, C.c_int32) for n in (
+        "lda", "ldw", "m", "n", "k", "act", "ld_res", "ld_res_lo", "ld_part", "ld_f32", "ld_lo", "split_col", "range_final", "dst_dtype",
+        "gemm_variant", "gemm4d_min_k", "gemm_tail_split", "gemm_tile_order", "gemm_group", "reserved")]
 
 
 class ZettSampledVocabRecord(C.Structure):
@@ -269,6 +280,7 @@ def load():
         lib.zett_op_fwd_ln_stats.argtypes = [I32, P, I32, I32, I32, F, P, P]
         lib.zett_op_fwd_fold_weight.argtypes = [I32, P, I32, I32, P, P, P, P, P, P, P, P]
         lib.zett_op_fwd_pair_qkv.argtypes = [I32, P, P, P, I32, I32, P, P, I64, I32, P, P, P, I32, P, P, I32, P, I64, P, P]
+        lib.zett_op_fwd_gemm.argtypes = [I32, C.POINTER(ZettFwdGemmDesc), C.POINTER(I32), C.POINTER(I32), P]
         lib.zett_op_col_moments_workspace_bytes.argtypes = [I64, I32, C.POINTER(I64)]
         lib.zett_op_col_moments.argtypes = [P, I32, I64, I64, I32, I32, P, I32, P, I64, P]
         lib.zett_op_rescaler_fit.argtypes = [P, I32, P, D, D, P, P, P]

@@ -987,10 +987,16 @@ hipError_t launch_gemm_4d_half(const GemmArgs<bf16_t>& g, hipStream_t stream, in
 hipError_t launch_gemm_4d_half_dst(const GemmArgs<f16_t>& g, hipStream_t stream, int mode);
 hipError_t launch_gemm_4d_half_dst(const GemmArgs<bf16_t>& g, hipStream_t stream, int mode);
 
+// The epilogue launch_gemm4d gives a launch (what gemm_4d_launch_mode of gemm_launch.hip.h reports): -1 = none, the launch is refused
+template <typename T>
+inline int gemm4d_launch_mode(const GemmArgs<T>& g, bool force_generic) {
+    return g.epi.dst ? gemm4d_dst_mode(g) : (force_generic && !g.epi.stats_part && !g.epi.fold_stats) ? G4D_EPI_GENERIC : gemm4d_epi_mode(g);
+}
+
 template <typename T>
 inline hipError_t launch_gemm4d(const GemmArgs<T>& g, hipStream_t stream, bool force_generic = false) {
     const bool dst = g.epi.dst != nullptr;
-    const int mode = dst ? gemm4d_dst_mode(g) : (force_generic && !g.epi.stats_part && !g.epi.fold_stats) ? G4D_EPI_GENERIC : gemm4d_epi_mode(g);
+    const int mode = gemm4d_launch_mode(g, force_generic);
     if (mode < 0) return hipErrorInvalidValue;       // a LayerNorm-fold launch whose outputs no instantiation carries (or a destination none takes)
     // g.row0 on entry: -1 = let the launcher cut the launch (gemm4d_row_split), 0 = full tiles only, > 0 = the caller's cut (a multiple
     // of 256), -2 = half tiles only (tests and A/Bs)

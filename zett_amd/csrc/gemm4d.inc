@@ -14,4 +14,6 @@ hipError_t launch_gemm_4d(const GemmArgs<ZETT_GEMM_T>& g, hipStream_t stream, bo
 
 int gemm_4d_dst_mode(const GemmArgs<ZETT_GEMM_T>& g) { return gemm4d_dst_mode<ZETT_GEMM_T>(g); }
 
+int gemm_4d_launch_mode(const GemmArgs<ZETT_GEMM_T>& g, bool generic_epilogue) { return gemm4d_launch_mode<ZETT_GEMM_T>(g, generic_epilogue); }
+
 }  // namespace zett

@@ -988,45 +988,22 @@ struct Runner {
     bool staged_dst = false;    // (zett_forward_into) the launch in flight writes the staged fp32 rows of a destination (gemm log bit 11)
     int stage_lane = 0;         // (zett_forward_into) which staging buffer head_gemm uses: the lane's own (h->dest_stage[lane])
 
-    // the tile variant a launch takes
-    int variant_for(int M, int N, int K, const GemmEpilogue<T>& e) const {
-        // Tile choice.  Small problems: 128x128.  Otherwise the 256x256 register-staged eight-wave kernel (gemm8r), unless the 384x256
-        // LDS-DMA tile needs fewer rounds over the 256 CUs (it runs ~1.7x as long per tile): wave quantisation decides, e.g. M = 5 111
-        // at N = 4096.  The 384-row kernel has no registers to spare for a residual or scale/shift epilogue (168 per wave: it would
-        // spill to scratch, and no kernel with scratch is ever launched) and does not clamp rows, so A must have `a_rows_readable` >=
-        // tiles*384 rows (every A operand here is a workspace buffer with that slack) and N must be a multiple of 256.  (The kernels
-        // that led to gemm8r and gemm4d -- four-wave register-staged, eight-wave LDS-DMA, gemm8r on 16x16x32 MFMAs -- live in
-        // tools/experiments/ with tools/gemm_bench on the `experiments` branch.)
-        constexpr bool is_f32 = std::is_same<T, float>::value;
-        int variant = h->gemm_variant;
-        if (variant == 0) {
-            variant = (M > 128 && N > 128) ? 2 : 1;
-            if (variant != 1 && N % 256 == 0 && !e.scale && !e.residual) {
-                const long t256 = (long)((M + 255) / 256) * (N / 256), t384 = (long)((M + 383) / 384) * (N / 256);
-                const double c256 = (double)((t256 + 255) / 256), c384 = 1.7 * (double)((t384 + 255) / 256);
-                if (c384 < c256) variant = 3;
-            }
-        }
-        if (variant == 3 && (N % 256 != 0 || (long)((M + 383) / 384) * 384 > a_rows_readable || e.scale || e.shift || e.residual || e.range_final)) variant = 2;
-        // 16-bit operands, K >= 2048: the four-wave direct-to-LDS tile on 16x16x32 MFMAs (4-8 % ahead of the
-        // register-staged eight-wave kernels on the launches of the benchmark step; identical bits).
-        if (h->gemm_variant == 0 && variant == 2 && !is_f32 && K >= h->gemm4d_min_k) variant = 7;
-        if ((variant == 7 || variant == 8) && is_f32) variant = 2;
-        // the large tiles drain eight columns per lane with 16-byte accesses
-        const bool wide_ok = N % 8 == 0 && (!e.out_lo || e.ld_lo % 8 == 0) && e.ld_f32 % 4 == 0 && (!e.residual || e.ld_res % 4 == 0) &&
-                             (e.split_col >= N || e.split_col % 8 == 0);
-        if (variant != 1 && !wide_ok) variant = 1;
-        if (e.residual && (e.scale || e.shift)) variant = 1;      // the large tiles compile their residual epilogues without the Rescaler
-        if (e.stats_part || e.fold_stats) variant = 7;       // LayerNorm-fold launches exist in gemm4d only (any M)
-        return variant;
+    // the handle's options that decide a launch (gemm_launch.hip.h)
+    GemmOptions gemm_options() const {
+        GemmOptions o;
+        o.gemm_variant = h->gemm_variant; o.gemm4d_min_k = h->gemm4d_min_k; o.gemm_tail_split = h->gemm_tail_split;
+        o.gemm_tile_order = h->gemm_tile_order; o.gemm_group = h->gemm_group;
+        return o;
     }
+    // the tile variant a launch takes: gemm_variant_for (gemm_launch.hip.h), the rule zett_op_fwd_gemm shares
+    int variant_for(int M, int N, int K, const GemmEpilogue<T>& e) const { return gemm_variant_for<T>(gemm_options(), a_rows_readable, M, N, K, e); }
 
     void gemm(const T* A, int lda, const T* Wp, int ldw, int M, int N, int K, const GemmEpilogue<T>& e) {
         if (rc || M <= 0) return;
         GemmArgs<T> g{A, lda, Wp, ldw, M, N, K, e};
         g.tile_order = h->gemm_tile_order;
         g.group = h->gemm_group;
-        g.row0 = h->gemm_tail_split == 1 ? -1 : h->gemm_tail_split == 2 ? ((M / 2 + 255) / 256) * 256 : h->gemm_tail_split == 3 ? -2 : 0;
+        g.row0 = gemm_row0_for(h->gemm_tail_split, M);
         const double fl = 2.0 * (double)M * (double)N * (double)K;
         hipEvent_t e0 = nullptr, e1 = nullptr;
         if (h->time_gemm) {
