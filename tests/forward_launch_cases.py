@@ -3,7 +3,7 @@ from the commit BEFORE a change of the forward's host orchestration, and tests/t
 under test.  Per case: the GEMM launch sequence (m, n, k, variant, epilogue), stats() without its timing fields, workspace_bytes()
 and the sha256 of every output's bytes.  The shapes are the smallest that reach each branch of the orchestration (csrc/zett_hip.hip):
 the LayerNorm launcher's four kernels, every ForwardMode, one and two chunks, two lanes, the pair lever, both head layouts, every
-destination store, the shared table, a prepared plan and the single-rows lever."""
+destination store, the shared table, a prepared plan, the single-rows lever, layer 0's Q/K/V per source id and the options of a GEMM launch."""
 import hashlib
 
 import numpy as np
@@ -58,6 +58,15 @@ CASES["prepared_other"] = ("h512", "f16", {}, "prepared_other")              # p
 for _cfg_name, _tag in (("h512", "single_rows"), ("h512_nolang", "single_rows_taken")):
     CASES[_tag] = (_cfg_name, "f16", {"single_rows": 2}, "forward")
     CASES[_tag + "_into"] = (_cfg_name, "f16", {"single_rows": 2}, "into_bf16_permuted")
+# "id_qkv": 2 (lever 6: layer 0's Q/K/V once per distinct source id, whenever possible — h512_nolang has no language position): alone, per
+# buffer row instead of per pair, over two chunks, through the fused destination store, and on a caller's table (the table_gather path)
+for _tag, _opt, _kind in (("id_qkv", {}, "forward"), ("id_qkv_nopairs", {"pair_dedupe": 0}, "forward"), ("id_qkv_chunks", {"max_chunk_tokens": 1024}, "forward"),
+                          ("id_qkv_into", {}, "into_bf16_permuted"), ("id_qkv_shared_table", {}, "shared_table")):
+    CASES[_tag] = ("h512_nolang", "f16", dict({"id_qkv": 2}, **_opt), _kind)
+# the options of a GEMM launch, "attention_fast" and "time_gemm" (event pairs around the launches: the same log and outputs as h512_default)
+for _tag, _opt in (("tail_split2", {"gemm_tail_split": 2}), ("tail_split3", {"gemm_tail_split": 3}), ("gemm_variant2", {"gemm_variant": 2}),
+                   ("attention_fast0", {"attention_fast": 0}), ("time_gemm", {"time_gemm": 1})):
+    CASES[f"h512_{_tag}"] = ("h512", "f16", _opt, "forward")
 
 TIMING_FIELDS = ("gemm_ms", "gemm_flops_timed")
 

@@ -37,3 +37,9 @@ def test_shared_table_reproduces_the_plain_forward():
     """(what the parent already guarantees, now on the recorded digests)"""
     assert GOLDEN["cases"]["shared_table"]["outputs"] == GOLDEN["cases"]["h512_default"]["outputs"]
     assert GOLDEN["cases"]["prepared"]["outputs"] == GOLDEN["cases"]["h512_default"]["outputs"]
+    assert GOLDEN["cases"]["id_qkv_shared_table"]["outputs"] == GOLDEN["cases"]["id_qkv"]["outputs"]
+
+
+def test_timing_the_launches_changes_neither_the_log_nor_the_outputs():
+    for key in ("gemm_log", "stats", "workspace_bytes", "outputs"):
+        assert GOLDEN["cases"]["h512_time_gemm"][key] == GOLDEN["cases"]["h512_default"][key], key

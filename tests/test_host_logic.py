@@ -550,6 +550,32 @@ def test_retokenizer_lexical_and_partition_are_units_of_their_own():
     assert {"retok.hip", "lexical.hip", "partition.hip"} <= set(build.SOURCES), build.SOURCES
 
 
+def test_model_plan_and_forward_are_units_of_their_own():
+    """The handle's three units see each other through forward_handle.hip.h and plan.hip.h only: the weights, options and getters
+    (model.hip) and the plan (plan.hip) reach no GEMM header, the plan not even the row kernels — an edit to a tile kernel or to a
+    row kernel recompiles neither — while the forward itself still reaches both."""
+    from zett_amd import build
+
+    def reached(name):
+        return {os.path.basename(p) for p in build._includes(os.path.join(build.CSRC, name))}
+
+    def gemm_headers(names):
+        return {n for n in names if n.startswith("gemm")}
+
+    assert {"model.hip", "plan.hip", "zett_hip.hip"} <= set(build.SOURCES), build.SOURCES
+    model, plan, forward = reached("model.hip"), reached("plan.hip"), reached("zett_hip.hip")
+    for unit in (model, plan, forward):
+        assert "forward_handle.hip.h" in unit and "common.hip.h" in unit, unit          # (the walk does follow the units' includes)
+    assert not gemm_headers(model), model
+    assert "rowops_launch.hip.h" in model, model                   # zett_finalize's conversions and one-off fold kernels
+    assert not gemm_headers(plan) and "rowops.hip.h" not in plan and "rowops_launch.hip.h" not in plan, plan
+    assert "scan.hip.h" in plan and "plan.hip.h" in plan, plan
+    assert {"rowops.hip.h", "gemm_launch.hip.h", "gemm.hip.h", "plan.hip.h"} <= forward, forward
+    assert not gemm_headers(reached("forward_handle.hip.h")) and not gemm_headers(reached("plan.hip.h"))
+    for name in ("model.hip", "plan.hip", "zett_hip.hip"):
+        assert not set(build.TRAINING_ONLY) & reached(name), name
+
+
 def test_training_primitives_refuse_bad_arguments_before_touching_the_device():
     """Error behaviour of the zett_op_* entry points at the boundary: arguments are validated before any launch, the return code is
     ZETT_E_INVALID and zett_last_error says why (no GPU needed: nothing is launched)."""

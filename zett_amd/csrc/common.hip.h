@@ -12,7 +12,7 @@
 #include <type_traits>
 
 #include "../../include/zett_hip.h"
-#include "gemm.hip.h"
+#include "elem.hip.h"
 
 namespace zett {
 
@@ -52,9 +52,13 @@ struct DeviceScope {
     ::zett::DeviceScope _scope(dev);                                                                 \
     if (_scope.err != hipSuccess) return ::zett::fail(ZETT_E_HIP, "hipSetDevice(%d) failed: %s", (int)(dev), hipGetErrorString(_scope.err))
 
-struct DevBuf {   // grow-only device allocation
+struct DevBuf {   // grow-only device allocation, freed with its owner
     void* p = nullptr;
     size_t bytes = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { release(); }
     int reserve(size_t need) {
         if (need <= bytes) return 0;
         if (p) { (void)hipFree(p); p = nullptr; bytes = 0; }
@@ -105,5 +109,18 @@ template <typename F> inline auto with_precision(int precision, F&& f) {
     if (precision == ZETT_PREC_BF16) return f(Arith<bf16_t>{});
     return f(Arith<float>{});
 }
+
+// The options of a handle that decide how one GEMM of the forward is launched (zett_set_option names; defaults of zett_create):
+// plain integers, kept here so that the handle can hold them without seeing a GEMM header (gemm_launch.hip.h reads them).
+struct GemmOptions {
+    int gemm_variant = 0;         // 0 auto, else the tile every launch that can takes: 1 = 128x128, 2 = 256x256 register-staged (8 waves),
+                                  // 3 = 384x256 LDS-DMA, 7 = 256x256 four-wave direct-to-LDS, 8 = as 7 with the generic epilogue drain
+    int gemm4d_min_k = 512;       // 16-bit launches with K >= this take the four-wave direct-to-LDS tile (r2: with the streamlined epilogues it is
+                                  // ahead of gemm8r down to K = 768: +1.8 % on the XLM-R workload)
+    int gemm_tail_split = 1;      // gemm4d: a launch's partly filled last round of 256 CUs as 128x256 tiles (gemm4d.hip.h gemm4d_row_split): 0 never,
+                                  // 1 when the split is cheaper (default), 2 = cut every launch in the middle, 3 = half tiles only (tests: same bits)
+    int gemm_tile_order = 0;      // gemm4d: 0 = column-tile-major groups, 1 = row-tile-major groups (A/B)
+    int gemm_group = 0;           // gemm4d: column (order 0) / row (order 1) tiles per group; 0 = the kernel's default, 4 (A/B)
+};
 
 }  // namespace zett

@@ -53,10 +53,7 @@ int run(const zett_fwd_gemm_desc& d, int32_t* variant_out, int32_t* mode_out, hi
     GemmOptions o;
     o.gemm_variant = d.gemm_variant; o.gemm4d_min_k = d.gemm4d_min_k; o.gemm_tail_split = d.gemm_tail_split;
     o.gemm_tile_order = d.gemm_tile_order; o.gemm_group = d.gemm_group;
-    GemmArgs<T> g{(const T*)d.a, d.lda, (const T*)d.w, d.ldw, d.m, d.n, d.k, e};
-    g.tile_order = o.gemm_tile_order;
-    g.group = o.gemm_group;
-    g.row0 = gemm_row0_for(o.gemm_tail_split, d.m);
+    const GemmArgs<T> g = gemm_args_for(o, (const T*)d.a, d.lda, (const T*)d.w, d.ldw, d.m, d.n, d.k, e);
     const int variant = gemm_variant_for<T>(o, (long)d.a_rows_readable, d.m, d.n, d.k, e);
     int mode = -1;
     if (variant == 7 || variant == 8) {

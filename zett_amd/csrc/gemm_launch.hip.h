@@ -12,6 +12,7 @@
 
 #include <type_traits>
 
+#include "common.hip.h"      // GemmOptions
 #include "gemm.hip.h"
 
 namespace zett {
@@ -36,15 +37,6 @@ inline int gemm_4d_dst_mode(const GemmArgs<float>&) { return -1; }
 int gemm_4d_launch_mode(const GemmArgs<f16_t>& g, bool generic_epilogue);
 int gemm_4d_launch_mode(const GemmArgs<bf16_t>& g, bool generic_epilogue);
 inline int gemm_4d_launch_mode(const GemmArgs<float>&, bool) { return -1; }
-
-// The options of a handle that decide how one GEMM of the forward is launched (zett_set_option names; defaults of zett_create).
-struct GemmOptions {
-    int gemm_variant = 0;         // 0 auto, else the tile every launch that can takes
-    int gemm4d_min_k = 512;       // 16-bit launches with K >= this take the four-wave direct-to-LDS tile
-    int gemm_tail_split = 1;      // gemm4d: 0 never, 1 auto (gemm4d_row_split), 2 cut every launch in the middle, 3 128x256 tiles only
-    int gemm_tile_order = 0;      // gemm4d: 0 = column-tile-major groups, 1 = row-tile-major groups
-    int gemm_group = 0;           // gemm4d: tiles per group; 0 = the kernel's default
-};
 
 // The tile variant a launch of the forward takes (Runner::gemm of zett_hip.hip and zett_op_fwd_gemm of gemm_entry.hip: the one rule).
 // a_rows_readable: rows the A operand buffer can be read for (the 384-row tile does not clamp rows).
@@ -84,6 +76,16 @@ inline int gemm_variant_for(const GemmOptions& o, long a_rows_readable, int M, i
 // GemmArgs::row0 as the launcher of gemm4d reads it (gemm4d.hip.h launch_gemm4d), from the gemm_tail_split option
 inline int gemm_row0_for(int gemm_tail_split, int M) {
     return gemm_tail_split == 1 ? -1 : gemm_tail_split == 2 ? ((M / 2 + 255) / 256) * 256 : gemm_tail_split == 3 ? -2 : 0;
+}
+
+// The arguments of one launch under the options `o`: what the launchers read of them besides the variant (Runner::gemm and zett_op_fwd_gemm)
+template <typename T>
+inline GemmArgs<T> gemm_args_for(const GemmOptions& o, const T* A, int lda, const T* W, int ldw, int M, int N, int K, const GemmEpilogue<T>& e) {
+    GemmArgs<T> g{A, lda, W, ldw, M, N, K, e};
+    g.tile_order = o.gemm_tile_order;
+    g.group = o.gemm_group;
+    g.row0 = gemm_row0_for(o.gemm_tail_split, M);
+    return g;
 }
 
 }  // namespace zett

@@ -1,6 +1,6 @@
 // rowops.hip.h — the HBM-bound kernels of the hypernet forward (gfx950).
 //
-//   plan_*          surface-form matrix -> packed-token plan (pad skipping, distinct ids)
+//   pair_rows       the plan (plan.hip.h; made by the kernels of plan.hip) per buffer row of a chunk
 //   gather_src      A2/A3: source-embedding gather + in_scaler + fallback select
 //   layernorm_rows  LayerNorm over H (+ the RobertaEmbeddings add for the embed variant)
 //   attention_rows  per-row bidirectional attention over <= L' packed positions
@@ -15,118 +15,14 @@
 
 #include <type_traits>
 
-#include "gemm.hip.h"
+#include "elem.hip.h"
+#include "plan.hip.h"
 #include "scan.hip.h"
 
 namespace zett {
 
 // (the kernels that are not templates are `static`: this header is part of more than one translation unit — zett_hip.hip and
 //  rowops_entry.hip — and each gets its own copy)
-
-// ---------------------------------------------------------------------------
-// Plan.  Reference semantics being preserved (modeling_hypernet.py:190, 220-234 and
-// the eager RobertaSelfAttention mask):
-//   * key j of row n is visible iff ids[n,j] != pad (the language token always is);
-//   * only hidden[:,0] is read out, so a position matters only as a visible key or as
-//     position 0 (a query even when it is pad);
-//   * a row whose keys are ALL masked attends uniformly to every position (additive
-//     finfo.min on every key), so such a row keeps all L positions, flagged uniform.
-// Everything else (pad positions of ordinary rows) never influences an output and is
-// not computed.
-// ---------------------------------------------------------------------------
-
-struct PlanArrays {
-    int32_t* row_count;     // [N]   packed positions of row n
-    int32_t* row_offset;    // [N+1] exclusive scan of row_count
-    uint8_t* row_uniform;   // [N]
-    int32_t* id_flag;       // [V]   1 if the id is referenced by a kept position
-    int32_t* id_slot;       // [V+1] exclusive scan of id_flag; id_slot[V] = distinct ids
-    int32_t* id_list;       // [<=V] slot -> id
-    int32_t* tok_slot;      // [T]   table slot of the token, -1 = language token
-    int32_t* tok_pos;       // [T]   position index (for position_embeddings)
-    int32_t* tok_row;       // [T]   row the packed position belongs to
-    // distinct (source id, position) pairs: what the embeddings' output — and so layer 0's Q/K/V — depends on
-    int32_t* tok_pkey;      // [T]   id * Lp + position (Lp = L + lang; the language token counts as id V)
-    int32_t* pair_flag;     // [(V+1)*Lp]   1 if the pair occurs (null: the lever is off for this call)
-    int32_t* pair_slot;     // [(V+1)*Lp+1] exclusive scan of pair_flag; last = distinct pairs
-    int32_t* tok_pair;      // [T]   pair slot of the packed position
-    int32_t* pair_tslot;    // [P]   table slot of the pair (-1 = language token)
-    int32_t* pair_pos;      // [P]   its position index
-    uint8_t* tok_key;       // [T]   visible as key
-    int32_t* err;           // [1]   set to 1 + row on an out-of-range id
-    int32_t* counters;      // [3]   behind row_offset[N]: distinct ids, the error word, distinct pairs — what the host reads with the row offsets, in ONE copy
-    int32_t n_pair_keys;    //       size of pair_flag (0: no pair plan)
-};
-
-static __global__ void plan_rows_kernel(const int32_t* __restrict__ sfm, int64_t n_rows, int seq, int pad, int lam,
-                                 int n_ids, PlanArrays p) {
-    const int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (n >= n_rows) return;
-    const int32_t* row = sfm + n * seq;
-    int visible = 0;
-    for (int j = 0; j < seq; ++j) {
-        const int id = row[j];
-        if (id < 0 || id >= n_ids) {          // F.embedding would raise IndexError here
-            atomicMax(p.err, (int)(n < 0x7ffffffe ? n + 1 : 0x7fffffff));
-            p.row_count[n] = 0;
-            p.row_uniform[n] = 2;             // poisoned: skipped by plan_tokens_kernel
-            return;
-        }
-        visible += (id != pad);
-    }
-    const bool uniform = (visible + lam) == 0;
-    int count;
-    if (uniform) {
-        count = seq;
-        for (int j = 0; j < seq; ++j) p.id_flag[row[j]] = 1;
-    } else {
-        count = visible + lam + (row[0] == pad ? 1 : 0);
-        for (int j = 0; j < seq; ++j)
-            if (j == 0 || row[j] != pad) p.id_flag[row[j]] = 1;
-    }
-    p.row_count[n] = count;
-    p.row_uniform[n] = uniform ? 1 : 0;
-}
-
-static __global__ void plan_tokens_kernel(const int32_t* __restrict__ sfm, int64_t n_rows, int seq, int pad, int lam,
-                                   int n_ids, PlanArrays p) {
-    const int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (n >= n_rows) return;
-    const int32_t* row = sfm + n * seq;
-    int t = p.row_offset[n];
-    if (p.row_uniform[n] == 2) return;
-    const bool uniform = p.row_uniform[n] == 1;
-    const int lp = seq + lam;
-    for (int j = 0; j < seq; ++j) {
-        const int id = row[j];
-        const bool vis = id != pad;
-        if (uniform || vis || j == 0) {
-            p.tok_slot[t] = p.id_slot[id];
-            p.tok_pos[t] = j;
-            p.tok_row[t] = (int32_t)n;
-            p.tok_key[t] = vis ? 1 : 0;
-            if (p.pair_flag) { const int key = id * lp + j; p.tok_pkey[t] = key; p.pair_flag[key] = 1; }
-            ++t;
-        }
-    }
-    if (lam) {
-        p.tok_slot[t] = -1;
-        p.tok_pos[t] = seq;
-        p.tok_row[t] = (int32_t)n;
-        p.tok_key[t] = 1;
-        if (p.pair_flag) { const int key = n_ids * lp + seq; p.tok_pkey[t] = key; p.pair_flag[key] = 1; }
-    }
-}
-
-// pair slot of every packed position, and (table slot, position) of every pair (tokens of one pair write the same values)
-static __global__ void plan_pairs_kernel(int64_t n_rows, PlanArrays p) {
-    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= p.row_offset[n_rows]) return;          // (the grid covers the worst case: the host does not know T yet)
-    const int ps = p.pair_slot[p.tok_pkey[t]];
-    p.tok_pair[t] = ps;
-    p.pair_tslot[ps] = p.tok_slot[t];
-    p.pair_pos[ps] = p.tok_pos[t];
-}
 
 // pair slot per BUFFER row of a chunk (position 0 first, chunk_row below): what the residual epilogue of layer 0 indexes with
 __device__ __forceinline__ int chunk_row(int t_rel, int row_rel, bool first, int rows, const int32_t* cls_slot);
@@ -136,16 +32,6 @@ static __global__ void pair_rows_kernel(int m, int tok0, int64_t row0, int rows,
     if (t >= m) return;
     const int n = p.tok_row[tok0 + t];
     brow_pair[chunk_row(t, (int)(n - row0), p.row_offset[n] == tok0 + t, rows, cls_slot)] = p.tok_pair[tok0 + t];
-}
-
-static __global__ void plan_idlist_kernel(int n_ids, PlanArrays p) {
-    const int id = blockIdx.x * blockDim.x + threadIdx.x;
-    if (id < n_ids && p.id_flag[id]) p.id_list[p.id_slot[id]] = id;
-    if (id == 0) {          // (the last kernel of a plan: every scan has run)
-        p.counters[0] = p.id_slot[n_ids];
-        p.counters[1] = p.err[0];
-        p.counters[2] = p.n_pair_keys ? p.pair_slot[p.n_pair_keys] : 0;
-    }
 }
 
 // ---------------------------------------------------------------------------

@@ -1,8 +1,10 @@
-// zett_hip.hip — C ABI of libzett_hip.so (see include/zett_hip.h).
+// zett_hip.hip — the hypernet forward of libzett_hip.so's C ABI (see include/zett_hip.h): zett_forward[_into],
+// zett_forward_table[_into], zett_table_rows, zett_workspace_bytes.  The handle they work on is forward_handle.hip.h; its weights,
+// options and getters are model.hip, the plan of a call plan.hip.
 //
 // Host-side orchestration of the hypernet forward on one MI355X:
 //
-//   plan      surface forms -> packed positions, distinct referenced source ids
+//   plan      surface forms -> packed positions, distinct referenced source ids (plan.hip)
 //   table     for each DISTINCT source id once: gather + in_scaler/fallback ->
 //             input_projection (Linear + ProjectorBlock)            [hoisting, exact]
 //   encoder   RobertaEmbeddings + hn_n_layers encoder layers over the PACKED
@@ -18,18 +20,15 @@
 #include <algorithm>
 #include <cstdlib>
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
-#include <cstring>
-#include <map>
-#include <string>
 #include <type_traits>
-#include <vector>
 
 #include "../../include/zett_hip.h"
 #include "common.hip.h"
+#include "forward_handle.hip.h"
 #include "gemm.hip.h"
 #include "gemm_launch.hip.h"
+#include "plan.hip.h"
 #include "rowops.hip.h"
 #include "rowops_launch.hip.h"
 
@@ -37,200 +36,7 @@ using namespace zett;
 
 namespace {
 
-struct Tensor {
-    float* f32 = nullptr;       // device fp32 copy (biases, LN, embeddings, ... and GEMM weights in F32 mode)
-    void* lo = nullptr;         // GEMM operand copy in the handle's arithmetic type
-    std::vector<int64_t> shape;
-    size_t numel = 0;
-};
-
 inline size_t round_up(size_t v, size_t m) { return (v + m - 1) / m * m; }
-
-// The model as the forward reads it: device pointers that own nothing (the handle's tensors and `owned` do), bound once by
-// zett_finalize.  A GEMM operand (Linear::w, Folded::w) is in the handle's arithmetic type, everything else fp32.  What the
-// config switches off stays null.
-struct Linear { const void* w = nullptr; const float* b = nullptr; };
-struct Affine { const float* w = nullptr; const float* b = nullptr; };      // LayerNorm (gamma, beta), Rescaler, bias projection
-struct Projector { Linear dense1, dense2; Affine ln; };
-// LayerNorm fold (16-bit modes): the gamma-folded operand of a GEMM that follows a LayerNorm, its row sums and beta-folded bias
-struct Folded { void* w = nullptr; float* c = nullptr; float* b = nullptr; };
-struct Layer {
-    Linear q, k, v;                    // as the checkpoint has them: read by zett_finalize only, which fuses them into
-    Linear qkv;                        // rows [q | k | v]: [3H, H], [3H]
-    Linear attn_out, up, down; Affine attn_ln, out_ln;
-    Folded fold_qkv, fold_up;          // qkv of layers >= 1 folded with the previous layer's out_ln, up with attn_ln
-};
-struct Head {
-    Projector block; Linear out;
-    const float* scale = nullptr; const float* shift = nullptr;      // Rescaler over the head's columns (first head: scaler | out_scaler for single_head)
-    Folded fold;                       // `out` folded with the block's LayerNorm (not for the split single head: its two-destination epilogue is the generic one)
-};
-struct Model {
-    const float* lang = nullptr; const float* token_type = nullptr; const float* position = nullptr; Affine emb_ln;
-    std::vector<Layer> layers;
-    const float* fallback = nullptr; Affine in_scaler, scaler, out_scaler, bias;
-    Linear in_proj; Projector in_block;      // input_projection.0 / .1
-    Head head_in, head_out;
-    float* head_one = nullptr;         // [head_out_width] ones / zeros: the Rescaler of a config without hn_rescale_embeddings, for the
-    float* head_zero = nullptr;        // folded head epilogue, which is compiled with it
-    // Lever 6 (id_qkv; null where it is not possible): layer 0's fused qkv folded with BOTH LayerNorms in front of it, for the GEMM on
-    // raw table rows — w = lo(gamma_t (.) gamma (.) W), c its row sums, b = (beta_t (.) gamma) W^T — and what the row kernel adds per
-    // position and column: id_cpos [max_positions, 3H] = (type0 + pos[p]) (gamma (.) W)^T, id_cw = colsum(gamma (.) W), id_bq = beta W^T + b
-    Folded id_u; float* id_cpos = nullptr; float* id_cw = nullptr; float* id_bq = nullptr;
-};
-// One weight of the declaration (declare_weights): its checkpoint name and shape, and the field of Model its device pointer goes
-// to — `operand` for a GEMM operand (converted to the arithmetic type, fp32 original freed in the 16-bit modes), else `vec`.
-struct WeightDecl { std::string name; std::vector<int64_t> shape; const void** operand; const float** vec; };
-
-}  // namespace
-
-constexpr int ID_QKV_MIN_HIDDEN = 4096;      // lever 6's default rule
-
-struct zett_hypernet {
-    zett_config cfg{};
-    int device = 0;
-    int precision = ZETT_PREC_BF16;
-    bool finalized = false;
-    std::map<std::string, Tensor> w;  // the uploaded tensors, by name: their owner (zett_load_weight, zett_finalize, zett_destroy)
-    std::vector<WeightDecl> decl;     // every weight the library reads, sorted by name (zett_create); its slots point into `m`
-    Model m;                          // what the forward reads
-    int ln_fold = 1;
-    std::vector<void*> owned;         // the fused / derived operands zett_finalize built: everything else to hipFree at destroy
-    // options
-    int64_t max_chunk_tokens = 0;          // 0 = auto: chunk_token_cap() below (131 072 at H = 4096, more for narrower hypernets)
-    int time_gemm = 0;
-    int cls_only_last = 1;
-    int pair_dedupe = 1;              // layer 0's Q/K/V once per distinct (source id, position) pair (do_forward)
-    int residual_lo = 1;              // 16-bit residual stream of the encoder (gemm4d LN16 producers): 1 = in f16 mode, 2 = in bf16 mode too (A/B), 0 = fp32 stream
-    int concurrent_lanes = 0;         // a one-chunk call as TWO half-vocabulary chunks on two streams (do_forward): 0 never, 1 auto (when the narrow GEMMs
-                                      // of the call leave > 8 % of their last round of 256 CUs idle: the 4 096-row shards of 8 GPUs), 2 always
-    hipStream_t lane_stream = nullptr;
-    hipEvent_t lane_ev[4] = {nullptr, nullptr, nullptr, nullptr};      // fork, lane 1: bias written / out_in written / done
-    int attention_fast = 1;           // rows of <= 8 packed positions: keys / values fetched once, all keys of a query side by side (rowops.hip.h)
-    int attention_pack = 1;           // a last column group of 256 / 128 / 64 columns (H = 768) takes 2 / 4 / 8 rows per wave instead of idle lanes (r6; same bits)
-    int gemm_tail_split = 1;          // gemm4d: a launch's partly filled last round of 256 CUs as 128x256 tiles (gemm4d.hip.h gemm4d_row_split): 0 never,
-                                      // 1 when the split is cheaper (default), 2 = cut every launch in the middle, 3 = half tiles only (tests: same bits)
-    int gemm_tile_order = 0;          // gemm4d: 0 = column-tile-major groups, 1 = row-tile-major groups (A/B)
-    int ln_rows8 = 1;                 // 16-bit modes, H <= 2048: LayerNorm launches on layernorm_rows8_kernel (eight columns per lane; rowops.hip.h); 0 = the float4 kernel (A/B)
-    int table_lo = 1;                 // 16-bit hoisted table with the ProjectorBlock's LayerNorm folded into the embeddings' kernel (with the 16-bit residual stream); 0 = fp32 table (A/B)
-    int gemm_group = 0;               // gemm4d: column (order 0) / row (order 1) tiles per group; 0 = the kernel's default, 4 (A/B)
-    int gemm4d_min_k = 512;           // 16-bit launches with K >= this take the four-wave direct-to-LDS tile (r2: with the streamlined epilogues it is ahead of gemm8r down to K = 768: +1.8 % on the XLM-R workload)
-    int gemm_variant = 0;             // 0 auto, 1 = 128x128, 2 = 256x256 register-staged (8 waves), 3 = 384x256 LDS-DMA,
-                                      // 7 = 256x256 four-wave direct-to-LDS, 8 = as 7 with the generic epilogue drain
-    // workspace
-    // The plan of a forward (integers: packed positions, distinct ids, pairs) lives in one of TWO slots that forwards take in
-    // turn, so that the plan of the NEXT forward can be made (zett_forward_prepare, on plan_stream) while the kernels of the
-    // current one still read theirs.
-    struct PlanSlot {
-        DevBuf i32, u8;
-        int32_t* host = nullptr;          // pinned: row offsets [N+1], distinct ids, error word, distinct pairs
-        size_t host_ints = 0;
-        hipEvent_t done = nullptr;        // the plan's kernels and copies have run
-        hipEvent_t released = nullptr;    // the forward that used this slot has finished with it
-        const int32_t* sfm = nullptr;     // what the slot was prepared for (zett_forward_prepare), pending until a forward takes it
-        int64_t n_rows = 0;
-        int seq = 0;
-        bool pair_plan = false;           // the layout it was made with (an option changed in between: the forward plans again)
-        const int32_t* ext_id_slot = nullptr;   // the id -> table-slot map its tok_slot was written with (null: the plan's own)
-        bool local_slots = false;         // lever 6 was configured: tok_slot holds the plan's own slots even with a caller's table
-        bool pending = false;
-    } plan[2];
-    PlanSlot table_plan;              // (ABI 8) scratch plan of zett_table_plan: the distinct ids of a WHOLE vocabulary, never taken by a forward
-    // (ABI 8) the hoisted table of the forward in flight comes from the caller (zett_forward_table): rows of the global distinct-id
-    // list computed by zett_table_rows — on this rank and on its peers — instead of this call's own distinct ids
-    struct ExtTable { const void* table = nullptr; const float* stats = nullptr; const int32_t* id_slot = nullptr; } ext;
-    int plan_cur = 0;                 // slot of the most recent forward
-    hipStream_t plan_stream = nullptr;
-    hipEvent_t plan_fork = nullptr;
-    DevBuf table, x0, yf, yt, big, pre, ctx, cf, ct, lnstats, lnparts;
-    hipEvent_t out_ready[2] = {nullptr, nullptr};      // zett_stream_wait_output: out_in / out_bias of the last forward complete
-    bool out_recorded = false;
-    int range_accumulate = 0;         // 1: zett_forward does not clear the range word, zett_check_range clears it after reading (a caller
-                                      // that runs several asynchronous forwards and asks once at the end: zett_amd/sharding.py)
-    int32_t* range_word = nullptr;    // device: zett_range_bits of the forward in flight (cleared when a forward starts)
-    int32_t* range_host = nullptr;    // pinned: where zett_check_range / zett_finalize read it
-    // (zett_forward_into) the row map's check against the destination (read with the plan's error word), and the fp32 rows of the head
-    // launches that take the staged fallback of the destination store (Runner::head_gemm)
-    // (dest_stage[1]: lane 1 of a "concurrent_lanes" pair — the two lanes' staged heads run at the same time)
-    DevBuf dest_word, dest_stage[2], dest_sink;
-    int32_t* dest_host = nullptr;
-    hipEvent_t dest_checked = nullptr;
-    // Lever 5 (Forward::plan_single_rows): rows with a single kept position first in the position-0 block, their query /
-    // key GEMM rows skipped.  single_map — reserved only when a forward takes the lever, outside zett_workspace_bytes like dest_sink —
-    // holds cls_row int64 [N] (buffer row -> vocabulary row), cls_slot int32 [N] (the inverse) and, behind them, the composition with a
-    // caller's row map; single_host is the pinned staging of the first two, single_copied the event behind their copy.
-    int single_rows = 1;              // 0 off, 1 auto (one chunk on one lane, at least one full round of 256x256 tiles saved per launch), 2 whenever possible
-    int64_t single_rows_last = 0;     // single rows the last forward skipped (zett_single_rows)
-    // Lever 6 (Forward::id_qkv_rows): layer 0's Q/K/V once per distinct source id
-    int id_qkv = 1;                   // 0 off, 1 when possible and hidden >= ID_QKV_MIN_HIDDEN, 2 whenever possible
-    int64_t id_qkv_last = 0;          // table rows layer 0's Q/K/V GEMM of the last forward ran on (zett_id_qkv)
-    DevBuf single_map;
-    void* single_host = nullptr;
-    size_t single_host_bytes = 0;
-    hipEvent_t single_copied = nullptr;
-    std::vector<hipEvent_t> ev;
-    size_t ev_used = 0;
-    std::vector<zett_gemm_record> gemm_log;     // every GEMM launch of the last forward (zett_get_gemm_log); "time_gemm": launch k has the event pair ev[2k], ev[2k + 1]
-    zett_stats stats{};
-};
-
-namespace {
-
-size_t elt_size(int precision) { return precision == ZETT_PREC_F32 ? 4 : 2; }
-
-// The ONE declaration of the model's weights (names and shapes: zett_amd/dims.py weight_shapes, minus the word-embedding table,
-// which nothing reads): what zett_load_weight accepts, what zett_finalize requires, converts and binds.  m.layers is sized here.
-std::vector<WeightDecl> declare_weights(const zett_config& c, Model& m) {
-    const int64_t H = c.hidden, I = c.intermediate, E = c.n_embd, EIN = c.n_in_embd;
-    std::vector<WeightDecl> d;
-    auto vec = [&](const std::string& n, std::vector<int64_t> shape, const float*& slot) { d.push_back({n, std::move(shape), nullptr, &slot}); };
-    auto linear = [&](const std::string& p, int64_t n, int64_t k, Linear& l) { d.push_back({p + "weight", {n, k}, &l.w, nullptr}); vec(p + "bias", {n}, l.b); };
-    auto norm = [&](const std::string& p, Affine& a) { vec(p + "weight", {H}, a.w); vec(p + "bias", {H}, a.b); };
-    auto scaler = [&](const std::string& p, int64_t n, Affine& a) { vec(p + "w", {1, n}, a.w); vec(p + "b", {1, n}, a.b); };
-    auto block = [&](const std::string& p, Projector& b) { linear(p + "dense1.", I, H, b.dense1); linear(p + "dense2.", H, I, b.dense2); norm(p + "ln.", b.ln); };
-    if (c.embed_lang) vec("lang_embeddings.weight", {c.n_langs, H}, m.lang);
-    vec("model.embeddings.token_type_embeddings.weight", {1, H}, m.token_type);
-    norm("model.embeddings.LayerNorm.", m.emb_ln);
-    vec("model.embeddings.position_embeddings.weight", {c.max_positions, H}, m.position);
-    m.layers.resize(c.layers);
-    for (int l = 0; l < c.layers; ++l) {
-        const std::string p = "model.encoder.layer." + std::to_string(l) + ".";
-        Layer& L = m.layers[l];
-        linear(p + "attention.self.query.", H, H, L.q); linear(p + "attention.self.key.", H, H, L.k); linear(p + "attention.self.value.", H, H, L.v);
-        linear(p + "attention.output.dense.", H, H, L.attn_out); norm(p + "attention.output.LayerNorm.", L.attn_ln);
-        linear(p + "intermediate.dense.", I, H, L.up);
-        linear(p + "output.dense.", H, I, L.down); norm(p + "output.LayerNorm.", L.out_ln);
-    }
-    vec("fallback_embeddings.weight", {c.n_extra, EIN}, m.fallback);
-    linear("input_projection.0.", H, EIN, m.in_proj); block("input_projection.1.", m.in_block);
-    block("output_projection.0.", m.head_in.block); linear("output_projection.1.", c.single_head ? EIN : E, H, m.head_in.out);
-    if (c.separate_out && !c.single_head) { block("output_projection_out.0.", m.head_out.block); linear("output_projection_out.1.", E, H, m.head_out.out); }
-    if (c.rescale) {
-        scaler("in_scaler.", EIN, m.in_scaler); scaler("scaler.", E, m.scaler);
-        if (c.separate_out) scaler("out_scaler.", E, m.out_scaler);
-    }
-    if (c.predict_bias) { vec("bias_projection.weight", {1, H}, m.bias.w); vec("bias_projection.bias", {1}, m.bias.b); }
-    std::sort(d.begin(), d.end(), [](const WeightDecl& a, const WeightDecl& b) { return a.name < b.name; });
-    return d;
-}
-
-int validate_config(const zett_config& c, int precision) {
-    if (c.n_embd <= 0 || c.hidden <= 0 || c.intermediate <= 0 || c.heads <= 0 || c.layers <= 0)
-        return fail(ZETT_E_INVALID, "non-positive dimension in zett_config");
-    if (c.n_in_embd != (c.separate_out ? 2 * c.n_embd : c.n_embd))
-        return fail(ZETT_E_INVALID, "n_in_embd must be 2*n_embd iff separate_out");
-    if (c.hidden % c.heads) return fail(ZETT_E_INVALID, "hidden %d not divisible by heads %d", c.hidden, c.heads);
-    const int d = c.hidden / c.heads;
-    if (d < 8 || d > 512 || (d & (d - 1))) return fail(ZETT_E_INVALID, "head_dim %d unsupported (need a power of two in [8,512])", d);
-    const int kq = precision == ZETT_PREC_F32 ? 32 : 64;
-    for (int k : {c.n_in_embd, c.hidden, c.intermediate})
-        if (k % kq) return fail(ZETT_E_INVALID, "contraction width %d is not a multiple of %d", k, kq);
-    if (c.n_embd % 4) return fail(ZETT_E_INVALID, "n_embd must be a multiple of 4");
-    if (c.n_extra < 1) return fail(ZETT_E_INVALID, "n_extra must be >= 1 (reference allocates max(hn_n_extra_tokens,1))");
-    if (c.pad_token_id < 0) return fail(ZETT_E_INVALID, "pad_token_id is required");
-    if (c.embed_lang && c.n_langs <= 0) return fail(ZETT_E_INVALID, "hn_embed_lang_id needs n_langs");
-    return 0;
-}
 
 // Device bytes zett_forward reserves, as a function of what the plan found (packed positions
 // Ttot, distinct ids D).  One definition shared by the forward, zett_table_rows and zett_workspace_bytes.
@@ -239,10 +45,6 @@ struct WorkspaceSizes {
     size_t table, x0, f32_rows, lo_rows, big, stats, parts;
     size_t total() const { return table + x0 + 3 * f32_rows + 3 * lo_rows + big + stats + parts; }
 };
-
-static int64_t pair_keys(const zett_config& c, int seq) {
-    return ((int64_t)c.original_vocab_size + c.n_extra + 1) * (int64_t)(seq + (c.embed_lang ? 1 : 0));
-}
 
 // Packed positions per encoder chunk when the caller has not set "max_chunk_tokens": 12 GiB of per-position workspace,
 // never under 131 072 positions.  That is 131 072 at H = 4096 (112 KB per position), 230 k at H = 2048, 640 k at
@@ -271,126 +73,16 @@ static WorkspaceSizes workspace_sizes(const zett_config& c, size_t es, int seq, 
     return w;
 }
 
-// Where the arrays of a plan lie in a slot (pure pointer arithmetic: the same answer when the plan is made and when a
-// forward takes it).  Pair plan (lever 4): only where it can pay — at least two encoder layers (layer 0 must not be the
-// position-0-only one), and a key space not much larger than the batch (a 250 k-id source vocabulary against 50 k rows
-// repeats few pairs and would pay for clearing and scanning 2 M flags).
-struct PlanLayout {
-    PlanArrays p{};
-    int32_t* scan_tmp = nullptr;
-    bool pair_plan = false;
-    int64_t PK = 0;
-    size_t n_clear = 0;          // int32 words at the head of the arena that a plan starts from zero
-    size_t words = 0;            // int32 words of the whole arena, scan scratch included
-};
-// s == null: sizes only (every pointer null).  worst_case: the arena of a plan WITH the pair plan, whatever the options say now.
-static PlanLayout plan_layout(const zett_hypernet* h, const zett_hypernet::PlanSlot* s, int64_t N, int seq, bool worst_case = false) {
-    const zett_config& c = h->cfg;
-    const int lam = c.embed_lang ? 1 : 0;
-    const int64_t V = (int64_t)c.original_vocab_size + c.n_extra;
-    const int64_t max_tok = N * (int64_t)(seq + lam);
-    PlanLayout L;
-    PlanArrays& p = L.p;
-    L.PK = pair_keys(c, seq);          // K = (V+1)(L+lang)
-    L.pair_plan = worst_case || (h->pair_dedupe && c.layers >= 2 && L.PK <= std::max<int64_t>(4 * max_tok, (int64_t)1 << 23) && L.PK < (int64_t)0x7fffffff);
-    int32_t* const base = s ? s->i32.as<int32_t>() : nullptr;
-    auto take = [&](int32_t*& array, int64_t n) { array = base ? base + L.words : nullptr; L.words += (size_t)n; };
-    // int32 arena, the one list of its arrays: what a plan clears first, in one piece — id_flag[V] pair_flag[PK] err[1] — then
-    // row_count[N] row_offset[N+1] counters[3] (read by the host in one copy with the row offsets) id_slot[V+1] id_list[V]
-    // tok_slot[T] tok_pos[T] tok_row[T] [pair plan: tok_pkey[T] tok_pair[T] pair_tslot[T] pair_pos[T] pair_slot[PK+1]] scan scratch
-    take(p.id_flag, V);
-    if (L.pair_plan) take(p.pair_flag, L.PK);
-    take(p.err, 1);
-    L.n_clear = L.words;
-    take(p.row_count, N); take(p.row_offset, N + 1); take(p.counters, 3);
-    take(p.id_slot, V + 1); take(p.id_list, V);
-    take(p.tok_slot, max_tok); take(p.tok_pos, max_tok); take(p.tok_row, max_tok);
-    p.n_pair_keys = L.pair_plan ? (int32_t)L.PK : 0;
-    if (L.pair_plan) {
-        take(p.tok_pkey, max_tok); take(p.tok_pair, max_tok); take(p.pair_tslot, max_tok); take(p.pair_pos, max_tok);
-        take(p.pair_slot, L.PK + 1);
-    }
-    take(L.scan_tmp, 2 * (std::max<int64_t>(std::max<int64_t>(N, V), L.PK) / SCAN_CHUNK + 2) + 1);
-    if (s) {
-        p.row_uniform = s->u8.as<uint8_t>();
-        p.tok_key = p.row_uniform + N;
-    }
-    return L;
-}
-// worst case of a slot's int32 arena for [N, seq] surface forms: what enqueue_plan reserves and zett_workspace_bytes counts
-static size_t plan_i32_bytes(const zett_hypernet* h, int64_t N, int seq) { return plan_layout(h, nullptr, N, seq, true).words * 4; }
-
-// Lever 6 as far as the configuration and the options decide it (what is left to the forward: ForwardMode::table_lo, which a
-// caller's table needs anyway): zett_finalize built the operands (16-bit mode, >= 2 layers, no language position) and the rule holds.
-static bool id_qkv_configured(const zett_hypernet* h) {
-    return h->id_qkv && h->m.id_u.w && (h->id_qkv == 2 || h->cfg.hidden >= ID_QKV_MIN_HIDDEN);
-}
-
-// The plan of one forward into slot s, on stream st: six small kernels, three scans, and the copy of the row offsets and the
-// three counters to pinned memory; s.done is recorded behind them.
-static int enqueue_plan(zett_hypernet* h, zett_hypernet::PlanSlot& s, const int32_t* sfm, int64_t N, int seq, hipStream_t st) {
-    const zett_config& c = h->cfg;
-    const int lam = c.embed_lang ? 1 : 0;
-    const int V = c.original_vocab_size + c.n_extra;
-    const int64_t max_tok = N * (int64_t)(seq + lam);
-    if (int rc = s.i32.reserve(plan_i32_bytes(h, N, seq))) return rc;
-    if (int rc = s.u8.reserve((size_t)N + (size_t)max_tok)) return rc;
-    const size_t need_ints = (size_t)N + 1 + 3;
-    if (s.host_ints < need_ints) {
-        if (s.host) (void)hipHostFree(s.host);
-        s.host = nullptr;
-        HIP_TRY(hipHostMalloc((void**)&s.host, need_ints * 4, hipHostMallocDefault));
-        s.host_ints = need_ints;
-    }
-    if (!s.done) HIP_TRY(hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
-    if (!s.released) HIP_TRY(hipEventCreateWithFlags(&s.released, hipEventDisableTiming));
-    const PlanLayout L = plan_layout(h, &s, N, seq);
-    const PlanArrays& p = L.p;
-    HIP_TRY(hipMemsetAsync(s.i32.p, 0, L.n_clear * 4, st));          // id_flag, pair_flag, err: one piece of the arena
-    const int rb = (int)((N + 255) / 256);
-    hipLaunchKernelGGL(plan_rows_kernel, dim3(rb), dim3(256), 0, st, sfm, N, seq, c.pad_token_id, lam, V, p);
-    launch_exclusive_scan(p.row_count, p.row_offset, N, L.scan_tmp, st);
-    launch_exclusive_scan(p.id_flag, p.id_slot, (int64_t)V, L.scan_tmp, st);
-    {
-        // (ABI 8) a forward on a caller-provided table: a token's table slot is its id's slot in the GLOBAL distinct-id list
-        PlanArrays pt = p;
-        // (lever 6 gathers the call's rows of that table into the handle's own table first and keeps the plan's own slots)
-        if (h->ext.id_slot && !id_qkv_configured(h)) pt.id_slot = const_cast<int32_t*>(h->ext.id_slot);
-        hipLaunchKernelGGL(plan_tokens_kernel, dim3(rb), dim3(256), 0, st, sfm, N, seq, c.pad_token_id, lam, V, pt);
-    }
-    if (L.pair_plan) {
-        launch_exclusive_scan(p.pair_flag, p.pair_slot, L.PK, L.scan_tmp, st);
-        hipLaunchKernelGGL(plan_pairs_kernel, dim3((unsigned)((max_tok + 255) / 256)), dim3(256), 0, st, N, p);
-    }
-    hipLaunchKernelGGL(plan_idlist_kernel, dim3((V + 255) / 256), dim3(256), 0, st, V, p);
-    HIP_TRY(hipGetLastError());
-    // the row offsets and, right behind them, the three counters (distinct ids, error word, distinct pairs) to the host: one copy
-    HIP_TRY(hipMemcpyAsync(s.host, p.row_offset, ((size_t)N + 1 + 3) * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipEventRecord(s.done, st));
-    s.sfm = sfm; s.n_rows = N; s.seq = seq; s.pair_plan = L.pair_plan; s.ext_id_slot = h->ext.id_slot; s.local_slots = id_qkv_configured(h);
-    return 0;
-}
-
 template <typename T>
-int do_forward(zett_hypernet* h, const int32_t* sfm, int64_t N, int seq, const void* src, int src_dtype, const zett_dest* dest,
+int do_forward(zett_hypernet* h, const ExtTable* ext, const int32_t* sfm, int64_t N, int seq, const void* src, int src_dtype, const zett_dest* dest,
                int lang_index, float* out_in, float* out_out, float* out_bias, hipStream_t st);
 template <typename T>
 int do_table_rows(zett_hypernet* h, const int32_t* id_list, int first, int count, const void* src, int src_dtype, void* table_out, float* stats_out, hipStream_t st);
 
-// What the entry points of the forward family (zett_forward[_into], zett_forward_table[_into], zett_forward_prepare, zett_table_plan,
-// zett_table_rows) check before they touch the device, in the one order in which they report it.  An entry point fills in what it
-// has; the fields say where the entry points differ.  Returns 0, an error code, or CALL_EMPTY: a valid call on no rows.
-constexpr int CALL_EMPTY = 1;
-struct CallCheck {
-    int64_t n_rows = 0; int32_t seq = 1;
-    bool shape = true;                  // [n_rows, seq] surface forms (zett_table_rows has a table range of its own instead)
-    bool empty_ok = false;              // n_rows == 0 is a call that does nothing, not a bad shape
-    bool null_arg = false, null_first = false;      // a required pointer is null; reported before the shape (zett_table_plan)
-    const char* null_text = "null tensor argument";
-    bool encoder = false, need_out_out = false; int32_t lang_index = 0;      // the call runs the encoder: positions, outputs, language
-    bool source = false; int src_dtype = ZETT_F32; int64_t v_src = 0;        // the call reads source embeddings
-    const char* table_mode = nullptr;   // the entry point's name when it needs the folded table, i.e. a 16-bit precision
-};
+}  // namespace
+
+namespace zett {
+
 int check_call(const zett_hypernet* h, const CallCheck& k) {
     if (!h) return fail(ZETT_E_INVALID, "null handle");
     if (!h->finalized) return fail(ZETT_E_STATE, "zett_finalize has not been called");
@@ -413,321 +105,10 @@ int check_call(const zett_hypernet* h, const CallCheck& k) {
     return 0;
 }
 
-}  // namespace
+}  // namespace zett
 
 // ---------------------------------------------------------------------------------
 extern "C" {
-
-const char* zett_last_error(void) { return g_err.c_str(); }
-int zett_abi_version(void) { return ZETT_ABI_VERSION; }
-
-int zett_create(const zett_config* cfg, int device, int precision, zett_hypernet** out) {
-    if (!cfg || !out) return fail(ZETT_E_INVALID, "null argument");
-    if (precision != ZETT_PREC_BF16 && precision != ZETT_PREC_F32 && precision != ZETT_PREC_F16) return fail(ZETT_E_INVALID, "unknown precision %d", precision);
-    if (int rc = validate_config(*cfg, precision)) return rc;
-    int ndev = 0;
-    HIP_TRY(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return fail(ZETT_E_INVALID, "device %d out of range (%d visible)", device, ndev);
-    ZETT_ON_DEVICE(device);
-    auto* h = new zett_hypernet();
-    h->cfg = *cfg;
-    h->device = device;
-    h->precision = precision;
-    h->decl = declare_weights(h->cfg, h->m);
-    if (hipMalloc((void**)&h->range_word, 64) != hipSuccess || hipHostMalloc((void**)&h->range_host, 64, hipHostMallocDefault) != hipSuccess ||
-        hipMemset(h->range_word, 0, 64) != hipSuccess) {
-        if (h->range_word) (void)hipFree(h->range_word);
-        if (h->range_host) (void)hipHostFree(h->range_host);
-        delete h;
-        return fail(ZETT_E_HIP, "allocation of the range word failed");
-    }
-    *out = h;
-    return 0;
-}
-
-int zett_destroy(zett_hypernet* h) {
-    if (!h) return 0;
-    ::zett::DeviceScope _scope(h->device);
-    for (auto& kv : h->w) {
-        if (kv.second.f32) (void)hipFree(kv.second.f32);
-        if (kv.second.lo && kv.second.lo != (void*)kv.second.f32) (void)hipFree(kv.second.lo);
-    }
-    for (void* p : h->owned) (void)hipFree(p);
-    for (DevBuf* b : {&h->table, &h->x0, &h->yf, &h->yt, &h->big, &h->pre, &h->ctx, &h->cf, &h->ct, &h->lnstats, &h->lnparts, &h->dest_word, &h->dest_stage[0], &h->dest_stage[1], &h->dest_sink, &h->single_map})
-        b->release();
-    if (h->single_host) (void)hipHostFree(h->single_host);
-    if (h->single_copied) (void)hipEventDestroy(h->single_copied);
-    for (zett_hypernet::PlanSlot* psp : {&h->plan[0], &h->plan[1], &h->table_plan}) {
-        zett_hypernet::PlanSlot& ps = *psp;
-        ps.i32.release(); ps.u8.release();
-        if (ps.host) (void)hipHostFree(ps.host);
-        if (ps.done) (void)hipEventDestroy(ps.done);
-        if (ps.released) (void)hipEventDestroy(ps.released);
-    }
-    if (h->plan_stream) (void)hipStreamDestroy(h->plan_stream);
-    if (h->plan_fork) (void)hipEventDestroy(h->plan_fork);
-    if (h->range_word) (void)hipFree(h->range_word);
-    if (h->range_host) (void)hipHostFree(h->range_host);
-    if (h->dest_host) (void)hipHostFree(h->dest_host);
-    if (h->dest_checked) (void)hipEventDestroy(h->dest_checked);
-    for (hipEvent_t e : h->out_ready) if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : h->lane_ev) if (e) (void)hipEventDestroy(e);
-    if (h->lane_stream) (void)hipStreamDestroy(h->lane_stream);
-    for (hipEvent_t e : h->ev) (void)hipEventDestroy(e);
-    delete h;
-    return 0;
-}
-
-int zett_load_weight(zett_hypernet* h, const char* name, const void* data, int dtype, const int64_t* shape, int ndim) {
-    if (!h || !name || !data || !shape || ndim < 1) return fail(ZETT_E_INVALID, "null argument");
-    if (h->finalized) return fail(ZETT_E_STATE, "weights are frozen after zett_finalize");
-    const std::string n(name);
-    auto it = std::lower_bound(h->decl.begin(), h->decl.end(), n, [](const WeightDecl& d, const std::string& key) { return d.name < key; });
-    if (it == h->decl.end() || it->name != n) return 0;   // e.g. model.embeddings.word_embeddings.weight: never read
-    std::vector<int64_t> got(shape, shape + ndim);
-    if (got != it->shape) {
-        std::string a, b;
-        for (auto v : got) a += std::to_string(v) + ",";
-        for (auto v : it->shape) b += std::to_string(v) + ",";
-        return fail(ZETT_E_INVALID, "%s: shape [%s] does not match the config's [%s]", name, a.c_str(), b.c_str());
-    }
-    ZETT_ON_DEVICE(h->device);
-    size_t numel = 1;
-    for (auto v : got) numel *= (size_t)v;
-    Tensor& t = h->w[n];
-    if (t.f32) { (void)hipFree(t.f32); t.f32 = nullptr; }
-    t.shape = got;
-    t.numel = numel;
-    HIP_TRY(hipMalloc((void**)&t.f32, numel * 4));
-    if (dtype == ZETT_F32) {
-        HIP_TRY(hipMemcpy(t.f32, data, numel * 4, hipMemcpyDefault));
-    } else if (dtype == ZETT_F16 || dtype == ZETT_BF16) {
-        void* stage = nullptr;
-        HIP_TRY(hipMalloc(&stage, numel * 2));
-        hipError_t e = hipMemcpy(stage, data, numel * 2, hipMemcpyDefault);
-        if (e == hipSuccess) {
-            const int blocks = (int)std::min<size_t>((numel + 255) / 256, 65535);
-            if (dtype == ZETT_F16) hipLaunchKernelGGL(convert_to_f32_kernel<1>, dim3(blocks), dim3(256), 0, 0, stage, t.f32, numel);
-            else hipLaunchKernelGGL(convert_to_f32_kernel<2>, dim3(blocks), dim3(256), 0, 0, stage, t.f32, numel);
-            e = hipDeviceSynchronize();
-        }
-        (void)hipFree(stage);
-        if (e != hipSuccess) return fail(ZETT_E_HIP, "upload of %s failed: %s", name, hipGetErrorString(e));
-    } else {
-        return fail(ZETT_E_INVALID, "unknown dtype %d", dtype);
-    }
-    return 0;
-}
-
-int zett_finalize(zett_hypernet* h) {
-    if (!h) return fail(ZETT_E_INVALID, "null handle");
-    if (h->finalized) return 0;
-    ZETT_ON_DEVICE(h->device);
-    std::vector<Tensor*> ts;          // the uploaded tensor of every declared weight, in the declaration's order
-    for (const WeightDecl& d : h->decl) {
-        auto it = h->w.find(d.name);
-        if (it == h->w.end()) return fail(ZETT_E_STATE, "missing weight: %s", d.name.c_str());
-        ts.push_back(&it->second);
-    }
-    const zett_config& c = h->cfg;
-    Model& m = h->m;
-    const size_t es = elt_size(h->precision);
-    // GEMM operands in the arithmetic type
-    for (size_t i = 0; i < ts.size(); ++i) {
-        Tensor& t = *ts[i];
-        if (!h->decl[i].operand) continue;
-        if (h->precision == ZETT_PREC_F32) { t.lo = t.f32; continue; }
-        HIP_TRY(hipMalloc(&t.lo, t.numel * 2));
-        const int blocks = (int)std::min<size_t>((t.numel / 4 + 255) / 256 + 1, 65535);
-        with_precision(h->precision, [&](auto a) {
-            using T = typename decltype(a)::type;
-            if constexpr (sizeof(T) == 2)       // (the fp32 mode left the loop above: no fp32 instantiation of the kernel exists)
-                hipLaunchKernelGGL(convert_f32_to_lo_kernel<T>, dim3(blocks), dim3(256), 0, 0, t.f32, (T*)t.lo, t.numel, h->range_word);
-        });
-    }
-    HIP_TRY(hipDeviceSynchronize());
-    // bind the model: a GEMM operand's copy in the arithmetic type, the fp32 tensor of everything else — the tensors as they are
-    // NOW, whatever order they were uploaded in and however often
-    for (size_t i = 0; i < ts.size(); ++i)
-        if (h->decl[i].operand) *h->decl[i].operand = ts[i]->lo;
-        else *h->decl[i].vec = ts[i]->f32;
-    auto original = [&](const Linear& l) -> const float* {      // the fp32 original of an operand (until it is freed below)
-        for (size_t i = 0; i < ts.size(); ++i)
-            if (h->decl[i].operand == &l.w) return ts[i]->f32;
-        return nullptr;
-    };
-    // fused QKV operand per layer: rows [q | k | v]
-    const size_t H = c.hidden;
-    for (Layer& L : m.layers) {
-        void* wq = nullptr; float* bq = nullptr;
-        HIP_TRY(hipMalloc(&wq, 3 * H * H * es));
-        HIP_TRY(hipMalloc((void**)&bq, 3 * H * 4));
-        h->owned.push_back(wq); h->owned.push_back(bq);
-        int k = 0;
-        for (const Linear* part : {&L.q, &L.k, &L.v}) {
-            HIP_TRY(hipMemcpy((char*)wq + (size_t)k * H * H * es, part->w, H * H * es, hipMemcpyDeviceToDevice));
-            HIP_TRY(hipMemcpy(bq + (size_t)k * H, part->b, H * 4, hipMemcpyDeviceToDevice));
-            ++k;
-        }
-        L.qkv = Linear{wq, bq};
-    }
-    // LayerNorm fold operands (rowops.hip.h fold_weight_kernel); needs the fp32 originals, which are freed below
-    if (h->precision != ZETT_PREC_F32 && c.hidden % 128 == 0) {
-        auto fold = [&](const float* w32, size_t N, size_t K, const Affine& ln, const float* bias, Folded& f) -> int {
-            HIP_TRY(hipMalloc(&f.w, N * K * es));
-            HIP_TRY(hipMalloc((void**)&f.c, N * 4));
-            HIP_TRY(hipMalloc((void**)&f.b, N * 4));
-            h->owned.push_back(f.w); h->owned.push_back(f.c); h->owned.push_back(f.b);
-            with_precision(h->precision, [&](auto a) {
-                using T = typename decltype(a)::type;
-                if constexpr (sizeof(T) == 2)
-                    launch_fold_weight<T>(0, w32, (int)N, (int)K, ln.w, ln.b, bias, (T*)f.w, f.c, f.b, h->range_word);
-            });
-            return 0;
-        };
-        float* tmp = nullptr;                       // fp32 [3H, H] fused QKV of one layer
-        HIP_TRY(hipMalloc((void**)&tmp, 3 * H * H * 4));
-        for (int l = 0; l < c.layers; ++l) {
-            Layer& L = m.layers[l];
-            if (int rc = fold(original(L.up), c.intermediate, H, L.attn_ln, L.up.b, L.fold_up)) return rc;
-            // lever 6 is possible for this configuration (what the options add: forward_mode's table_lo)
-            const bool id_qkv = l == 0 && c.layers >= 2 && !c.embed_lang && H * sizeof(float) <= 64 * 1024;
-            if (l == 0 && !id_qkv) continue;
-            int k = 0;
-            for (const Linear* part : {&L.q, &L.k, &L.v}) {
-                HIP_TRY(hipMemcpy(tmp + (size_t)k * H * H, original(*part), H * H * 4, hipMemcpyDeviceToDevice));
-                ++k;
-            }
-            if (l > 0) {
-                if (int rc = fold(tmp, 3 * H, H, m.layers[l - 1].out_ln, L.qkv.b, L.fold_qkv)) return rc;
-                continue;
-            }
-            // gamma_t (.) gamma and beta_t (.) gamma (fp32 products, made on the host), no bias: the fold of layer 0's qkv onto raw table rows
-            std::vector<float> gt(H), bt(H), ge(H), g2(H), b2(H);
-            HIP_TRY(hipMemcpy(gt.data(), m.in_block.ln.w, H * 4, hipMemcpyDeviceToHost));
-            HIP_TRY(hipMemcpy(bt.data(), m.in_block.ln.b, H * 4, hipMemcpyDeviceToHost));
-            HIP_TRY(hipMemcpy(ge.data(), m.emb_ln.w, H * 4, hipMemcpyDeviceToHost));
-            for (size_t i = 0; i < H; ++i) { g2[i] = gt[i] * ge[i]; b2[i] = bt[i] * ge[i]; }
-            float* aux = nullptr;                   // [H] gamma'', [H] beta'', [3H] zero bias
-            HIP_TRY(hipMalloc((void**)&aux, 5 * H * 4));
-            HIP_TRY(hipMemset(aux, 0, 5 * H * 4));
-            HIP_TRY(hipMemcpy(aux, g2.data(), H * 4, hipMemcpyHostToDevice));
-            HIP_TRY(hipMemcpy(aux + H, b2.data(), H * 4, hipMemcpyHostToDevice));
-            const Affine ln2{aux, aux + H};
-            if (int rc = fold(tmp, 3 * H, H, ln2, aux + 2 * H, m.id_u)) return rc;
-            HIP_TRY(hipMalloc((void**)&m.id_cpos, (size_t)c.max_positions * 3 * H * 4));
-            HIP_TRY(hipMalloc((void**)&m.id_cw, 3 * H * 4));
-            HIP_TRY(hipMalloc((void**)&m.id_bq, 3 * H * 4));
-            h->owned.push_back(m.id_cpos); h->owned.push_back(m.id_cw); h->owned.push_back(m.id_bq);
-            launch_pos_qkv(0, tmp, (int)(3 * H), (int)H, m.emb_ln.w, m.emb_ln.b, L.qkv.b, m.token_type, m.position, c.max_positions, m.id_cpos, m.id_cw, m.id_bq);
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipDeviceSynchronize());
-            (void)hipFree(aux);
-        }
-        // the output heads: Linear(LN_1e-6(.)) with the ProjectorBlock's LayerNorm folded in (not for the split single head,
-        // whose two-destination epilogue is the generic one)
-        if (!(c.single_head && c.separate_out)) {
-            const size_t w0 = c.single_head ? c.n_in_embd : c.n_embd;      // (= n_embd: a single head is not split here)
-            for (Head* hd : {&m.head_in, &m.head_out})
-                if (hd->out.w)
-                    if (int rc = fold(original(hd->out), w0, H, hd->block.ln, hd->out.b, hd->fold)) return rc;
-            std::vector<float> ones(w0, 1.0f), zeros(w0, 0.0f);
-            HIP_TRY(hipMalloc((void**)&m.head_one, w0 * 4));
-            HIP_TRY(hipMalloc((void**)&m.head_zero, w0 * 4));
-            h->owned.push_back(m.head_one); h->owned.push_back(m.head_zero);
-            HIP_TRY(hipMemcpy(m.head_one, ones.data(), w0 * 4, hipMemcpyHostToDevice));
-            HIP_TRY(hipMemcpy(m.head_zero, zeros.data(), w0 * 4, hipMemcpyHostToDevice));
-        }
-        HIP_TRY(hipDeviceSynchronize());
-        (void)hipFree(tmp);
-    }
-    // range guard: a weight (or gamma-folded weight) that does not fit the operand type is an error here, not an inf later
-    HIP_TRY(hipMemcpy(h->range_host, h->range_word, 4, hipMemcpyDeviceToHost));
-    if (h->range_host[0] & ZETT_RANGE_WEIGHT)
-        return fail(ZETT_E_RANGE, "a GEMM weight (or a LayerNorm-folded weight W*gamma) exceeds the half range (|w| > 65504 or not finite): "
-                                  "this checkpoint needs ZETT_PREC_BF16 or ZETT_PREC_F32");
-    // output Rescaler vectors laid out over the first head's columns
-    if (c.rescale) {
-        const size_t w0 = c.single_head ? c.n_in_embd : c.n_embd;
-        float* scale = nullptr; float* shift = nullptr;
-        HIP_TRY(hipMalloc((void**)&scale, w0 * 4));
-        HIP_TRY(hipMalloc((void**)&shift, w0 * 4));
-        h->owned.push_back(scale); h->owned.push_back(shift);
-        HIP_TRY(hipMemcpy(scale, m.scaler.w, c.n_embd * 4, hipMemcpyDeviceToDevice));
-        HIP_TRY(hipMemcpy(shift, m.scaler.b, c.n_embd * 4, hipMemcpyDeviceToDevice));
-        if (c.single_head && c.separate_out) {
-            HIP_TRY(hipMemcpy(scale + c.n_embd, m.out_scaler.w, c.n_embd * 4, hipMemcpyDeviceToDevice));
-            HIP_TRY(hipMemcpy(shift + c.n_embd, m.out_scaler.b, c.n_embd * 4, hipMemcpyDeviceToDevice));
-        }
-        m.head_in.scale = scale; m.head_in.shift = shift;
-        m.head_out.scale = m.out_scaler.w; m.head_out.shift = m.out_scaler.b;
-    }
-    // the fp32 originals of 16-bit GEMM operands are no longer needed
-    if (h->precision != ZETT_PREC_F32)
-        for (size_t i = 0; i < ts.size(); ++i)
-            if (h->decl[i].operand && ts[i]->f32) { (void)hipFree(ts[i]->f32); ts[i]->f32 = nullptr; }
-    h->finalized = true;
-    return 0;
-}
-
-int zett_set_option(zett_hypernet* h, const char* key, int64_t value) {
-    if (!h || !key) return fail(ZETT_E_INVALID, "null argument");
-    const std::string k(key);
-    if (k == "max_chunk_tokens") {
-        if (value < 1024) return fail(ZETT_E_INVALID, "max_chunk_tokens must be >= 1024");
-        h->max_chunk_tokens = value;
-    } else if (k == "time_gemm") {
-        h->time_gemm = value != 0;
-    } else if (k == "cls_only_last_layer") {
-        h->cls_only_last = value != 0;
-    } else if (k == "pair_dedupe") {
-        h->pair_dedupe = value != 0;
-    } else if (k == "residual_lo") {
-        if (value < 0 || value > 2) return fail(ZETT_E_INVALID, "residual_lo must be 0 (fp32 residual stream), 1 (16-bit stream in f16 mode) or 2 (in bf16 mode too)");
-        h->residual_lo = (int)value;
-    } else if (k == "concurrent_lanes") {
-        if (value < 0 || value > 2) return fail(ZETT_E_INVALID, "concurrent_lanes must be 0 (never), 1 (auto) or 2 (whenever a call is one chunk of >= 512 rows)");
-        h->concurrent_lanes = (int)value;
-    } else if (k == "attention_fast") {
-        h->attention_fast = value != 0;
-    } else if (k == "ln_fold") {
-        if (value < 0 || value > 2) return fail(ZETT_E_INVALID, "ln_fold must be 0 (off), 1 (encoder and output heads) or 2 (encoder only: A/B)");
-        h->ln_fold = (int)value;
-    } else if (k == "gemm_tail_split") {
-        if (value < 0 || value > 3) return fail(ZETT_E_INVALID, "gemm_tail_split must be 0 (never), 1 (auto), 2 (cut every gemm4d launch in the middle) or 3 (128x256 tiles only)");
-        h->gemm_tail_split = (int)value;
-    } else if (k == "attention_pack") {
-        h->attention_pack = value != 0;
-    } else if (k == "ln_rows8") {
-        h->ln_rows8 = value != 0;
-    } else if (k == "table_lo") {
-        h->table_lo = value != 0;
-    } else if (k == "gemm_group") {
-        if (value < 0 || value > 64) return fail(ZETT_E_INVALID, "gemm_group must be 0 (default: 4) .. 64");
-        h->gemm_group = (int)value;
-    } else if (k == "gemm_tile_order") {
-        if (value < 0 || value > 1) return fail(ZETT_E_INVALID, "gemm_tile_order must be 0 or 1");
-        h->gemm_tile_order = (int)value;
-    } else if (k == "gemm4d_min_k") {
-        if (value < 64) return fail(ZETT_E_INVALID, "gemm4d_min_k must be >= 64");
-        h->gemm4d_min_k = (int)value;
-    } else if (k == "range_accumulate") {
-        h->range_accumulate = value != 0;
-    } else if (k == "single_rows") {
-        if (value < 0 || value > 2) return fail(ZETT_E_INVALID, "single_rows must be 0 (off), 1 (auto) or 2 (whenever a call is one chunk on one lane)");
-        h->single_rows = (int)value;
-    } else if (k == "id_qkv") {
-        if (value < 0 || value > 2) return fail(ZETT_E_INVALID, "id_qkv must be 0 (off), 1 (when possible and hidden >= 4096) or 2 (whenever possible)");
-        h->id_qkv = (int)value;
-    } else if (k == "gemm_variant") {
-        if (value != 0 && value != 1 && value != 2 && value != 3 && value != 7 && value != 8)
-            return fail(ZETT_E_INVALID, "gemm_variant must be 0 (auto), 1 (128x128), 2 (256x256 register-staged), 3 (384x256), 7 (256x256 four-wave direct-to-LDS) or 8 (7 with the generic epilogue drain)");
-        h->gemm_variant = (int)value;
-    } else {
-        return fail(ZETT_E_INVALID, "unknown option %s", key);
-    }
-    return 0;
-}
 
 int zett_workspace_bytes(const zett_hypernet* h, int64_t n_rows, int32_t seq, int64_t* out_bytes) {
     if (!h || !out_bytes) return fail(ZETT_E_INVALID, "null argument");
@@ -736,82 +117,8 @@ int zett_workspace_bytes(const zett_hypernet* h, int64_t n_rows, int32_t seq, in
     const int64_t V = (int64_t)c.original_vocab_size + c.n_extra;
     const int64_t max_tok = n_rows * (int64_t)(seq + (c.embed_lang ? 1 : 0));
     // worst case of the plan: no pad position, every position a different source id
-    const WorkspaceSizes w = workspace_sizes(c, elt_size(h->precision), seq, max_tok, std::min<int64_t>(V, max_tok), h->max_chunk_tokens);
+    const WorkspaceSizes w = workspace_sizes(c, elt_size(h->precision), seq, max_tok, std::min<int64_t>(V, max_tok), h->opt.max_chunk_tokens);
     *out_bytes = (int64_t)(w.total() + plan_i32_bytes(h, n_rows, seq) + (size_t)n_rows + (size_t)max_tok);
-    return 0;
-}
-
-int zett_get_stats(const zett_hypernet* h, zett_stats* out) {
-    if (!h || !out) return fail(ZETT_E_INVALID, "null argument");
-    *out = h->stats;
-    return 0;
-}
-
-int zett_single_rows(const zett_hypernet* h, int64_t* out) {
-    if (!h || !out) return fail(ZETT_E_INVALID, "null argument");
-    *out = h->single_rows_last;
-    return 0;
-}
-
-int zett_id_qkv(const zett_hypernet* h, int64_t* out) {
-    if (!h || !out) return fail(ZETT_E_INVALID, "null argument");
-    *out = h->id_qkv_last;
-    return 0;
-}
-
-int zett_stream_wait_output(zett_hypernet* h, int which, void* stream) {
-    if (!h) return fail(ZETT_E_INVALID, "null handle");
-    if (which != ZETT_OUT_IN && which != ZETT_OUT_BIAS) return fail(ZETT_E_INVALID, "which must be ZETT_OUT_IN or ZETT_OUT_BIAS");
-    if (!h->out_recorded) return fail(ZETT_E_STATE, "no forward has run on this handle");
-    ZETT_ON_DEVICE(h->device);
-    HIP_TRY(hipStreamWaitEvent((hipStream_t)stream, h->out_ready[which], 0));
-    return 0;
-}
-
-int zett_get_gemm_log(const zett_hypernet* h, zett_gemm_record* out, int64_t capacity, int64_t* count) {
-    if (!h || !count || capacity < 0 || (capacity > 0 && !out)) return fail(ZETT_E_INVALID, "null argument");
-    *count = (int64_t)h->gemm_log.size();
-    for (int64_t i = 0; i < capacity && i < *count; ++i) out[i] = h->gemm_log[(size_t)i];
-    return 0;
-}
-
-int zett_check_range(zett_hypernet* h, void* stream, int32_t* flags) {
-    if (!h) return fail(ZETT_E_INVALID, "null handle");
-    ZETT_ON_DEVICE(h->device);
-    hipStream_t st = (hipStream_t)stream;
-    HIP_TRY(hipMemcpyAsync(h->range_host, h->range_word, 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    const int32_t w = h->range_host[0];
-    if (h->range_accumulate && w) HIP_TRY(hipMemsetAsync(h->range_word, 0, 4, st));
-    if (flags) *flags = w;
-    if (!w) return 0;
-    return fail(ZETT_E_RANGE, "the last forward left the range of its arithmetic:%s%s%s%s (precision %s)",
-                (w & ZETT_RANGE_SOURCE) ? " in_scaler(source_embeddings) beyond the half range;" : "",
-                (w & ZETT_RANGE_ACTIVATION) ? " a 16-bit activation (Q/K/V, FFN intermediate or the operand copy of the residual sum) beyond the half range;" : "",
-                (w & ZETT_RANGE_OUTPUT) ? " non-finite predicted embeddings;" : "",
-                (w & ZETT_RANGE_DEST) ? " a finite value beyond the range of an f16 destination (stored as inf);" : "",
-                h->precision == ZETT_PREC_F16 ? "f16: re-run with ZETT_PREC_BF16" : h->precision == ZETT_PREC_BF16 ? "bf16" : "f32");
-}
-
-int zett_forward_prepare(zett_hypernet* h, const int32_t* surface_forms, int64_t n_rows, int32_t seq, void* input_stream) {
-    CallCheck k;
-    k.n_rows = n_rows; k.seq = seq; k.empty_ok = true; k.null_arg = !surface_forms;
-    if (int rc = check_call(h, k)) return rc == CALL_EMPTY ? 0 : rc;
-    ZETT_ON_DEVICE(h->device);
-    if (!h->plan_stream) {      // highest priority: the plan's small workgroups must get CUs while a forward's GEMM tiles own the chip
-        int least = 0, greatest = 0;
-        HIP_TRY(hipDeviceGetStreamPriorityRange(&least, &greatest));
-        HIP_TRY(hipStreamCreateWithPriority(&h->plan_stream, hipStreamNonBlocking, greatest));
-    }
-    if (!h->plan_fork) HIP_TRY(hipEventCreateWithFlags(&h->plan_fork, hipEventDisableTiming));
-    zett_hypernet::PlanSlot& ps = h->plan[h->plan_cur ^ 1];
-    if (ps.pending) HIP_TRY(hipEventSynchronize(ps.done));           // replaces a prepared plan nobody took
-    // behind the surface forms (whatever input_stream holds now) and behind the forward that last read this slot
-    HIP_TRY(hipEventRecord(h->plan_fork, (hipStream_t)input_stream));
-    HIP_TRY(hipStreamWaitEvent(h->plan_stream, h->plan_fork, 0));
-    if (ps.released) HIP_TRY(hipStreamWaitEvent(h->plan_stream, ps.released, 0));
-    if (int rc = enqueue_plan(h, ps, surface_forms, n_rows, seq, h->plan_stream)) return rc;
-    ps.pending = true;
     return 0;
 }
 
@@ -849,16 +156,16 @@ int forward_entry(zett_hypernet* h, const int32_t* surface_forms, int64_t n_rows
     hipStream_t st = (hipStream_t)stream;
     if (checked == CALL_EMPTY) {
         h->stats = zett_stats{};
-        if (!h->range_accumulate) HIP_TRY(hipMemsetAsync(h->range_word, 0, 4, st));
-        for (hipEvent_t& e : h->out_ready) {
-            if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        if (!h->opt.range_accumulate) HIP_TRY(hipMemsetAsync(h->range_word.p, 0, 4, st));
+        for (Event& e : h->out_ready) {
+            if (!e) HIP_TRY(hipEventCreateWithFlags(&e.e, hipEventDisableTiming));
             HIP_TRY(hipEventRecord(e, st));
         }
         h->out_recorded = true;
         return 0;
     }
     return with_precision(h->precision, [&](auto a) {
-        return do_forward<typename decltype(a)::type>(h, surface_forms, n_rows, seq, source_embeddings, src_dtype, dest, lang_index, out_in, out_out, out_bias, st);
+        return do_forward<typename decltype(a)::type>(h, nullptr, surface_forms, n_rows, seq, source_embeddings, src_dtype, dest, lang_index, out_in, out_out, out_bias, st);
     });
 }
 
@@ -880,35 +187,6 @@ int zett_forward_into(zett_hypernet* h, const int32_t* surface_forms, int64_t n_
 }
 
 // ---- (ABI 8) the hoisted table shared between ranks: SURVEY 8e's optional second exchange ---------------------------------
-int zett_table_plan(zett_hypernet* h, const int32_t* surface_forms, int64_t n_rows, int32_t seq, int32_t* id_slot_out, int32_t* id_list_out,
-                    int64_t* n_ids_out, void* stream) {
-    CallCheck k;
-    k.n_rows = n_rows; k.seq = seq;
-    k.null_arg = !surface_forms || !id_slot_out || !id_list_out || !n_ids_out; k.null_text = "null argument"; k.null_first = true;
-    if (int rc = check_call(h, k)) return rc;
-    const zett_config& c = h->cfg;
-    const int V = c.original_vocab_size + c.n_extra;
-    ZETT_ON_DEVICE(h->device);
-    hipStream_t st = (hipStream_t)stream;
-    zett_hypernet::PlanSlot& ps = h->table_plan;
-    const zett_hypernet::ExtTable saved = h->ext;
-    h->ext = zett_hypernet::ExtTable{};          // (this plan numbers the ids itself)
-    const int rc = enqueue_plan(h, ps, surface_forms, n_rows, seq, st);
-    h->ext = saved;
-    if (rc) return rc;
-    HIP_TRY(hipEventSynchronize(ps.done));
-    const int32_t* hoff = ps.host;
-    if (hoff[n_rows + 2] != 0)
-        return fail(ZETT_E_INDEX, "surface-form row %d holds an id outside [0, %d) (original_vocab_size %d + %d fallback rows)",
-                    hoff[n_rows + 2] - 1, V, c.original_vocab_size, c.n_extra);
-    const int D = hoff[n_rows + 1];
-    const PlanLayout L = plan_layout(h, &ps, n_rows, seq);
-    HIP_TRY(hipMemcpyAsync(id_slot_out, L.p.id_slot, ((size_t)V + 1) * 4, hipMemcpyDeviceToDevice, st));
-    if (D > 0) HIP_TRY(hipMemcpyAsync(id_list_out, L.p.id_list, (size_t)D * 4, hipMemcpyDeviceToDevice, st));
-    *n_ids_out = D;
-    return 0;
-}
-
 int zett_table_rows(zett_hypernet* h, const int32_t* id_list, int64_t first, int64_t count, const void* source_embeddings, int src_dtype,
                     int64_t v_src, void* table_out, float* stats_out, void* stream) {
     CallCheck k;
@@ -940,12 +218,10 @@ int forward_table_entry(zett_hypernet* h, const int32_t* surface_forms, int64_t 
     if (int rc = check_call(h, k)) return rc;
     ZETT_ON_DEVICE(h->device);
     hipStream_t st = (hipStream_t)stream;
-    h->ext.table = table; h->ext.stats = table_stats; h->ext.id_slot = id_slot;
-    const int rc = with_precision(h->precision, [&](auto a) {
-        return do_forward<typename decltype(a)::type>(h, surface_forms, n_rows, seq, nullptr, ZETT_F32, dest, lang_index, out_in, out_out, out_bias, st);
+    const ExtTable ext{table, table_stats, id_slot};
+    return with_precision(h->precision, [&](auto a) {
+        return do_forward<typename decltype(a)::type>(h, &ext, surface_forms, n_rows, seq, nullptr, ZETT_F32, dest, lang_index, out_in, out_out, out_bias, st);
     });
-    h->ext = zett_hypernet::ExtTable{};
-    return rc;
 }
 
 }  // namespace
@@ -980,7 +256,7 @@ struct Runner {
     GemmEpilogue<T> epi() {
         GemmEpilogue<T> e{};
         e.split_col = 0x7fffffff;
-        e.range_flag = h->range_word;
+        e.range_flag = h->range_word.p;
         return e;
     }
 
@@ -988,29 +264,21 @@ struct Runner {
     bool staged_dst = false;    // (zett_forward_into) the launch in flight writes the staged fp32 rows of a destination (gemm log bit 11)
     int stage_lane = 0;         // (zett_forward_into) which staging buffer head_gemm uses: the lane's own (h->dest_stage[lane])
 
-    // the handle's options that decide a launch (gemm_launch.hip.h)
-    GemmOptions gemm_options() const {
-        GemmOptions o;
-        o.gemm_variant = h->gemm_variant; o.gemm4d_min_k = h->gemm4d_min_k; o.gemm_tail_split = h->gemm_tail_split;
-        o.gemm_tile_order = h->gemm_tile_order; o.gemm_group = h->gemm_group;
-        return o;
-    }
+    bool timing = false;        // "time_gemm": an event pair around every launch (a forward's; zett_table_rows keeps no log of its own)
+
     // the tile variant a launch takes: gemm_variant_for (gemm_launch.hip.h), the rule zett_op_fwd_gemm shares
-    int variant_for(int M, int N, int K, const GemmEpilogue<T>& e) const { return gemm_variant_for<T>(gemm_options(), a_rows_readable, M, N, K, e); }
+    int variant_for(int M, int N, int K, const GemmEpilogue<T>& e) const { return gemm_variant_for<T>(h->opt.gemm, a_rows_readable, M, N, K, e); }
 
     void gemm(const T* A, int lda, const T* Wp, int ldw, int M, int N, int K, const GemmEpilogue<T>& e) {
         if (rc || M <= 0) return;
-        GemmArgs<T> g{A, lda, Wp, ldw, M, N, K, e};
-        g.tile_order = h->gemm_tile_order;
-        g.group = h->gemm_group;
-        g.row0 = gemm_row0_for(h->gemm_tail_split, M);
+        const GemmArgs<T> g = gemm_args_for(h->opt.gemm, A, lda, Wp, ldw, M, N, K, e);
         const double fl = 2.0 * (double)M * (double)N * (double)K;
         hipEvent_t e0 = nullptr, e1 = nullptr;
-        if (h->time_gemm) {
+        if (timing) {
             while (h->ev.size() < h->ev_used + 2) {
                 hipEvent_t ev;
                 if (hipEventCreate(&ev) != hipSuccess) { rc = fail(ZETT_E_HIP, "hipEventCreate failed"); return; }
-                h->ev.push_back(ev);
+                h->ev.emplace_back().e = ev;
             }
             e0 = h->ev[h->ev_used++];
             e1 = h->ev[h->ev_used++];
@@ -1032,7 +300,7 @@ struct Runner {
             h->gemm_log.push_back(r);
         }
         const hipError_t err = launch_gemm_variant(variant, g, st);      // gemm_launch.hip.h: the tile kernels live in their own translation units
-        if (h->time_gemm) (void)hipEventRecord(e1, st);
+        if (timing) (void)hipEventRecord(e1, st);
         if (err != hipSuccess) { rc = fail(ZETT_E_HIP, "gemm launch failed: %s", hipGetErrorString(err)); return; }
         h->stats.executed_flops += fl;
         h->stats.gemm_launches += 1;
@@ -1074,8 +342,8 @@ struct Runner {
         const dim3 grid((unsigned)std::min<int64_t>(rows, 65535 * 16));
         with_dtype(d.dtype, [&](auto dt) {
             using OT = elem_t<decltype(dt)::value>;
-            if (vec) hipLaunchKernelGGL((dest_store_rows_kernel<OT, true>), grid, dim3(256), 0, st, S, ld_s, (OT*)d.p, d.ld, d.rows, (int64_t)rows, cols, h->range_word);
-            else hipLaunchKernelGGL((dest_store_rows_kernel<OT, false>), grid, dim3(256), 0, st, S, ld_s, (OT*)d.p, d.ld, d.rows, (int64_t)rows, cols, h->range_word);
+            if (vec) hipLaunchKernelGGL((dest_store_rows_kernel<OT, true>), grid, dim3(256), 0, st, S, ld_s, (OT*)d.p, d.ld, d.rows, (int64_t)rows, cols, h->range_word.p);
+            else hipLaunchKernelGGL((dest_store_rows_kernel<OT, false>), grid, dim3(256), 0, st, S, ld_s, (OT*)d.p, d.ld, d.rows, (int64_t)rows, cols, h->range_word.p);
         });
         check("dest_store");
     }
@@ -1092,7 +360,7 @@ struct Runner {
     void ln_launch(const char* what, const float* in, int rows, const float* gamma, const float* beta, float eps, float* of, T* ol, float* stats,
                    float* sum, const LnEmbed& embed, int t0, const LnReadout& readout) {
         const int H = h->cfg.hidden;
-        launch_layernorm<T, EMBED, READOUT, BT>(st, H, h->ln_rows8, in, H, rows, gamma, beta, eps, of, ol, stats, sum, embed, t0, readout);
+        launch_layernorm<T, EMBED, READOUT, BT>(st, H, h->opt.ln_rows8, in, H, rows, gamma, beta, eps, of, ol, stats, sum, embed, t0, readout);
         check(what);
     }
 
@@ -1170,10 +438,10 @@ template <typename T>
 ForwardMode forward_mode(const zett_hypernet* h) {
     const zett_config& c = h->cfg;
     ForwardMode m{};
-    m.fold = h->ln_fold && !std::is_same<T, float>::value && h->gemm_variant == 0 && c.hidden % 128 == 0 && c.hidden >= 512 && h->m.layers.back().fold_up.w != nullptr;
-    m.lo_stream = m.fold && c.layers >= 1 && sizeof(T) == 2 && (h->residual_lo == 2 || (h->residual_lo == 1 && std::is_same<T, f16_t>::value));
-    m.table_lo = m.lo_stream && h->table_lo != 0;
-    m.fold_heads = m.fold && h->ln_fold == 1 && h->m.head_in.fold.w != nullptr;
+    m.fold = h->opt.ln_fold && !std::is_same<T, float>::value && h->opt.gemm.gemm_variant == 0 && c.hidden % 128 == 0 && c.hidden >= 512 && h->m.layers.back().fold_up.w != nullptr;
+    m.lo_stream = m.fold && c.layers >= 1 && sizeof(T) == 2 && (h->opt.residual_lo == 2 || (h->opt.residual_lo == 1 && std::is_same<T, f16_t>::value));
+    m.table_lo = m.lo_stream && h->opt.table_lo != 0;
+    m.fold_heads = m.fold && h->opt.ln_fold == 1 && h->m.head_in.fold.w != nullptr;
     return m;
 }
 int needs_folded_table(const char* entry) {
@@ -1232,7 +500,7 @@ void table_phase(Runner<T>& R, const Workspace<T>& w, const int32_t* id_list, in
     for (int s0 = first; s0 < first + count && !R.rc; s0 += (int)MC) {
         const int m = (int)std::min<int64_t>(MC, first + count - s0);
         with_dtype(src_dtype, [&](auto sd) {          // (in_scaler: null without hn_rescale_embeddings)
-            launch_gather_src<T, decltype(sd)::value>(R.st, id_list, s0, m, src, c.n_in_embd, c.original_vocab_size, md.fallback, md.in_scaler.w, md.in_scaler.b, w.X0, h->range_word);
+            launch_gather_src<T, decltype(sd)::value>(R.st, id_list, s0, m, src, c.n_in_embd, c.original_vocab_size, md.fallback, md.in_scaler.w, md.in_scaler.b, w.X0, h->range_word.p);
         });
         R.check("gather_src");
         GemmEpilogue<T> e0 = R.epi();
@@ -1248,14 +516,12 @@ template <typename T>
 int do_table_rows(zett_hypernet* h, const int32_t* id_list, int first, int count, const void* src, int src_dtype, void* table_out, float* stats_out, hipStream_t st) {
     const ForwardMode mode = forward_mode<T>(h);
     if (!mode.table_lo) return needs_folded_table("zett_table_rows");
-    const WorkspaceSizes ws = workspace_sizes(h->cfg, sizeof(T), 1, count, count, h->max_chunk_tokens);
+    const WorkspaceSizes ws = workspace_sizes(h->cfg, sizeof(T), 1, count, count, h->opt.max_chunk_tokens);
     const size_t MCS = (size_t)ws.chunk_tokens + 768;
     if (int rc = reserve_workspace(h, ws, mode.fold, false)) return rc;
     Runner<T> R{h, st};
     R.a_rows_readable = (long)MCS;
-    // (per-launch events and the launch log belong to a forward: zett_forward resets both when it starts)
-    struct NoTiming { zett_hypernet* h; int saved; ~NoTiming() { h->time_gemm = saved; } } no_timing{h, h->time_gemm};
-    h->time_gemm = 0;
+    // (R.timing stays off: per-launch events and the launch log belong to a forward, which resets both when it starts)
     table_phase<T>(R, lane_workspace<T>(h, 0, MCS), id_list, first, count, src, src_dtype, ws.chunk_tokens, true, (T*)table_out, stats_out, nullptr);
     return R.rc;
 }
@@ -1265,7 +531,7 @@ int do_table_rows(zett_hypernet* h, const int32_t* id_list, int first, int count
 // second lane is joined to `st` and ps.released is recorded behind everything, so that a later zett_forward_prepare / zett_forward
 // never rewrites the plan under kernels still in flight.
 struct SlotGuard {
-    zett_hypernet* h; zett_hypernet::PlanSlot* ps; hipStream_t st; bool lane_forked = false;
+    zett_hypernet* h; PlanSlot* ps; hipStream_t st; bool lane_forked = false;
     ~SlotGuard() {
         if (lane_forked && h->lane_stream && h->lane_ev[3]) {
             (void)hipEventRecord(h->lane_ev[3], h->lane_stream);
@@ -1297,8 +563,8 @@ int read_gemm_timing(zett_hypernet* h, hipStream_t st) {
 template <typename T>
 struct Forward {
     using DestOut = typename Runner<T>::DestOut;
-    // the call
-    zett_hypernet* h; const int32_t* sfm; int64_t N; int seq; const void* src; int src_dtype; const zett_dest* dest; int lang_index;
+    // the call (ext: the caller's table of zett_forward_table[_into], else null)
+    zett_hypernet* h; const ExtTable* ext; const int32_t* sfm; int64_t N; int seq; const void* src; int src_dtype; const zett_dest* dest; int lang_index;
     float* out_in; float* out_out; float* out_bias; hipStream_t st;
     // what the stages find
     Runner<T> R{h, st};
@@ -1306,7 +572,7 @@ struct Forward {
     const Model& md = h->m;
     const int H = c.hidden, I = c.intermediate, E = c.n_embd;
     const ForwardMode mode = forward_mode<T>(h);
-    zett_hypernet::PlanSlot* ps = nullptr;
+    PlanSlot* ps = nullptr;
     PlanArrays p{};
     bool pair_plan = false;
     const int32_t* hoff = nullptr;        // pinned: row offsets [N + 1], then distinct ids, error word, distinct pairs
@@ -1330,19 +596,20 @@ struct Forward {
         h->stats.rows = N;
         h->ev_used = 0;
         h->gemm_log.clear();
+        R.timing = h->opt.time_gemm != 0;
         if (int rc = take_plan()) return rc;
         SlotGuard guard{h, ps, st};
         if (int rc = read_plan()) return rc;
         if (int rc = reserve()) return rc;
         // ---- table: input_projection once per distinct source id (A2-A4) -----------------
-        if (!h->ext.table)
+        if (!ext)
             table_phase<T>(R, lane_workspace<T>(h, 0, MCS), p.id_list, 0, D, src, src_dtype, MC, mode.table_lo, TBL16, TBLST, TBL);
         id_qkv_rows();
         if (R.rc) return R.rc;
         if (int rc = plan_single_rows()) return rc;      // (host work, under the table phase enqueued above)
         if (int rc = run_chunks(guard)) return rc;
         h->out_recorded = true;          // (ps.released — the plan slot may be rewritten behind it, zett_forward_prepare — is recorded by the guard)
-        return h->time_gemm ? read_gemm_timing(h, st) : 0;
+        return h->opt.time_gemm ? read_gemm_timing(h, st) : 0;
     }
 
     // ---- plan ---------------------------------------------------------------------
@@ -1350,14 +617,14 @@ struct Forward {
     // plan stream, the host waits for THAT (not for earlier work on st) and st is ordered behind it.  Otherwise the plan is
     // made here, on st, and the host waits for it — and so for whatever was enqueued on st before.
     int take_plan() {
-        zett_hypernet::PlanSlot& s = h->plan[h->plan_cur ^ 1];
+        PlanSlot& s = h->plan[h->plan_cur ^ 1];
         if (s.pending && s.sfm == sfm && s.n_rows == N && s.seq == seq && s.pair_plan == plan_layout(h, &s, N, seq).pair_plan &&
-            s.ext_id_slot == h->ext.id_slot && s.local_slots == id_qkv_configured(h)) {
+            s.ext_id_slot == (ext ? ext->id_slot : nullptr) && s.local_slots == id_qkv_configured(h)) {
             HIP_TRY(hipStreamWaitEvent(st, s.done, 0));
         } else {
             if (s.pending) HIP_TRY(hipEventSynchronize(s.done));       // a prepared plan nobody took: let it finish before the slot is reused
             if (s.released) HIP_TRY(hipStreamWaitEvent(st, s.released, 0));      // (the forward before the previous one read this slot)
-            if (int rc = enqueue_plan(h, s, sfm, N, seq, st)) return rc;
+            if (int rc = enqueue_plan(h, s, ext, sfm, N, seq, st)) return rc;
         }
         s.pending = false;
         h->plan_cur ^= 1;
@@ -1372,29 +639,29 @@ struct Forward {
         const PlanLayout PL = plan_layout(h, ps, N, seq);
         p = PL.p;
         pair_plan = PL.pair_plan;
-        if (!h->range_accumulate) HIP_TRY(hipMemsetAsync(h->range_word, 0, 4, st));          // range guard: the word of THIS forward (zett_check_range)
-        for (hipEvent_t& e : h->out_ready)
-            if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        if (!h->opt.range_accumulate) HIP_TRY(hipMemsetAsync(h->range_word.p, 0, 4, st));          // range guard: the word of THIS forward (zett_check_range)
+        for (Event& e : h->out_ready)
+            if (!e) HIP_TRY(hipEventCreateWithFlags(&e.e, hipEventDisableTiming));
         const bool dest_check = dest && dest->rows;
         if (dest_check) {
             if (int rc = h->dest_word.reserve(4)) return rc;
-            if (!h->dest_host) HIP_TRY(hipHostMalloc((void**)&h->dest_host, 4, hipHostMallocDefault));
-            if (!h->dest_checked) HIP_TRY(hipEventCreateWithFlags(&h->dest_checked, hipEventDisableTiming));
+            if (!h->dest_host.p) HIP_TRY(h->dest_host.alloc(4));
+            if (!h->dest_checked) HIP_TRY(hipEventCreateWithFlags(&h->dest_checked.e, hipEventDisableTiming));
             HIP_TRY(hipMemsetAsync(h->dest_word.p, 0, 4, st));
             hipLaunchKernelGGL(dest_rows_check_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, dest->rows, N, dest->n_dest_rows, h->dest_word.as<int32_t>());
             HIP_TRY(hipGetLastError());
-            HIP_TRY(hipMemcpyAsync(h->dest_host, h->dest_word.p, 4, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(h->dest_host.p, h->dest_word.p, 4, hipMemcpyDeviceToHost, st));
             HIP_TRY(hipEventRecord(h->dest_checked, st));
         }
         HIP_TRY(hipEventSynchronize(ps->done));
-        hoff = ps->host;
+        hoff = ps->host.p;
         if (hoff[N + 2] != 0)
             return fail(ZETT_E_INDEX, "surface-form row %d holds an id outside [0, %d) (original_vocab_size %d + %d fallback rows)",
                         hoff[N + 2] - 1, c.original_vocab_size + c.n_extra, c.original_vocab_size, c.n_extra);
         if (dest_check) {
             HIP_TRY(hipEventSynchronize(h->dest_checked));
-            if (h->dest_host[0] != 0)
-                return fail(ZETT_E_INDEX, "destination row map: rows[%d] is outside the destination's %lld rows", h->dest_host[0] - 1, (long long)dest->n_dest_rows);
+            if (h->dest_host.p[0] != 0)
+                return fail(ZETT_E_INDEX, "destination row map: rows[%d] is outside the destination's %lld rows", h->dest_host.p[0] - 1, (long long)dest->n_dest_rows);
         }
         Ttot = hoff[N];
         D = hoff[N + 1];
@@ -1406,20 +673,19 @@ struct Forward {
 
     // ---- workspace ------------------------------------------------------------------
     int reserve() {
-        const WorkspaceSizes ws = workspace_sizes(c, sizeof(T), seq, Ttot, D, h->max_chunk_tokens);
+        const WorkspaceSizes ws = workspace_sizes(c, sizeof(T), seq, Ttot, D, h->opt.max_chunk_tokens);
         MC = ws.chunk_tokens;
         MCS = (size_t)MC + 768;      // slack rows: the 384-row GEMM tile reads whole tiles of A (per lane, two lanes)
         if (int rc = reserve_workspace(h, ws, mode.fold, true)) return rc;
         R.a_rows_readable = (long)MCS;
         // (ABI 8) zett_forward_table: the table is the caller's — rows of the GLOBAL distinct-id list in the folded 16-bit layout,
         // computed by zett_table_rows here and on the peer ranks; tok_slot already holds global slots (enqueue_plan)
-        const bool ext_table = h->ext.table != nullptr;
-        if (ext_table && !mode.table_lo) return needs_folded_table("zett_forward_table");
+        if (ext && !mode.table_lo) return needs_folded_table("zett_forward_table");
         TBL = h->table.as<float>();
         // (lever 6: the call's rows of a caller's table are gathered into the handle's own table — gather_ext_table — and read from there)
-        const bool ext_direct = ext_table && !id_qkv_configured(h);
-        TBL16 = ext_direct ? (T*)const_cast<void*>(h->ext.table) : (T*)h->table.as<float>();
-        TBLST = ext_direct ? const_cast<float*>(h->ext.stats) : (float*)((char*)h->table.as<float>() + (((size_t)D * H * sizeof(T) + 15) / 16) * 16);
+        const bool ext_direct = ext && !id_qkv_configured(h);
+        TBL16 = ext_direct ? (T*)const_cast<void*>(ext->table) : (T*)h->table.as<float>();
+        TBLST = ext_direct ? const_cast<float*>(ext->stats) : (float*)((char*)h->table.as<float>() + (((size_t)D * H * sizeof(T) + 15) / 16) * 16);
         lang_vec = c.embed_lang ? md.lang + (size_t)lang_index * H : nullptr;
         return reserve_id_qkv(ws);
     }
@@ -1458,8 +724,8 @@ struct Forward {
     // behind reads the copy — the same bits.
     void id_qkv_rows() {
         if (!Du || R.rc) return;
-        if (h->ext.table) {
-            if constexpr (sizeof(T) == 2) launch_table_gather<T>(st, (const T*)h->ext.table, h->ext.stats, h->ext.id_slot, p.id_list, D, H, TBL16, TBLST);
+        if (ext) {
+            if constexpr (sizeof(T) == 2) launch_table_gather<T>(st, (const T*)ext->table, ext->stats, ext->id_slot, p.id_list, D, H, TBL16, TBLST);
             R.check("table_gather");
         }
         GemmEpilogue<T> e = R.epi();
@@ -1479,21 +745,20 @@ struct Forward {
     // launch loses — fill at least one round of the 256 CUs (less only empties part of a last round that is partly empty anyway).
     int plan_single_rows() {
         h->single_rows_last = 0;
-        if (!h->single_rows || seq + (c.embed_lang ? 1 : 0) <= 1 || Ttot > MC || two_lanes()) return 0;
+        if (!h->opt.single_rows || seq + (c.embed_lang ? 1 : 0) <= 1 || Ttot > MC || two_lanes()) return 0;
         int64_t ns = 0;
         for (int64_t n = 0; n < N; ++n) ns += hoff[n + 1] - hoff[n] == 1;
-        if (ns == 0 || (h->single_rows == 1 && (ns / 256) * (int64_t)(2 * H / 256) < 256)) return 0;
+        if (ns == 0 || (h->opt.single_rows == 1 && (ns / 256) * (int64_t)(2 * H / 256) < 256)) return 0;
         const size_t map_bytes = (size_t)N * 12, comp_at = round_up(map_bytes, 16);
         if (h->single_copied) HIP_TRY(hipEventSynchronize(h->single_copied));      // the staging's last copy has left it
-        else HIP_TRY(hipEventCreateWithFlags(&h->single_copied, hipEventDisableTiming));
+        else HIP_TRY(hipEventCreateWithFlags(&h->single_copied.e, hipEventDisableTiming));
         if (h->single_host_bytes < map_bytes) {
-            if (h->single_host) (void)hipHostFree(h->single_host);
-            h->single_host = nullptr; h->single_host_bytes = 0;
-            HIP_TRY(hipHostMalloc(&h->single_host, map_bytes, hipHostMallocDefault));
+            h->single_host_bytes = 0;
+            HIP_TRY(h->single_host.alloc(map_bytes));
             h->single_host_bytes = map_bytes;
         }
         if (int rc = h->single_map.reserve(comp_at + (size_t)N * 8)) return rc;
-        int64_t* hrow = (int64_t*)h->single_host;
+        int64_t* hrow = (int64_t*)h->single_host.p;
         int32_t* hslot = (int32_t*)(hrow + N);
         int64_t at_single = 0, at_other = ns;
         for (int64_t n = 0; n < N; ++n) {
@@ -1501,7 +766,7 @@ struct Forward {
             hslot[n] = (int32_t)slot;
             hrow[slot] = n;
         }
-        HIP_TRY(hipMemcpyAsync(h->single_map.p, h->single_host, map_bytes, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(h->single_map.p, h->single_host.p, map_bytes, hipMemcpyHostToDevice, st));
         HIP_TRY(hipEventRecord(h->single_copied, st));
         n_s = (int)ns;
         cls_row = h->single_map.as<int64_t>();
@@ -1591,7 +856,7 @@ struct Forward {
     // Self-attention of layer l: fused QKV (per distinct pair in layer 0 under lever 4), attention_rows_kernel into CTX.
     void attention(Chunk& k, int l, const Layer& L) {
         const Workspace<T>& w = k.w;
-        const bool cls_only = h->cls_only_last && l == c.layers - 1;
+        const bool cls_only = h->opt.cls_only_last && l == c.layers - 1;
         // raw: Zt holds the 16-bit copy of the pre-LayerNorm sum (LayerNorm fold: the previous layer's FFN-down wrote it
         // with the statistics in hs_stats) instead of the normalised operand — then this layer's QKV runs on the folded weight
         const T* wqkv = k.raw ? (const T*)L.fold_qkv.w : R.W(L.qkv);
@@ -1616,7 +881,7 @@ struct Forward {
             if constexpr (sizeof(T) == 2) {
                 const PairQkvRows rw = by_pair ? PairQkvRows{p.pair_tslot, p.pair_pos, 0, nullptr, nullptr, 0, 0, nullptr}
                                                : PairQkvRows{p.tok_slot, p.tok_pos, k.tok0, p.tok_row, p.row_offset, k.r0, k.rows, cls_slot};
-                launch_pair_qkv<T>(k.st, U, rw, by_pair ? k.P : k.m, k.hs_stats, md.id_cpos, seq, md.id_cw, md.id_bq, 3 * H, w.BIG, ld_q, h->range_word);
+                launch_pair_qkv<T>(k.st, U, rw, by_pair ? k.P : k.m, k.hs_stats, md.id_cpos, seq, md.id_cw, md.id_bq, 3 * H, w.BIG, ld_q, h->range_word.p);
                 R.check("pair_qkv");
             }
         } else if (!cls_only) {
@@ -1641,7 +906,7 @@ struct Forward {
             qkv(0, H, n_s, k.rows, w.BIG + (size_t)k.m * 2 * H, ld_q);   // Q [rows, H]  (rows <= m, BIG holds >= m x 3H)
             k.zrows = k.rows;
         }
-        launch_attention<T>(k.st, H, h->attention_fast, h->attention_pack, Q, ld_q, KV, KV + H, ld_kv, H / c.heads, p.row_offset, p.row_uniform, p.tok_key,
+        launch_attention<T>(k.st, H, h->opt.attention_fast, h->opt.attention_pack, Q, ld_q, KV, KV + H, ld_kv, H / c.heads, p.row_offset, p.row_uniform, p.tok_key,
                             k.r0, k.rows, k.tok0, scaling, cls_only ? 1 : 0, by_pair ? (const int32_t*)p.tok_pair : (const int32_t*)nullptr, w.CTX, cls_slot, n_s ? 1 : 0);
         R.check(cls_only ? "attention(position 0)" : "attention");
     }
@@ -1743,7 +1008,7 @@ struct Forward {
             if (!dest) bias_dtype = ZETT_F32;
             else ro.out_bias = (float*)dest->bias;
         }
-        ro.range_flag = h->range_word;
+        ro.range_flag = h->range_word.p;
         ro.in_lo = mode.lo_stream ? (const T*)k.w.Zt : (const T*)nullptr;       // (16-bit residual stream: the rows are read from the 16-bit copy of the sum)
         R.layernorm(k.hs_sum, k.rows, k.hs_gamma, k.hs_beta, c.ln_eps_encoder, k.w.Cf, k.w.Ct, nullptr, ro, bias_dtype);
         return R.rc ? 0 : output_ready(k, ZETT_OUT_BIAS, h->lane_ev[1]);      // out_bias complete
@@ -1805,19 +1070,19 @@ struct Forward {
     // vocabulary slower (28.9 -> 29.8; headline 53.1 -> 55.2 with the pair lever lost): the dispatcher interleaves the two
     // chains' workgroups, but each 256x256 tile still owns its CU, so only the partial last rounds gain.
     bool two_lanes() const {
-        if (!h->concurrent_lanes || Ttot > MC || N < 512) return false;
+        if (!h->opt.concurrent_lanes || Ttot > MC || N < 512) return false;
         const int Pn = pair_plan ? hoff[N + 3] : 0;
         const bool pairs_taken = pair_plan && Pn > 0 && (int64_t)Pn * 100 <= Ttot * 85;
         const double r = (double)((Ttot + 255) / 256) * (double)((H + 255) / 256) / 256.0;
-        return h->concurrent_lanes == 2 || (!pairs_taken && !h->time_gemm && H >= 1024 && r < 4.0 && (std::ceil(r) - r) / std::ceil(r) > 0.08);
+        return h->opt.concurrent_lanes == 2 || (!pairs_taken && !h->opt.time_gemm && H >= 1024 && r < 4.0 && (std::ceil(r) - r) / std::ceil(r) > 0.08);
     }
 
     // lane selection and the join
     int run_chunks(SlotGuard& guard) {
         if (two_lanes()) {
-            if (!h->lane_stream) HIP_TRY(hipStreamCreateWithFlags(&h->lane_stream, hipStreamNonBlocking));
-            for (hipEvent_t& e : h->lane_ev)
-                if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+            if (!h->lane_stream) HIP_TRY(hipStreamCreateWithFlags(&h->lane_stream.s, hipStreamNonBlocking));
+            for (Event& e : h->lane_ev)
+                if (!e) HIP_TRY(hipEventCreateWithFlags(&e.e, hipEventDisableTiming));
             // the split is a multiple of 256 rows (the position-0-only last layer and the heads keep their number of row tiles)
             int64_t ra = ((N / 2 + 128) / 256) * 256;
             ra = std::min<int64_t>(std::max<int64_t>(ra, 256), N - 1);
@@ -1848,9 +1113,9 @@ struct Forward {
 };
 
 template <typename T>
-int do_forward(zett_hypernet* h, const int32_t* sfm, int64_t N, int seq, const void* src, int src_dtype, const zett_dest* dest,
+int do_forward(zett_hypernet* h, const ExtTable* ext, const int32_t* sfm, int64_t N, int seq, const void* src, int src_dtype, const zett_dest* dest,
                int lang_index, float* out_in, float* out_out, float* out_bias, hipStream_t st) {
-    Forward<T> f{h, sfm, N, seq, src, src_dtype, dest, lang_index, out_in, out_out, out_bias, st};
+    Forward<T> f{h, ext, sfm, N, seq, src, src_dtype, dest, lang_index, out_in, out_out, out_bias, st};
     return f.run();
 }
 
