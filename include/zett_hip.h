@@ -960,7 +960,21 @@ int zett_op_pad_vocabulary(const void* surface_forms, int32_t sf_bytes, int64_t 
  * *status (device) is written by the call: an OR of zett_encode_status bits, 0 when all is well.  With a bit set the outputs are
  * unspecified, but every write stays inside them.  Integers only, the only atomic is the OR into *status: the same inputs give the same
  * bits.  Asynchronous on `stream`, no allocation: `workspace` (device, 16-byte aligned, zett_encode_workspace_bytes: about 180 bytes per
- * byte of text, most of it the worst-case state of words too long for LDS) is free once the call's work is done.  n_texts == 0 is a no-op. */
+ * byte of text, most of it the worst-case state of words too long for LDS) is free once the call's work is done.  n_texts == 0 is a no-op.
+ *
+ * zett_encode_texts_added: the same call with the tokenizer's ADDED TOKENS split out of the texts, as the library's added vocabulary does
+ * for tokens with normalized = false and no lstrip / rstrip / single_word.  The table is DEVICE memory: n_added
+ * tokens, token k the bytes added_bytes[added_offsets[k] .. added_offsets[k + 1]) (int32 offsets from 0 to n_added_bytes), each of 2 to 64
+ * bytes, in strictly ascending byte order (a token before every longer one that starts with it), with the id added_ids[k]; at most 512
+ * tokens.  A table that breaks this sets ZETT_ENCODE_BAD_TABLE (its offsets are clamped like the texts').
+ *   matches       leftmost-longest and non-overlapping on the raw bytes of every text: from byte i the first byte m >= i where a token
+ *                 matches is taken with the longest token that matches there; the search goes on behind the match.  A match lies wholly
+ *                 inside one text.
+ *   sections      what lies between two matches (or a text's end) is encoded as a text of its own — its own prefix decision, the
+ *                 pattern sees its end as a text's end —, an empty section gives nothing.
+ *   a match       gives exactly one id, added_ids[k]; it counts towards the cut at block_size and map_from / map_to apply to it.
+ * n_added == 0 writes exactly what zett_encode_texts writes (the table pointers may be null) and needs the same workspace;
+ * zett_encode_added_workspace_bytes is a few bytes per position more otherwise.  No atomic beyond the OR into *status. */
 #define ZETT_ENCODE_MAX_TEMPLATE 8
 enum zett_encode_flags {
     ZETT_ENCODE_MARKS_ARE_LETTERS = 1,   /* the letter class is [\p{L}\p{M}] (zett/utils.py:29) */
@@ -970,13 +984,20 @@ enum zett_encode_flags {
 enum zett_encode_prefix { ZETT_ENCODE_PREFIX_NONE = 0, ZETT_ENCODE_PREFIX_ALWAYS = 1, ZETT_ENCODE_PREFIX_UNLESS_SPACE = 2 };
 enum zett_encode_status {
     ZETT_ENCODE_NO_UNK = 1,        /* a word needs an unk id the model does not have (the library raises) */
-    ZETT_ENCODE_BAD_OFFSETS = 2    /* text_offsets is not non-decreasing from 0 to n_text */
+    ZETT_ENCODE_BAD_OFFSETS = 2,   /* text_offsets is not non-decreasing from 0 to n_text */
+    ZETT_ENCODE_BAD_TABLE = 4      /* zett_encode_texts_added: the token table's offsets, lengths or order */
 };
 int zett_encode_workspace_bytes(int64_t n_text, int64_t n_texts, int64_t* bytes);
 int zett_encode_texts(zett_retok* r, const uint8_t* text, const int64_t* text_offsets, int64_t n_texts, int64_t n_text, const uint8_t* class_table,
                       int64_t n_code_points, int32_t flags, int32_t prefix_mode, int32_t block_size, const int32_t* prefix_ids, int32_t n_prefix,
                       const int32_t* suffix_ids, int32_t n_suffix, const int32_t* map_from, const int32_t* map_to, int32_t n_map, int32_t pad_id, void* input_ids,
                       void* attention_mask, int32_t out_bytes, int64_t ld_out, void* workspace, int64_t workspace_bytes, int32_t* status, void* stream);
+int zett_encode_added_workspace_bytes(int64_t n_text, int64_t n_texts, int32_t n_added, int64_t* bytes);
+int zett_encode_texts_added(zett_retok* r, const uint8_t* text, const int64_t* text_offsets, int64_t n_texts, int64_t n_text, const uint8_t* class_table,
+                            int64_t n_code_points, int32_t flags, int32_t prefix_mode, int32_t block_size, const int32_t* prefix_ids, int32_t n_prefix,
+                            const int32_t* suffix_ids, int32_t n_suffix, const int32_t* map_from, const int32_t* map_to, int32_t n_map, int32_t pad_id, void* input_ids,
+                            void* attention_mask, int32_t out_bytes, int64_t ld_out, const uint8_t* added_bytes, const int32_t* added_offsets, const int32_t* added_ids,
+                            int32_t n_added, int32_t n_added_bytes, void* workspace, int64_t workspace_bytes, int32_t* status, void* stream);
 
 /* ---- tokenizer sampling (zett_amd/tokenizer_sampling.py DeviceTokenizerSampler; additive, ABI 8) -----------------------------------
  * What rust_utils.TokenizerSampler.sample_tokenizer computes for a batch of texts (rust_utils/src/lib.rs:70-249; restated in

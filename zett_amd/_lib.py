@@ -35,7 +35,8 @@ LABEL_WORKSPACE_BYTES = 16384                        # ZETT_LABEL_WORKSPACE_BYTE
 ENCODE_MAX_TEMPLATE = 8                              # ZETT_ENCODE_MAX_TEMPLATE
 ENCODE_MARKS_ARE_LETTERS, ENCODE_RESPLIT = 1, 2      # zett_encode_flags
 ENCODE_PREFIX_NONE, ENCODE_PREFIX_ALWAYS, ENCODE_PREFIX_UNLESS_SPACE = 0, 1, 2      # zett_encode_prefix
-ENCODE_NO_UNK, ENCODE_BAD_OFFSETS = 1, 2             # zett_encode_status
+ENCODE_NO_UNK, ENCODE_BAD_OFFSETS, ENCODE_BAD_TABLE = 1, 2, 4      # zett_encode_status
+ENCODE_MAX_ADDED, ENCODE_MAX_ADDED_BYTES = 512, 64   # zett_encode_texts_added: tokens of a table, bytes of a token
 SAMPLE_BAD_OFFSETS, SAMPLE_TABLE_FULL, SAMPLE_LIST_FULL, SAMPLE_SUM_OVERFLOW, SAMPLE_OUT_FULL = 2, 4, 8, 16, 32      # zett_sample_status
 VOCAB_NOT_A_SAMPLE, VOCAB_DUPLICATE, VOCAB_TABLE_FULL, VOCAB_OUT_FULL = 1, 2, 4, 8      # zett_vocab_status
 VOCAB_SCORES_THROUGH_JSON = 1                        # zett_vocab_flags
@@ -68,7 +69,7 @@ ABI_SYMBOLS = (
     # the rest of the collator (zett_amd/collate.py label_batch, pad_vocabulary)
     "zett_op_label_batch", "zett_op_pad_vocabulary",
     # text encoding (zett_amd/text_encode.py DeviceTextEncoder)
-    "zett_encode_workspace_bytes", "zett_encode_texts",
+    "zett_encode_workspace_bytes", "zett_encode_texts", "zett_encode_added_workspace_bytes", "zett_encode_texts_added",
     # tokenizer sampling (zett_amd/tokenizer_sampling.py DeviceTokenizerSampler)
     "zett_sampler_create", "zett_sampler_destroy", "zett_sampler_depth", "zett_sampler_workspace_bytes", "zett_sampler_sample", "zett_sampler_table",
     # the sampled tokenizer's vocabulary and encoder tables (zett_amd/sampled_vocab.py DeviceSampledVocabulary)
@@ -261,6 +262,8 @@ def load():
         lib.zett_op_pad_vocabulary.argtypes = [P, I32, I64, I32, I64, I64, P, I32, P, P, P, P, P]
         lib.zett_encode_workspace_bytes.argtypes = [I64, I64, C.POINTER(I64)]
         lib.zett_encode_texts.argtypes = [P, P, P, I64, I64, P, I64, I32, I32, I32, P, I32, P, I32, P, P, I32, I32, P, P, I32, I64, P, I64, P, P]
+        lib.zett_encode_added_workspace_bytes.argtypes = [I64, I64, I32, C.POINTER(I64)]
+        lib.zett_encode_texts_added.argtypes = [P, P, P, I64, I64, P, I64, I32, I32, I32, P, I32, P, I32, P, P, I32, I32, P, P, I32, I64, P, P, P, I32, I32, P, I64, P, P]
         lib.zett_sampler_create.argtypes = [C.c_int, I32, I64, I64, I64, C.POINTER(P)]
         lib.zett_sampler_destroy.argtypes = [P]
         lib.zett_sampler_depth.argtypes = [P, C.POINTER(I32)]

@@ -296,7 +296,7 @@ class DeviceCollator:
         if list(tokenizer.all_special_tokens) != self.special_tokens:
             raise ValueError("the tokenizer's special tokens are not the reference's")
         self.tokenizer = tokenizer
-        self.encoder = DeviceTextEncoder.from_tokenizer(tokenizer, self.device)
+        self.encoder = DeviceTextEncoder.from_tokenizer(tokenizer, self.device, split_added_tokens=True)          # (packed texts hold the eos string)
         v = len(tokenizer)
         tokens = tokenizer.convert_ids_to_tokens(range(v))
         import numpy as np

@@ -11,6 +11,10 @@
 //   walk       a lane per text: the leftmost-first matches of the split pattern as a state machine over the code bytes; a flag at
 //              every match start (ZETT_ENCODE_RESPLIT: every match is matched again, on its own, with the plain pattern).  Sequential by
 //              definition: where a match starts depends on where the previous one ended
+//   (cut)      zett_encode_texts_added with a table of added tokens, between classify and walk: a thread per byte finds the longest
+//              token that matches there inside the byte's own text (the sorted table narrowed byte by byte), and the walk takes the
+//              candidates leftmost-first, walks every section between two matches as a text of its own and flags the match as a word
+//              of one id.  The match's last position is the slot of the section behind it, so no position is added
 //   compact    the flags into the word list woff[] — scan.hip.h's count / scan / place: a wave owns 1024 positions, one workgroup
 //              scans the segment counts
 //              (these three are the word stage of text_words.hip.h — kernels, workspace layout and launches: tokenizer_sample.hip
@@ -51,9 +55,10 @@ static_assert(sizeof(Lists) < 4096 - 512, "the lists must fit the kernel-argumen
 // workspace, in bytes: the word stage, then what the words and pack kernels add (every array starts on a 16-byte boundary)
 struct Layout {
     WordLayout words;
-    int64_t counts, ids, scratch, bytes;
+    int64_t counts, ids, scratch, first, cand, bytes;
 };
-Layout layout(int64_t n_text, int64_t b) {
+// added: the cut step's two arrays behind everything else (what comes before them does not move)
+Layout layout(int64_t n_text, int64_t b, bool added = false) {
     Layout L{};
     Carve w;
     L.words = word_layout(w, n_text, b);
@@ -61,15 +66,22 @@ Layout layout(int64_t n_text, int64_t b) {
     L.counts = w.take(np * 4);
     L.ids = w.take(np * 8);                         // 2 ids per position
     L.scratch = w.take((np * kScrPerByte + 64) * 4);
+    if (added) {
+        L.first = w.take(257 * 4);
+        L.cand = w.take(np * 2);
+    }
     L.bytes = w.bytes;
     return L;
 }
 
 // Stage 2 of the retokenizer, a lane per word (retok_tokens_kernel's shape): no special-token lookup, no byte table — the word's bytes
-// are the text's bytes.  ids of word w at ids[2 * woff[w] ...), its count in counts[w].
+// are the text's bytes.  ids of word w at ids[2 * woff[w] ...), its count in counts[w].  ADDED: a word with kFlagAdded is a split-out
+// token and gives its one id from the table.
+template <bool ADDED>
 __global__ __launch_bounds__(64) void encode_words_kernel(RetokTables t, const uint8_t* __restrict__ raw, const uint8_t* __restrict__ flags,
                                                           const int32_t* __restrict__ woff, const int32_t* __restrict__ totals, int32_t* __restrict__ ids,
-                                                          int32_t* __restrict__ counts, int32_t* __restrict__ scratch, int* __restrict__ status) {
+                                                          int32_t* __restrict__ counts, int32_t* __restrict__ scratch, int* __restrict__ status,
+                                                          const uint16_t* __restrict__ cand, const int32_t* __restrict__ added_ids, int n_added) {
     __shared__ RetokLds L;
     __shared__ __attribute__((aligned(16))) uint8_t s_text[RT_TEXT_BYTES + 16];
     __shared__ __attribute__((aligned(8))) int32_t s_arena[RT_ARENA_WORDS];
@@ -93,6 +105,11 @@ __global__ __launch_bounds__(64) void encode_words_kernel(RetokTables t, const u
     const uint8_t* sg = raw + o0;
     RowWriter w{ids + 2 * (int64_t)o0, 2 * len, 0};
     bool todo = live && len > 0 && !(flags[o0] & 2);
+    if (ADDED && todo && (flags[o0] & kFlagAdded)) {
+        const int k = cand[o0];
+        w.push(added_ids[(k < 1 ? 1 : (k > n_added ? n_added : k)) - 1]);
+        todo = false;
+    }
     if (todo && t.kind == ZETT_RETOK_BPE && t.ignore_merges) {
         const int id = text_lds ? whole_token_id<LdsMem>(t.pieces, t.piece_mask, t.piece_blob, sl, len)
                                 : whole_token_id<GlobalMem>(t.pieces, t.piece_mask, t.piece_blob, sg, len);
@@ -221,10 +238,28 @@ int zett_encode_workspace_bytes(int64_t n_text, int64_t n_texts, int64_t* bytes)
     return 0;
 }
 
+int zett_encode_added_workspace_bytes(int64_t n_text, int64_t n_texts, int32_t n_added, int64_t* bytes) {
+    if (int rc = shape_args("text encoding", n_text, n_texts)) return rc;
+    if (!bytes) return fail(ZETT_E_INVALID, "null argument");
+    if (n_added < 0 || n_added > kMaxAdded) return fail(ZETT_E_INVALID, "%d added tokens: a table holds at most %d", (int)n_added, kMaxAdded);
+    *bytes = layout(n_text, n_texts, n_added > 0).bytes;
+    return 0;
+}
+
 int zett_encode_texts(zett_retok* r, const uint8_t* text, const int64_t* text_offsets, int64_t n_texts, int64_t n_text, const uint8_t* class_table,
                       int64_t n_code_points, int32_t flags, int32_t prefix_mode, int32_t block_size, const int32_t* prefix_ids, int32_t n_prefix,
                       const int32_t* suffix_ids, int32_t n_suffix, const int32_t* map_from, const int32_t* map_to, int32_t n_map, int32_t pad_id, void* input_ids,
                       void* attention_mask, int32_t out_bytes, int64_t ld_out, void* workspace, int64_t workspace_bytes, int32_t* status, void* stream) {
+    return zett_encode_texts_added(r, text, text_offsets, n_texts, n_text, class_table, n_code_points, flags, prefix_mode, block_size, prefix_ids, n_prefix, suffix_ids,
+                                   n_suffix, map_from, map_to, n_map, pad_id, input_ids, attention_mask, out_bytes, ld_out, nullptr, nullptr, nullptr, 0, 0, workspace,
+                                   workspace_bytes, status, stream);
+}
+
+int zett_encode_texts_added(zett_retok* r, const uint8_t* text, const int64_t* text_offsets, int64_t n_texts, int64_t n_text, const uint8_t* class_table,
+                      int64_t n_code_points, int32_t flags, int32_t prefix_mode, int32_t block_size, const int32_t* prefix_ids, int32_t n_prefix,
+                      const int32_t* suffix_ids, int32_t n_suffix, const int32_t* map_from, const int32_t* map_to, int32_t n_map, int32_t pad_id, void* input_ids,
+                      void* attention_mask, int32_t out_bytes, int64_t ld_out, const uint8_t* added_bytes, const int32_t* added_offsets, const int32_t* added_ids,
+                      int32_t n_added, int32_t n_added_bytes, void* workspace, int64_t workspace_bytes, int32_t* status, void* stream) {
     if (!r) return fail(ZETT_E_INVALID, "null argument");
     if (!r->tokenizes()) return fail(ZETT_E_STATE, "the handle's tables are built on the device: zett_sampled_vocab_build and zett_sampled_vocab_commit come first");
     if (r->t.kind != ZETT_RETOK_BPE && r->t.kind != ZETT_RETOK_UNIGRAM)
@@ -244,12 +279,18 @@ int zett_encode_texts(zett_retok* r, const uint8_t* text, const int64_t* text_of
     if (ld_out < block_size) return fail(ZETT_E_INVALID, "ld_out = %lld must be at least block_size = %d", (long long)ld_out, (int)block_size);
     if (n_texts && (!input_ids || !attention_mask)) return fail(ZETT_E_INVALID, "null argument");
     if (n_texts && (!aligned(input_ids, out_bytes) || !aligned(attention_mask, out_bytes))) return fail(ZETT_E_INVALID, "misaligned output");
+    if (n_added < 0 || n_added > kMaxAdded) return fail(ZETT_E_INVALID, "%d added tokens: a table holds at most %d", (int)n_added, kMaxAdded);
+    if (n_added && (!added_bytes || !added_offsets || !added_ids)) return fail(ZETT_E_INVALID, "null argument");
+    if (n_added && (n_added_bytes < 2 * n_added || n_added_bytes > kMaxAddedBytes * n_added))
+        return fail(ZETT_E_INVALID, "%d bytes for %d added tokens: a token has 2 to %d bytes", (int)n_added_bytes, (int)n_added, kMaxAddedBytes);
+    if (n_added && !aligned(added_offsets, 4)) return fail(ZETT_E_INVALID, "misaligned added_offsets");
+    if (n_added && !aligned(added_ids, 4)) return fail(ZETT_E_INVALID, "misaligned added_ids");
     Lists ls{};
     ls.n_prefix = n_prefix; ls.n_suffix = n_suffix; ls.n_map = n_map; ls.pad_id = pad_id;
     for (int i = 0; i < n_prefix; ++i) ls.prefix[i] = prefix_ids[i];
     for (int i = 0; i < n_suffix; ++i) ls.suffix[i] = suffix_ids[i];
     for (int i = 0; i < n_map; ++i) { ls.map_from[i] = map_from[i]; ls.map_to[i] = map_to[i]; }
-    const Layout L = layout(n_text, n_texts);
+    const Layout L = layout(n_text, n_texts, n_added > 0);
     if (int rc = word_stage_args(text, text_offsets, n_texts, n_text, class_table, n_code_points, workspace, workspace_bytes, L.bytes, status)) return rc;
     ZETT_ON_DEVICE(r->device);
     hipStream_t st = (hipStream_t)stream;
@@ -260,10 +301,14 @@ int zett_encode_texts(zett_retok* r, const uint8_t* text, const int64_t* text_of
     int32_t* counts = (int32_t*)((char*)workspace + L.counts);
     int32_t* ids = (int32_t*)((char*)workspace + L.ids);
     int32_t* scratch = (int32_t*)((char*)workspace + L.scratch);
+    const AddedCut cut{AddedTable{added_bytes, added_offsets, added_ids, n_added, n_added_bytes}, (int32_t*)((char*)workspace + L.first), (uint16_t*)((char*)workspace + L.cand)};
     launch_word_stage(text, text_offsets, n_texts, n_text, class_table, n_code_points, (int)prefix_mode, (flags & ZETT_ENCODE_MARKS_ARE_LETTERS) != 0,
-                      (flags & ZETT_ENCODE_RESPLIT) != 0, false, L.words, a, status, st);
-    hipLaunchKernelGGL(encode_words_kernel, dim3((unsigned)((L.words.np + 63) / 64)), dim3(64), 0, st, r->t, (const uint8_t*)a.raw, (const uint8_t*)a.flags, (const int32_t*)a.woff,
-                       (const int32_t*)a.totals, ids, counts, scratch, status);
+                      (flags & ZETT_ENCODE_RESPLIT) != 0, false, L.words, a, status, st, n_added ? &cut : nullptr);
+#define ZETT_WORDS(ADDED)                                                                                                                                          \
+    hipLaunchKernelGGL(encode_words_kernel<ADDED>, dim3((unsigned)((L.words.np + 63) / 64)), dim3(64), 0, st, r->t, (const uint8_t*)a.raw, (const uint8_t*)a.flags, \
+                       (const int32_t*)a.woff, (const int32_t*)a.totals, ids, counts, scratch, status, (const uint16_t*)cut.cand, added_ids, (int)n_added)
+    if (n_added) ZETT_WORDS(true); else ZETT_WORDS(false);
+#undef ZETT_WORDS
     const int per = out_bytes == 8 ? 2 : 4;
     const bool vec = block_size % per == 0 && ld_out % per == 0 && aligned(input_ids, 16) && aligned(attention_mask, 16);
     const size_t lds = (size_t)block_size * 4;

@@ -1,7 +1,7 @@
 // text_words.hip.h — the word stage: the split of a batch of texts into words, shared by text_encode.hip (zett_encode_texts) and
 // tokenizer_sample.hip (zett_sampler_sample).  The kernels (classify / walk, from the text bytes to a flag at every word start) and
 // their host half: the layout of the stage's seven workspace arrays, the checks both entry points make, and the one launch sequence
-// that ends in scan.hip.h's compaction of the flags into the word list woff[].  The stages are described at the head of
+// (with the cut step of zett_encode_texts_added between classify and walk: added tokens split out of the texts) that ends in scan.hip.h's compaction of the flags into the word list woff[].  The stages are described at the head of
 // text_encode.hip.  Everything here has internal linkage: a translation unit that includes the header gets its own copy (of
 // sample_mark_first_kernel too, whether it launches it or not).
 #pragma once
@@ -146,6 +146,138 @@ __global__ __launch_bounds__(64) void encode_walk_kernel(const int64_t* __restri
     }
 }
 
+// ---- the cut step: added tokens split out of the texts (zett_encode_texts_added alone) ------------------------------------------------
+// The table: n tokens in strictly ascending byte order (a token before every longer one it starts), token k at
+// bytes[offsets[k] .. offsets[k + 1]), each of 2 .. kMaxAddedBytes bytes.  A match [m, m + len) becomes one word of one id on its first
+// len - 1 positions (flag 8); its LAST position is the slot of the section behind it — prefix space or dead word, as a text's slot.
+constexpr int kMaxAdded = 512;              // tokens of a table
+constexpr int kMaxAddedBytes = 64;          // bytes of a token
+constexpr int kFlagAdded = 8;               // flags[]: the word is a split-out token, its table index + 1 in cand[]
+
+struct AddedTable {
+    const uint8_t* bytes;
+    const int32_t* offsets;      // n + 1
+    const int32_t* ids;          // n
+    int32_t n, n_bytes;
+};
+
+__device__ __forceinline__ int added_off(const AddedTable& tb, int k) {
+    const int o = tb.offsets[k];
+    return o < 0 ? 0 : (o > tb.n_bytes ? tb.n_bytes : o);
+}
+__device__ __forceinline__ int added_len(const AddedTable& tb, int k) {
+    const int n = added_off(tb, k + 1) - added_off(tb, k);
+    return n < 0 ? 0 : (n > kMaxAddedBytes ? kMaxAddedBytes : n);
+}
+// byte d of token k; 0 behind its end
+__device__ __forceinline__ int added_byte(const AddedTable& tb, int k, int d) { return d < added_len(tb, k) ? tb.bytes[added_off(tb, k) + d] : 0; }
+
+// One workgroup: the table's checks (offsets from 0 to n_bytes, lengths, the order) and first[c] = the first token whose first byte is
+// >= c (first[256] = n), which is where every search of the candidates kernel starts.
+__global__ __launch_bounds__(256) void encode_added_prepare_kernel(AddedTable tb, int32_t* __restrict__ first, int* __restrict__ status) {
+    const int tid = threadIdx.x;
+    bool bad = tid == 0 && (tb.offsets[0] != 0 || tb.offsets[tb.n] != tb.n_bytes);
+    for (int k = tid; k < tb.n; k += 256) {
+        const int o0 = tb.offsets[k], n = tb.offsets[k + 1] - o0;
+        if (o0 < 0 || o0 > tb.n_bytes || n < 2 || n > kMaxAddedBytes) bad = true;
+        if (k + 1 < tb.n) {                                            // strictly below its successor
+            const int la = added_len(tb, k), lb = added_len(tb, k + 1);
+            int d = 0;
+            while (d < la && d < lb && added_byte(tb, k, d) == added_byte(tb, k + 1, d)) ++d;
+            if (d == lb || (d < la && added_byte(tb, k, d) > added_byte(tb, k + 1, d))) bad = true;
+        }
+    }
+    if (bad) atomicOr(status, ZETT_ENCODE_BAD_TABLE);
+    int lo = 0, hi = tb.n;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (added_byte(tb, mid, 0) < tid) lo = mid + 1; else hi = mid;
+    }
+    first[tid] = lo;
+    if (tid == 0) first[256] = tb.n;
+}
+
+// A thread per byte / slot: cand[p] = 1 + the longest token that matches at the byte and ends inside the byte's own text, 0: none.
+// The tokens that share the d bytes read so far are a range of the sorted table; one of d bytes can only be its first.
+__global__ __launch_bounds__(256) void encode_candidates_kernel(const uint8_t* __restrict__ text, const int64_t* __restrict__ off, int64_t b, int64_t n_text,
+                                                                AddedTable tb, const int32_t* __restrict__ first, uint16_t* __restrict__ cand) {
+    const int64_t item = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (item >= n_text + b) return;
+    if (item >= n_text) { cand[clamp_off(off[item - n_text], n_text) + (item - n_text)] = 0; return; }
+    int64_t tl = 0, th = b - 1;                                       // the last text whose offset is <= item
+    while (tl < th) {
+        const int64_t mid = (tl + th + 1) >> 1;
+        if (off[mid] <= item) tl = mid; else th = mid - 1;
+    }
+    const int c = text[item];
+    int lo = std::min(std::max(first[c], 0), (int)tb.n), hi = std::min(std::max(first[c + 1], lo), (int)tb.n);
+    int best = 0;
+    if (lo < hi) {
+        const int64_t avail = clamp_off(off[tl + 1], n_text) - item;     // bytes up to the text's end
+        for (int d = 1; lo < hi && d <= kMaxAddedBytes; ++d) {
+            if (added_len(tb, lo) <= d) {
+                best = lo + 1;
+                if (++lo >= hi) break;
+            }
+            if (d >= avail) break;
+            const int ch = text[item + d];
+            int a = lo, z = hi;                                        // the first token whose byte d is >= ch
+            while (a < z) {
+                const int mid = (a + z) >> 1;
+                if (added_byte(tb, mid, d) < ch) a = mid + 1; else z = mid;
+            }
+            lo = a;
+            z = hi;                                                    // the first whose byte d is > ch
+            while (a < z) {
+                const int mid = (a + z) >> 1;
+                if (added_byte(tb, mid, d) <= ch) a = mid + 1; else z = mid;
+            }
+            hi = a;
+        }
+    }
+    cand[item + tl + 1] = (uint16_t)best;
+}
+
+// The walk with cuts, a lane per text: the leftmost candidate at or behind i is taken (the longest at its byte), what lies in front of
+// it is walked as a text of its own behind slot s, and i moves behind the match — candidates inside it are never looked at.
+__global__ __launch_bounds__(64) void encode_walk_cut_kernel(const int64_t* __restrict__ off, int64_t b, int64_t n_text, uint8_t* codes, uint8_t* flags, uint8_t* raw,
+                                                             const uint16_t* __restrict__ cand, AddedTable tb, int prefix_mode, int marks, int resplit) {
+    const int64_t t = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    if (t >= b) return;
+    const int64_t lo = clamp_off(off[t], n_text), end = std::max(lo, clamp_off(off[t + 1], n_text));
+    const int64_t hi = end + t + 1;
+    int64_t s = lo + t, q = s + 1;                                    // the section's slot and its first byte
+    for (;;) {
+        int64_t m = q;
+        int k = 0;
+        while (m < hi && (k = cand[m]) == 0) ++m;
+        int len = 0;
+        if (m < hi) {
+            len = added_len(tb, std::min(k, (int)tb.n) - 1);
+            if (len > hi - m) len = (int)(hi - m);
+            if (len < 2) { m = hi; len = 0; }                          // (a table that failed its checks: nothing is cut)
+        }
+        const bool prefixed = m > q && (prefix_mode == ZETT_ENCODE_PREFIX_ALWAYS || (prefix_mode == ZETT_ENCODE_PREFIX_UNLESS_SPACE && raw[q] != 0x20));
+        raw[s] = 0x20;
+        codes[s] = prefixed ? (uint8_t)(C_S | (A_SPACE << 3)) : (uint8_t)C_SKIP;
+        flags[s] = prefixed ? 0 : 2;
+        int64_t i = prefixed ? s : q;
+        while (i < m) {
+            const int64_t e = match_end(codes, i, m, marks);
+            if (resplit) {
+                for (int64_t j = i; j < e; j = match_end(codes, j, e, 0)) flags[j] = 1;
+            } else {
+                flags[i] = 1;
+            }
+            i = e;
+        }
+        if (m >= hi) break;
+        flags[m] = 1 | kFlagAdded;
+        s = m + len - 1;
+        q = m + len;
+    }
+}
+
 // the sampler's extra step: the slot of every text starts the text's first word
 __global__ __launch_bounds__(256) void sample_mark_first_kernel(const int64_t* __restrict__ off, int64_t b, int64_t n_text, uint8_t* __restrict__ flags) {
     const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -204,12 +336,29 @@ inline int word_stage_args(const uint8_t* text, const int64_t* text_offsets, int
     return 0;
 }
 
-// classify, walk, (mark_first: the sampler's flag on the first word of every text,) compact: a.woff[0 .. a.totals[0]] is the word list
+// the cut step's table and its two arrays in the caller's workspace: first int32 [257], cand uint16 [np]
+struct AddedCut {
+    AddedTable table;
+    int32_t* first;
+    uint16_t* cand;
+};
+
+// classify, (cut: the candidates of the added tokens,) walk, (mark_first: the sampler's flag on the first word of every text,) compact:
+// a.woff[0 .. a.totals[0]] is the word list
 inline void launch_word_stage(const uint8_t* text, const int64_t* text_offsets, int64_t n_texts, int64_t n_text, const uint8_t* class_table, int64_t n_code_points,
-                              int prefix_mode, int marks, int resplit, bool mark_first, const WordLayout& L, const WordArrays& a, int32_t* status, hipStream_t st) {
+                              int prefix_mode, int marks, int resplit, bool mark_first, const WordLayout& L, const WordArrays& a, int32_t* status, hipStream_t st,
+                              const AddedCut* cut = nullptr) {
     hipLaunchKernelGGL(encode_classify_kernel, dim3((unsigned)((L.np + 255) / 256)), dim3(256), 0, st, text, text_offsets, n_texts, n_text, class_table, n_code_points,
                        prefix_mode, a.codes, a.flags, a.raw, status);
-    hipLaunchKernelGGL(encode_walk_kernel, dim3((unsigned)((n_texts + 63) / 64)), dim3(64), 0, st, text_offsets, n_texts, n_text, (const uint8_t*)a.codes, a.flags, marks, resplit);
+    if (cut) {
+        hipLaunchKernelGGL(encode_added_prepare_kernel, dim3(1), dim3(256), 0, st, cut->table, cut->first, status);
+        hipLaunchKernelGGL(encode_candidates_kernel, dim3((unsigned)((L.np + 255) / 256)), dim3(256), 0, st, text, text_offsets, n_texts, n_text, cut->table,
+                           (const int32_t*)cut->first, cut->cand);
+        hipLaunchKernelGGL(encode_walk_cut_kernel, dim3((unsigned)((n_texts + 63) / 64)), dim3(64), 0, st, text_offsets, n_texts, n_text, a.codes, a.flags, a.raw,
+                           (const uint16_t*)cut->cand, cut->table, prefix_mode, marks, resplit);
+    } else {
+        hipLaunchKernelGGL(encode_walk_kernel, dim3((unsigned)((n_texts + 63) / 64)), dim3(64), 0, st, text_offsets, n_texts, n_text, (const uint8_t*)a.codes, a.flags, marks, resplit);
+    }
     if (mark_first) hipLaunchKernelGGL(sample_mark_first_kernel, dim3((unsigned)((n_texts + 255) / 256)), dim3(256), 0, st, text_offsets, n_texts, n_text, a.flags);
     zett::launch_compact(a.flags, L.np, a.woff, a.segcnt, a.segoff, a.totals, st);
 }

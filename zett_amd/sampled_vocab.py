@@ -224,7 +224,7 @@ class DeviceSampledVocabulary:
         # normalizer, pre-tokenizer, post-processor and special strings as the installed library serialises them for a tokenizer built the
         # reference's way — read, never guessed; the pad id alone depends on the step (the pad token may sit beyond the end)
         fixed_tokenizer = build_sampled_tokenizer(fixed_pieces(), reference, add_prefix_space)[0]
-        self.encode_spec = EncodeSpec.from_tokenizer(fixed_tokenizer)
+        self.encode_spec = EncodeSpec.from_tokenizer(fixed_tokenizer, split_added_tokens=True)          # (its backend holds no added token: a special's string is text)
         self._pad_k = tokens.index(reference.pad_token)
         self.scores_through_json = self._probe_scores(fixed_tokenizer, tokens)
         self.hn = device_retokenizer(hn_tokenizer, self.device) if hn_tokenizer is not None else None

@@ -17,13 +17,20 @@ pre-tokenizers, once per process (``class_table()``).
 Everything the kernels do not reproduce is refused here, on the host, with NotImplementedError / ValueError: another normalizer,
 pre-tokenizer, post-processor, padding or truncation side; WordPiece models; ``block_size <= n_prefix + n_suffix``; a text that holds the
 string of an added or special token (the library would split it out).  There is no CPU path.
+
+``split_added_tokens=True`` (``from_tokenizer``, ``from_tokenizer_json``, ``from_handle``) lifts the last refusal the way the library
+does: the BACKEND's added tokens (``tokenizer._tokenizer``'s ``added_tokens``, not ``all_special_tokens``) are cut out of every text on
+the device at leftmost-longest matches, each match gives the token's one id and every section between two matches is encoded as a
+text of its own.  Tokens the kernels do not carry (``lstrip`` / ``rstrip`` / ``single_word``, one byte, ``normalized`` under
+``Prepend``) keep the refusal, and only for a text that holds them.  The host's work per call does not grow with the table.
 """
 from __future__ import annotations
 
 import ctypes as C
 import json
+import dataclasses
 from dataclasses import dataclass
-from typing import Dict, List, Mapping, Optional, Sequence, Tuple
+from typing import Dict, List, Mapping, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -37,7 +44,8 @@ SPLIT_PATTERN_PLAIN = r"'s|'t|'re|'ve|'m|'ll|'d| ?\p{L}+| ?\p{N}+| ?[^\s\p{L}\p{
 CLASS_O, CLASS_L, CLASS_M, CLASS_N, CLASS_S = 0, 1, 2, 3, 4
 N_CODE_POINTS = 0x110000
 PREFIX_NONE, PREFIX_ALWAYS, PREFIX_UNLESS_SPACE = _lib.ENCODE_PREFIX_NONE, _lib.ENCODE_PREFIX_ALWAYS, _lib.ENCODE_PREFIX_UNLESS_SPACE
-ENCODE_NO_UNK, ENCODE_BAD_OFFSETS = _lib.ENCODE_NO_UNK, _lib.ENCODE_BAD_OFFSETS
+ENCODE_NO_UNK, ENCODE_BAD_OFFSETS, ENCODE_BAD_TABLE = _lib.ENCODE_NO_UNK, _lib.ENCODE_BAD_OFFSETS, _lib.ENCODE_BAD_TABLE
+MAX_ADDED_TOKENS, MAX_ADDED_TOKEN_BYTES = _lib.ENCODE_MAX_ADDED, _lib.ENCODE_MAX_ADDED_BYTES
 MAX_BLOCK_SIZE = 8192
 _CHUNK = 256          # probes per call of a pre-tokenizer: its cost grows faster than the text
 
@@ -170,6 +178,16 @@ def flatten_texts(texts: Sequence[str], joined: Optional[str] = None) -> Tuple[b
 
 
 # ---- what the kernels need to know about a tokenizer -------------------------------------------------------------------------------
+class AddedToken(NamedTuple):
+    """An entry of the backend's ``added_tokens`` list, as ``tokenizer._tokenizer.to_str()`` serialises it."""
+    content: str
+    id: int
+    normalized: bool = False
+    lstrip: bool = False
+    rstrip: bool = False
+    single_word: bool = False
+
+
 @dataclass
 class EncodeSpec:
     """Normalizer, pre-tokenizer, post-processor and padding of a tokenizer, as the arguments of zett_encode_texts."""
@@ -180,6 +198,8 @@ class EncodeSpec:
     suffix_ids: Tuple[int, ...]
     pad_id: int
     special_strings: Tuple[str, ...]          # contents of the added tokens: a text that holds one is refused
+    added_tokens: Tuple[AddedToken, ...] = ()   # the backend's added tokens; looked at with split_added_tokens alone
+    split_added_tokens: bool = False          # the plain added tokens are split out on the device, and special_strings refuses nothing
 
     @staticmethod
     def _template(post: Optional[dict]) -> Tuple[Tuple[int, ...], Tuple[int, ...]]:
@@ -207,7 +227,8 @@ class EncodeSpec:
         raise NotImplementedError(f"post-processor {post.get('type')!r} (TemplateProcessing, RobertaProcessing, ByteLevel or none)")
 
     @classmethod
-    def from_tokenizer_json(cls, data: Mapping, pad_id: Optional[int], padding_side: str = "right", truncation_side: str = "right") -> "EncodeSpec":
+    def from_tokenizer_json(cls, data: Mapping, pad_id: Optional[int], padding_side: str = "right", truncation_side: str = "right",
+                            split_added_tokens: bool = False) -> "EncodeSpec":
         if padding_side != "right" or truncation_side != "right":
             raise NotImplementedError(f"padding_side = {padding_side!r}, truncation_side = {truncation_side!r}: rows are cut and padded on the right")
         for key in ("padding", "truncation"):          # what an earlier call left switched on in the backend
@@ -249,16 +270,56 @@ class EncodeSpec:
         if len(prefix) > _lib.ENCODE_MAX_TEMPLATE or len(suffix) > _lib.ENCODE_MAX_TEMPLATE:
             raise NotImplementedError(f"more than {_lib.ENCODE_MAX_TEMPLATE} template ids on one side")
         strings = tuple(a["content"] for a in data.get("added_tokens") or [] if a.get("content"))
-        return cls(prefix_mode, marks, resplit, prefix, suffix, int(pad_id), strings)
+        spec = cls(prefix_mode, marks, resplit, prefix, suffix, int(pad_id), strings)
+        if split_added_tokens:
+            spec.split_added_tokens = True
+            spec.added_tokens = tuple(AddedToken(a["content"], int(a["id"]), bool(a.get("normalized")), bool(a.get("lstrip")), bool(a.get("rstrip")), bool(a.get("single_word")))
+                                      for a in data.get("added_tokens") or [] if a.get("content"))
+            spec.added_table()          # (the cap refusals, before any device work)
+        return spec
 
     @classmethod
-    def from_tokenizer(cls, tokenizer) -> "EncodeSpec":
+    def from_tokenizer(cls, tokenizer, split_added_tokens: bool = False) -> "EncodeSpec":
         """From a transformers fast tokenizer (what ``Collator.sample_tokenizer`` returns, zett/collator.py:414-431)."""
         data = json.loads(tokenizer._tokenizer.to_str())
         strings = {a["content"] for a in data.get("added_tokens") or []} | set(getattr(tokenizer, "all_special_tokens", ()))
-        spec = cls.from_tokenizer_json(data, tokenizer.pad_token_id, getattr(tokenizer, "padding_side", "right"), getattr(tokenizer, "truncation_side", "right"))
+        spec = cls.from_tokenizer_json(data, tokenizer.pad_token_id, getattr(tokenizer, "padding_side", "right"), getattr(tokenizer, "truncation_side", "right"),
+                                       split_added_tokens)
         spec.special_strings = tuple(sorted(s for s in strings if s))
         return spec
+
+    def is_plain(self, token: AddedToken) -> bool:
+        """Does the device split this token out?  Matched on the raw bytes, nothing swallowed around it: no ``lstrip`` / ``rstrip`` /
+        ``single_word``, at least two bytes, and ``normalized`` only where there is no normalizer to look through."""
+        if token.lstrip or token.rstrip or token.single_word or len(token.content.encode("utf-8")) < 2:
+            return False
+        return not (token.normalized and self.prefix_mode == PREFIX_ALWAYS)          # (PREFIX_ALWAYS is the Prepend(" ") normalizer)
+
+    def added_table(self) -> Tuple[bytes, np.ndarray, np.ndarray]:
+        """(bytes, int32 offsets [n + 1], int32 ids [n]) of the plain added tokens in ascending byte order: the table of
+        zett_encode_texts_added.  Empty without ``split_added_tokens``."""
+        plain: Dict[bytes, int] = {}
+        for token in self.added_tokens if self.split_added_tokens else ():
+            if self.is_plain(token):
+                plain.setdefault(token.content.encode("utf-8"), token.id)
+        if len(plain) > MAX_ADDED_TOKENS:
+            raise NotImplementedError(f"{len(plain)} added tokens to split out: the device table holds {MAX_ADDED_TOKENS}")
+        for raw, token_id in plain.items():
+            if len(raw) > MAX_ADDED_TOKEN_BYTES:
+                raise NotImplementedError(f"the added token {raw.decode('utf-8')!r} has {len(raw)} bytes, the device table carries {MAX_ADDED_TOKEN_BYTES}")
+            if not -2 ** 31 <= token_id < 2 ** 31:
+                raise ValueError(f"the added token {raw.decode('utf-8')!r} has an id outside int32")
+        keys = sorted(plain)
+        offsets = np.zeros(len(keys) + 1, dtype=np.int32)
+        np.cumsum(np.array([len(k) for k in keys], dtype=np.int32), out=offsets[1:])
+        return b"".join(keys), offsets, np.array([plain[k] for k in keys], dtype=np.int32)
+
+    @property
+    def refused_strings(self) -> Tuple[str, ...]:
+        """What a text must not hold: every added or special string, or with ``split_added_tokens`` the backend tokens that are not plain."""
+        if not self.split_added_tokens:
+            return self.special_strings
+        return tuple(a.content for a in self.added_tokens if not self.is_plain(a))
 
     @property
     def flags(self) -> int:
@@ -277,7 +338,7 @@ class EncodeSpec:
         if any(not -2 ** 31 <= x < 2 ** 31 for p in pairs for x in p):
             raise ValueError("special_ids_map holds an id outside int32")
         joined = "".join(texts)
-        for s in self.special_strings:          # one str.find per special; the texts themselves only where the joined text has a hit
+        for s in self.refused_strings:          # one str.find per refused string; the texts themselves only where the joined text has a hit
             if joined.find(s) >= 0 and any(s in x for x in texts):
                 raise NotImplementedError(f"a text holds the added token {s!r}: the library would split it out")
         return joined, pairs
@@ -301,36 +362,50 @@ class DeviceTextEncoder:
         k = _lib.ENCODE_MAX_TEMPLATE
         self._prefix = (C.c_int32 * k)(*encode_spec.prefix_ids)
         self._suffix = (C.c_int32 * k)(*encode_spec.suffix_ids)
+        self._added = None          # the device table of zett_encode_texts_added: (bytes, offsets, ids, n, n_bytes)
+        if encode_spec.split_added_tokens:
+            raw, offsets, ids = encode_spec.added_table()
+            if len(ids):
+                import torch
+                up = lambda a: torch.from_numpy(np.ascontiguousarray(a).copy()).to(self.device)          # noqa: E731
+                self._added = (up(np.frombuffer(raw, dtype=np.uint8)), up(offsets), up(ids), len(ids), len(raw))
         self._owns_handle = owns_handle
 
     @classmethod
-    def from_handle(cls, retok, encode_spec: EncodeSpec, table: Optional[np.ndarray] = None, d_table=None) -> "DeviceTextEncoder":
+    def from_handle(cls, retok, encode_spec: EncodeSpec, table: Optional[np.ndarray] = None, d_table=None, split_added_tokens: Optional[bool] = None) -> "DeviceTextEncoder":
         """On a retokenizer handle that is already there and stays its owner's — ``DeviceSampledVocabulary`` rebuilds the tables of one
         handle every step (zett_amd/sampled_vocab.py).  ``retok``: a ``DeviceRetokenizer``; ``d_table``: the packed class table on its
-        device, if the caller keeps one.  ``close()`` leaves the handle alone."""
+        device, if the caller keeps one.  ``close()`` leaves the handle alone.  ``split_added_tokens``: the spec's switch, set anew
+        (the spec's ``added_tokens`` are what is split)."""
         self = cls.__new__(cls)
+        if split_added_tokens is not None and bool(split_added_tokens) != encode_spec.split_added_tokens:
+            encode_spec = dataclasses.replace(encode_spec, split_added_tokens=bool(split_added_tokens))
         self.device = retok.device
         self._adopt(retok, encode_spec, table, d_table, False)
         return self
 
     @classmethod
-    def from_tokenizer(cls, tokenizer, device=None) -> "DeviceTextEncoder":
+    def from_tokenizer(cls, tokenizer, device=None, split_added_tokens: bool = False) -> "DeviceTextEncoder":
         from .surface_forms import HnTokenizerSpec
-        encode_spec = EncodeSpec.from_tokenizer(tokenizer)          # (refusals first: no device work for a tokenizer that is not carried)
+        encode_spec = EncodeSpec.from_tokenizer(tokenizer, split_added_tokens)          # (refusals first: no device work for a tokenizer that is not carried)
         return cls(HnTokenizerSpec.from_tokenizer(tokenizer), encode_spec, device)
 
     @classmethod
     def from_tokenizer_json(cls, data: Mapping, pad_token_id: int, special_tokens: Sequence[str] = (), special_ids: Sequence[int] = (), padding_side: str = "right",
-                            truncation_side: str = "right", device=None) -> "DeviceTextEncoder":
+                            truncation_side: str = "right", device=None, split_added_tokens: bool = False) -> "DeviceTextEncoder":
         """From a ``tokenizer.json`` dict and what transformers adds to it: the pad id, ``all_special_tokens`` / ``all_special_ids``, the sides."""
         from .surface_forms import HnTokenizerSpec
-        encode_spec = EncodeSpec.from_tokenizer_json(data, pad_token_id, padding_side, truncation_side)
+        encode_spec = EncodeSpec.from_tokenizer_json(data, pad_token_id, padding_side, truncation_side, split_added_tokens)
         encode_spec.special_strings = tuple(sorted(set(encode_spec.special_strings) | {s for s in special_tokens if s}))
         return cls(HnTokenizerSpec.from_model_json(data["model"], list(special_tokens), list(special_ids), pad_token_id), encode_spec, device)
 
     def workspace_bytes(self, n_text: int, n_texts: int) -> int:
         out = C.c_int64(0)
-        _lib.check(self.lib.zett_encode_workspace_bytes(int(n_text), int(n_texts), C.byref(out)), "zett_encode_workspace_bytes")
+        if self.spec.split_added_tokens:
+            n_added = self._added[3] if self._added else 0
+            _lib.check(self.lib.zett_encode_added_workspace_bytes(int(n_text), int(n_texts), n_added, C.byref(out)), "zett_encode_added_workspace_bytes")
+        else:
+            _lib.check(self.lib.zett_encode_workspace_bytes(int(n_text), int(n_texts), C.byref(out)), "zett_encode_workspace_bytes")
         return out.value
 
     def __call__(self, texts: Sequence[str], block_size: int, special_ids_map: Optional[Dict[int, int]] = None, dtype=None, check: bool = True, out=None):
@@ -362,15 +437,21 @@ class DeviceTextEncoder:
             m_from = (C.c_int32 * max(n_map, 1))(*[p[0] for p in pairs])
             m_to = (C.c_int32 * max(n_map, 1))(*[p[1] for p in pairs])
             ld = ids.stride(0) if b > 1 else t
-            rc = self.lib.zett_encode_texts(self.retok.handle, ptr(d_text), ptr(d_off), b, len(blob), ptr(self._d_table), len(self.table), self.spec.flags,
-                                            self.spec.prefix_mode, t, self._prefix, len(self.spec.prefix_ids), self._suffix, len(self.spec.suffix_ids), m_from, m_to, n_map,
-                                            self.spec.pad_id, ptr(ids if b else None), ptr(mask if b else None), ids.element_size(), ld, ptr(work), work.numel(),
-                                            ptr(status), stream(self.device))
-            _lib.check(rc, "zett_encode_texts")
+            head = (self.retok.handle, ptr(d_text), ptr(d_off), b, len(blob), ptr(self._d_table), len(self.table), self.spec.flags, self.spec.prefix_mode, t,
+                    self._prefix, len(self.spec.prefix_ids), self._suffix, len(self.spec.suffix_ids), m_from, m_to, n_map, self.spec.pad_id, ptr(ids if b else None),
+                    ptr(mask if b else None), ids.element_size(), ld)
+            tail = (ptr(work), work.numel(), ptr(status), stream(self.device))
+            if self.spec.split_added_tokens:
+                a_bytes, a_off, a_ids, n_added, n_added_bytes = self._added or (None, None, None, 0, 0)
+                _lib.check(self.lib.zett_encode_texts_added(*head, ptr(a_bytes), ptr(a_off), ptr(a_ids), n_added, n_added_bytes, *tail), "zett_encode_texts_added")
+            else:
+                _lib.check(self.lib.zett_encode_texts(*head, *tail), "zett_encode_texts")
         if check:
             bits = int(status.item())          # (the one host read of this call)
             if bits & ENCODE_BAD_OFFSETS:
                 raise ValueError("encode_texts: the text offsets are not non-decreasing from 0 to the text length")
+            if bits & ENCODE_BAD_TABLE:
+                raise ValueError("encode_texts: the table of added tokens is not sorted, or holds a token of fewer than 2 or more than 64 bytes")
             if bits & ENCODE_NO_UNK:
                 raise Exception("Encountered an unknown token but `unk_id` is missing")          # tokenizers raises a bare Exception here
         self.last_status = status          # device int32 [1]: what a caller with check=False may look at later
@@ -382,7 +463,8 @@ class DeviceTextEncoder:
 
 
 def encode_texts(tokenizer_or_encoder, texts: Sequence[str], block_size: int, special_ids_map: Optional[Dict[int, int]] = None, dtype=None, check: bool = True,
-                 device=None):
-    """``DeviceTextEncoder.from_tokenizer(tokenizer)(texts, block_size, ...)``; pass the encoder itself to keep its tables."""
-    enc = tokenizer_or_encoder if isinstance(tokenizer_or_encoder, DeviceTextEncoder) else DeviceTextEncoder.from_tokenizer(tokenizer_or_encoder, device)
+                 device=None, split_added_tokens: bool = False):
+    """``DeviceTextEncoder.from_tokenizer(tokenizer)(texts, block_size, ...)``; pass the encoder itself to keep its tables (and its
+    ``split_added_tokens``: the switch is for a tokenizer)."""
+    enc = tokenizer_or_encoder if isinstance(tokenizer_or_encoder, DeviceTextEncoder) else DeviceTextEncoder.from_tokenizer(tokenizer_or_encoder, device, split_added_tokens)
     return enc(texts, block_size, special_ids_map, dtype=dtype, check=check)

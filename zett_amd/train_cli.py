@@ -3,8 +3,7 @@
 ``log`` call, to ``output_dir/metrics.jsonl``.
 
 Left out, each refused where it is asked for: training the backbone, ``apply_lexical_loss_to_init``, ``mix_languages``,
-``use_passthrough_hypernet``, ``do_sequence_packing`` when the reference tokenizer has an eos token (the device text encoder refuses a text
-that holds the string of an added token, and packed texts hold the eos string), more than one language without ``lang,weight`` lines (the page counts that weigh languages are not
+``use_passthrough_hypernet``, more than one language without ``lang,weight`` lines (the page counts that weigh languages are not
 here), an ``init_from_params`` that is not a local directory, backbones other than causal language models and RoBERTa / XLM-R."""
 import copy
 import dataclasses
@@ -151,9 +150,7 @@ def main(argv: Optional[List[str]] = None) -> None:
 
     # data (train.py:378-556)
     loss, sampling = training_args.loss, bool(data_args.do_tokenizer_sampling)
-    if data_args.do_sequence_packing and reference.eos_token:
-        # packed texts hold the eos string between their rows, and DeviceTextEncoder refuses a text that holds the string of an added token
-        raise NotImplementedError("do_sequence_packing with an eos token: the device text encoder does not split added tokens out of a text; set do_sequence_packing to false")
+    # (packed texts hold the eos string between their rows: the collator's encoders split added tokens out of a text as the library does)
     train_datasets = [TrainDataset([lang], data_args.train_directory, np.array([1.0]), training_args.train_batch_size, data_args.block_size,
                                    do_sequence_packing=data_args.do_sequence_packing, eos_token=reference.eos_token) for lang in langs]
     target = None if sampling else AutoTokenizer.from_pretrained(data_args.target_tokenizer_name)
