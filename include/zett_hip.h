@@ -499,7 +499,10 @@ int zett_lexical_rows_into(zett_lexical* h, const int32_t* ids, const int32_t* c
  * the forward that keeps its activations and the backward from.  All pointers are device pointers, fp32, row-major;
  * `stream` is a hipStream_t.  Dense contractions — forward, dgrad, wgrad — are ONE entry point on the library's TN
  * GEMM family (fp32 MFMA): dgrad is the same contraction against the transposed weight, wgrad the same contraction of
- * the two transposed activations (zett_op_transpose_f32 zero-pads the row count to the 32-wide K step). */
+ * the two transposed activations (zett_op_transpose_f32 zero-pads the row count to the 32-wide K step).
+ * One unit per family under zett_amd/csrc/, each with its kernels, its launch and its entry points: train_gemm.hip (the
+ * contractions), train_operands.hip (conversions, transposes, sums, element-wise forms, the GELUs), train_layernorm.hip,
+ * train_attention.hip, train_gather.hip (indexed rows, the source-embedding gather). */
 /* out[m, n] = act(a[m, :] . w[n, :] + bias[n]) + residual[m, n]   (bias, residual nullable; act: 0 none, 1 tanh-GELU, 2 erf-GELU;
  * k % 32 == 0, lda / ldw % 4 == 0)
  * Pointers (this entry point and zett_op_gemm_lo): every tile fetches the operands as 16-byte pieces of a row, so `a` and `w` must be

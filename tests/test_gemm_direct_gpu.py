@@ -29,10 +29,10 @@ T128, TREG, TLDS, TLDS_GENERIC = "128x128", "256x256 register-staged", "256x256 
 def expected_tile(kind, m, n, k, act, has_res, ld_out, ld_res, out_align=16, res_align=16, bias_align=16):
     """The tile a call takes.  Mirrors, line for line,
 
-        zett_amd/csrc/train_ops.hip  gemm_wide_ok:      n % 8 == 0 && ld_out % 4 == 0 && (!residual || ld_res % 4 == 0)
+        zett_amd/csrc/train_gemm.hip gemm_wide_ok:      n % 8 == 0 && ld_out % 4 == 0 && (!residual || ld_res % 4 == 0)
                                                         && out, residual, bias 16-byte aligned
-                                     zett_op_gemm_f32:  variant = (m > 128 && n > 128 && wide_ok) ? 2 : 1
-                                     gemm_lo:           variant = (m > 128 && n > 128 && wide_ok) ? (k >= 512 ? 7 : 2) : 1
+                                     gemm_tile_for:     fp32:   variant = (m > 128 && n > 128 && wide_ok) ? 2 : 1
+                                                        16-bit: variant = (m > 128 && n > 128 && wide_ok) ? (k >= 512 ? 7 : 2) : 1
         zett_amd/csrc/gemm4d.hip.h   gemm4d_epi_mode:   fp32 output, no scale / shift: G4D_EPI_F32 (streamlined) for
                                                         act == none, or tanh-GELU WITH a residual; G4D_EPI_GENERIC otherwise
     (variant 1 = 128x128, 2 = gemm8r, 7 = gemm4d)."""

@@ -576,6 +576,23 @@ def test_model_plan_and_forward_are_units_of_their_own():
         assert not set(build.TRAINING_ONLY) & reached(name), name
 
 
+def test_training_primitives_are_units_of_their_own():
+    """The training primitives are one unit per family, each with its kernels, its launch and its entry points: all share
+    train_common.hip.h, only the contractions see the GEMM launchers, and none reaches the forward's row kernels, handle or plan —
+    an edit to one family recompiles that family."""
+    from zett_amd import build
+
+    units = ("train_gemm.hip", "train_operands.hip", "train_layernorm.hip", "train_attention.hip", "train_gather.hip")
+    assert set(units) <= set(build.SOURCES), build.SOURCES
+    assert set(units) <= set(build.TRAINING_ONLY), build.TRAINING_ONLY
+    assert not os.path.exists(os.path.join(build.CSRC, "train_ops.hip"))
+    for name in units:
+        reached = {os.path.basename(p) for p in build._includes(os.path.join(build.CSRC, name))}
+        assert "train_common.hip.h" in reached, (name, reached)
+        assert ("gemm_launch.hip.h" in reached) == (name == "train_gemm.hip"), (name, reached)
+        assert not {"rowops.hip.h", "forward_handle.hip.h", "plan.hip.h"} & reached, (name, reached)
+
+
 def test_training_primitives_refuse_bad_arguments_before_touching_the_device():
     """Error behaviour of the zett_op_* entry points at the boundary: arguments are validated before any launch, the return code is
     ZETT_E_INVALID and zett_last_error says why (no GPU needed: nothing is launched)."""

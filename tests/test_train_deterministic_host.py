@@ -42,7 +42,7 @@ def test_entry_points_are_exported_and_bound_as_declared(name):
 
 def test_the_units_stay_out_of_the_forward_hash():
     from zett_amd import build
-    assert {"train_embed.hip", "train_ops.hip"} <= set(build.TRAINING_ONLY)
+    assert {"train_embed.hip", "train_gather.hip"} <= set(build.TRAINING_ONLY)
 
 
 def test_entry_points_refuse_bad_arguments_before_touching_the_device():

@@ -231,7 +231,7 @@ def test_the_16_bit_rule():
 
 # ---- the case tables reach every branch --------------------------------------------------------------------------------------
 def _transpose_branches(case):
-    """The forms transpose_lo_kernel takes for a case, restated from zett_amd/csrc/train_ops.hip:
+    """The forms transpose_lo_kernel takes for a case, restated from zett_amd/csrc/train_operands.hip:
         load4_edge:  one access where c + 3 < C and ld_in % 4 == 0, the element tail otherwise (same for act_z with ld_z)
         plain:       store4 where c + 3 < C and ld_plain % 4 == 0, scalar otherwise
         transposed:  store4 where r + 3 < Rpad and ld_out % 4 == 0, scalar otherwise (the last group of a band when Rpad % 4 != 0)

@@ -1,4 +1,4 @@
-"""The training row primitives of zett_amd/csrc/train_ops.hip called directly through the C ABI and checked ELEMENT BY ELEMENT
+"""The training row primitives of zett_amd/csrc/train_{operands,layernorm,attention,gather}.hip called directly through the C ABI and checked ELEMENT BY ELEMENT
 against float64 on the same values (tests/train_ops_check.py), at the layout edges: leading dimensions wider than the data and not
 multiples of four, row and column counts one short of, at and one past a tile, padding bands, grid-stride loops that stride, every
 register layout of LayerNorm and attention in the dense, packed and position-0-only forms.

@@ -1,4 +1,4 @@
-"""Element-by-element check of the training row primitives (zett_amd/csrc/train_ops.hip) against float64 on the SAME values
+"""Element-by-element check of the training row primitives (zett_amd/csrc/train_{operands,layernorm,attention,gather}.hip) against float64 on the SAME values
 (no GPU in here): the sibling of tests/gemm_check.py, whose buffer discipline (Framed, check_canary, CANARY_BITS) and unit U
 it uses.
 

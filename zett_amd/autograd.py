@@ -9,7 +9,7 @@ hypernetwork's parameters, the source embeddings and the language model are froz
 First slice.  fp32 arithmetic, the reference's as-written dense ``[N, L', H]`` layout (every position computed, pads
 masked as keys), one ``torch.autograd.Function`` for the whole hypernetwork: its forward keeps the activations the
 backward needs, its backward is straight-line code.  Both are sequences of HIP launches through the C ABI
-(include/zett_hip.h "training use", zett_amd/csrc/train_ops.hip): every dense contraction — forward, dgrad, wgrad — is
+(include/zett_hip.h "training use", zett_amd/csrc/train_{gemm,operands,layernorm,attention,gather}.hip): every dense contraction — forward, dgrad, wgrad — is
 the library's TN MFMA GEMM (dgrad against the transposed weight, wgrad of the two transposed activations); LayerNorm,
 the two GELUs, masked attention and the source-embedding gather have forward and backward row kernels.  torch holds the
 tensors and the autograd tape, allocates, slices and concatenates (layout plumbing, parameter-sized glue); it computes
@@ -69,6 +69,10 @@ class Ops:
         self.lo_dtype = {"f32": None, "bf16": torch.bfloat16, "f16": torch.float16}[precision]
         self.kstep = K_STEP if self.prec is None else 64          # contraction widths are multiples of this
 
+    def _call(self, name, *args):
+        """a zett_op_* primitive on this device's current stream, its return code checked under its name"""
+        _lib.check(getattr(self.lib, name)(*args, stream(self.device)), name)
+
     def new(self, *shape) -> torch.Tensor:
         return torch.empty(shape, dtype=torch.float32, device=self.device)
 
@@ -91,7 +95,7 @@ class Ops:
         r, c = x.shape
         cp = -(-c // 64) * 64
         out = torch.empty((r, cp), dtype=self.lo_dtype, device=self.device)
-        _lib.check(self.lib.zett_op_convert_lo(self.prec, ptr(x), x.stride(0), ptr(out), cp, r, c, cp, stream(self.device)), "zett_op_convert_lo")
+        self._call("zett_op_convert_lo", self.prec, ptr(x), x.stride(0), ptr(out), cp, r, c, cp)
         return out
 
     def gemm(self, x, w, bias=None, act=ACT_NONE, residual=None, out=None):
@@ -106,8 +110,8 @@ class Ops:
             if out is None:
                 out = self.new(m, n)
             assert out.shape == (m, n) and out.is_contiguous()
-            _lib.check(self.lib.zett_op_gemm_lo(self.prec, ptr(xa), xa.stride(0), ptr(wa), wa.stride(0), m, n, k, ptr(bias), act,
-                                                ptr(residual), 0 if residual is None else residual.stride(0), ptr(out), n, stream(self.device)), "zett_op_gemm_lo")
+            self._call("zett_op_gemm_lo", self.prec, ptr(xa), xa.stride(0), ptr(wa), wa.stride(0), m, n, k, ptr(bias), act,
+                       ptr(residual), 0 if residual is None else residual.stride(0), ptr(out), n)
             return out
         assert x.shape[1] == w.shape[1]
         m, k = x.shape
@@ -115,8 +119,8 @@ class Ops:
         if out is None:
             out = self.new(m, n)
         assert out.shape == (m, n) and out.is_contiguous()
-        _lib.check(self.lib.zett_op_gemm_f32(ptr(x), x.stride(0), ptr(w), w.stride(0), m, n, k, ptr(bias), act,
-                                             ptr(residual), 0 if residual is None else residual.stride(0), ptr(out), n, stream(self.device)), "zett_op_gemm_f32")
+        self._call("zett_op_gemm_f32", ptr(x), x.stride(0), ptr(w), w.stride(0), m, n, k, ptr(bias), act,
+                   ptr(residual), 0 if residual is None else residual.stride(0), ptr(out), n)
         return out
 
     def wgrad(self, dy_t, x_t):
@@ -156,12 +160,12 @@ class Ops:
             out = torch.empty((c, rp), dtype=self.lo_dtype, device=self.device)
             src = x if x.dtype == self.lo_dtype else self._twin(x)
             if src is not None:
-                _lib.check(self.lib.zett_op_transpose_lo16(self.prec, ptr(src), src.stride(0), ptr(out), rp, r, c, rp, stream(self.device)), "zett_op_transpose_lo16")
+                self._call("zett_op_transpose_lo16", self.prec, ptr(src), src.stride(0), ptr(out), rp, r, c, rp)
             else:
-                _lib.check(self.lib.zett_op_transpose_lo(self.prec, ptr(x), x.stride(0), ptr(out), rp, r, c, rp, stream(self.device)), "zett_op_transpose_lo")
+                self._call("zett_op_transpose_lo", self.prec, ptr(x), x.stride(0), ptr(out), rp, r, c, rp)
             return out
         out = self.new(c, rp)
-        _lib.check(self.lib.zett_op_transpose_f32(ptr(x), x.stride(0), ptr(out), rp, r, c, rp, stream(self.device)), "zett_op_transpose_f32")
+        self._call("zett_op_transpose_f32", ptr(x), x.stride(0), ptr(out), rp, r, c, rp)
         return out
 
     def _colsum_raw(self, x, out=None, accumulate=False):
@@ -169,7 +173,7 @@ class Ops:
         r, c = x.shape
         if out is None:
             out = self.new(c)
-        _lib.check(self.lib.zett_op_colsum_f32(ptr(x), x.stride(0), r, c, ptr(out), int(accumulate), stream(self.device)), "zett_op_colsum_f32")
+        self._call("zett_op_colsum_f32", ptr(x), x.stride(0), r, c, ptr(out), int(accumulate))
         return out
 
     def colsum(self, x, out=None, accumulate=False):
@@ -195,8 +199,7 @@ class Ops:
         out = self.new(*(ref.shape if ref is not None else (rows, cols)))
         for t in (a, b):
             assert t is None or t.is_contiguous()
-        _lib.check(self.lib.zett_op_elementwise_f32(op, ptr(a), ptr(b), ptr(vec), ptr(vec2), ptr(s), ptr(out), n, cols, stream(self.device)),
-                   "zett_op_elementwise_f32")
+        self._call("zett_op_elementwise_f32", op, ptr(a), ptr(b), ptr(vec), ptr(vec2), ptr(s), ptr(out), n, cols)
         return out
 
     def add(self, a, b):
@@ -217,7 +220,7 @@ class Ops:
     def rowdot(self, a, w, b=None):
         assert a.dim() == 2 and a.stride(1) == 1
         out = self.new(a.shape[0])
-        _lib.check(self.lib.zett_op_rowdot_f32(ptr(a), a.stride(0), ptr(w), ptr(b), ptr(out), a.shape[0], a.shape[1], stream(self.device)), "zett_op_rowdot_f32")
+        self._call("zett_op_rowdot_f32", ptr(a), a.stride(0), ptr(w), ptr(b), ptr(out), a.shape[0], a.shape[1])
         return out
 
     def layernorm(self, x, gamma, beta, eps):
@@ -227,8 +230,8 @@ class Ops:
         r, h = x.shape
         y, stats = self.new(r, h), self.new(r, 2)
         twin = torch.empty((r, h), dtype=self.lo_dtype, device=self.device) if self.prec is not None and h % 64 == 0 else None
-        _lib.check(self.lib.zett_op_layernorm_fwd_f32(ptr(x), x.stride(0), ptr(gamma), ptr(beta), float(eps), ptr(y), ptr(stats), r, h, ptr(twin),
-                                                      self.prec if twin is not None else 0, stream(self.device)), "zett_op_layernorm_fwd_f32")
+        self._call("zett_op_layernorm_fwd_f32", ptr(x), x.stride(0), ptr(gamma), ptr(beta), float(eps), ptr(y), ptr(stats), r, h, ptr(twin),
+                   self.prec if twin is not None else 0)
         if twin is not None:
             y._zett_lo = twin
         return y, stats
@@ -240,8 +243,7 @@ class Ops:
         r, h = x.shape
         n_part = max(1, min(r, 1024))
         dx, part = self.new(r, h), self.new(n_part, 2 * h)
-        _lib.check(self.lib.zett_op_layernorm_bwd_f32(ptr(dy), ptr(dy2), ptr(x), x.stride(0), ptr(stats), ptr(gamma), ptr(dx), ptr(part), n_part, r, h,
-                                                      stream(self.device)), "zett_op_layernorm_bwd_f32")
+        self._call("zett_op_layernorm_bwd_f32", ptr(dy), ptr(dy2), ptr(x), x.stride(0), ptr(stats), ptr(gamma), ptr(dx), ptr(part), n_part, r, h)
         g = self._colsum_raw(part)
         return dx, g[:h], g[h:]
 
@@ -250,16 +252,16 @@ class Ops:
         its fp32 form is never stored"""
         if operand and self.prec is not None and z.shape[-1] % 64 == 0 and z.is_contiguous():
             h = torch.empty(z.shape, dtype=self.lo_dtype, device=self.device)
-            _lib.check(self.lib.zett_op_gelu_fwd_lo(self.prec, ptr(z), ptr(h), z.numel(), kind, stream(self.device)), "zett_op_gelu_fwd_lo")
+            self._call("zett_op_gelu_fwd_lo", self.prec, ptr(z), ptr(h), z.numel(), kind)
             return h
         h = self.new(*z.shape)
-        _lib.check(self.lib.zett_op_gelu_fwd_f32(ptr(z), ptr(h), z.numel(), kind, stream(self.device)), "zett_op_gelu_fwd_f32")
+        self._call("zett_op_gelu_fwd_f32", ptr(z), ptr(h), z.numel(), kind)
         return h
 
     def gelu_bwd(self, z, dh, kind):
         assert dh.is_contiguous() and z.is_contiguous()
         dz = self.new(*z.shape)
-        _lib.check(self.lib.zett_op_gelu_bwd_f32(ptr(z), ptr(dh), ptr(dz), z.numel(), kind, stream(self.device)), "zett_op_gelu_bwd_f32")
+        self._call("zett_op_gelu_bwd_f32", ptr(z), ptr(dh), ptr(dz), z.numel(), kind)
         return dz
 
     def attention(self, q, k, v, mask, row_offset, n_rows, seq, heads, hidden, cls_only=False, operand=False):
@@ -271,39 +273,34 @@ class Ops:
         lo = operand and self.prec is not None and hidden % 64 == 0
         ctx = torch.empty((q.shape[0], hidden), dtype=self.lo_dtype if lo else torch.float32, device=self.device)
         probs = torch.zeros((n_rows, heads, seq, seq), dtype=torch.float32, device=self.device)
-        _lib.check(self.lib.zett_op_attention_fwd_f32(ptr(q), q.stride(0), ptr(k), ptr(v), k.stride(0), ptr(mask), ptr(row_offset), n_rows, seq, heads, d,
-                                                      int(cls_only), ptr(None if lo else ctx), hidden, ptr(probs), ptr(ctx if lo else None),
-                                                      self.prec if lo else 0, stream(self.device)), "zett_op_attention_fwd_f32")
+        self._call("zett_op_attention_fwd_f32", ptr(q), q.stride(0), ptr(k), ptr(v), k.stride(0), ptr(mask), ptr(row_offset), n_rows, seq, heads, d,
+                   int(cls_only), ptr(None if lo else ctx), hidden, ptr(probs), ptr(ctx if lo else None), self.prec if lo else 0)
         return ctx, probs
 
     def attention_bwd(self, dctx, q, k, v, probs, row_offset, n_rows, seq, heads, hidden, dq, dk, dv, cls_only=False):
         """writes dq (rows like q), dk / dv (rows like k; column views of one buffer with equal row stride)"""
         assert dctx.is_contiguous() and dk.stride(0) == dv.stride(0)
         d = hidden // heads
-        _lib.check(self.lib.zett_op_attention_bwd_f32(ptr(dctx), hidden, ptr(q), q.stride(0), ptr(k), ptr(v), k.stride(0), ptr(probs), ptr(row_offset),
-                                                      n_rows, seq, heads, d, int(cls_only), ptr(dq), dq.stride(0), ptr(dk), ptr(dv), dk.stride(0),
-                                                      stream(self.device)), "zett_op_attention_bwd_f32")
+        self._call("zett_op_attention_bwd_f32", ptr(dctx), hidden, ptr(q), q.stride(0), ptr(k), ptr(v), k.stride(0), ptr(probs), ptr(row_offset),
+                   n_rows, seq, heads, d, int(cls_only), ptr(dq), dq.stride(0), ptr(dk), ptr(dv), dk.stride(0))
 
     def gather_rows(self, src, idx, a=None):
         """out[r] = (a[r] if a is given else 0) + src[idx[r]]"""
         assert src.stride(1) == 1 and idx.dtype == torch.int32 and (a is None or a.is_contiguous())
         out = self.new(idx.numel(), src.shape[1])
-        _lib.check(self.lib.zett_op_gather_rows_f32(ptr(a), ptr(src), src.stride(0), ptr(idx), ptr(out), idx.numel(), src.shape[1], stream(self.device)),
-                   "zett_op_gather_rows_f32")
+        self._call("zett_op_gather_rows_f32", ptr(a), ptr(src), src.stride(0), ptr(idx), ptr(out), idx.numel(), src.shape[1])
         return out
 
     def scatter_add_rows(self, dst, idx, src):
         """dst[idx[r]] += src[r] (in place; dst must be initialised)"""
         assert dst.stride(1) == 1 and src.is_contiguous() and idx.dtype == torch.int32 and idx.numel() == src.shape[0]
-        _lib.check(self.lib.zett_op_scatter_add_rows_f32(ptr(dst), dst.stride(0), ptr(idx), ptr(src), idx.numel(), src.shape[1], stream(self.device)),
-                   "zett_op_scatter_add_rows_f32")
+        self._call("zett_op_scatter_add_rows_f32", ptr(dst), dst.stride(0), ptr(idx), ptr(src), idx.numel(), src.shape[1])
         return dst
 
     def gather(self, ids, src, v0, fallback, sw, sb):
         t = ids.numel()
         x = self.new(t, src.shape[1])
-        _lib.check(self.lib.zett_op_gather_fwd_f32(ptr(ids), t, ptr(src), zett_dtypes()[src.dtype], src.shape[1], v0, ptr(fallback), ptr(sw), ptr(sb),
-                                                   ptr(x), stream(self.device)), "zett_op_gather_fwd_f32")
+        self._call("zett_op_gather_fwd_f32", ptr(ids), t, ptr(src), zett_dtypes()[src.dtype], src.shape[1], v0, ptr(fallback), ptr(sw), ptr(sb), ptr(x))
         return x
 
     def index_sum_rows(self, idx, src, n_dst, id_base=0):
@@ -325,13 +322,11 @@ class Ops:
         if deterministic:
             assert dx.is_contiguous()
             prod, keep = self.new(t, e_in), self.new(t, e_in)
-            _lib.check(self.lib.zett_op_gather_bwd_rows_f32(ptr(ids), t, ptr(src), zett_dtypes()[src.dtype], e_in, v0, ptr(dx), ptr(prod), ptr(keep),
-                                                            stream(self.device)), "zett_op_gather_bwd_rows_f32")
+            self._call("zett_op_gather_bwd_rows_f32", ptr(ids), t, ptr(src), zett_dtypes()[src.dtype], e_in, v0, ptr(dx), ptr(prod), ptr(keep))
             return self.index_sum_rows(ids, dx, n_fallback, id_base=v0), self.colsum(prod), self.colsum(keep)
         dfb = torch.zeros((n_fallback, e_in), dtype=torch.float32, device=self.device)
         prod, keep = self.new(t, e_in), self.new(t, e_in)
-        _lib.check(self.lib.zett_op_gather_bwd_f32(ptr(ids), t, ptr(src), zett_dtypes()[src.dtype], e_in, v0, ptr(dx), ptr(dfb), ptr(prod), ptr(keep),
-                                                   stream(self.device)), "zett_op_gather_bwd_f32")
+        self._call("zett_op_gather_bwd_f32", ptr(ids), t, ptr(src), zett_dtypes()[src.dtype], e_in, v0, ptr(dx), ptr(dfb), ptr(prod), ptr(keep))
         return dfb, self.colsum(prod), self.colsum(keep)
 
     # ---- Linear backward on the same GEMM: dgrad against W^T, wgrad of the transposed activations
@@ -345,8 +340,8 @@ class Ops:
         dy_t = torch.empty((n, mp), dtype=self.lo_dtype, device=self.device)
         part = self.new(bands, n)
         assert act_z is None or (act_z.shape == dy.shape and act_z.stride(1) == 1)
-        _lib.check(self.lib.zett_op_grad_operands_lo(self.prec, ptr(dy), dy.stride(0), ptr(act_z), 0 if act_z is None else act_z.stride(0), act_kind, m, n, mp,
-                                                     ptr(dy_lo), n, ptr(dy_t), mp, ptr(part), stream(self.device)), "zett_op_grad_operands_lo")
+        self._call("zett_op_grad_operands_lo", self.prec, ptr(dy), dy.stride(0), ptr(act_z), 0 if act_z is None else act_z.stride(0), act_kind, m, n, mp,
+                   ptr(dy_lo), n, ptr(dy_t), mp, ptr(part))
         return dy_lo, dy_t, self.colsum(part)
 
     def linear_bwd(self, dy, x, w, act_z=None, act_kind=0):

@@ -23,8 +23,8 @@ OBJ_DIR = os.path.join(CSRC, "build")
 
 
 # primitives of zett_amd/autograd.py and zett_amd/training.py, and the header only they include: not on the path bench.py measures
-TRAINING_ONLY = ("train_common.hip.h", "train_optim.hip.h", "train_adafactor.hip", "train_batch.hip", "train_dist.hip", "train_embed.hip", "train_init.hip", "train_loss.hip",
-                 "train_ops.hip", "train_step.hip")
+TRAINING_ONLY = ("train_common.hip.h", "train_optim.hip.h", "train_adafactor.hip", "train_attention.hip", "train_batch.hip", "train_dist.hip", "train_embed.hip",
+                 "train_gather.hip", "train_gemm.hip", "train_init.hip", "train_layernorm.hip", "train_loss.hip", "train_operands.hip", "train_step.hip")
 
 
 def source_hash() -> str:

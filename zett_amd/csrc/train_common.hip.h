@@ -1,4 +1,4 @@
-// train_common.hip.h — the small device / host layer the training units (train_ops.hip, train_dist.hip, train_step.hip,
+// train_common.hip.h — the small device / host layer the training units (train_gemm.hip, train_operands.hip, train_layernorm.hip, train_attention.hip, train_gather.hip, train_dist.hip, train_step.hip,
 // train_adafactor.hip, train_loss.hip, train_embed.hip, train_batch.hip, train_init.hip) share: element accessors over gemm.hip.h's conversions (to_lo, lo_to_f32, pack2_lo, unpack2_lo: widen on load —
 // bf16 by the 16-bit left shift —, round to nearest even on store), the reductions, the id read and the splitmix64 finalizer.  (The zett_dtype ->
 // storage-type map and the dtype dispatch of the launches — elem_t, is_dtype, with_dtype — are common.hip.h's: the forward uses
@@ -64,7 +64,7 @@ __device__ __forceinline__ float wave_sum(float v) {
 }
 // The two sums of a 256-thread workgroup differ in how the four wave results are added, and the bits of their callers depend on it:
 // they are not interchangeable.
-// left to right, ((r0 + r1) + r2) + r3: train_ops.hip (LayerNorm forward statistics, rowdot)
+// left to right, ((r0 + r1) + r2) + r3: train_layernorm.hip (the forward's statistics), train_operands.hip (rowdot)
 __device__ __forceinline__ float block_sum_ltr(float v, float* red /* [4] */) {
     v = wave_sum(v);
     __syncthreads();
@@ -95,11 +95,23 @@ __device__ __forceinline__ double block_sum_f64(double v, double* red /* [256] *
 
 // ---- host side ------------------------------------------------------------------------------------------------------------------
 // Declared here, DEFINED in train_loss.hip, which holds the one column-sum kernel and the one converting-copy kernel of the training
-// units: out[c] (+)= sum_r in[r, c], and out[r, c] = convert(in[r, c]) with columns [cols, cols_padded) zero.  train_ops.hip
+// units: out[c] (+)= sum_r in[r, c], and out[r, c] = convert(in[r, c]) with columns [cols, cols_padded) zero.  train_operands.hip
 // (zett_op_colsum_f32, the general path of zett_op_convert_lo) links against them; they are internal to the library (hidden).
 // Arguments are the callers' to check.
 __attribute__((visibility("hidden"))) void launch_colsum(int32_t dtype, const void* in, int64_t ld, int64_t rows, int cols, float* out, int accumulate, hipStream_t st);
 __attribute__((visibility("hidden"))) void launch_cast(int32_t in_dtype, int32_t out_dtype, const void* in, int64_t ld_in, void* out, int64_t ld_out, int64_t rows, int cols,
                                                        int cols_padded, hipStream_t st);
+
+// The 16-bit operand type of a training primitive.  lo_prec_ok refuses anything but the two; `who_takes` opens the sentence
+// ("zett_op_gemm_lo takes", "the 16-bit transposes take").  with_lo(prec, f) is f(Arith<f16_t | bf16_t>{}) for a prec that passed it
+// (with_precision, common.hip.h, without the fp32 arm: no training kernel has one); returns what f returns.
+inline int lo_prec_ok(int32_t prec, const char* who_takes) {
+    if (prec != ZETT_PREC_BF16 && prec != ZETT_PREC_F16) return fail(ZETT_E_INVALID, "%s ZETT_PREC_BF16 or ZETT_PREC_F16", who_takes);
+    return 0;
+}
+template <typename F> inline auto with_lo(int32_t prec, F&& f) {
+    if (prec == ZETT_PREC_F16) return f(Arith<f16_t>{});
+    return f(Arith<bf16_t>{});
+}
 
 }  // namespace zett
