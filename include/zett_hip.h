@@ -346,8 +346,17 @@ int zett_scatter_rows(const void* src, void* dst, const int64_t* order, int64_t 
  * zett_table_rows: table rows [first, first + count) of that list — gather + in_scaler + fallback, input_projection.0, the
  * ProjectorBlock up to its pre-LayerNorm sum — into table_out (rows of `hidden` values of the handle's 16-bit type; the buffer
  * holds the WHOLE table, row i at table_out + i * hidden) and stats_out (float [*, 2]: mean, rstd of row i at stats_out + 2 i).
- * Asynchronous on `stream`.
- * zett_forward_table: zett_forward on that table (complete: this rank's rows and its peers') instead of source embeddings. */
+ * Asynchronous on `stream`.  Overflows of the 16-bit type are OR-ed into the handle's range word (zett_check_range), which the next
+ * forward clears unless "range_accumulate" is on: ask after building the table, not after the forwards on it.  Whether the handle
+ * builds table rows at all (precision, fold, "table_lo") is decided BEFORE the empty slice: a call with count == 0 gives that
+ * ZETT_E_INVALID too, so that ranks with and without rows of a small table agree; behind that check count == 0 returns ZETT_OK
+ * without reading a pointer, so `zett_table_rows(h, NULL, 0, 0, NULL, ZETT_F32, 0, NULL, NULL, NULL)` is the probe "does this handle
+ * have the folded table".
+ * zett_forward_table: zett_forward on that table (complete: this rank's rows and its peers') instead of source embeddings.  Every
+ * id the call references (position 0, visible positions, every position of a row without a visible key) must own a row of the
+ * table, i.e. id_slot[id + 1] != id_slot[id]: id_slot is an exclusive scan, so an id the planned matrix never referenced carries its
+ * successor's slot.  Otherwise ZETT_E_INDEX ("... not in the table", with the number of the last offending row; an id outside
+ * the vocabulary is reported first, with zett_forward's message), at the plan's host read: no output or destination row is written. */
 int zett_table_plan(zett_hypernet* h, const int32_t* surface_forms, int64_t n_rows, int32_t seq, int32_t* id_slot_out, int32_t* id_list_out,
                     int64_t* n_ids_out, void* stream);
 int zett_table_rows(zett_hypernet* h, const int32_t* id_list, int64_t first, int64_t count, const void* source_embeddings, int src_dtype,

@@ -22,8 +22,10 @@ static int64_t pair_keys(const zett_config& c, int seq) {
 }
 
 // ---- the plan's kernels (launched by enqueue_plan below and from nowhere else) ---------------------------------------------------
+// ext_slot: the id_slot of a caller's table (zett_forward_table; null otherwise).  An id this row REFERENCES — what id_flag marks — must
+// own a row of that table: id_slot is an exclusive scan, so an id the table's matrix never referenced carries the NEXT id's slot.
 static __global__ void plan_rows_kernel(const int32_t* __restrict__ sfm, int64_t n_rows, int seq, int pad, int lam,
-                                 int n_ids, PlanArrays p) {
+                                 int n_ids, const int32_t* __restrict__ ext_slot, PlanArrays p) {
     const int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (n >= n_rows) return;
     const int32_t* row = sfm + n * seq;
@@ -31,7 +33,7 @@ static __global__ void plan_rows_kernel(const int32_t* __restrict__ sfm, int64_t
     for (int j = 0; j < seq; ++j) {
         const int id = row[j];
         if (id < 0 || id >= n_ids) {          // F.embedding would raise IndexError here
-            atomicMax(p.err, (int)(n < 0x7ffffffe ? n + 1 : 0x7fffffff));
+            atomicMax(p.err, PLAN_ERR_RANGE | (int)(n + 1));
             p.row_count[n] = 0;
             p.row_uniform[n] = 2;             // poisoned: skipped by plan_tokens_kernel
             return;
@@ -40,14 +42,20 @@ static __global__ void plan_rows_kernel(const int32_t* __restrict__ sfm, int64_t
     }
     const bool uniform = (visible + lam) == 0;
     int count;
+    bool absent = false;
+    auto reference = [&](int id) {
+        p.id_flag[id] = 1;
+        if (ext_slot && ext_slot[id + 1] == ext_slot[id]) absent = true;
+    };
     if (uniform) {
         count = seq;
-        for (int j = 0; j < seq; ++j) p.id_flag[row[j]] = 1;
+        for (int j = 0; j < seq; ++j) reference(row[j]);
     } else {
         count = visible + lam + (row[0] == pad ? 1 : 0);
         for (int j = 0; j < seq; ++j)
-            if (j == 0 || row[j] != pad) p.id_flag[row[j]] = 1;
+            if (j == 0 || row[j] != pad) reference(row[j]);
     }
+    if (absent) atomicMax(p.err, (int)(n + 1));          // (below every PLAN_ERR_RANGE word: an id outside the vocabulary is reported first)
     p.row_count[n] = count;
     p.row_uniform[n] = uniform ? 1 : 0;
 }
@@ -103,6 +111,17 @@ static __global__ void plan_idlist_kernel(int n_ids, PlanArrays p) {
 }
 
 // ---- host --------------------------------------------------------------------------------------------------------------------------
+
+int plan_error(const zett_hypernet* h, int32_t word) {
+    const zett_config& c = h->cfg;
+    if (word & PLAN_ERR_RANGE)
+        return fail(ZETT_E_INDEX, "surface-form row %d holds an id outside [0, %d) (original_vocab_size %d + %d fallback rows)",
+                    (word & ~PLAN_ERR_RANGE) - 1, c.original_vocab_size + c.n_extra, c.original_vocab_size, c.n_extra);
+    if (word)
+        return fail(ZETT_E_INDEX, "surface-form row %d references a source id that is not in the table: the matrix the table was planned from "
+                                  "(zett_table_plan) never referenced it, so id_slot gives it no row", word - 1);
+    return 0;
+}
 
 PlanLayout plan_layout(const zett_hypernet* h, const PlanSlot* s, int64_t N, int seq, bool worst_case) {
     const zett_config& c = h->cfg;
@@ -163,10 +182,11 @@ int enqueue_plan(zett_hypernet* h, PlanSlot& s, const ExtTable* ext, const int32
     const PlanArrays& p = L.p;
     HIP_TRY(hipMemsetAsync(s.i32.p, 0, L.n_clear * 4, st));          // id_flag, pair_flag, err: one piece of the arena
     const int rb = (int)((N + 255) / 256);
-    hipLaunchKernelGGL(plan_rows_kernel, dim3(rb), dim3(256), 0, st, sfm, N, seq, c.pad_token_id, lam, V, p);
+    const int32_t* ext_id_slot = ext ? ext->id_slot : nullptr;
+    // (both arms of a forward on a caller's table — plan_tokens_kernel's lookup below, lever 6's gather — are checked here, where every referenced id passes)
+    hipLaunchKernelGGL(plan_rows_kernel, dim3(rb), dim3(256), 0, st, sfm, N, seq, c.pad_token_id, lam, V, ext_id_slot, p);
     launch_exclusive_scan(p.row_count, p.row_offset, N, L.scan_tmp, st);
     launch_exclusive_scan(p.id_flag, p.id_slot, (int64_t)V, L.scan_tmp, st);
-    const int32_t* ext_id_slot = ext ? ext->id_slot : nullptr;
     {
         // (ABI 8) a forward on a caller-provided table: a token's table slot is its id's slot in the GLOBAL distinct-id list
         PlanArrays pt = p;
@@ -228,9 +248,7 @@ int zett_table_plan(zett_hypernet* h, const int32_t* surface_forms, int64_t n_ro
     if (int rc = enqueue_plan(h, ps, nullptr, surface_forms, n_rows, seq, st)) return rc;          // (this plan numbers the ids itself)
     HIP_TRY(hipEventSynchronize(ps.done));
     const int32_t* hoff = ps.host.p;
-    if (hoff[n_rows + 2] != 0)
-        return fail(ZETT_E_INDEX, "surface-form row %d holds an id outside [0, %d) (original_vocab_size %d + %d fallback rows)",
-                    hoff[n_rows + 2] - 1, V, c.original_vocab_size, c.n_extra);
+    if (int rc = plan_error(h, hoff[n_rows + 2])) return rc;
     const int D = hoff[n_rows + 1];
     const PlanLayout L = plan_layout(h, &ps, n_rows, seq);
     HIP_TRY(hipMemcpyAsync(id_slot_out, L.p.id_slot, ((size_t)V + 1) * 4, hipMemcpyDeviceToDevice, st));

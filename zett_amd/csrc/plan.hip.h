@@ -40,10 +40,16 @@ struct PlanArrays {
     int32_t* pair_tslot;    // [P]   table slot of the pair (-1 = language token)
     int32_t* pair_pos;      // [P]   its position index
     uint8_t* tok_key;       // [T]   visible as key
-    int32_t* err;           // [1]   set to 1 + row on an out-of-range id
+    int32_t* err;           // [1]   the plan's error word (plan_error): the largest of PLAN_ERR_RANGE | (1 + row) over the rows with an id outside the
+                            //       vocabulary and 1 + row over the rows that reference an id a caller's table does not hold
     int32_t* counters;      // [3]   behind row_offset[N]: distinct ids, the error word, distinct pairs — what the host reads with the row offsets, in ONE copy
     int32_t n_pair_keys;    //       size of pair_flag (0: no pair plan)
 };
+
+// A row number fits under the bit: a call holds fewer than 2^31 - 1 positions of at least two per row (check_call).
+constexpr int32_t PLAN_ERR_RANGE = 0x40000000;
+// the plan's error word as the host read it -> 0, or ZETT_E_INDEX with the message of its kind
+int plan_error(const zett_hypernet* h, int32_t word);
 
 // Where the arrays of a plan lie in a slot (pure pointer arithmetic: the same answer when the plan is made and when a
 // forward takes it).  Pair plan (lever 4): only where it can pay — at least two encoder layers (layer 0 must not be the
@@ -68,7 +74,7 @@ bool id_qkv_configured(const zett_hypernet* h);
 
 // The plan of one forward into slot s, on stream st: six small kernels, three scans, and the copy of the row offsets and the
 // three counters to pinned memory; s.done is recorded behind them.  ext: the caller's table of the forward the plan is for (null:
-// the plan numbers the ids itself).
+// the plan numbers the ids itself); every id the call references must then own a row of it, or the error word says which row does not.
 int enqueue_plan(zett_hypernet* h, PlanSlot& s, const ExtTable* ext, const int32_t* sfm, int64_t N, int seq, hipStream_t st);
 
 }  // namespace zett

@@ -78,6 +78,8 @@ int do_forward(zett_hypernet* h, const ExtTable* ext, const int32_t* sfm, int64_
                int lang_index, float* out_in, float* out_out, float* out_bias, hipStream_t st);
 template <typename T>
 int do_table_rows(zett_hypernet* h, const int32_t* id_list, int first, int count, const void* src, int src_dtype, void* table_out, float* stats_out, hipStream_t st);
+// 0 when the handle's precision and options give ForwardMode::table_lo (below), else `entry`'s refusal: host state only, no device call
+int check_folded_table(const zett_hypernet* h, const char* entry);
 
 }  // namespace
 
@@ -193,6 +195,9 @@ int zett_table_rows(zett_hypernet* h, const int32_t* id_list, int64_t first, int
     k.shape = false;                    // (a range of table rows instead of surface forms: checked here, between the handle and the tensors)
     if (int rc = check_call(h, k)) return rc;
     if (first < 0 || count < 0 || first + count >= (int64_t)0x7fffffff) return fail(ZETT_E_INVALID, "bad table range [%lld, +%lld)", (long long)first, (long long)count);
+    // whether this handle builds table rows at all is answered before the empty slice: the ranks of a small vocabulary, some with rows and
+    // some without, then agree — and a call with count == 0 and null tensors is the probe for it
+    if (int rc = check_folded_table(h, "zett_table_rows")) return rc;
     if (count == 0) return 0;
     k.null_arg = !id_list || !source_embeddings || !table_out || !stats_out;
     k.source = true; k.src_dtype = src_dtype; k.v_src = v_src;
@@ -447,6 +452,11 @@ ForwardMode forward_mode(const zett_hypernet* h) {
 int needs_folded_table(const char* entry) {
     return fail(ZETT_E_INVALID, "%s needs the folded 16-bit table: f16 arithmetic with the LayerNorm fold, the 16-bit residual stream and table_lo on", entry);
 }
+int check_folded_table(const zett_hypernet* h, const char* entry) {
+    if (h->precision == ZETT_PREC_F32) return fail(ZETT_E_INVALID, "%s: the folded 16-bit table exists in the 16-bit modes only", entry);
+    const bool table_lo = with_precision(h->precision, [&](auto a) { return forward_mode<typename decltype(a)::type>(h).table_lo; });
+    return table_lo ? 0 : needs_folded_table(entry);
+}
 
 // ---- workspace ---------------------------------------------------------------------------------------------------------------------
 // The buffers behind WorkspaceSizes.  encoder = false: what the table phase alone touches (zett_table_rows reserves no more).
@@ -655,9 +665,7 @@ struct Forward {
         }
         HIP_TRY(hipEventSynchronize(ps->done));
         hoff = ps->host.p;
-        if (hoff[N + 2] != 0)
-            return fail(ZETT_E_INDEX, "surface-form row %d holds an id outside [0, %d) (original_vocab_size %d + %d fallback rows)",
-                        hoff[N + 2] - 1, c.original_vocab_size + c.n_extra, c.original_vocab_size, c.n_extra);
+        if (int rc = plan_error(h, hoff[N + 2])) return rc;          // an id outside the vocabulary, or (a caller's table) one the table does not hold
         if (dest_check) {
             HIP_TRY(hipEventSynchronize(h->dest_checked));
             if (h->dest_host.p[0] != 0)

@@ -93,6 +93,7 @@ class HipEngine:
         _lib.check(self.lib.zett_create(C.byref(cfg), index, _PRECISIONS[precision], C.byref(handle)), "zett_create")
         self.handle = handle
         self.weights_stamp = None
+        self.range_accumulate = False           # the "range_accumulate" option as set_option last set it (zett_create's default: off)
 
     def load_weights(self, tensors: Dict[str, torch.Tensor]) -> None:
         for name, t in tensors.items():
@@ -106,6 +107,8 @@ class HipEngine:
 
     def set_option(self, key: str, value: int) -> None:
         _lib.check(self.lib.zett_set_option(self.handle, key.encode(), int(value)), f"zett_set_option({key})")
+        if key == "range_accumulate":           # (remembered: sharding.SharedTable must not consume an accumulating word)
+            self.range_accumulate = bool(int(value))
 
     def workspace_bytes(self, n_rows: int, seq: int) -> int:
         """Upper bound of the device bytes a [n_rows, seq] forward reserves (zett_workspace_bytes)."""
@@ -272,6 +275,7 @@ class HipEngine:
         """zett_forward_table_into: forward_table() storing into a destination, as forward_into()."""
         if surface_forms.dim() != 2 or surface_forms.device != self.device:
             raise ValueError(f"target_surface_forms must be [n_tokens, surface_maxlen] on {self.device}")
+        self._check_table(table, stats, id_slot)
         ids = surface_forms.to(torch.int32).contiguous()
         n, seq = ids.shape
         dest, keep = self._dest(n, out_in, out_out, out_bias, rows)
@@ -298,9 +302,39 @@ class HipEngine:
                                                 ptr(id_list), C.byref(n_ids), _glue.stream(self.device)), "zett_table_plan")
         return id_slot, id_list[:n_ids.value], int(n_ids.value)
 
+    def has_folded_table(self) -> bool:
+        """Whether this engine builds and reads the folded 16-bit table at all (table_rows / forward_table): its precision, hidden size
+        and options decide, nothing about a call does — zett_table_rows on an empty slice with null tensors is the probe (include/zett_hip.h)."""
+        rc = self.lib.zett_table_rows(self.handle, None, 0, 0, None, _lib.DTYPE_F32, 0, None, None, None)
+        if rc not in (_lib.ZETT_OK, _lib.E_INVALID):
+            _lib.check(rc, "zett_table_rows")
+        return rc == _lib.ZETT_OK
+
+    def _table_dtype(self) -> Optional[torch.dtype]:
+        return {"f16": torch.float16, "fp16": torch.float16, "float16": torch.float16, "bf16": torch.bfloat16, "bfloat16": torch.bfloat16}.get(self.precision)
+
+    def _check_table(self, table, stats, id_slot) -> None:
+        """The table arguments of forward_table[_into], before the library sees them as raw pointers."""
+        d = self.dims
+        lo = self._table_dtype()
+        if lo is None:
+            raise ValueError("the folded 16-bit table exists in the 16-bit modes only")
+        for t, what in ((table, "table"), (stats, "stats"), (id_slot, "id_slot")):
+            if not torch.is_tensor(t) or t.device != self.device:
+                raise ValueError(f"{what} must be a tensor on {self.device}")
+            if not t.is_contiguous():
+                raise ValueError(f"{what} must be contiguous")
+        if table.dtype != lo or table.dim() != 2 or table.shape[1] != d.hidden:
+            raise ValueError(f"table must be [rows, {d.hidden}] {lo} (this engine's 16-bit type), got {tuple(table.shape)} {table.dtype}")
+        if stats.dtype != torch.float32 or stats.dim() != 2 or stats.shape[1] != 2 or stats.shape[0] != table.shape[0]:
+            raise ValueError(f"stats must be float32 [{table.shape[0]}, 2] (mean, rstd of every table row), got {tuple(stats.shape)} {stats.dtype}")
+        v = d.original_vocab_size + d.n_extra
+        if id_slot.dtype != torch.int32 or tuple(id_slot.shape) != (v + 1,):
+            raise ValueError(f"id_slot must be int32 [{v + 1}] (table_plan's), got {tuple(id_slot.shape)} {id_slot.dtype}")
+
     def table_buffers(self, n_rows: int):
         """Empty buffers of a folded table of n_rows rows: (table [n_rows, H] in the engine's 16-bit type, stats float32 [n_rows, 2])."""
-        lo = {"f16": torch.float16, "fp16": torch.float16, "float16": torch.float16, "bf16": torch.bfloat16}.get(self.precision)
+        lo = self._table_dtype()
         if lo is None:
             raise ValueError("the folded 16-bit table exists in the 16-bit modes only")
         return (torch.empty((n_rows, self.dims.hidden), dtype=lo, device=self.device), torch.empty((n_rows, 2), dtype=torch.float32, device=self.device))
@@ -324,6 +358,7 @@ class HipEngine:
         d = self.dims
         if surface_forms.dim() != 2 or surface_forms.device != self.device:
             raise ValueError(f"target_surface_forms must be [n_tokens, surface_maxlen] on {self.device}")
+        self._check_table(table, stats, id_slot)
         ids = surface_forms.to(torch.int32).contiguous()
         n, seq = ids.shape
         out_in = torch.empty((n, d.n_embd), dtype=torch.float32, device=self.device)

@@ -339,6 +339,14 @@ def all_gather_rows(local: torch.Tensor, n_rows: int, per: int, group=None) -> t
     return full[:n_rows]
 
 
+def reduce_flag_word(word: int, device, group=None, bits: int = 8) -> int:
+    """Bitwise OR of a small flag word over the ranks.  RCCL has no BOR ("Cannot use ReduceOp.BOR with NCCL"), and MAX of the
+    words would lose bits (max(1, 2) = 2): one int32 per bit, reduced with MAX — works on nccl and gloo alike."""
+    vec = torch.tensor([(int(word) >> b) & 1 for b in range(bits)], dtype=torch.int32, device=device)
+    dist.all_reduce(vec, op=dist.ReduceOp.MAX, group=group)
+    return sum(int(v) << b for b, v in enumerate(vec.tolist()))
+
+
 class SharedTable:
     """The hoisted input-projection table computed ONCE across the ranks (SURVEY.md 8e's optional second exchange; zett_table_* of
     ABI 8).  `input_projection(in_scaler(source_embeddings[id]))` depends on the source id only; a rank of a row-sharded prediction
@@ -351,6 +359,20 @@ class SharedTable:
 
         shared = SharedTable(engine, sfm_all, source_embeddings)            # every rank, same arguments
         full = predict_sharded(shared.predict(lang), sfm_all, ready=engine.stream_wait_output)
+        flags = shared.range_flags | engine.range_flags()                    # the table's build and the last forward on it
+
+    Range guard.  zett_table_rows raises its overflow bits (RANGE_SOURCE: in_scaler(source_embeddings) of a referenced id left the half
+    range; RANGE_ACTIVATION) in the engine's range word, and the first forward on the table starts a word of its own: what the build saw
+    would be gone when the caller asks.  `range_flags` keeps it: the bits raised while THIS rank built its slices, OR-ed over the group
+    when an exchange took place (one word, reduced with the table's exchange: every rank holds the same value).  The constructor
+    takes over the engine's word for that — cleared before the build, read and cleared after it, two waits for the stream — so a
+    direct user ORs `shared.range_flags` into every check of a forward on the table, as above; a saturated table row makes every row
+    that references its id wrong, whichever call reads it.  With the engine's "range_accumulate" option on (predict_vocabulary) the
+    engine's word is not touched: it already carries the build's bits into the caller's one check at the end, and `range_flags` is None.
+    (None as well for a stand-in engine without a range word.)
+
+    An id that `surface_forms_all` never referenced has no row here: `predict` on rows that reference one raises IndexError
+    (zett_forward_table), it does not read a neighbour's row.
 
     Without a process group it is one rank's whole table (the single-GPU proxy and the tests)."""
 
@@ -379,17 +401,32 @@ class SharedTable:
         self.ranges = []
         works = []
         cs = self.piece_rows
-        for k in range(self.pieces):
-            lo = min((k * self.world + self.rank) * cs, self.n_ids)
-            hi = min(lo + cs, self.n_ids)
-            self.ranges.append((lo, hi))
-            engine.table_rows(self.id_list, lo, hi - lo, source_embeddings, self.table, self.stats)
-            if exchange:
-                # (the padding rows behind n_ids travel too and are never read: id_slot only names rows < n_ids.  Bytes: a dtype every backend carries)
-                for buf in (self.table.view(torch.uint8), self.stats):
-                    region = buf[k * self.world * cs:(k + 1) * self.world * cs]
-                    mine = region[self.rank * cs:(self.rank + 1) * cs].clone()
-                    works.append(dist.all_gather_into_tensor(region, mine, group=group, async_op=True))
+        # the range word of the build (class docstring): the engine's own word for the time of the build, unless it accumulates anyway
+        own_word = hasattr(engine, "range_flags") and hasattr(engine, "set_option") and not getattr(engine, "range_accumulate", False)
+        self.range_flags: Optional[int] = None
+        if own_word:
+            engine.set_option("range_accumulate", 1)
+        try:
+            if own_word:
+                engine.range_flags()          # (accumulating: the read clears what an earlier forward left)
+            for k in range(self.pieces):
+                lo = min((k * self.world + self.rank) * cs, self.n_ids)
+                hi = min(lo + cs, self.n_ids)
+                self.ranges.append((lo, hi))
+                engine.table_rows(self.id_list, lo, hi - lo, source_embeddings, self.table, self.stats)
+                if exchange:
+                    # (the padding rows behind n_ids travel too and are never read: id_slot only names rows < n_ids.  Bytes: a dtype every backend carries)
+                    for buf in (self.table.view(torch.uint8), self.stats):
+                        region = buf[k * self.world * cs:(k + 1) * self.world * cs]
+                        mine = region[self.rank * cs:(self.rank + 1) * cs].clone()
+                        works.append(dist.all_gather_into_tensor(region, mine, group=group, async_op=True))
+            if own_word:
+                self.range_flags = int(engine.range_flags())
+        finally:
+            if own_word:
+                engine.set_option("range_accumulate", 0)
+        if own_word and exchange:
+            self.range_flags = reduce_flag_word(self.range_flags, self.stats.device, group)
         for w in works:
             w.wait()          # (device tensors: the current stream waits; the host does not)
         self.rows = self.ranges[0] if self.pieces == 1 else None

@@ -217,12 +217,12 @@ def predict_vocabulary(hypernet, target_surface_form_matrix: torch.Tensor, sourc
             eng.set_option("range_accumulate", 1)
             eng.range_flags()                           # (clears whatever an earlier call left)
             shared = None
-            if want_table(precision):
+            # Table or no table is decided from the configuration and the options alone (no folded table for H < 512 or with the LayerNorm
+            # fold off: predict as before), so every rank decides the same — a rank whose slice of a small table is empty included — and
+            # an error of the build itself is an error, not a quiet fallback.  (The engine's word accumulates: it keeps the build's bits.)
+            if want_table(precision) and eng.has_folded_table():
                 from zett_amd.sharding import SharedTable
-                try:
-                    shared = SharedTable(eng, target_surface_form_matrix.to(device=device, dtype=torch.int32).contiguous(), source_embeddings)
-                except ValueError:                      # no folded table for this hypernet / mode (H < 512, LayerNorm fold off): predict as before
-                    shared = None
+                shared = SharedTable(eng, target_surface_form_matrix.to(device=device, dtype=torch.int32).contiguous(), source_embeddings)
             predict_vocabulary.last_job_table = shared is not None      # (what the last call did: tests, logs)
             fwd = (lambda r: eng.forward_table(r, shared.table, shared.stats, shared.id_slot, lang)) if shared is not None else \
                   (lambda r: eng.forward(r, source_embeddings, lang))
@@ -284,12 +284,9 @@ def _lib_range_error(msg: str):
 
 
 def reduce_flag_word(word: int, device, group=None, bits: int = 8) -> int:
-    """Bitwise OR of a small flag word over the ranks.  RCCL has no BOR ("Cannot use ReduceOp.BOR with NCCL"), and MAX of the
-    words would lose bits (max(1, 2) = 2): one int32 per bit, reduced with MAX — works on nccl and gloo alike."""
-    import torch.distributed as dist
-    vec = torch.tensor([(int(word) >> b) & 1 for b in range(bits)], dtype=torch.int32, device=device)
-    dist.all_reduce(vec, op=dist.ReduceOp.MAX, group=group)
-    return sum(int(v) << b for b, v in enumerate(vec.tolist()))
+    """Bitwise OR of a small flag word over the ranks (zett_amd.sharding.reduce_flag_word, where the shared table reduces its own)."""
+    from zett_amd.sharding import reduce_flag_word as reduce
+    return reduce(word, device, group, bits)
 
 
 def _world_size() -> int:
